@@ -16,9 +16,15 @@ Consecutive steps are independent batches: step k has its OWN grid (seed SEED_GR
 steps are simply enqueued, `--group` consecutive steps per library call, calls round-robin on `--depth` contexts (a
 context = one HIP stream + its scratch); one host thread, one synchronisation at the end.  The K-step region is timed
 `--repeats` times (barrier + synchronise on both sides of each, max over ranks): `value` is the MEDIAN repeat, minimum
-and maximum beside it.  `value_depth1` = one call per step on one stream (what ONE call of 1024 queries gets).
+and maximum beside it.  A plain run times the region once (exactly K timed steps); `--full` times it 5 times by default.
 
-Also measured (outside the timed steps, reported in the same line):
+A plain run does only what the headline needs: set up, warm up, time the K steps, write the outputs (`--dump-outputs
+DIR`: the last timed step's distance map and A* results [and gathered paths], as float64 .npy, at most 64 MB) and print
+the line.  Everything below runs only with `--full`.
+
+  value_depth1 -- one call per step on one stream (what ONE call of 1024 queries gets); per-kernel times of the steps.
+
+Also measured with --full (outside the timed steps, reported in the same line):
   roofline     -- the EDT kernels on a batch of 64 grids (one 1024^2 grid is 5.2 MB: launch-bound
                   and cache-resident, SURVEY.md 8d), timed with HIP events on the stream the kernels run on;
                   achieved = 5 B/cell * cells / (colbits + band time).  Other map families and 4096^2 beside it.
@@ -61,6 +67,40 @@ def make_grid(name, W, H, seed=None):
     raise ValueError(name)
 
 
+DUMP_BYTES_MAX = 64 << 20
+
+
+def dump_outputs(dirname, d2, out, gath, lmax, gathered_rows, Qloc):
+    """--dump-outputs: what one timed step handed its caller, as float64 .npy under `dirname` (every int32 value exact).
+    d2 [H, W] distance map; path [Q, lmax] with the cells past each query's `len` set to -1 (never written by the kernel);
+    len / cost / status [Q]; with the gather on, the gathered len / cost / status of this step for every rank and the cells
+    of their paths.  Arrays larger than their share of 64 MB keep a fixed seeded sample of their rows, and `<name>_rows`
+    holds the row numbers kept."""
+    ln = out["len"].cpu().numpy()
+    pth = out["path"].cpu().numpy()
+    pth = np.where(np.arange(lmax)[None, :] < np.clip(ln, 0, lmax)[:, None], pth, -1)
+    arrays = {"d2": d2.cpu().numpy(), "path": pth, "len": ln, "cost": out["cost"].cpu().numpy(), "status": out["status"].cpu().numpy()}
+    if gath is not None:
+        off = gath["offsets"].cpu().numpy()
+        rows = np.concatenate([np.arange(r0, r0 + Qloc) for r0 in gathered_rows])
+        for k in ("len", "cost", "status"):
+            arrays["gather_" + k] = gath[k].cpu().numpy()[rows]
+        cells = gath["cells"].cpu().numpy()
+        arrays["gather_cells"] = np.concatenate([cells[off[r0]:off[r0 + Qloc]] for r0 in gathered_rows])
+        arrays["gather_truncated"] = gath["truncated"].cpu().numpy()
+    total = sum(8 * a.size for a in arrays.values())
+    scale = min(1.0, 0.9 * DUMP_BYTES_MAX / total)       # 10 % left for the row numbers of sampled arrays
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        a = a.astype(np.float64)
+        if scale < 1.0 and a.shape[0] > 1:
+            keep = max(1, int(a.shape[0] * scale))
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))
+            a = a[rows]
+            np.save(os.path.join(dirname, name + "_rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -79,7 +119,13 @@ def main():
                          "0 = the largest divisor of --steps that is <= 32 (20 steps: one call of 20; 64 steps: 32 per call, "
                          "alternating between the contexts), so that exactly --steps steps are timed.  Measured: 20 steps as "
                          "2 x 10 on two contexts 478 k plans/s, as one call 559 k; 64 steps as 4 x 16, 2 x 32 or 1 x 64: 544-557 k")
-    ap.add_argument("--repeats", type=int, default=5, help="how many times the K-step region is timed (value = median)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="how many times the K-step region is timed (value = median); default 1, 5 with --full")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the headline: depth-1 run, per-kernel times, other maps, configs2, roofline, "
+                         "TOPP-RA, replan stream, configs[3], smoothing, FMT*, CPU baseline and the gather checks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float64, at most 64 MB in all)")
     ap.add_argument("--lmax", type=int, default=4096)
     ap.add_argument("--edt-batch", type=int, default=64)
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -87,6 +133,8 @@ def main():
     ap.add_argument("--replan-frames", type=int, default=20,
                     help="frames of the dynamic-obstacle replan stream (BASELINE configs[4]) timed at N=1; 0 = skip")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -148,9 +196,10 @@ def main():
     # on the headline map); a rank whose paths do not fit is flagged in `gather.truncated`
     cap_cells = Qloc * args.lmax // 4
 
-    def run_map(family, steps, warmup, depth, with_toppra=False, group=1, repeats=1):
+    def run_map(family, steps, warmup, depth, with_toppra=False, group=1, repeats=1, timing=True):
         """Timed region for one obstacle family: `steps` x (EDT + batched A* [+ gather] [+ TOPP-RA]) on `depth` contexts,
-        `group` consecutive steps per library call (every step still has its own grid buffer, distance map and results)."""
+        `group` consecutive steps per library call (every step still has its own grid buffer, distance map and results).
+        timing=False: no per-kernel event brackets on context 0 and no statistics beyond the step time."""
         G = max(1, min(group, steps))
         # step k of a call: its own grid and its own queries (query block k of the generator, drawn from that grid's largest
         # free component -- needs each grid's traversable mask once, on the host)
@@ -201,8 +250,9 @@ def main():
         run_steps(((max(warmup, depth * G) + G - 1) // G) * G)   # every context allocates its scratch on its first call: not timed
         fence()
         keep.clear()
-        ctx.set_timing(True)
-        ctx.reset_timing()
+        if timing:
+            ctx.set_timing(True)
+            ctx.reset_timing()
         dts, t_enq = [], 0.0
         for _ in range(max(1, repeats)):
             fence()
@@ -218,6 +268,13 @@ def main():
             dts.append(dt_r)
             keep.clear()
         dt = float(np.median(dts))
+        jl = (steps // G - 1) % depth                      # context of the region's last call; its step G - 1 is the last step
+        res = dict(value=Qtot * steps / dt, ms_per_step=1e3 * dt / steps, host_enqueue_ms_per_step=1e3 * t_enq / steps,
+                   repeats=len(dts), value_min=Qtot * steps / max(dts), value_max=Qtot * steps / min(dts),
+                   ms_per_region=[1e3 * d for d in dts], steps=steps, group=G,
+                   last_step=dict(d2=d2s[jl][G - 1], out=view(outs[jl], G - 1), gath=gath[jl]))
+        if not timing:
+            return res
         kern = {}
         for name, kid in (("edt_colbits", sc.K_EDT_COLBITS), ("edt_band", sc.K_EDT_BAND), ("moves", sc.K_MOVES), ("astar", sc.K_ASTAR),
                           ("gather", sc.K_GATHER), ("toppra", sc.K_TOPPRA), ("toppra_sample", sc.K_TOPPRA_SAMPLE)):
@@ -231,16 +288,13 @@ def main():
         ln = out["len"].cpu().numpy()
         astar_ms = kern["astar"]["ms_per_launch_on_context0"]
         lastk = G - 1
-        res = dict(value=Qtot * steps / dt, ms_per_step=1e3 * dt / steps, host_enqueue_ms_per_step=1e3 * t_enq / steps, kernels=kern,
-                   repeats=len(dts), value_min=Qtot * steps / max(dts), value_max=Qtot * steps / min(dts),
-                   ms_per_region=[1e3 * d for d in dts],
+        res.update(kernels=kern,
                    astar={"expansions_per_step_rank0": expansions,
                           "launch_ms_on_context0": astar_ms,
                           "expansions_per_s_whole_job": expansions * world * steps / dt,
                           "algorithmic_GBps_whole_job": 104 * expansions * world * steps / dt / 1e9,
                           "found": int((st == 0).sum()), "no_path": int((st == 1).sum()), "ring_overflow": int((st == 4).sum()),
                           "mean_path_len": float(ln[st == 0].mean()) if (st == 0).any() else 0.0},
-                   steps=steps, group=G,
                    _host=dict(occ=occ_h, s=s_h, g=g_h, out=out, st=st, d2=d2s[0][0], gath=gath[0],
                               lastk=lastk, occ_last=occ_hs[lastk], s_last=sg[lastk][0], g_last=sg[lastk][1], out_last=view(outs[0], lastk)))
         if with_toppra:
@@ -251,7 +305,42 @@ def main():
     if args.group <= 0:
         args.group = max(g for g in range(1, 33) if args.steps % g == 0)
     assert (args.group * Qtot) % world == 0
-    main_run = run_map(args.map, args.steps, args.warmup, depth_max, group=args.group, repeats=args.repeats)
+    main_run = run_map(args.map, args.steps, args.warmup, depth_max, group=args.group, repeats=args.repeats, timing=args.full)
+    if args.dump_outputs and rank == 0:
+        ls = main_run["last_step"]
+        dump_outputs(args.dump_outputs, ls["d2"], ls["out"], ls["gath"], args.lmax,
+                     gathered_rows=[(r * main_run["group"] + main_run["group"] - 1) * Qloc for r in range(world)], Qloc=Qloc)
+    result = None
+    if rank == 0:
+        result = {
+            "metric": "plans/sec (batched start-goal, 1024^2 grid)", "value": main_run["value"], "unit": "plans/s",
+            "n_gpus": world, "steps": main_run["steps"], "warmup": args.warmup, "ms_per_step": main_run["ms_per_step"],
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "int32", "data": "synthetic",
+            "repeats": main_run["repeats"], "value_is": "median over the repeats of the timed K-step region",
+            "value_min": main_run["value_min"], "value_max": main_run["value_max"], "ms_per_region": main_run["ms_per_region"],
+            "config": {"workload": f"{W}x{H} random-obstacle grids ({args.map}, one grid and one query block per step), EDT + A*, {Qloc} batched "
+                                   f"queries per GPU and step, {main_run['group']} steps = {main_run['group'] * Qloc} queries per library call"
+                                   + (", RCCL all-gather of paths" if use_gather else ""),
+                       "queries_per_launch": main_run["group"] * Qloc,
+                       "grid": [W, H], "map": args.map, "queries_per_gpu": Qloc, "queries_total": Qtot, "lmax": args.lmax,
+                       "parallelism": f"query-sharded x{world}", "contexts_in_flight": depth_max, "steps_per_call": main_run["group"],
+                       "hw_queues": os.environ.get("GPU_MAX_HW_QUEUES", "runtime default")},
+            "host_enqueue_ms_per_step": main_run["host_enqueue_ms_per_step"],
+        }
+
+    def finish():
+        if rank == 0:
+            print(json.dumps(result))
+        for c in ctxs:
+            c.close()
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+
+    if not args.full:
+        finish()
+        return
+
     seq_run = run_map(args.map, max(2, min(args.steps, 4)), 1, 1, repeats=args.repeats)   # one call per step, one stream
     qst = ctx.astar_debug_stats(Qloc)            # of seq_run's last call: expansions, popped entries, kilo-cycles, steps per query
     kc = np.sort(qst[2].astype(np.float64))
@@ -314,25 +403,11 @@ def main():
                        "paths_checked": "own block (first step cell for cell, last step sampled)" + (f"; {checked_other} queries of rank {(rank + 1) % world}'s block replanned here and compared" if world > 1 else ""),
                        "consistent_on_all_ranks": True}
 
-    result = None
     if rank == 0:
-        result = {
-            "metric": "plans/sec (batched start-goal, 1024^2 grid)", "value": main_run["value"], "unit": "plans/s",
-            "n_gpus": world, "steps": main_run["steps"], "warmup": args.warmup, "ms_per_step": main_run["ms_per_step"],
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "int32", "data": "synthetic",
-            "repeats": main_run["repeats"], "value_is": "median over the repeats of the timed K-step region",
-            "value_min": main_run["value_min"], "value_max": main_run["value_max"], "ms_per_region": main_run["ms_per_region"],
-            "config": {"workload": f"{W}x{H} random-obstacle grids ({args.map}, one grid and one query block per step), EDT + A*, {Qloc} batched "
-                                   f"queries per GPU and step, {main_run['group']} steps = {main_run['group'] * Qloc} queries per library call"
-                                   + (", RCCL all-gather of paths" if use_gather else ""),
-                       "queries_per_launch": main_run["group"] * Qloc,
-                       "grid": [W, H], "map": args.map, "queries_per_gpu": Qloc, "queries_total": Qtot, "lmax": args.lmax,
-                       "parallelism": f"query-sharded x{world}", "contexts_in_flight": depth_max, "steps_per_call": main_run["group"],
-                       "hw_queues": os.environ.get("GPU_MAX_HW_QUEUES", "runtime default")},
+        result.update({
             "value_depth1": seq_run["value"], "ms_per_step_depth1": seq_run["ms_per_step"],
             "value_depth1_is": f"one library call per step ({Qloc} queries per launch) on one stream: what BASELINE configs[1] literally describes",
             "per_query_depth1": per_query,
-            "host_enqueue_ms_per_step": main_run["host_enqueue_ms_per_step"],
             "kernels": main_run["kernels"], "astar": main_run["astar"],
             "other_maps": {f: {"value": r["value"], "ms_per_step": r["ms_per_step"],
                                "expansions_per_step_rank0": r["astar"]["expansions_per_step_rank0"]} for f, r in others.items()},
@@ -340,7 +415,7 @@ def main():
                          "value": cfg2["value"], "ms_per_step": cfg2["ms_per_step"], "toppra_ok": cfg2.get("toppra_ok"),
                          "toppra_plans_per_call": cfg2.get("toppra_plans_per_call"),
                          "note": "the plans of a call's steps are handed over in one sc_toppra_hermite_batch call, as its queries are in one sc_astar_batch_multi call; toppra_ok counts the whole call"},
-        }
+        })
         if gather_info:
             result["gather"] = gather_info
 
@@ -689,13 +764,7 @@ def main():
                                   "single_thread_value": 128 / (t_edt * 128 / Qloc + t_1),
                                   "gpu_matches_cpu_on_sample": ok,
                                   "gpu_matches_cpu_on_step": {"step_of_the_call": hl["lastk"], "matches": ok_last}}
-    if rank == 0:
-        print(json.dumps(result))
-    for c in ctxs:
-        c.close()
-    if dist is not None:
-        dist.barrier()
-        dist.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

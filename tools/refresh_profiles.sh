@@ -7,13 +7,13 @@ R=$PWD
 O=$R/gpurun_out/prof
 rm -rf $O && mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-timeout -k 5 400 python3 $R/bench.py > $O/bench_default.json 2> $O/bench_default.err
+timeout -k 5 400 python3 $R/bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 echo bench done
-SC_BENCH_FORCE_DIST=1 timeout -k 5 300 python3 $R/bench.py --no-cpu-baseline --replan-frames 0 > $O/bench_forced_dist.json 2> $O/bench_forced_dist.err
+SC_BENCH_FORCE_DIST=1 timeout -k 5 300 python3 $R/bench.py --full --no-cpu-baseline --replan-frames 0 > $O/bench_forced_dist.json 2> $O/bench_forced_dist.err
 echo forced-dist bench done
-timeout -k 5 200 python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --only-main-map --replan-frames 0 > $O/bench_steps20.json 2> $O/bench_steps20.err
+timeout -k 5 200 python3 $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --only-main-map --replan-frames 0 > $O/bench_steps20.json 2> $O/bench_steps20.err
 echo 20-step bench done
-timeout -k 5 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_stats -o b -- python3 $R/bench.py --steps 16 --warmup 16 --no-cpu-baseline --repeats 2 > $O/bench_stats.log 2>&1
+timeout -k 5 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_stats -o b -- python3 $R/bench.py --full --steps 16 --warmup 16 --no-cpu-baseline --repeats 2 > $O/bench_stats.log 2>&1
 echo bench stats done
 for cfg in "1024 64 salt20" "1024 64 blocks" "1024 64 salt05" "4096 4 salt20" "4096 4 blocks" "4096 16 salt20"; do
     set -- $cfg
