@@ -48,8 +48,9 @@ typedef enum {
     SC_Q_NO_PATH = 1,
     SC_Q_BAD_ENDPOINT = 2, /* start/goal out of range or not traversable */
     SC_Q_TRUNCATED = 3,    /* path longer than Lmax: len holds the needed length, path is unspecified */
-    SC_Q_RING_OVERFLOW = 4 /* the search's frontier outgrew the device queues twice (16x the usual space on the second
-                            * attempt); no result for this query.  sc_ctx_synchronize enlarges the queues of later calls */
+    SC_Q_RING_OVERFLOW = 4, /* the search's frontier outgrew the device queues twice (16x the usual space on the second
+                             * attempt); no result for this query.  sc_ctx_synchronize enlarges the queues of later calls */
+    SC_Q_BAD_PATH = 5       /* sc_path_waypoints_batch: the input path is not a legal A* move sequence */
 } sc_query_status;
 
 /* kernels timed by sc_ctx_set_timing (indices for sc_ctx_get_timing) */
@@ -67,7 +68,8 @@ typedef enum {
     SC_K_NEAREST = 10,    /* nearest obstacle cell from d2 */
     SC_K_FMT = 11,        /* FMT* over Halton samples (the reference's own planner), one wavefront per query */
     SC_K_GATHER = 12,     /* gather of result paths: pack, ncclAllGather, unpack */
-    SC_K_COUNT = 13
+    SC_K_WAYPOINTS = 13,  /* A* cell paths -> line-of-sight waypoints, one wavefront per path */
+    SC_K_COUNT = 14
 } sc_kernel_id;
 
 #define SC_EDT_INF INT32_MAX /* d2 of every cell of a grid without obstacles */
@@ -165,6 +167,34 @@ int sc_astar_debug_peek(sc_ctx* ctx, int32_t* out16);
  * expanded -- E = {n : g*(n) + h(n) <= C*}, all that paths and parents are read from -- and 0xFFFFFFFF elsewhere. */
 int sc_astar_gfield(sc_ctx* ctx, const int32_t* d2, int W, int H, int32_t r2_clear,
                     int32_t start, int32_t goal, uint32_t* gfield, int32_t* cost, int32_t* status);
+
+/* ---- line-of-sight waypoints of A* paths ---------------------------------------------------------------
+ * Shortcuts every cell path of sc_astar_batch to the cells where it has to turn, the short waypoint list the
+ * reference's planner hands to from_path (examples/test.cpp:284 -> :300).  Cells are integer points (x, y), index
+ * y*W + x; T(c) <=> d2[c] >= max(r2_clear, 1) (the rule of sc_moves_i32_u8 and A*).
+ *   Visible(a, b): every cell whose CLOSED unit square meets the closed segment between the centres of a and b is
+ *     traversable (the segment's supercover; through a cell corner it needs both side cells: A*'s no-corner-cutting
+ *     rule).  Exact integer arithmetic.
+ *   Greedy prefix shortcut: out = [p0], anchor a = 0; j = the largest index with Visible(p[a], p[k]) for every k in
+ *     a+1..j; emit p[j]; stop at j = L-1, else a = j and repeat.
+ *   Collinear merge, as points are emitted: before w is appended, the last output point b is dropped while
+ *     out[-2], b, w are collinear in the same direction (cross = 0, dot > 0).
+ *   Reverse rule: if out[-2], p[a], p[j] are collinear in the reverse direction (cross = 0, dot < 0), j is lowered
+ *     (not below a+1) until they are not.  A defined treatment: it fires on no A* path of the tests.
+ *   So no interior waypoint is collinear with its neighbours, every output leg is Visible, and the output is a
+ *   subsequence of the path from its first to its last cell.  All integers: bit-exact.
+ * Inputs: d2 int32 [H][W]; path int32 [Q][Lmax], len [Q] and astar_status [Q] (may be NULL) as sc_astar_batch writes
+ * them, so the device form chains on the stream.  Outputs: wp int32 [Q][Wmax] (cell indices, start..goal), n_wp and
+ * status int32 [Q]:
+ *   SC_Q_OK; the input status passed through with n_wp = 0 when astar_status[q] != SC_Q_OK; SC_Q_TRUNCATED with n_wp
+ *   = the count needed when Wmax is too small (wp then holds the first Wmax points); SC_Q_BAD_PATH with n_wp = 0 when
+ *   len is outside 1..Lmax, a cell is outside the grid, consecutive cells are not 8-adjacent or not Visible, or the
+ *   only cell of a len-1 path is not traversable.
+ * Scratch: Q * (Lmax - Wmax) int32 when Wmax < Lmax. */
+int sc_path_waypoints_batch(sc_ctx* ctx, const int32_t* d2, int W, int H, int32_t r2_clear, const int32_t* path, const int32_t* len,
+                            const int32_t* astar_status, int Q, int Lmax, int Wmax, int32_t* wp, int32_t* n_wp, int32_t* status);
+int sc_path_waypoints_batch_host(sc_ctx* ctx, const int32_t* d2, int W, int H, int32_t r2_clear, const int32_t* path, const int32_t* len,
+                                 const int32_t* astar_status, int Q, int Lmax, int Wmax, int32_t* wp, int32_t* n_wp, int32_t* status);
 
 /* ---- batched TOPP-RA ---------------------------------------------------
  * P independent plans; path of plan p is the 2-knot cubic Hermite spline the

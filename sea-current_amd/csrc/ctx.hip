@@ -50,7 +50,7 @@ extern "C" int sc_ctx_destroy(sc_ctx* ctx) {
     for (auto e : ctx->ev_pool) (void)hipEventDestroy(e);
     if (ctx->wait_ev) (void)hipEventDestroy(ctx->wait_ev);
     free_scratch(&ctx->colbits); free_scratch(&ctx->updown); free_scratch(&ctx->edt_fault); free_scratch(&ctx->fmt_nbr); free_scratch(&ctx->edt_flags); free_scratch(&ctx->moves); free_scratch(&ctx->gslots);
-    free_scratch(&ctx->buckets); free_scratch(&ctx->qstats); free_scratch(&ctx->closed); free_scratch(&ctx->actr); free_scratch(&ctx->bez_tang); free_scratch(&ctx->bez_gl); free_scratch(&ctx->bez_seginfo); free_scratch(&ctx->cheb_a); free_scratch(&ctx->gather_msg);
+    free_scratch(&ctx->buckets); free_scratch(&ctx->qstats); free_scratch(&ctx->closed); free_scratch(&ctx->actr); free_scratch(&ctx->bez_tang); free_scratch(&ctx->bez_gl); free_scratch(&ctx->bez_seginfo); free_scratch(&ctx->cheb_a); free_scratch(&ctx->gather_msg); free_scratch(&ctx->wp_spill);
     for (auto& s : ctx->staging) free_scratch(&s);
     (void)hipStreamDestroy(ctx->own_stream);
     delete ctx;
@@ -129,7 +129,7 @@ int sc_scratch_reserve(sc_ctx* ctx, sc_scratch* s, size_t bytes) {
 extern "C" int sc_ctx_scratch_bytes(sc_ctx* ctx, int64_t* bytes) {
     if (!ctx || !bytes) return SC_ERR_INVALID;
     size_t b = ctx->colbits.bytes + ctx->updown.bytes + ctx->edt_fault.bytes + ctx->edt_flags.bytes + ctx->moves.bytes + ctx->gslots.bytes + ctx->closed.bytes + ctx->buckets.bytes +
-               ctx->qstats.bytes + ctx->actr.bytes + ctx->bez_tang.bytes + ctx->bez_gl.bytes + ctx->bez_seginfo.bytes + ctx->cheb_a.bytes + ctx->gather_msg.bytes + ctx->fmt_nbr.bytes;
+               ctx->qstats.bytes + ctx->actr.bytes + ctx->bez_tang.bytes + ctx->bez_gl.bytes + ctx->bez_seginfo.bytes + ctx->cheb_a.bytes + ctx->gather_msg.bytes + ctx->fmt_nbr.bytes + ctx->wp_spill.bytes;
     for (auto& s : ctx->staging) b += s.bytes;
     *bytes = (int64_t)b;
     return SC_OK;
@@ -249,6 +249,33 @@ extern "C" int sc_astar_batch_host(sc_ctx* ctx, const int32_t* d2, int W, int H,
                            (int32_t*)ctx->staging[4].p, (int32_t*)ctx->staging[5].p, (int32_t*)ctx->staging[6].p);
     if (r != SC_OK) return r;
     D2H(path, 3, (size_t)Q * Lmax * 4); D2H(len, 4, (size_t)Q * 4); D2H(cost, 5, (size_t)Q * 4); D2H(status, 6, (size_t)Q * 4);
+    return sc_ctx_synchronize(ctx);
+}
+
+extern "C" int sc_path_waypoints_batch_host(sc_ctx* ctx, const int32_t* d2, int W, int H, int32_t r2_clear, const int32_t* path,
+                                            const int32_t* len, const int32_t* astar_status, int Q, int Lmax, int Wmax, int32_t* wp,
+                                            int32_t* n_wp, int32_t* status) {
+    if (!ctx || !d2 || !path || !len || !wp || !n_wp || !status || W <= 0 || H <= 0 || Q < 0 || Lmax <= 0 || Wmax <= 0)
+        return SC_ERR_INVALID;
+    if (Q == 0) return SC_OK;
+    SC_HIP(ctx, hipSetDevice(ctx->device));
+    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t n = (size_t)W * H, qb = al((size_t)Q * 4);
+    const size_t o_d2 = 0, o_p = al(n * 4), o_len = o_p + al((size_t)Q * Lmax * 4), o_as = o_len + qb, o_wp = o_as + qb,
+                 o_n = o_wp + al((size_t)Q * Wmax * 4), o_st = o_n + qb, total = o_st + qb;
+    STAGE(8, total);
+    char* b = (char*)ctx->staging[8].p;
+    SC_HIP(ctx, hipMemcpyAsync(b + o_d2, d2, n * 4, hipMemcpyHostToDevice, ctx->stream));
+    SC_HIP(ctx, hipMemcpyAsync(b + o_p, path, (size_t)Q * Lmax * 4, hipMemcpyHostToDevice, ctx->stream));
+    SC_HIP(ctx, hipMemcpyAsync(b + o_len, len, (size_t)Q * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (astar_status) SC_HIP(ctx, hipMemcpyAsync(b + o_as, astar_status, (size_t)Q * 4, hipMemcpyHostToDevice, ctx->stream));
+    int r = sc_path_waypoints_batch(ctx, (const int32_t*)(b + o_d2), W, H, r2_clear, (const int32_t*)(b + o_p), (const int32_t*)(b + o_len),
+                                    astar_status ? (const int32_t*)(b + o_as) : nullptr, Q, Lmax, Wmax, (int32_t*)(b + o_wp),
+                                    (int32_t*)(b + o_n), (int32_t*)(b + o_st));
+    if (r != SC_OK) return r;
+    SC_HIP(ctx, hipMemcpyAsync(wp, b + o_wp, (size_t)Q * Wmax * 4, hipMemcpyDeviceToHost, ctx->stream));
+    SC_HIP(ctx, hipMemcpyAsync(n_wp, b + o_n, (size_t)Q * 4, hipMemcpyDeviceToHost, ctx->stream));
+    SC_HIP(ctx, hipMemcpyAsync(status, b + o_st, (size_t)Q * 4, hipMemcpyDeviceToHost, ctx->stream));
     return sc_ctx_synchronize(ctx);
 }
 

@@ -45,7 +45,8 @@ struct sc_ctx {
     sc_scratch cheb_a;      // chebfit: double [rows][degree + 1], the [T | y] matrices of a batch
     sc_scratch fmt_nbr;     // FMT*: uint16 [n][256] samples in range of every sample | int32 count [n] | int32 overflow
     sc_scratch gather_msg;  // gather: this rank's message, every rank's messages, local offsets
-    sc_scratch staging[8];  // _host wrappers
+    sc_scratch wp_spill;    // waypoints: int32 [Q][Lmax - Wmax] output points past Wmax (needed count of a truncated path)
+    sc_scratch staging[9];  // _host wrappers
     int astar_cap = 1 << 16;          // ring entries per bucket (power of two)
     size_t astar_slot_budget = (size_t)96 << 30;  // bytes of g + bitmap + ring scratch this context may take (SC_ASTAR_SLOT_GB), further bounded by what the device has free; 4096^2: 96 GiB = 1966 slots measured best (48: -34 %, 160: -17 %)
     int last_Q = 0;

@@ -18,8 +18,9 @@ LIB_PATH = os.environ.get("SC_LIB_PATH") or os.path.join(NATIVE_DIR, "libsea_cur
 HEADER_PATH = os.path.join(REPO_ROOT, "include", "sea_current_hip.h")
 
 EDT_INF = 2**31 - 1
-Q_OK, Q_NO_PATH, Q_BAD_ENDPOINT, Q_TRUNCATED, Q_RING_OVERFLOW = 0, 1, 2, 3, 4
+Q_OK, Q_NO_PATH, Q_BAD_ENDPOINT, Q_TRUNCATED, Q_RING_OVERFLOW, Q_BAD_PATH = 0, 1, 2, 3, 4, 5
 K_EDT_COLBITS, K_EDT_BAND, K_MOVES, K_ASTAR, K_TOPPRA, K_TOPPRA_SAMPLE, K_BEZIER, K_ARCLENGTH, K_RESAMPLE, K_OCC, K_NEAREST, K_FMT, K_GATHER = range(13)
+K_WAYPOINTS = 13
 
 _lib = None
 
@@ -60,6 +61,8 @@ _SIGNATURES = {
     "sc_astar_debug_stats": (_i, [_vp, _vp, _i]),
     "sc_astar_debug_peek": (_i, [_vp, _vp]),
     "sc_astar_gfield": (_i, [_vp, _vp, _i, _i, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp]),
+    "sc_path_waypoints_batch": (_i, [_vp, _vp, _i, _i, C.c_int32, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "sc_path_waypoints_batch_host": (_i, [_vp, _vp, _i, _i, C.c_int32, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "sc_toppra_hermite_batch": (_i, [_vp, _i, _i, _i] + [_vp] * 6 + [_i, _vp, _vp, _d, _d] + [_vp] * 5),
     "sc_toppra_hermite_batch_host": (_i, [_vp, _i, _i, _i] + [_vp] * 6 + [_i, _vp, _vp, _d, _d] + [_vp] * 5),
     "sc_toppra_sample_batch": (_i, [_vp, _i, _i, _i] + [_vp] * 6 + [_d, _i] + [_vp] * 5),
@@ -231,6 +234,24 @@ class Context:
                        cost=torch.empty(Q, dtype=torch.int32, device=dev), status=torch.empty(Q, dtype=torch.int32, device=dev))
         self._ck(self._l.sc_astar_batch_multi(self._h, _ptr(d2), G, _ptr(qgrid), W, H, r2, _ptr(start), _ptr(goal), Q, Lmax,
                                               _ptr(out["path"]), _ptr(out["len"]), _ptr(out["cost"]), _ptr(out["status"])), "sc_astar_batch_multi")
+        return out
+
+    def path_waypoints(self, d2, res, r2=0, Wmax=None, out=None):
+        """Line-of-sight waypoints of astar_batch's paths (sc_path_waypoints_batch).  d2 int32 [H,W] and `res` (the dict
+        astar_batch returned, same r2) on the GPU; Wmax defaults to its Lmax.  Returns dict(wp int32 [Q,Wmax] cell indices,
+        n int32 [Q], status int32 [Q]) as GPU tensors."""
+        import torch
+        H, W = d2.shape
+        Q, Lmax = res["path"].shape
+        if Wmax is None:
+            Wmax = Lmax
+        dev = d2.device
+        if out is None:
+            out = dict(wp=torch.empty((Q, Wmax), dtype=torch.int32, device=dev), n=torch.empty(Q, dtype=torch.int32, device=dev),
+                       status=torch.empty(Q, dtype=torch.int32, device=dev))
+        st = res.get("status")
+        self._ck(self._l.sc_path_waypoints_batch(self._h, _ptr(d2), W, H, r2, _ptr(res["path"]), _ptr(res["len"]), _ptr(st), Q, Lmax, Wmax,
+                                                 _ptr(out["wp"]), _ptr(out["n"]), _ptr(out["status"])), "sc_path_waypoints_batch")
         return out
 
     # ---- multi-GPU gather (RCCL through the C ABI) ----
@@ -482,4 +503,18 @@ class Context:
         self._ck(self._l.sc_astar_batch_host(self._h, _ptr(d2), W, H, r2, _ptr(start), _ptr(goal), Q, Lmax,
                                              _ptr(out["path"]), _ptr(out["len"]), _ptr(out["cost"]),
                                              _ptr(out["status"])), "sc_astar_batch_host")
+        return out
+
+    def path_waypoints_host(self, d2, path, lens, status=None, r2=0, Wmax=None):
+        """Host form of path_waypoints (numpy in, numpy out): path int32 [Q,Lmax], lens / status int32 [Q] (status may be None)."""
+        d2 = np.ascontiguousarray(d2, dtype=np.int32)
+        path = np.ascontiguousarray(path, dtype=np.int32)
+        lens = np.ascontiguousarray(lens, dtype=np.int32)
+        status = None if status is None else np.ascontiguousarray(status, dtype=np.int32)
+        H, W = d2.shape
+        Q, Lmax = path.shape
+        Wmax = Lmax if Wmax is None else Wmax
+        out = dict(wp=np.full((Q, Wmax), -1, dtype=np.int32), n=np.zeros(Q, np.int32), status=np.zeros(Q, np.int32))
+        self._ck(self._l.sc_path_waypoints_batch_host(self._h, _ptr(d2), W, H, r2, _ptr(path), _ptr(lens), _ptr(status), Q, Lmax, Wmax,
+                                                      _ptr(out["wp"]), _ptr(out["n"]), _ptr(out["status"])), "sc_path_waypoints_batch_host")
         return out

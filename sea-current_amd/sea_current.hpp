@@ -20,6 +20,7 @@
 //   vel_lim_func                       :1175              same shape
 //   gen_vel_prof<N>                    :1191-1265         same argument order (END before START), GPU TOPP-RA
 //   (new) occupancy_grid, planning_space::plan_batch, gen_vel_prof_batch: the batched entry points
+//   (new) occupancy_grid::waypoints_batch, planning_space::simplify_paths: A* cell paths -> line-of-sight waypoints
 //
 // Differences that are deliberate: obstacle::closed is initialised (the reference leaves it
 // uninitialised, :197); library code never prints or calls std::exit (SC_ASSERT throws in DEBUG);
@@ -377,6 +378,25 @@ public:
                                       r.path.data(), r.len.data(), r.cost.data(), r.status.data()), "sc_astar_batch_host");
         return r;
     }
+    struct waypoint_result {
+        std::vector<int32_t> wp, n, status;  // wp is [Q][Wmax] cell indices, start..goal; n / status [Q]
+        int Wmax = 0;
+    };
+    // Line-of-sight waypoints of astar_batch's paths (sc_path_waypoints_batch, same r2_clear): every cell path shortened to
+    // the cells where it has to turn, each leg a straight segment whose cells (supercover) are all traversable, no interior
+    // waypoint collinear with its neighbours.  Wmax = the batch's Lmax, so no path is truncated.
+    waypoint_result waypoints_batch(const batch_result& br, int32_t r2_clear = 0, gpu_context& ctx = default_context()) {
+        if (d2.size() != occ.size()) edt(ctx);
+        waypoint_result r;
+        const int Q = (int)br.len.size();
+        r.Wmax = br.Lmax;
+        r.wp.assign((size_t)Q * r.Wmax, -1); r.n.assign(Q, 0); r.status.assign(Q, SC_Q_NO_PATH);
+        if (Q == 0) return r;
+        ctx.check(sc_path_waypoints_batch_host(ctx.get(), d2.data(), W, H, r2_clear, br.path.data(), br.len.data(), br.status.data(), Q,
+                                               br.Lmax, r.Wmax, r.wp.data(), r.n.data(), r.status.data()),
+                  "sc_path_waypoints_batch_host");
+        return r;
+    }
 };
 
 // ---- planning_space (sea_current.hpp:298-319, 1272-1407) --------------------------------------------
@@ -436,6 +456,15 @@ public:
     halton_state y_state;
     int grid_cells = 256;       // cells along the longer side of bound_rect (new knob)
     float clearance = 0.0f;     // required obstacle clearance in world units (new knob)
+    // (new knob) plan_batch / fast_marching_trees return the exact start, the centres of the path's line-of-sight waypoints
+    // (occupancy_grid::waypoints_batch) and the exact goal instead of every cell centre: the short, non-collinear list the
+    // reference's planner hands to bezier_spline::from_path (examples/test.cpp:284 -> :300).  Limits:
+    //   - clearance 0: the guarantee is visibility on the grid only.  Polygon edges are rasterised by sampling, so a long
+    //     leg can graze an edge that missed a corner cell.
+    //   - clearance >= 1.5 cells (r2 >= 3): a free cell that an edge only grazed borders a marked cell, so its d2 <= 2 and it
+    //     is not traversable; legs should then also clear the polygons (cost() < FLT_MAX).  An argument, not a proof; the
+    //     tests check it with cost() on their worlds.
+    bool simplify_paths = false;
 
     planning_space(const bounding_rect& br) : bound_rect(br) {}
 
@@ -555,14 +584,21 @@ public:
         std::vector<int32_t> s(starts.size()), t(goals.size());
         for (size_t i = 0; i < starts.size(); ++i) { s[i] = g.cell_of(starts[i]); t[i] = g.cell_of(goals[i]); }
         const float cc = clearance / g.resolution;
-        auto br = g.astar_batch(s, t, (int32_t)std::ceil(cc * cc), 0, ctx);
+        const int32_t r2 = (int32_t)std::ceil(cc * cc);
+        auto br = g.astar_batch(s, t, r2, 0, ctx);
+        occupancy_grid::waypoint_result wr;
+        if (simplify_paths) wr = g.waypoints_batch(br, r2, ctx);
         std::vector<std::optional<std::vector<Vector2f>>> out(starts.size());
         for (size_t q = 0; q < starts.size(); ++q) {
             if (br.status[q] != SC_Q_OK) continue;
+            if (simplify_paths && wr.status[q] != SC_Q_OK)
+                throw std::runtime_error("planning_space::plan_batch: waypoints of an A* path: status " + std::to_string(wr.status[q]));
+            const int32_t* cells = simplify_paths ? &wr.wp[(size_t)q * wr.Wmax] : &br.path[(size_t)q * br.Lmax];
+            const int n = simplify_paths ? wr.n[q] : br.len[q];
             std::vector<Vector2f> wp;
-            wp.reserve(br.len[q] + 2);
+            wp.reserve(n + 2);
             wp.push_back(starts[q]);
-            for (int i = 1; i + 1 < br.len[q]; ++i) wp.push_back(g.centre_of(br.path[(size_t)q * br.Lmax + i]));
+            for (int i = 1; i + 1 < n; ++i) wp.push_back(g.centre_of(cells[i]));
             wp.push_back(goals[q]);
             out[q] = std::move(wp);
         }
