@@ -69,7 +69,9 @@ typedef enum {
     SC_K_FMT = 11,        /* FMT* over Halton samples (the reference's own planner), one wavefront per query */
     SC_K_GATHER = 12,     /* gather of result paths: pack, ncclAllGather, unpack */
     SC_K_WAYPOINTS = 13,  /* A* cell paths -> line-of-sight waypoints, one wavefront per path */
-    SC_K_COUNT = 14
+    SC_K_SMOOTH = 14,     /* sc_smooth_paths_batch's own kernels (checks, scans, compaction, TOPP-RA inputs, ang_vel) and
+                           * sc_cells_to_points_batch; the library kernels it runs keep their own ids */
+    SC_K_COUNT = 15
 } sc_kernel_id;
 
 #define SC_EDT_INF INT32_MAX /* d2 of every cell of a grid without obstacles */
@@ -294,6 +296,68 @@ int sc_bezier_resample_batch(sc_ctx* ctx, const float* ctrl, const float* cum, c
 int sc_bezier_resample_batch_host(sc_ctx* ctx, const float* ctrl, const float* cum, const float* arclength, const int32_t* seg_off,
                                   int B, int S, int nsub, float* profile_pos, const int32_t* prof_off, int nudge, float* pts,
                                   float* tpar, int32_t* seg, float* curvature, int32_t* status);
+
+/* ---- the post-planner sequence in one call ---------------------------------------------------------------
+ * What the reference runs on every planned path (examples/zmq_test.cpp:66-93), for P paths at once:
+ *   from_path(path, space) -> arclength -> gen_vel_prof<1>(arclength, 0, 0, 0, limits) -> resample(nudge) -> angular velocity
+ * with the library kernels of those steps (sc_bezier_from_path_batch, sc_bezier_arclength_batch, sc_toppra_hermite_batch
+ * with vlim_per_stage = 0, the sampler of sc_toppra_sample_batch, sc_bezier_resample_batch), so every value is the one
+ * those calls give on the same inputs.  Device pointers; enqueues only: no host synchronisation, no device-to-host copy.
+ * Inputs
+ *   path float [P][n_max][2], npts int32 [P] (ragged, as sc_bezier_from_path_batch); limits fp64 [P][4] = (vel_min, vel_max,
+ *   acc_min, acc_max) of every path; start_angle (NaN = along the first leg); lines float [nlines][4] obstacle edges (may be
+ *   NULL); dt (the reference's float), N TOPP-RA stages, nsub = 1/precision sub-intervals (<= SC_RESAMPLE_MAX_NSUB);
+ *   sample_capacity: the samples the per-sample outputs have room for (<= INT32_MAX).  P <= SC_SMOOTH_MAX_PATHS.
+ * Per path
+ *   ctrl float [P*(n_max-1)][4][2] (room for every leg): path p's legs at seg_off[p] .. seg_off[p+1]-1, int32 [P+1];
+ *   arclength float [P]: the float32 sum of the legs' lengths in leg order (bezier_spline::arclength);
+ *   length int32 [P]: samples of the profile, ceil(T / dt) with T the time of the last knot the sampler keeps;
+ *   offsets int32 [P+1]: exclusive scan of length (saturated at INT32_MAX); status int32 [P] (sc_smooth_status);
+ *   needed int64 [1]: offsets[P] without saturation, the sample_capacity that holds every path.
+ * Per sample, path p's samples at offsets[p] .. offsets[p] + length[p] - 1 (what serialize_path_to_json prints):
+ *   time fp64, pos float (nudged as resample leaves it), vel, acc float, pts float [2], curvature float, ang_vel float =
+ *   vel * curvature, tpar float (curve parameter), seg int32 (leg within the path).  pos and pts are required, the
+ *   others may be NULL.
+ * Status, first that applies: SC_SMOOTH_BAD_INPUT (npts < 2, npts > n_max or a waypoint not finite; no legs),
+ *   SC_SMOOTH_NONFINITE (a control point or the arclength not finite, as the reference's tangent rule gives on float-collinear
+ *   triples), SC_SMOOTH_TOPPRA_FAILED (TOPP-RA status != 0, or a final time that is not finite), SC_SMOOTH_TRUNCATED
+ *   (offsets[p] + length[p] > sample_capacity: length holds the count, no sample of the path is written; every path after
+ *   it that has samples is truncated too), SC_SMOOTH_EMPTY_SEGMENT (resample status 1: a leg received no sample, where the
+ *   reference indexes out of range; the samples were written, pts are unspecified).  For every status but OK and
+ *   TRUNCATED length is 0; an EMPTY_SEGMENT path keeps its slot offsets[p] .. offsets[p+1]-1.  Samples past the written
+ *   ones are not touched.
+ * Launches are sized by P, P*(n_max-1) and sample_capacity; kernels read the real counts on the device.  Scratch: about
+ * P*(n_max-1)*(4 nsub + 40) + P*(40 N + 120) bytes. */
+#define SC_SMOOTH_MAX_PATHS 65536
+typedef enum {
+    SC_SMOOTH_OK = 0,
+    SC_SMOOTH_BAD_INPUT = 1,
+    SC_SMOOTH_NONFINITE = 2,
+    SC_SMOOTH_TOPPRA_FAILED = 3,
+    SC_SMOOTH_TRUNCATED = 4,
+    SC_SMOOTH_EMPTY_SEGMENT = 5
+} sc_smooth_status;
+int sc_smooth_paths_batch(sc_ctx* ctx, const float* path, const int32_t* npts, int P, int n_max, const double* limits, float start_angle,
+                          const float* lines, int nlines, float dt, int N, int nsub, int64_t sample_capacity, float* ctrl,
+                          int32_t* seg_off, float* arclength, int32_t* length, int32_t* offsets, int32_t* status, int64_t* needed,
+                          double* time, float* pos, float* vel, float* acc, float* pts, float* curvature, float* ang_vel, float* tpar,
+                          int32_t* seg);
+/* Host pointers: the same call on device copies, then the results copied back (synchronises).  sample_capacity is the
+ * room of the caller's per-sample arrays; *needed says how much a call that truncated would have needed. */
+int sc_smooth_paths_batch_host(sc_ctx* ctx, const float* path, const int32_t* npts, int P, int n_max, const double* limits,
+                               float start_angle, const float* lines, int nlines, float dt, int N, int nsub, int64_t sample_capacity,
+                               float* ctrl, int32_t* seg_off, float* arclength, int32_t* length, int32_t* offsets, int32_t* status,
+                               int64_t* needed, double* time, float* pos, float* vel, float* acc, float* pts, float* curvature,
+                               float* ang_vel, float* tpar, int32_t* seg);
+/* sc_path_waypoints_batch's cells -> the path input above, on the device: path[q][i] = the centre of cell wp[q][i] of a
+ * W-wide grid, (x_min + (c % W + 0.5) * res_x, y_min + (c / W + 0.5) * res_y) in float32 without contraction
+ * (occupancy_grid::centre_of); npts[q] = n_wp[q] when status[q] == SC_Q_OK and 1 <= n_wp[q] <= Wmax, else 0.  With starts
+ * / goals (float [Q][2], both or neither) the first and last points are the exact start and goal, as
+ * planning_space::plan_batch does: a one-cell path then becomes (start, goal), npts 2 (needs Wmax >= 2).  status may be
+ * NULL (all OK).  Points past npts[q] are not written. */
+int sc_cells_to_points_batch(sc_ctx* ctx, const int32_t* wp, const int32_t* n_wp, const int32_t* status, int Q, int Wmax, int W,
+                             float x_min, float y_min, float res_x, float res_y, const float* starts, const float* goals, float* path,
+                             int32_t* npts);
 
 /* ---- the reference's own planner, batched -----------------------------------------------
  * planning_space::fast_marching_trees (sea_current.hpp:1339-1407) with near (:1328-1337), cost (:1315-1326) and

@@ -130,9 +130,10 @@ bezier_eval_kernel(const float* __restrict__ ctrl, const int32_t* __restrict__ s
 // one wavefront per segment; gl = 32 nodes then 32 weights; cum [S][nsub+1], seg_len [S]
 __global__ void __launch_bounds__(64)
 bezier_arclength_kernel(const float* __restrict__ ctrl, int S, int nsub, const double* __restrict__ gl, float* __restrict__ cum,
-                        float* __restrict__ seg_len) {
+                        float* __restrict__ seg_len, const int32_t* __restrict__ S_dev) {
     extern __shared__ double sub[];   // [nsub] arclength of each sub-interval
     const int s = blockIdx.x, lane = threadIdx.x;
+    if (S_dev && s >= *S_dev) return;   // launched for an upper bound: the real count is on the device
     const float* c = ctrl + (size_t)s * 8;
     for (int k = lane; k < nsub; k += 64) {
         const double a = (double)k / nsub, b = (double)(k + 1) / nsub;
@@ -261,11 +262,12 @@ resample_prepare_kernel(const float* __restrict__ cum, const int32_t* __restrict
 __global__ void __launch_bounds__(256)
 resample_eval_kernel(const float* __restrict__ ctrl, const float* __restrict__ cum, int nsub, const float* __restrict__ pp_all,
                      const int32_t* __restrict__ prof_off, const int4* __restrict__ seginfo, float* __restrict__ pts,
-                     float* __restrict__ tpar, int32_t* __restrict__ seg, float* __restrict__ curv) {
+                     float* __restrict__ tpar, int32_t* __restrict__ seg, float* __restrict__ curv, const int32_t* __restrict__ S_dev) {
     extern __shared__ double A[];                 // [m][nc]
     __shared__ double coef[10];
     __shared__ double xr[2];
     const int s = blockIdx.x, tid = threadIdx.x;
+    if (S_dev && s >= *S_dev) return;
     const int4 info = seginfo[s];
     const int m = nsub + 1, deg = m < 10 ? m : 10, nc = deg + 1;
     const float* tab = cum + (size_t)s * m;
@@ -436,11 +438,11 @@ template <int RPL>
 __global__ void __launch_bounds__(256)
 resample_eval_reg_kernel(const float* __restrict__ ctrl, const float* __restrict__ cum, int nsub, int S, const float* __restrict__ pp_all,
                          const int32_t* __restrict__ prof_off, const int4* __restrict__ seginfo, float* __restrict__ pts,
-                         float* __restrict__ tpar, int32_t* __restrict__ seg, float* __restrict__ curv) {
+                         float* __restrict__ tpar, int32_t* __restrict__ seg, float* __restrict__ curv, const int32_t* __restrict__ S_dev) {
     constexpr int DEG = 10, NC = DEG + 1;
     const int lane = threadIdx.x & 63;
     const int s = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (s >= S) return;
+    if (s >= S || (S_dev && s >= *S_dev)) return;   // wave-uniform
     const int4 info = seginfo[s];
     const int m = nsub + 1;
     const float* tab = cum + (size_t)s * m;
@@ -725,6 +727,10 @@ extern "C" int sc_chebeval_batch(sc_ctx* ctx, const float* x, const int32_t* off
 
 extern "C" int sc_bezier_arclength_batch(sc_ctx* ctx, const float* ctrl, int S, int nsub, float* cum, float* seg_len) {
     if (!ctx || !ctrl || !cum || !seg_len || S <= 0 || nsub <= 0 || nsub > 4096) return SC_ERR_INVALID;
+    return sc_launch_arclength(ctx, ctrl, S, nsub, cum, seg_len, nullptr);
+}
+
+int sc_launch_arclength(sc_ctx* ctx, const float* ctrl, int S, int nsub, float* cum, float* seg_len, const int32_t* S_dev) {
     SC_HIP(ctx, hipSetDevice(ctx->device));
     if (!ctx->bez_gl.p) {
         int r = sc_scratch_reserve(ctx, &ctx->bez_gl, 64 * sizeof(double));
@@ -735,7 +741,7 @@ extern "C" int sc_bezier_arclength_batch(sc_ctx* ctx, const float* ctrl, int S, 
     }
     int tk = sc_time_begin(ctx, SC_K_ARCLENGTH);
     hipLaunchKernelGGL(bezier_arclength_kernel, dim3(S), dim3(64), (size_t)nsub * sizeof(double), ctx->stream, ctrl, S, nsub,
-                       (const double*)ctx->bez_gl.p, cum, seg_len);
+                       (const double*)ctx->bez_gl.p, cum, seg_len, S_dev);
     sc_time_end(ctx, tk);
     SC_HIP(ctx, hipGetLastError());
     return SC_OK;
@@ -747,6 +753,13 @@ extern "C" int sc_bezier_resample_batch(sc_ctx* ctx, const float* ctrl, const fl
     if (!ctx || !ctrl || !cum || !arclength || !seg_off || !profile_pos || !prof_off || !status || B <= 0 || S <= 0 || nsub <= 0 ||
         nsub > SC_RESAMPLE_MAX_NSUB)
         return SC_ERR_INVALID;
+    return sc_launch_resample(ctx, ctrl, cum, arclength, seg_off, B, S, nsub, profile_pos, prof_off, nudge, pts, tpar, seg, curvature, status,
+                              nullptr);
+}
+
+int sc_launch_resample(sc_ctx* ctx, const float* ctrl, const float* cum, const float* arclength, const int32_t* seg_off, int B, int S,
+                       int nsub, float* profile_pos, const int32_t* prof_off, int nudge, float* pts, float* tpar, int32_t* seg,
+                       float* curvature, int32_t* status, const int32_t* S_dev) {
     SC_HIP(ctx, hipSetDevice(ctx->device));
     int r = sc_scratch_reserve(ctx, &ctx->bez_seginfo, (size_t)S * sizeof(int4));
     if (r != SC_OK) return r;
@@ -758,7 +771,7 @@ extern "C" int sc_bezier_resample_batch(sc_ctx* ctx, const float* ctrl, const fl
     // tables of 10 .. 256 rows: the fit in registers, one wavefront per segment; others: the LDS form, one workgroup per segment
 #define SC_RESAMPLE_REG(RPL)                                                                                                         \
     hipLaunchKernelGGL(resample_eval_reg_kernel<RPL>, dim3((S + 3) / 4), dim3(256), 0, ctx->stream, ctrl, cum, nsub, S,               \
-                       (const float*)profile_pos, prof_off, (const int4*)seginfo, pts, tpar, seg, curvature)
+                       (const float*)profile_pos, prof_off, (const int4*)seginfo, pts, tpar, seg, curvature, S_dev)
     static const bool lds_form = getenv("SC_RESAMPLE_LDS") != nullptr;   // A/B switch: the LDS form for every table size
     const bool reg = !lds_form && m >= 10;
     if (reg && m <= 64) SC_RESAMPLE_REG(1);
@@ -767,7 +780,7 @@ extern "C" int sc_bezier_resample_batch(sc_ctx* ctx, const float* ctrl, const fl
     else if (reg && m <= 256) SC_RESAMPLE_REG(4);
     else
         hipLaunchKernelGGL(resample_eval_kernel, dim3(S), dim3(256), (size_t)m * nc * sizeof(double), ctx->stream, ctrl, cum, nsub,
-                           (const float*)profile_pos, prof_off, (const int4*)seginfo, pts, tpar, seg, curvature);
+                           (const float*)profile_pos, prof_off, (const int4*)seginfo, pts, tpar, seg, curvature, S_dev);
 #undef SC_RESAMPLE_REG
     sc_time_end(ctx, tk);
     SC_HIP(ctx, hipGetLastError());

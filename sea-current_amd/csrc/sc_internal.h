@@ -46,6 +46,12 @@ struct sc_ctx {
     sc_scratch fmt_nbr;     // FMT*: uint16 [n][256] samples in range of every sample | int32 count [n] | int32 overflow
     sc_scratch gather_msg;  // gather: this rank's message, every rank's messages, local offsets
     sc_scratch wp_spill;    // waypoints: int32 [Q][Lmax - Wmax] output points past Wmax (needed count of a truncated path)
+    sc_scratch sm_ctrl;     // smoothing: float [P][n_max-1][4][2] control points of from_path before compaction
+    sc_scratch sm_cum;      // smoothing: float [P (n_max-1)][nsub+1] arclength tables | float [P (n_max-1)] segment lengths
+    sc_scratch sm_tp;       // smoothing: fp64 TOPP-RA inputs p0 p1 v0 v1 vlo vhi alo ahi [P] | K [P][N+1][2] x t [P][N+1] u [P][N]
+    sc_scratch sm_int;      // smoothing: int32 npts [P] | TOPP-RA status [P] | resample status [P] | resample offsets [P+1]
+    sc_scratch sm_smp;      // smoothing: float vel | curvature [capacity] when the caller wants ang_vel without them
+    sc_scratch sm_stage;    // smoothing: sc_smooth_paths_batch_host's device copies
     sc_scratch staging[9];  // _host wrappers
     int astar_cap = 1 << 16;          // ring entries per bucket (power of two)
     size_t astar_slot_budget = (size_t)96 << 30;  // bytes of g + bitmap + ring scratch this context may take (SC_ASTAR_SLOT_GB), further bounded by what the device has free; 4096^2: 96 GiB = 1966 slots measured best (48: -34 %, 160: -17 %)
@@ -85,6 +91,14 @@ int sc_time_chain(sc_ctx* ctx, int token, int kid);
 // kernels' host launchers (defined in the respective .hip files)
 int sc_launch_edt(sc_ctx* ctx, const uint8_t* occ, int W, int H, int batch, int32_t* d2);
 int sc_launch_moves(sc_ctx* ctx, const int32_t* d2, int W, int Hall, int H, int32_t r2, uint8_t* moves);   // Hall / H grids of H rows, stacked
+// S_dev (may be NULL): a device count; blocks of segments at or past it exit (launches sized by an upper bound)
+int sc_launch_arclength(sc_ctx* ctx, const float* ctrl, int S, int nsub, float* cum, float* seg_len, const int32_t* S_dev);
+int sc_launch_resample(sc_ctx* ctx, const float* ctrl, const float* cum, const float* arclength, const int32_t* seg_off, int B, int S,
+                       int nsub, float* profile_pos, const int32_t* prof_off, int nudge, float* pts, float* tpar, int32_t* seg,
+                       float* curvature, int32_t* status, const int32_t* S_dev);
+int sc_launch_toppra_sample_packed(sc_ctx* ctx, int P, int dof, int N, const double* p0, const double* p1, const double* v0,
+                                   const double* v1, const double* x, const double* t, double dt, const int32_t* offsets,
+                                   const int32_t* plen, const int32_t* skip, float* pos, float* vel, float* acc, double* times);
 
 // Raise a kernel's dynamic-LDS limit (> 64 KiB needs hipFuncSetAttribute, which is per DEVICE): once per context, i.e.
 // once per device and host thread -- a process-wide flag would leave a second GPU's copy of the kernel at the default

@@ -676,6 +676,9 @@ struct sample_args {
     float *pos, *vel, *acc;
     double* times;
     int32_t* length;
+    // packed form only: plan p's samples go to offsets[p] .. offsets[p] + plen[p] - 1 (pos / vel / acc as a [dof][plen[p]]
+    // block from offsets[p] * dof), plans with skip[p] != 0 are left out; vel, acc and times may be NULL
+    const int32_t *offsets, *plen, *skip;
 };
 
 // One block (256 threads) per plan; dynamic LDS: (2 + 3 dof)(N + 1) doubles + (N + 1) 16-bit knot indices.  All threads
@@ -684,7 +687,9 @@ struct sample_args {
 // on the knot times only and are shared); then a thread takes a sample, finds its knot interval once and evaluates every
 // joint there.  The eliminations and the per-sample cubic multiply by reciprocals (one division per pivot, one per
 // sample) where the oracle divides: results agree to a few units in the last place.
+// PACKED: the same arithmetic, only the addresses of the stores differ (sc_smooth_paths_batch).
 #define TS_THREADS 256
+template <bool PACKED>
 __global__ void __launch_bounds__(TS_THREADS) toppra_sample_kernel(sample_args a) {
     extern __shared__ __align__(16) double sm[];
     const int N = a.N, n1 = N + 1, dof = a.dof;
@@ -696,6 +701,7 @@ __global__ void __launch_bounds__(TS_THREADS) toppra_sample_kernel(sample_args a
     unsigned short* idx = reinterpret_cast<unsigned short*>(dp + (size_t)dof * n1);   // [n1] stage of each knot
     __shared__ int s_cnt[TS_THREADS / 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, p = blockIdx.x;
+    if (PACKED && a.skip[p] != 0) return;   // block-uniform, before the first barrier
     const double* t = a.t + (size_t)p * n1;
     const double* x = a.x + (size_t)p * n1;
     // knots with a (nearly) zero time increment are dropped, as parametrizer::Spline does
@@ -770,11 +776,13 @@ __global__ void __launch_bounds__(TS_THREADS) toppra_sample_kernel(sample_args a
     __syncthreads();
     const double T = tk[n - 1];
     const int length = (int)ceil(T / a.dt);
-    const int wl = min(length, a.max_len);
-    if (tid == 0) a.length[p] = length;
+    const int wl = min(length, PACKED ? a.plen[p] : a.max_len);
+    if (!PACKED && tid == 0) a.length[p] = length;
+    const size_t obase = PACKED ? (size_t)a.offsets[p] : 0;
     for (int j = tid; j < wl; j += TS_THREADS) {
         const double tt = length > 1 ? (j == length - 1 ? T : (T * j) / (length - 1)) : 0.0;
-        a.times[(size_t)p * a.max_len + j] = tt;
+        if (!PACKED) a.times[(size_t)p * a.max_len + j] = tt;
+        else if (a.times) a.times[obase + j] = tt;
         int seg = 0;
         if (n > 1) {
             // largest seg with tk[seg] < tt (seg = 0 if none), capped at n-2
@@ -800,8 +808,15 @@ __global__ void __launch_bounds__(TS_THREADS) toppra_sample_kernel(sample_args a
                 V_ = (m1 * bb * bb - m0 * aa * aa) * i2h - ca + cb;
                 A_ = (m0 * aa + m1 * bb) * ih;
             }
-            const size_t o = ((size_t)p * dof + k) * a.max_len + j;
-            a.pos[o] = (float)P_; a.vel[o] = (float)V_; a.acc[o] = (float)A_;
+            if (!PACKED) {
+                const size_t o = ((size_t)p * dof + k) * a.max_len + j;
+                a.pos[o] = (float)P_; a.vel[o] = (float)V_; a.acc[o] = (float)A_;
+            } else {
+                const size_t o = obase * dof + (size_t)k * wl + j;
+                a.pos[o] = (float)P_;
+                if (a.vel) a.vel[o] = (float)V_;
+                if (a.acc) a.acc[o] = (float)A_;
+            }
         }
     }
 }
@@ -814,15 +829,38 @@ extern "C" int sc_toppra_sample_batch(sc_ctx* ctx, int P, int dof, int N,
         !x || !t || !pos || !vel || !acc || !times || !length)
         return SC_ERR_INVALID;
     SC_HIP(ctx, hipSetDevice(ctx->device));
-    sample_args a{P, dof, N, max_len, p0, p1, v0, v1, x, t, dt, pos, vel, acc, times, length};
+    sample_args a{P, dof, N, max_len, p0, p1, v0, v1, x, t, dt, pos, vel, acc, times, length, nullptr, nullptr, nullptr};
     const size_t lds = (size_t)(2 + 3 * dof) * (N + 1) * sizeof(double) + (((size_t)(N + 1) * 2 + 15) & ~(size_t)15);
     if (lds > 140 * 1024) { snprintf(ctx->err, sizeof(ctx->err), "sc_toppra_sample_batch: (2 + 3 dof)(N + 1) doubles exceed the LDS of a CU"); return SC_ERR_INVALID; }
     {
-        int r_ = sc_allow_big_lds(ctx, reinterpret_cast<const void*>(toppra_sample_kernel), 140 * 1024);
+        int r_ = sc_allow_big_lds(ctx, reinterpret_cast<const void*>(toppra_sample_kernel<false>), 140 * 1024);
         if (r_ != SC_OK) return r_;
     }
     int tk = sc_time_begin(ctx, SC_K_TOPPRA_SAMPLE);
-    hipLaunchKernelGGL(toppra_sample_kernel, dim3((unsigned)P), dim3(TS_THREADS), lds, ctx->stream, a);
+    hipLaunchKernelGGL(toppra_sample_kernel<false>, dim3((unsigned)P), dim3(TS_THREADS), lds, ctx->stream, a);
+    sc_time_end(ctx, tk);
+    SC_HIP(ctx, hipGetLastError());
+    return SC_OK;
+}
+
+// The packed form (sc_smooth_paths_batch): plan p's samples at offsets[p] + j, plans with skip[p] != 0 left out, at most
+// plen[p] samples written.  Device pointers; vel, acc and times may be NULL.
+int sc_launch_toppra_sample_packed(sc_ctx* ctx, int P, int dof, int N, const double* p0, const double* p1, const double* v0,
+                                   const double* v1, const double* x, const double* t, double dt, const int32_t* offsets,
+                                   const int32_t* plen, const int32_t* skip, float* pos, float* vel, float* acc, double* times) {
+    if (!ctx || P <= 0 || dof <= 0 || N <= 0 || N > 65534 || !(dt > 0) || !p0 || !p1 || !v0 || !v1 || !x || !t || !offsets || !plen ||
+        !skip || !pos)
+        return SC_ERR_INVALID;
+    SC_HIP(ctx, hipSetDevice(ctx->device));
+    sample_args a{P, dof, N, 0, p0, p1, v0, v1, x, t, dt, pos, vel, acc, times, nullptr, offsets, plen, skip};
+    const size_t lds = (size_t)(2 + 3 * dof) * (N + 1) * sizeof(double) + (((size_t)(N + 1) * 2 + 15) & ~(size_t)15);
+    if (lds > 140 * 1024) { snprintf(ctx->err, sizeof(ctx->err), "sc_smooth_paths_batch: (2 + 3 dof)(N + 1) doubles exceed the LDS of a CU"); return SC_ERR_INVALID; }
+    {
+        int r_ = sc_allow_big_lds(ctx, reinterpret_cast<const void*>(toppra_sample_kernel<true>), 140 * 1024);
+        if (r_ != SC_OK) return r_;
+    }
+    int tk = sc_time_begin(ctx, SC_K_TOPPRA_SAMPLE);
+    hipLaunchKernelGGL(toppra_sample_kernel<true>, dim3((unsigned)P), dim3(TS_THREADS), lds, ctx->stream, a);
     sc_time_end(ctx, tk);
     SC_HIP(ctx, hipGetLastError());
     return SC_OK;

@@ -21,6 +21,8 @@ EDT_INF = 2**31 - 1
 Q_OK, Q_NO_PATH, Q_BAD_ENDPOINT, Q_TRUNCATED, Q_RING_OVERFLOW, Q_BAD_PATH = 0, 1, 2, 3, 4, 5
 K_EDT_COLBITS, K_EDT_BAND, K_MOVES, K_ASTAR, K_TOPPRA, K_TOPPRA_SAMPLE, K_BEZIER, K_ARCLENGTH, K_RESAMPLE, K_OCC, K_NEAREST, K_FMT, K_GATHER = range(13)
 K_WAYPOINTS = 13
+K_SMOOTH = 14
+SMOOTH_OK, SMOOTH_BAD_INPUT, SMOOTH_NONFINITE, SMOOTH_TOPPRA_FAILED, SMOOTH_TRUNCATED, SMOOTH_EMPTY_SEGMENT = range(6)
 
 _lib = None
 
@@ -87,6 +89,9 @@ _SIGNATURES = {
     "sc_bezier_arclength_batch": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "sc_bezier_resample_batch": (_i, [_vp] * 5 + [_i, _i, _i, _vp, _vp, _i] + [_vp] * 5),
     "sc_bezier_resample_batch_host": (_i, [_vp] * 5 + [_i, _i, _i, _vp, _vp, _i] + [_vp] * 5),
+    "sc_smooth_paths_batch": (_i, [_vp, _vp, _vp, _i, _i, _vp, C.c_float, _vp, _i, C.c_float, _i, _i, C.c_int64] + [_vp] * 16),
+    "sc_smooth_paths_batch_host": (_i, [_vp, _vp, _vp, _i, _i, _vp, C.c_float, _vp, _i, C.c_float, _i, _i, C.c_int64] + [_vp] * 16),
+    "sc_cells_to_points_batch": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, C.c_float, C.c_float, C.c_float, C.c_float, _vp, _vp, _vp, _vp]),
     "sc_rank_range": (None, [_i, _i, _i, C.POINTER(_i), C.POINTER(_i)]),
     "sc_comm_unique_id": (_i, [_vp]),
     "sc_comm_init": (_i, [_vp, _vp, _i, _i]),
@@ -253,6 +258,93 @@ class Context:
         self._ck(self._l.sc_path_waypoints_batch(self._h, _ptr(d2), W, H, r2, _ptr(res["path"]), _ptr(res["len"]), _ptr(st), Q, Lmax, Wmax,
                                                  _ptr(out["wp"]), _ptr(out["n"]), _ptr(out["status"])), "sc_path_waypoints_batch")
         return out
+
+    def cells_to_points(self, wr, W, x_min, y_min, res_x, res_y, starts=None, goals=None):
+        """path_waypoints' result (dict wp int32 [Q,Wmax], n, status) -> (path float32 [Q,Wmax,2], npts int32 [Q]), the cell
+        centres of a W-wide grid (sc_cells_to_points_batch); starts / goals float32 [Q,2] replace the two ends."""
+        import torch
+        Q, Wmax = wr["wp"].shape
+        dev = wr["wp"].device
+        path = torch.zeros((Q, Wmax, 2), dtype=torch.float32, device=dev)
+        npts = torch.empty(Q, dtype=torch.int32, device=dev)
+        self._ck(self._l.sc_cells_to_points_batch(self._h, _ptr(wr["wp"]), _ptr(wr["n"]), _ptr(wr.get("status")), Q, Wmax, W, x_min, y_min,
+                                                  res_x, res_y, _ptr(starts), _ptr(goals), _ptr(path), _ptr(npts)), "sc_cells_to_points_batch")
+        return path, npts
+
+    @staticmethod
+    def _smooth_estimate(wp, npts, limits, dt):
+        """Samples to reserve for smooth_paths(capacity=None), the rule of the C++ header's smooth_paths_batch: per path
+        (1.5 * polyline length / vel_max + 2 vel_max / acc_max) / dt * 1.25 + 64 (64 where that is not finite).  Only a
+        first guess: a call that needs more is repeated with the exact count."""
+        import torch
+        n_max = wp.shape[1]
+        leg = (wp[:, 1:] - wp[:, :-1]).double().norm(dim=-1)
+        use = torch.arange(n_max - 1, device=wp.device)[None, :] < (npts.long()[:, None] - 1)
+        poly = torch.where(use, leg, torch.zeros_like(leg)).sum(1)
+        v = torch.where(limits[:, 1] > 0, limits[:, 1], torch.ones_like(limits[:, 1]))
+        a = torch.where(limits[:, 3] > 0, limits[:, 3], torch.ones_like(limits[:, 3]))
+        T = 1.5 * poly / v + 2.0 * v / a
+        est = torch.where(torch.isfinite(T), (T / dt * 1.25).clamp(max=1e6).floor() + 64, torch.full_like(T, 64.0))
+        return int(est.sum().item())
+
+    def smooth_paths(self, wp, npts, limits, dt=0.02, N=100, nsub=100, start_angle=float("nan"), lines=None, capacity=None, out=None):
+        """The post-planner sequence for a batch of paths in one call (sc_smooth_paths_batch).  wp float32 [P,n_max,2],
+        npts int32 [P], limits float64 [P,4] (vel_min, vel_max, acc_min, acc_max) or 4 numbers for every path, lines float32
+        [E,4] or None; all on the GPU.  capacity=None: room for an estimate of the samples, the call repeated once with the
+        exact count if that was short (reads `needed`: synchronises), and the per-sample outputs cut to `needed`.  With a
+        capacity the call only enqueues.  `out`: the dict of an earlier call with the same P, n_max and capacity, reused.
+        Returns dict(ctrl [P*(n_max-1),4,2], seg_off, arclength, length, offsets, status, needed [1], and per sample time,
+        pos, vel, acc, pts [M,2], curvature, ang_vel, tpar, seg)."""
+        import torch
+        P, n_max, _ = wp.shape
+        dev = wp.device
+        if not torch.is_tensor(limits):
+            limits = torch.tensor([list(map(float, limits))] * P, dtype=torch.float64, device=dev)
+        limits = limits.to(torch.float64).expand(P, 4).contiguous()
+        nl = 0 if lines is None else lines.shape[0]
+        auto = capacity is None
+        cap = min(self._smooth_estimate(wp, npts, limits, dt), 2**31 - 1) if auto else int(capacity)
+
+        def run(cap, o):
+            if o is None or o["pos"].shape[0] != cap or o["status"].shape[0] != P or o["ctrl"].shape[0] != P * (n_max - 1):
+                f = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
+                i = lambda *s: torch.empty(s, dtype=torch.int32, device=dev)
+                o = dict(ctrl=f(P * (n_max - 1), 4, 2), seg_off=i(P + 1), arclength=f(P), length=i(P), offsets=i(P + 1), status=i(P),
+                         needed=torch.empty(1, dtype=torch.int64, device=dev), time=torch.empty(cap, dtype=torch.float64, device=dev),
+                         pos=f(cap), vel=f(cap), acc=f(cap), pts=f(cap, 2), curvature=f(cap), ang_vel=f(cap), tpar=f(cap), seg=i(cap))
+            self._ck(self._l.sc_smooth_paths_batch(
+                self._h, _ptr(wp), _ptr(npts), P, n_max, _ptr(limits), start_angle, _ptr(lines) if nl else None, nl, dt, N, nsub, cap,
+                *[_ptr(o[k]) for k in ("ctrl", "seg_off", "arclength", "length", "offsets", "status", "needed", "time", "pos", "vel", "acc",
+                                       "pts", "curvature", "ang_vel", "tpar", "seg")]), "sc_smooth_paths_batch")
+            return o
+
+        o = run(cap, out)
+        if not auto:
+            return o
+        need = int(o["needed"][0])
+        if need > cap:
+            o = run(need, None)
+        return {k: (v[:need] if k in ("time", "pos", "vel", "acc", "pts", "curvature", "ang_vel", "tpar", "seg") else v) for k, v in o.items()}
+
+    def smooth_paths_host(self, wp, npts, limits, capacity, dt=0.02, N=100, nsub=100, start_angle=float("nan"), lines=None):
+        """Host form (numpy in, numpy out) of smooth_paths with room for `capacity` samples (sc_smooth_paths_batch_host)."""
+        wp = np.ascontiguousarray(wp, dtype=np.float32)
+        npts = np.ascontiguousarray(npts, dtype=np.int32)
+        P, n_max, _ = wp.shape
+        limits = np.ascontiguousarray(np.broadcast_to(np.asarray(limits, dtype=np.float64), (P, 4)))
+        lines = None if lines is None else np.ascontiguousarray(lines, dtype=np.float32)
+        nl = 0 if lines is None else lines.shape[0]
+        cap = int(capacity)
+        o = dict(ctrl=np.zeros((P * (n_max - 1), 4, 2), np.float32), seg_off=np.zeros(P + 1, np.int32), arclength=np.zeros(P, np.float32),
+                 length=np.zeros(P, np.int32), offsets=np.zeros(P + 1, np.int32), status=np.zeros(P, np.int32), needed=np.zeros(1, np.int64),
+                 time=np.zeros(cap), pos=np.zeros(cap, np.float32), vel=np.zeros(cap, np.float32), acc=np.zeros(cap, np.float32),
+                 pts=np.zeros((cap, 2), np.float32), curvature=np.zeros(cap, np.float32), ang_vel=np.zeros(cap, np.float32),
+                 tpar=np.zeros(cap, np.float32), seg=np.zeros(cap, np.int32))
+        self._ck(self._l.sc_smooth_paths_batch_host(
+            self._h, _ptr(wp), _ptr(npts), P, n_max, _ptr(limits), start_angle, _ptr(lines) if nl else None, nl, dt, N, nsub, cap,
+            *[_ptr(o[k]) for k in ("ctrl", "seg_off", "arclength", "length", "offsets", "status", "needed", "time", "pos", "vel", "acc",
+                                   "pts", "curvature", "ang_vel", "tpar", "seg")]), "sc_smooth_paths_batch_host")
+        return o
 
     # ---- multi-GPU gather (RCCL through the C ABI) ----
     @staticmethod

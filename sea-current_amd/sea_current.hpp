@@ -21,6 +21,7 @@
 //   gen_vel_prof<N>                    :1191-1265         same argument order (END before START), GPU TOPP-RA
 //   (new) occupancy_grid, planning_space::plan_batch, gen_vel_prof_batch: the batched entry points
 //   (new) occupancy_grid::waypoints_batch, planning_space::simplify_paths: A* cell paths -> line-of-sight waypoints
+//   (new) smooth_paths_batch: from_path -> arclength -> gen_vel_prof<1> -> resample(nudge) -> ang_vel for many paths, one call
 //
 // Differences that are deliberate: obstacle::closed is initialised (the reference leaves it
 // uninitialised, :197); library code never prints or calls std::exit (SC_ASSERT throws in DEBUG);
@@ -1024,6 +1025,95 @@ velocity_profile gen_vel_prof(const VectorNd<N>& pos_end, const VectorNd<N>& pos
     }
     r.vel_lim = vel_lim;
     return std::move(gen_vel_prof_batch({r}, dt)[0]);
+}
+
+// ---- the service's per-request sequence for a batch (examples/zmq_test.cpp:66-93) ------------------------------------
+// from_path(path, space) -> arclength -> gen_vel_prof<1>(arclength, 0, 0, 0, limits) -> resample(nudge) -> angular velocity
+// for every request, in ONE sc_smooth_paths_batch_host call.  Each result holds what serialize_path_to_json takes: the
+// resampled spline (ctrl_pts, pts, positions), the profile, the arclength (the tables are not returned) and ang_vel =
+// vel * curvature (the curvature of the resample kernel; bezier_spline::curvature goes through the hodograph on the host,
+// so the two agree to rounding).  status is an sc_smooth_status; the other members are empty unless it is SC_SMOOTH_OK.
+struct smooth_request {
+    std::vector<Vector2f> path;
+    double vel_min, vel_max, acc_min, acc_max;
+};
+struct smooth_result {
+    int status = SC_SMOOTH_BAD_INPUT;
+    bezier_spline spline;
+    velocity_profile profile{{}, {}, {}, toppra_compat::Vector()};
+    arclength_data arclength;
+    std::vector<float> ang_vel;
+};
+inline std::vector<smooth_result> smooth_paths_batch(const std::vector<smooth_request>& requests, const planning_space& space,
+                                                     float dt = 0.02f, float precision = 0.01f, gpu_context& ctx = default_context()) {
+    const int P = (int)requests.size();
+    std::vector<smooth_result> out(P);
+    if (P == 0) return out;
+    int n_max = 2;
+    for (const auto& r : requests) n_max = std::max(n_max, (int)r.path.size());
+    std::vector<float> xy((size_t)P * n_max * 2, 0.f), lines;
+    std::vector<int32_t> npts(P);
+    std::vector<double> lim((size_t)P * 4);
+    int64_t cap = 0;
+    for (int p = 0; p < P; ++p) {
+        const auto& r = requests[p];
+        npts[p] = (int32_t)r.path.size();
+        float poly = 0;
+        for (size_t i = 0; i < r.path.size(); ++i) {
+            xy[((size_t)p * n_max + i) * 2] = r.path[i].x(); xy[((size_t)p * n_max + i) * 2 + 1] = r.path[i].y();
+            if (i) poly += pt_dist(r.path[i], r.path[i - 1]);
+        }
+        lim[4 * (size_t)p] = r.vel_min; lim[4 * (size_t)p + 1] = r.vel_max; lim[4 * (size_t)p + 2] = r.acc_min; lim[4 * (size_t)p + 3] = r.acc_max;
+        // a first guess of the samples (the call is repeated with the exact count if it was short)
+        const double v = r.vel_max > 0 ? r.vel_max : 1.0, a = r.acc_max > 0 ? r.acc_max : 1.0;
+        const double T = 1.5 * poly / v + 2.0 * v / a;
+        cap += std::isfinite(T) ? (int64_t)std::min(T / dt * 1.25, 1e6) + 64 : 64;
+    }
+    for (const auto& ob : space.obstacles)
+        for (const auto& [a, b] : ob.lines) { lines.push_back(a.x()); lines.push_back(a.y()); lines.push_back(b.x()); lines.push_back(b.y()); }
+    const int nsub = (int)std::lround(1.0f / precision), S = P * (n_max - 1);
+    std::vector<float> ctrl((size_t)S * 8), al(P), pos, vel, acc, pts, ang, tpar;
+    std::vector<int32_t> seg_off(P + 1), length(P), offsets(P + 1), status(P), seg;
+    std::vector<double> times;
+    int64_t needed = 0;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        cap = std::min<int64_t>(std::max<int64_t>(cap, 1), INT32_MAX);
+        pos.resize(cap); vel.resize(cap); acc.resize(cap); pts.resize(2 * (size_t)cap); ang.resize(cap); tpar.resize(cap); seg.resize(cap);
+        times.resize(cap);
+        ctx.check(sc_smooth_paths_batch_host(ctx.get(), xy.data(), npts.data(), P, n_max, lim.data(), NAN, lines.empty() ? nullptr : lines.data(),
+                                             (int)(lines.size() / 4), dt, SC_TOPPRA_GRID, nsub, cap, ctrl.data(), seg_off.data(), al.data(),
+                                             length.data(), offsets.data(), status.data(), &needed, times.data(), pos.data(), vel.data(),
+                                             acc.data(), pts.data(), nullptr, ang.data(), tpar.data(), seg.data()),
+                  "sc_smooth_paths_batch_host");
+        if (needed <= cap) break;
+        cap = needed;
+    }
+    for (int p = 0; p < P; ++p) {
+        smooth_result& res = out[p];
+        res.status = status[p];
+        res.arclength.arclength = al[p];
+        if (status[p] != SC_SMOOTH_OK) continue;
+        const int s0 = seg_off[p], ns = seg_off[p + 1] - s0, o = offsets[p], L = length[p];
+        bezier_spline& bs = res.spline;
+        bs.ctrl_pts.resize(ns);
+        for (int i = 0; i < ns; ++i)
+            for (int k = 0; k < 4; ++k) bs.ctrl_pts[i].push_back(Vector2f(ctrl[((size_t)(s0 + i)) * 8 + 2 * k], ctrl[((size_t)(s0 + i)) * 8 + 2 * k + 1]));
+        bs.pts = points_matrix::Zero(L, 2);
+        std::vector<int> cnt(ns, 0);
+        for (int j = 0; j < L; ++j) { bs.pts(j, 0) = pts[2 * (size_t)(o + j)]; bs.pts(j, 1) = pts[2 * (size_t)(o + j) + 1]; ++cnt[seg[o + j]]; }
+        for (int i = 0, k0 = o; i < ns; ++i) {
+            VectorXf v = VectorXf::Zero(cnt[i]);
+            for (int k = 0; k < cnt[i]; ++k) v(k) = tpar[k0 + k];
+            k0 += cnt[i];
+            bs.positions.push_back(std::move(v));
+        }
+        std::vector<VectorXf> ps(1, VectorXf::Zero(L)), vs(1, VectorXf::Zero(L)), as(1, VectorXf::Zero(L));
+        toppra_compat::Vector tm(L);
+        for (int j = 0; j < L; ++j) { ps[0](j) = pos[o + j]; vs[0](j) = vel[o + j]; as[0](j) = acc[o + j]; tm(j) = times[o + j]; }
+        res.profile = velocity_profile(std::move(ps), std::move(vs), std::move(as), std::move(tm));
+        res.ang_vel.assign(ang.begin() + o, ang.begin() + o + L);
+    }
+    return out;
 }
 
 // ---- wire formats of the example service ---------------------------------------------------
