@@ -64,7 +64,7 @@ typedef enum {
     SC_K_BEZIER = 6,      /* tangents + control points, curve evaluation */
     SC_K_ARCLENGTH = 7,   /* GL-32 arclength tables */
     SC_K_RESAMPLE = 8,    /* resample: nudge + split, Chebyshev fit + evaluation */
-    SC_K_OCC = 9,         /* occupancy grid from a rectangle list (dynamic-obstacle frames) */
+    SC_K_OCC = 9,         /* occupancy grids from rectangles or polygons (sc_occ_from_rects, sc_occ_from_polygons) */
     SC_K_NEAREST = 10,    /* nearest obstacle cell from d2 */
     SC_K_FMT = 11,        /* FMT* over Halton samples (the reference's own planner), one wavefront per query */
     SC_K_GATHER = 12,     /* gather of result paths: pack, ncclAllGather, unpack */
@@ -127,6 +127,45 @@ int sc_edt_nearest_i32(sc_ctx* ctx, const uint8_t* occ, const int32_t* d2, int W
  * reference edits planning_space::obstacles (sea_current.hpp:314) between plans; the EDT is then recomputed in full
  * by sc_edt_u8_i32 (exact, ~10 us at 1024^2).  Device pointers; rects int32 [R][4]. */
 int sc_occ_from_rects(sc_ctx* ctx, const uint8_t* base, const int32_t* rects, int R, int W, int H, int free_border, uint8_t* occ);
+
+/* Occupancy grids from polygon obstacles: the successor header's host occupancy_grid::rasterize (sea_current.hpp), which
+ * stays the definition, byte for byte, for G grids at once.  The reference describes its world as polygons (obstacle,
+ * sea_current.hpp:193-284); this puts them on the grid the EDT, A*, waypoints and smoothing work on, on the device.
+ *   Frame, shared by the G grids: W, H, x_min, y_min, res_x, res_y (what sc_cells_to_points_batch takes; the header passes
+ *   bound_rect.x_min, bound_rect.y_min, resolution and (y_max - y_min) / (float)H).
+ *     cx(x) = clamp((int)floor((x - x_min) / res_x), 0, W-1), cy(y) likewise with y_min, res_y, H;
+ *     centre of cell (ix, iy) = (x_min + ((float)ix + 0.5f) * res_x, y_min + ((float)iy + 0.5f) * res_y).
+ *   Obstacle o: lines obs_off[o] .. obs_off[o+1]-1 of lines (float [n_lines][4] x0,y0,x1,y1, the layout of
+ *     sc_fmt_star_batch), each an edge (a, b); box B = obs_box[o] (x_max, x_min, y_max, y_min: bound_rect's member order;
+ *     obs_box NULL = min / max of o's own lines); closed = obs_closed[o] (NULL = all closed, the header's default).
+ *     Grid g owns obstacles grid_off[g] .. grid_off[g+1]-1 (grid_off int32 [G+1]; NULL only with G == 1: all of them).
+ *     An obstacle without edges is skipped.  The edge-list constructor starts its box at vertices[0] even when no edge
+ *     uses it (sea_current.hpp), so such obstacles need an explicit obs_box.
+ *   Closed fill: for iy in cy(B.y_min) .. cy(B.y_max), ix in cx(B.x_min) .. cx(B.x_max), with p the cell's centre: set if
+ *     p is inside B (inclusive) and odd is the count of edges with (a.y > p.y) != (b.y > p.y) and
+ *     p.x < a.x + (p.y - a.y) * (b.x - a.x) / (b.y - a.y)   (evaluated in exactly that order).
+ *   Edges of every obstacle, open or closed: dx = b.x - a.x, dy = b.y - a.y, len = sqrt(dx*dx + dy*dy) (float sum, correctly
+ *     rounded float sqrt), n = max(1, (int)ceil(len / (0.5f * min(res_x, res_y)))); for k = 0 .. n: t = (float)k / (float)n,
+ *     set cell (cx(a.x + dx*t), cy(a.y + dy*t)).  Clamping: an edge outside the frame paints border cells, as the host does.
+ *   occ uint8 [G][H][W] = base [G][H][W] (all free when base is NULL; base == occ paints in place) OR the cells set by grid
+ *     g's obstacles.
+ *   Arithmetic: IEEE float32 throughout, no contraction, correctly rounded division and sqrt.  The header's host code gives
+ *     these bytes when built as the tests build it (g++ -std=c++17, x86-64, no FMA contraction).
+ * Contract: every coordinate (lines, obs_box, the frame) is finite, res_x, res_y > 0; every (x - x_min) / res_x and
+ *   (y - y_min) / res_y of a vertex or box lies within +-2^30 (the host's float-to-int casts are undefined past it); every
+ *   edge has n <= 2^24 (an edge about 8 M cells long); 0 <= obs_off[0] <= .. <= obs_off[n_obs] <= n_lines and
+ *   0 <= grid_off[0] <= .. <= grid_off[G] <= n_obs.  Limits: W, H <= SC_MAX_DIM, 1 <= G <= 65535, n_obs >= 0.
+ * sc_occ_from_polygons: device pointers; enqueues only (no host synchronisation, no device-to-host copy), so it chains as
+ *   sc_occ_from_polygons -> sc_edt_u8_i32 (batch = G) -> sc_astar_batch_multi on one stream.  Scratch: 24 B per obstacle
+ *   (grows only).  Outside the contract the result is unspecified; every index is clamped, so writes stay inside occ.
+ * sc_occ_from_polygons_host: host pointers; checks the contract on the data and returns SC_ERR_INVALID before any launch,
+ *   then copies, runs, copies occ back and synchronises.  Timed as SC_K_OCC. */
+int sc_occ_from_polygons(sc_ctx* ctx, const uint8_t* base, int G, int W, int H, float x_min, float y_min, float res_x, float res_y,
+                         const float* lines, int n_lines, const int32_t* obs_off, int n_obs, const float* obs_box,
+                         const uint8_t* obs_closed, const int32_t* grid_off, uint8_t* occ);
+int sc_occ_from_polygons_host(sc_ctx* ctx, const uint8_t* base, int G, int W, int H, float x_min, float y_min, float res_x,
+                              float res_y, const float* lines, int n_lines, const int32_t* obs_off, int n_obs, const float* obs_box,
+                              const uint8_t* obs_closed, const int32_t* grid_off, uint8_t* occ);
 
 /* Legal-move mask per cell: bit d set iff move d (dx={1,-1,0,0,1,-1,1,-1},
  * dy={0,0,1,-1,1,1,-1,-1}) out of the cell is allowed: both cells have

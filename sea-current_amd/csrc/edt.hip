@@ -1552,8 +1552,10 @@ edt_band_k16_kernel(const uint32_t* __restrict__ colbits, int W, int H, int nb, 
         open_sites = edt_k16_site_row<FULL>(cb + (size_t)b * W, udg + ((size_t)g * nb + b) * W, W, i, lane, tr, smem + (size_t)wave * (WP / 4), out);
         if (lane == 0) g_edt_open[1] = 1;
         if (open_sites <= 508) { row_done = true; break; }
-        // more sites than the search's LDS holds: the rest of the 175 steps after all
+        // more sites than the search's LDS holds: the rest of the 175 steps after all; when the first try already ran
+        // all of them, the row stays saturated and takes the exact 32-bit cascade below
         it = direct ? 1 : it + 1;
+        if (it > EDT_W_ITMAX) break;
         next_chk = it;
         it_lim = EDT_W_ITMAX;
         saturated = false;

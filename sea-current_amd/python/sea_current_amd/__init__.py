@@ -73,6 +73,8 @@ _SIGNATURES = {
     "sc_fmt_star_batch_host": (_i, [_vp, _vp, _i, _vp, _vp, _i, C.c_float, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "sc_edt_nearest_i32": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "sc_occ_from_rects": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "sc_occ_from_polygons": (_i, [_vp, _vp, _i, _i, _i] + [C.c_float] * 4 + [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp]),
+    "sc_occ_from_polygons_host": (_i, [_vp, _vp, _i, _i, _i] + [C.c_float] * 4 + [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     "sc_bezier_from_path_batch": (_i, [_vp, _vp, _vp, _i, _i, C.c_float, _vp, _i, _vp]),
     "sc_bezier_from_path_batch_host": (_i, [_vp, _vp, _vp, _i, _i, C.c_float, _vp, _i, _vp]),
     "sc_bezier_shrink_tangent_batch": (_i, [_vp, _vp, _vp, _i, C.c_float, _vp, _i, _vp]),
@@ -506,6 +508,22 @@ class Context:
                                            1 if free_border else 0, _ptr(occ)), "sc_occ_from_rects")
         return occ
 
+    def occ_from_polygons(self, lines, obs_off, W, H, x_min, y_min, res_x, res_y, closed=None, box=None, grid_off=None, base=None,
+                          out=None):
+        """Polygon obstacles -> occupancy grids (sc_occ_from_polygons), GPU tensors: lines float32 [E,4] (x0,y0,x1,y1),
+        obs_off int32 [n_obs+1], closed uint8 [n_obs] (None: all closed), box float32 [n_obs,4] in bound_rect order
+        (x_max, x_min, y_max, y_min; None: each obstacle's own lines), grid_off int32 [G+1] (None: one grid).  Returns uint8
+        [H,W] without grid_off, else [G,H,W]; base (same shape) is painted over, base is out paints in place."""
+        import torch
+        G = 1 if grid_off is None else grid_off.shape[0] - 1
+        shape = (H, W) if grid_off is None else (G, H, W)
+        occ = out if out is not None else torch.empty(shape, dtype=torch.uint8, device=obs_off.device)
+        n_obs = obs_off.shape[0] - 1
+        self._ck(self._l.sc_occ_from_polygons(self._h, _ptr(base), G, W, H, x_min, y_min, res_x, res_y,
+                                              _ptr(lines) if lines.shape[0] else None, lines.shape[0], _ptr(obs_off), n_obs,
+                                              _ptr(box), _ptr(closed), _ptr(grid_off), _ptr(occ)), "sc_occ_from_polygons")
+        return occ
+
     def bezier_from_path(self, path, npts, start_angle=float("nan"), lines=None):
         """path float32 [P,n_max,2], npts int32 [P] (GPU) -> ctrl float32 [P,n_max-1,4,2]."""
         import torch
@@ -583,6 +601,23 @@ class Context:
         d2 = np.empty(o3.shape, dtype=np.int32)
         self._ck(self._l.sc_edt_u8_i32_host(self._h, _ptr(o3), W, H, B, _ptr(d2)), "sc_edt_u8_i32_host")
         return d2 if occ.ndim == 3 else d2[0]
+
+    def occ_from_polygons_host(self, lines, obs_off, W, H, x_min, y_min, res_x, res_y, closed=None, box=None, grid_off=None,
+                               base=None):
+        """Host form of occ_from_polygons (numpy in, numpy out; sc_occ_from_polygons_host checks the contract first)."""
+        lines = np.ascontiguousarray(lines, dtype=np.float32).reshape(-1, 4)
+        obs_off = np.ascontiguousarray(obs_off, dtype=np.int32)
+        closed = None if closed is None else np.ascontiguousarray(closed, dtype=np.uint8)
+        box = None if box is None else np.ascontiguousarray(box, dtype=np.float32).reshape(-1, 4)
+        grid_off = None if grid_off is None else np.ascontiguousarray(grid_off, dtype=np.int32)
+        G = 1 if grid_off is None else grid_off.shape[0] - 1
+        shape = (H, W) if grid_off is None else (G, H, W)
+        occ = np.zeros(shape, np.uint8) if base is None else np.array(base, dtype=np.uint8, copy=True).reshape(shape)
+        self._ck(self._l.sc_occ_from_polygons_host(self._h, _ptr(occ) if base is not None else None, G, W, H, x_min, y_min, res_x,
+                                                   res_y, _ptr(lines) if lines.shape[0] else None, lines.shape[0], _ptr(obs_off),
+                                                   obs_off.shape[0] - 1, _ptr(box), _ptr(closed), _ptr(grid_off), _ptr(occ)),
+                 "sc_occ_from_polygons_host")
+        return occ
 
     def astar_batch_host(self, d2, start, goal, r2=0, Lmax=4096):
         d2 = np.ascontiguousarray(d2, dtype=np.int32)

@@ -22,6 +22,7 @@
 //   (new) occupancy_grid, planning_space::plan_batch, gen_vel_prof_batch: the batched entry points
 //   (new) occupancy_grid::waypoints_batch, planning_space::simplify_paths: A* cell paths -> line-of-sight waypoints
 //   (new) smooth_paths_batch: from_path -> arclength -> gen_vel_prof<1> -> resample(nudge) -> ang_vel for many paths, one call
+//   (new) occupancy_grid::rasterize(obstacles, ctx), planning_space::make_grid(ctx): the polygon rasteriser on the GPU
 //
 // Differences that are deliberate: obstacle::closed is initialised (the reference leaves it
 // uninitialised, :197); library code never prints or calls std::exit (SC_ASSERT throws in DEBUG);
@@ -357,6 +358,26 @@ public:
             }
         }
     }
+    // the same bytes as rasterize(obstacles), painted over the current occ on the GPU (sc_occ_from_polygons_host: throws
+    // when an obstacle breaks the contract of sea_current_hip.h -- finite coordinates within 2^30 cells, edges of at
+    // most 2^24 samples)
+    void rasterize(const std::vector<obstacle>& obstacles, gpu_context& ctx) {
+        const float ry = (bound_rect.y_max - bound_rect.y_min) / (float)H;
+        std::vector<float> lines, box;
+        std::vector<int32_t> off{0};
+        std::vector<uint8_t> closed;
+        for (const auto& ob : obstacles) {
+            for (const auto& [a, b] : ob.lines) { lines.push_back(a.x()); lines.push_back(a.y()); lines.push_back(b.x()); lines.push_back(b.y()); }
+            off.push_back((int32_t)(lines.size() / 4));
+            box.push_back(ob.bound_rect.x_max); box.push_back(ob.bound_rect.x_min); box.push_back(ob.bound_rect.y_max); box.push_back(ob.bound_rect.y_min);
+            closed.push_back(ob.closed ? 1 : 0);
+        }
+        const int n_obs = (int)obstacles.size();
+        ctx.check(sc_occ_from_polygons_host(ctx.get(), occ.data(), 1, W, H, bound_rect.x_min, bound_rect.y_min, resolution, ry,
+                                            lines.empty() ? nullptr : lines.data(), (int)(lines.size() / 4), off.data(), n_obs,
+                                            n_obs ? box.data() : nullptr, n_obs ? closed.data() : nullptr, nullptr, occ.data()),
+                  "sc_occ_from_polygons_host");
+    }
     // exact squared EDT on the GPU
     void edt(gpu_context& ctx = default_context()) {
         d2.resize(occ.size());
@@ -534,11 +555,20 @@ public:
         return pt_dist(a, b);
     }
     occupancy_grid make_grid() const {
-        const float wx = bound_rect.x_max - bound_rect.x_min, wy = bound_rect.y_max - bound_rect.y_min;
-        const float res = std::max(wx, wy) / (float)grid_cells;
-        occupancy_grid g(bound_rect, std::max(1, (int)std::ceil(wx / res)), std::max(1, (int)std::ceil(wy / res)));
+        occupancy_grid g = empty_grid();
         g.rasterize(obstacles);
         return g;
+    }
+    // the same grid, rasterised on the GPU (occupancy_grid::rasterize(obstacles, ctx))
+    occupancy_grid make_grid(gpu_context& ctx) const {
+        occupancy_grid g = empty_grid();
+        g.rasterize(obstacles, ctx);
+        return g;
+    }
+    occupancy_grid empty_grid() const {
+        const float wx = bound_rect.x_max - bound_rect.x_min, wy = bound_rect.y_max - bound_rect.y_min;
+        const float res = std::max(wx, wy) / (float)grid_cells;
+        return occupancy_grid(bound_rect, std::max(1, (int)std::ceil(wx / res)), std::max(1, (int)std::ceil(wy / res)));
     }
     // Same role and result type as the reference's FMT* planner: start -> goal waypoint list, nullopt if
     // no path.  `n` and `rn` (sample count, connection radius) are accepted for source compatibility;
@@ -580,7 +610,7 @@ public:
     // batched form: one grid, one EDT, Q queries in one GPU launch
     std::vector<std::optional<std::vector<Vector2f>>> plan_batch(const std::vector<Vector2f>& starts, const std::vector<Vector2f>& goals,
                                                                  gpu_context& ctx = default_context()) {
-        occupancy_grid g = make_grid();
+        occupancy_grid g = make_grid(ctx);
         g.edt(ctx);
         std::vector<int32_t> s(starts.size()), t(goals.size());
         for (size_t i = 0; i < starts.size(); ++i) { s[i] = g.cell_of(starts[i]); t[i] = g.cell_of(goals[i]); }
