@@ -58,7 +58,8 @@ typedef enum {
     SC_K_EDT_COLBITS = 0, /* occupancy bytes -> transposed per-band column bit words */
     SC_K_EDT_BAND = 1,    /* per 32-row band: vertical distances + exact row envelope -> d2 */
     SC_K_MOVES = 2,       /* d2 + clearance -> legal-move byte per cell */
-    SC_K_ASTAR = 3,       /* batched A*: two wavefronts per query (prep + search + retry launches) */
+    SC_K_ASTAR = 3,       /* batched A*: two wavefronts per query (prep + search + retry launches); also the cost fields and
+                           * their read-out (sc_cost_field_batch, sc_field_paths_batch) */
     SC_K_TOPPRA = 4,      /* batched TOPP-RA: computeParams + backward + forward sweep */
     SC_K_TOPPRA_SAMPLE = 5,
     SC_K_BEZIER = 6,      /* tangents + control points, curve evaluation */
@@ -208,6 +209,50 @@ int sc_astar_debug_peek(sc_ctx* ctx, int32_t* out16);
  * expanded -- E = {n : g*(n) + h(n) <= C*}, all that paths and parents are read from -- and 0xFFFFFFFF elsewhere. */
 int sc_astar_gfield(sc_ctx* ctx, const int32_t* d2, int W, int H, int32_t r2_clear,
                     int32_t start, int32_t goal, uint32_t* gfield, int32_t* cost, int32_t* status);
+
+/* ---- cost-to-come fields ------------------------------------------------------------------------------
+ * One exact shortest-path search from a root over the whole grid, then paths to any number of targets read from it.
+ * Queries that share an endpoint (a fleet heading to one goal, one robot ranking candidate goals, the replan loop) need
+ * one field instead of one A* search each.  Graph: the one A* uses -- 8 moves dx = {1,-1,0,0,1,-1,1,-1}, dy =
+ * {0,0,1,-1,1,1,-1,-1}, cost 10 for d < 4 and 14 for d >= 4, cell c traversable iff d2[c] >= max(r2_clear, 1), a diagonal
+ * needs both orthogonal side cells traversable, no move leaves the grid.
+ *   Field of root r: g[c] = the optimal cost from r to c (exact integer), SC_FIELD_INF when c is unreachable or not
+ *     traversable.  r out of range or not traversable: every cell SC_FIELD_INF and status SC_Q_BAD_ENDPOINT.  Costs fit
+ *     in int32 at every allowed size (14 * 8192^2 < 2^31).
+ *   Path to target t: the oracle's parent rule from t back to r -- parent(c) = the smallest d such that n = c - (dx_d,
+ *     dy_d), the move n->c is legal and g[n] + w_d == g[c].  to_root = 0 writes r..t, to_root = 1 the same cells t..r
+ *     (what a robot standing at t follows to reach r).
+ *   Equality with A*: for every (r, t), status, len, cost and (when SC_Q_OK) path equal what sc_astar_batch returns for
+ *     start r and goal t with the same r2_clear and Lmax: SC_Q_BAD_ENDPOINT if r or t is out of range or not traversable,
+ *     r == t gives len 1 and cost 0, SC_Q_NO_PATH gives len 0 and cost -1, SC_Q_TRUNCATED gives len = the needed count
+ *     and cost (path unspecified).  DESIGN.md section 12 has the argument.
+ * sc_cost_field_batch: F fields; field f is rooted at root[f] on grid fgrid[f] of d2 int32 [G][H][W] (fgrid may be NULL
+ *   only when G == 1).  g: int32 [F][H][W] (4 MiB per 1024^2 field, the caller's); fstatus: int32 [F] (SC_Q_OK /
+ *   SC_Q_BAD_ENDPOINT), may be NULL.  An out-of-range fgrid[f] gives that field SC_Q_BAD_ENDPOINT.  The call fills g
+ *   itself.  rounds: the chip-wide relaxation launches before the per-field finisher completes what is left; the result
+ *   is identical for every value.  rounds < 0 = the library default 2 * (ceil(W/64) + ceil(H/64)) + 16 (80 at 1024^2).
+ * sc_field_paths_batch: Q read-outs; query q reads field qfield[q] (its root root[qfield[q]], its grid fgrid[qfield[q]],
+ *   its values g[qfield[q]]) towards target[q].  path [Q][Lmax], len / cost / status [Q]: sc_astar_batch's layout and
+ *   conventions.  An out-of-range qfield[q] gives that query SC_Q_BAD_ENDPOINT.  g must be what sc_cost_field_batch wrote
+ *   for the same d2, fgrid, root and r2_clear.
+ * Both device forms only enqueue (no host synchronisation, no device-to-host copy), so this chain runs on one stream:
+ *   sc_occ_from_polygons / sc_occ_from_rects -> sc_edt_u8_i32 -> sc_cost_field_batch -> sc_field_paths_batch ->
+ *   sc_path_waypoints_batch -> sc_cells_to_points_batch -> sc_smooth_paths_batch.
+ * Errors: SC_ERR_INVALID for NULL pointers, W or H outside 1..SC_MAX_DIM, F <= 0, G <= 0, Q < 0, Lmax <= 0.  Q == 0 is a
+ *   no-op.  Scratch: G * W * ceil(H/64) * 8 B of traversability masks and about 12 B per (field, 64 x 64 tile), grows
+ *   only.  The _host forms take host pointers, check the data (sc_field_paths_batch_host: every g value >= 0) before any
+ *   launch, copy, run, copy back and synchronise.  Timed as SC_K_ASTAR. */
+#define SC_FIELD_INF INT32_MAX
+int sc_cost_field_batch(sc_ctx* ctx, const int32_t* d2, int G, const int32_t* fgrid, int W, int H, int32_t r2_clear,
+                        const int32_t* root, int F, int rounds, int32_t* g, int32_t* fstatus);
+int sc_cost_field_batch_host(sc_ctx* ctx, const int32_t* d2, int G, const int32_t* fgrid, int W, int H, int32_t r2_clear,
+                             const int32_t* root, int F, int rounds, int32_t* g, int32_t* fstatus);
+int sc_field_paths_batch(sc_ctx* ctx, const int32_t* d2, int G, const int32_t* fgrid, int W, int H, int32_t r2_clear,
+                         const int32_t* g, const int32_t* root, int F, const int32_t* qfield, const int32_t* target, int Q,
+                         int Lmax, int to_root, int32_t* path, int32_t* len, int32_t* cost, int32_t* status);
+int sc_field_paths_batch_host(sc_ctx* ctx, const int32_t* d2, int G, const int32_t* fgrid, int W, int H, int32_t r2_clear,
+                              const int32_t* g, const int32_t* root, int F, const int32_t* qfield, const int32_t* target, int Q,
+                              int Lmax, int to_root, int32_t* path, int32_t* len, int32_t* cost, int32_t* status);
 
 /* ---- line-of-sight waypoints of A* paths ---------------------------------------------------------------
  * Shortcuts every cell path of sc_astar_batch to the cells where it has to turn, the short waypoint list the

@@ -52,6 +52,7 @@ extern "C" int sc_ctx_destroy(sc_ctx* ctx) {
     free_scratch(&ctx->colbits); free_scratch(&ctx->updown); free_scratch(&ctx->edt_fault); free_scratch(&ctx->fmt_nbr); free_scratch(&ctx->edt_flags); free_scratch(&ctx->moves); free_scratch(&ctx->gslots);
     free_scratch(&ctx->buckets); free_scratch(&ctx->qstats); free_scratch(&ctx->closed); free_scratch(&ctx->actr); free_scratch(&ctx->bez_tang); free_scratch(&ctx->bez_gl); free_scratch(&ctx->bez_seginfo); free_scratch(&ctx->cheb_a); free_scratch(&ctx->gather_msg); free_scratch(&ctx->wp_spill);
     free_scratch(&ctx->sm_ctrl); free_scratch(&ctx->sm_cum); free_scratch(&ctx->sm_tp); free_scratch(&ctx->sm_int); free_scratch(&ctx->sm_smp); free_scratch(&ctx->sm_stage); free_scratch(&ctx->occ_prep); free_scratch(&ctx->occ_stage);
+    free_scratch(&ctx->fld_mask); free_scratch(&ctx->fld_state); free_scratch(&ctx->fld_stage);
     for (auto& s : ctx->staging) free_scratch(&s);
     (void)hipStreamDestroy(ctx->own_stream);
     delete ctx;
@@ -131,7 +132,8 @@ extern "C" int sc_ctx_scratch_bytes(sc_ctx* ctx, int64_t* bytes) {
     if (!ctx || !bytes) return SC_ERR_INVALID;
     size_t b = ctx->colbits.bytes + ctx->updown.bytes + ctx->edt_fault.bytes + ctx->edt_flags.bytes + ctx->moves.bytes + ctx->gslots.bytes + ctx->closed.bytes + ctx->buckets.bytes +
                ctx->qstats.bytes + ctx->actr.bytes + ctx->bez_tang.bytes + ctx->bez_gl.bytes + ctx->bez_seginfo.bytes + ctx->cheb_a.bytes + ctx->gather_msg.bytes + ctx->fmt_nbr.bytes + ctx->wp_spill.bytes +
-               ctx->sm_ctrl.bytes + ctx->sm_cum.bytes + ctx->sm_tp.bytes + ctx->sm_int.bytes + ctx->sm_smp.bytes + ctx->sm_stage.bytes + ctx->occ_prep.bytes + ctx->occ_stage.bytes;
+               ctx->sm_ctrl.bytes + ctx->sm_cum.bytes + ctx->sm_tp.bytes + ctx->sm_int.bytes + ctx->sm_smp.bytes + ctx->sm_stage.bytes + ctx->occ_prep.bytes + ctx->occ_stage.bytes +
+               ctx->fld_mask.bytes + ctx->fld_state.bytes + ctx->fld_stage.bytes;
     for (auto& s : ctx->staging) b += s.bytes;
     *bytes = (int64_t)b;
     return SC_OK;

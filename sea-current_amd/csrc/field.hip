@@ -1,0 +1,533 @@
+// field.hip -- cost-to-come fields over the A* graph (sc_cost_field_batch) and path read-out (sc_field_paths_batch).
+//
+// Graph (the one A* uses, oracle/sc_oracle.h): 8 moves, costs 10 / 14, T(c) <=> d2[c] >= max(r2_clear, 1), a diagonal
+// needs both orthogonal side cells traversable, no move leaves the grid.  A field holds the exact optimal cost from its
+// root to every cell, SC_FIELD_INF where there is none.  DESIGN.md section 12.
+//
+// Field kernels.  The grid is cut into 64 x 64 tiles.  A tile visit is one wavefront: lane x holds column x of the tile,
+// its 64 g values in registers, and the column's traversability as a 64-bit mask (field_mask_kernel packs them once per
+// call).  The visit relaxes the tile to its local fixed point against a one-cell halo with row sweeps, down and up in
+// turn: every row takes the moves from the row before it, then a segmented min-plus scan across the lanes closes the row
+// (g'[x] = min over its traversable run of g[k] + 10 |x - k|).  It stops after a sweep, not the first, that changed
+// nothing.  Changed cells are stored; each of the up to 8 neighbour tiles whose halo holds a changed cell is queued.
+//   Chip-wide rounds: `rounds` launches of field_round_kernel, each visiting the queued tiles of every field.  A tile is
+//   queued for round r + 1 by raising its stamp to r + 2 (atomicMax: at most one entry per round); round r reads list
+//   r % 2 and appends to list (r + 1) % 2.  A visit may read a neighbour's border while that neighbour is rewritten: every
+//   value it sees is the cost of a legal path, and the neighbour queues this tile again.  No workgroup waits for another.
+//   Finisher: one workgroup per field takes the tiles still queued (stamp == rounds + 1) and runs rounds of its own, its
+//   8 wavefronts claiming tiles from an LDS bitmap between barriers, until no tile is queued.  Values only fall and a tile
+//   is queued only when a value fell, so it terminates; what it returns is the unique fixed point.
+// Read-out: one wavefront per query walks the parent rule from the target, 32 x 32 cells of g at a time in LDS.
+#include "sc_internal.h"
+
+namespace {
+
+constexpr int FT = 64;                     // tile edge (= wavefront width: lane = column)
+constexpr uint32_t FINF = 0x7FFFFFFFu;     // SC_FIELD_INF; INF + 640 still fits in uint32, so sums need no saturation
+constexpr int FIN_WAVES = 8;               // wavefronts of a finisher workgroup
+constexpr int FIN_MAX_TILES = (SC_MAX_DIM / FT) * (SC_MAX_DIM / FT);
+constexpr int RP_WIN = 32;                 // read-out window edge
+constexpr int RP_WAVES = 4;
+
+struct field_args {
+    const uint64_t* mask;    // [G][TY][W] bit y: T(x, ty*64 + y)
+    const int32_t* d2;       // [G][H][W]
+    const int32_t* fgrid;    // [F] or NULL (G == 1)
+    const int32_t* root;     // [F]
+    int32_t* g;              // [F][H][W]
+    int32_t* ok;             // [F] 1: the field is computed
+    int32_t* stamp;          // [F][nt] round + 1 a tile is queued for (grows only)
+    int32_t* list[2];        // [F * nt] each: f * nt + tile
+    int32_t* ctr;            // [rounds + 1] list length of each round
+    int G, W, H, F, TX, TY, nt;
+    int32_t thr;
+};
+
+__device__ __forceinline__ uint32_t shup(uint32_t v, int s) { return (uint32_t)__shfl_up((int)v, s, 64); }
+__device__ __forceinline__ uint32_t shdn(uint32_t v, int s) { return (uint32_t)__shfl_down((int)v, s, 64); }
+__device__ __forceinline__ uint64_t shup64(uint64_t v) {
+    return ((uint64_t)shup((uint32_t)(v >> 32), 1) << 32) | shup((uint32_t)v, 1);
+}
+__device__ __forceinline__ uint64_t shdn64(uint64_t v) {
+    return ((uint64_t)shdn((uint32_t)(v >> 32), 1) << 32) | shdn((uint32_t)v, 1);
+}
+__device__ __forceinline__ uint32_t rdl(uint32_t v, int l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, l); }
+
+// traversability of row y (-1 .. 64) of a column: m = rows 0..63, ex bit 0 = row -1, bit 1 = row 64
+__device__ __forceinline__ bool tbit(uint64_t m, uint32_t ex, int y) {
+    return y < 0 ? (ex & 1u) != 0 : (y >= FT ? (ex & 2u) != 0 : ((m >> y) & 1ull) != 0);
+}
+
+// close row values v across the lanes: segmented min-plus scans left-to-right then right-to-left over runs of traversable
+// lanes (tmask = ballot of T in this row)
+__device__ __forceinline__ uint32_t close_row(uint32_t v, uint64_t tmask, bool tc, int lane) {
+    const uint64_t blocked = ~tmask;
+    const uint64_t below = blocked & ((1ull << lane) - 1ull);
+    const int rs = below ? 64 - __clzll((long long)below) : 0;
+    const uint64_t above = lane == 63 ? 0ull : (blocked & (~0ull << (lane + 1)));
+    const int re = above ? __ffsll((long long)above) - 2 : 63;
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) {
+        const uint32_t o = shup(v, s) + 10u * s;
+        if (tc && lane - s >= rs) v = min(v, o);
+    }
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) {
+        const uint32_t o = shdn(v, s) + 10u * s;
+        if (tc && lane + s <= re) v = min(v, o);
+    }
+    return v;
+}
+
+struct tile_state {
+    uint32_t g[FT];          // column `lane`, rows 0..63
+    uint64_t m, mL, mR;      // T of this column and of the columns to the left / right, rows 0..63
+    uint32_t ex, exL, exR;   // the same for rows -1 and 64
+    uint32_t gu, gd;         // g of rows -1 and 64 in this column
+    uint32_t hla, hlb, hra, hrb;   // g of the halo columns: lane l of *a = row l - 1, lanes 0, 1 of *b = rows 63, 64
+    uint64_t chg;            // rows changed in this visit
+};
+
+__device__ __forceinline__ uint32_t HL(const tile_state& s, int y) { return y + 1 < 64 ? rdl(s.hla, y + 1) : rdl(s.hlb, y - 63); }
+__device__ __forceinline__ uint32_t HR(const tile_state& s, int y) { return y + 1 < 64 ? rdl(s.hra, y + 1) : rdl(s.hrb, y - 63); }
+
+// one row step of a sweep: row y takes the moves from row yp = y -/+ 1, then closes; returns whether it changed.  Called
+// from fully unrolled loops only, so every g index is a constant and the column stays in registers.
+__device__ __forceinline__ bool row_step(tile_state& s, int y, int yp, int lane, bool force) {
+    const uint32_t pv = yp < 0 ? s.gu : (yp >= FT ? s.gd : s.g[yp]);
+    uint32_t pl = shup(pv, 1), pr = shdn(pv, 1);
+    if (lane == 0) pl = HL(s, yp);
+    if (lane == 63) pr = HR(s, yp);
+    const bool tc = tbit(s.m, s.ex, y), tcp = tbit(s.m, s.ex, yp);
+    const bool tl = tbit(s.mL, s.exL, y), tr = tbit(s.mR, s.exR, y);
+    const uint32_t old = s.g[y];
+    uint32_t v = old;
+    if (tc) {
+        v = min(v, pv + 10u);
+        if (tl && tcp) v = min(v, pl + 14u);
+        if (tr && tcp) v = min(v, pr + 14u);
+        if (lane == 0) v = min(v, HL(s, y) + 10u);
+        if (lane == 63) v = min(v, HR(s, y) + 10u);
+    }
+    if ((__ballot(v < old) != 0ull || force) && __ballot(v < FINF) != 0ull) v = close_row(v, __ballot(tc), tc, lane);
+    s.g[y] = v;
+    if (v < old) s.chg |= 1ull << y;
+    return __ballot(v < old) != 0ull;
+}
+
+__device__ __forceinline__ bool sweep(tile_state& s, bool down, int lane, bool force) {
+    bool c = false;
+    if (down) {
+#pragma unroll
+        for (int y = 0; y < FT; ++y) c |= row_step(s, y, y - 1, lane, force);
+    } else {
+#pragma unroll
+        for (int y = FT - 1; y >= 0; --y) c |= row_step(s, y, y + 1, lane, force);
+    }
+    return c;
+}
+
+// Visit tile (tx, ty) of field f with one wavefront; mark(tx', ty') queues a neighbour (called by every lane, uniform).
+template <class Mark>
+__device__ __forceinline__ void visit_tile(const field_args& a, int f, int tx, int ty, Mark mark) {
+    const int lane = threadIdx.x & 63;
+    const int W = a.W, H = a.H;
+    const int gi = a.fgrid ? a.fgrid[f] : 0;
+    const uint64_t* M = a.mask + (size_t)gi * a.TY * W;
+    int32_t* G = a.g + (size_t)f * W * H;
+    const int x0 = tx * FT, y0 = ty * FT;
+    const int tw = min(FT, W - x0), th = min(FT, H - y0);
+    const int cx = x0 + lane;
+    const bool colin = lane < tw;
+    tile_state s;
+    s.m = colin ? M[(size_t)ty * W + cx] : 0ull;
+    s.ex = 0;
+    if (colin && ty > 0) s.ex |= (uint32_t)(M[(size_t)(ty - 1) * W + cx] >> 63);
+    if (colin && ty + 1 < a.TY) s.ex |= (uint32_t)(M[(size_t)(ty + 1) * W + cx] & 1ull) << 1;
+    // halo columns: lane 0 loads column x0 - 1, lane 63 column x0 + 64
+    const int hc = lane == 0 ? x0 - 1 : x0 + FT;
+    const bool hv = (lane == 0 || lane == 63) && hc >= 0 && hc < W;
+    uint64_t hm = hv ? M[(size_t)ty * W + hc] : 0ull;
+    uint32_t hex = 0;
+    if (hv && ty > 0) hex |= (uint32_t)(M[(size_t)(ty - 1) * W + hc] >> 63);
+    if (hv && ty + 1 < a.TY) hex |= (uint32_t)(M[(size_t)(ty + 1) * W + hc] & 1ull) << 1;
+    s.mL = shup64(s.m); s.exL = shup(s.ex, 1);
+    s.mR = shdn64(s.m); s.exR = shdn(s.ex, 1);
+    if (lane == 0) { s.mL = hm; s.exL = hex; }
+    if (lane == 63) { s.mR = hm; s.exR = hex; }
+#pragma unroll
+    for (int y = 0; y < FT; ++y) s.g[y] = (colin && y < th) ? (uint32_t)G[(size_t)(y0 + y) * W + cx] : FINF;
+    s.gu = (colin && y0 > 0) ? (uint32_t)G[(size_t)(y0 - 1) * W + cx] : FINF;
+    s.gd = (colin && y0 + FT < H) ? (uint32_t)G[(size_t)(y0 + FT) * W + cx] : FINF;
+    {
+        const int ra = y0 - 1 + lane, rb = y0 + 63 + lane;
+        const bool va = ra >= 0 && ra < H, vb = lane < 2 && rb < H;
+        s.hla = (va && x0 > 0) ? (uint32_t)G[(size_t)ra * W + x0 - 1] : FINF;
+        s.hra = (va && x0 + FT < W) ? (uint32_t)G[(size_t)ra * W + x0 + FT] : FINF;
+        s.hlb = (vb && x0 > 0) ? (uint32_t)G[(size_t)rb * W + x0 - 1] : FINF;
+        s.hrb = (vb && x0 + FT < W) ? (uint32_t)G[(size_t)rb * W + x0 + FT] : FINF;
+    }
+    s.chg = 0;
+    // the root's tile starts with rows that are not closed (0 at the root, INF beside it): its first sweep closes every row
+    const int rt = a.root[f];
+    const bool force = (rt % W) / FT == tx && (rt / W) / FT == ty;
+    bool down = true;
+    for (int n = 0;; ++n) {
+        const bool c = sweep(s, down, lane, force && n == 0);
+        if (!c && n >= 1) break;
+        down = !down;
+    }
+#pragma unroll
+    for (int y = 0; y < FT; ++y)
+        if ((s.chg >> y) & 1ull) G[(size_t)(y0 + y) * W + cx] = (int32_t)s.g[y];
+    // neighbours whose halo holds a changed cell
+    const uint64_t any = __ballot(s.chg != 0ull);
+    if (any == 0ull) return;
+    const bool top = __ballot(s.chg & 1ull) != 0ull, bot = __ballot((s.chg >> (th - 1)) & 1ull) != 0ull;
+    const uint64_t cl = __builtin_amdgcn_readlane((int)(uint32_t)s.chg, 0) | ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(s.chg >> 32), 0) << 32);
+    const uint64_t cr = __builtin_amdgcn_readlane((int)(uint32_t)s.chg, tw - 1) |
+                        ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(s.chg >> 32), tw - 1) << 32);
+    const bool hasL = tx > 0, hasR = tx + 1 < a.TX, hasU = ty > 0, hasD = ty + 1 < a.TY;
+    if (hasU && top) mark(tx, ty - 1);
+    if (hasD && bot) mark(tx, ty + 1);
+    if (hasL && cl) mark(tx - 1, ty);
+    if (hasR && cr) mark(tx + 1, ty);
+    if (hasU && hasL && (cl & 1ull)) mark(tx - 1, ty - 1);
+    if (hasU && hasR && (cr & 1ull)) mark(tx + 1, ty - 1);
+    if (hasD && hasL && ((cl >> (th - 1)) & 1ull)) mark(tx - 1, ty + 1);
+    if (hasD && hasR && ((cr >> (th - 1)) & 1ull)) mark(tx + 1, ty + 1);
+}
+
+// T of 64 rows per (grid, tile row, column)
+__global__ void field_mask_kernel(const int32_t* __restrict__ d2, int G, int W, int H, int TY, int32_t thr, uint64_t* __restrict__ mask) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)G * TY * W) return;
+    const int x = (int)(i % W);
+    const size_t gt = i / W;
+    const int ty = (int)(gt % TY), gi = (int)(gt / TY);
+    const int32_t* D = d2 + (size_t)gi * W * H;
+    uint64_t m = 0;
+    const int y0 = ty * FT, th = min(FT, H - y0);
+    for (int y = 0; y < th; ++y) m |= (uint64_t)(D[(size_t)(y0 + y) * W + x] >= thr) << y;
+    mask[i] = m;
+}
+
+__device__ __forceinline__ bool field_root_ok(const field_args& a, int f) {
+    const int gi = a.fgrid ? a.fgrid[f] : 0;
+    const int r = a.root[f];
+    return gi >= 0 && gi < a.G && r >= 0 && (long long)r < (long long)a.W * a.H && a.d2[(size_t)gi * a.W * a.H + r] >= a.thr;
+}
+
+// g = INF everywhere, 0 at a valid root; grid (blocks, fields), fields strided.  Block 0 of a field writes its status and queues the root's tile
+// for round 0 (stamp 1).
+__global__ void field_init_kernel(field_args a, int32_t* fstatus) {
+    const size_t n = (size_t)a.W * a.H;
+    for (int f = blockIdx.y; f < a.F; f += gridDim.y) {
+        const bool ok = field_root_ok(a, f);
+        const int r = ok ? a.root[f] : -1;
+        int32_t* G = a.g + (size_t)f * n;
+        for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+            G[i] = (int64_t)i == r ? 0 : (int32_t)FINF;
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+            a.ok[f] = ok;
+            if (fstatus) fstatus[f] = ok ? SC_Q_OK : SC_Q_BAD_ENDPOINT;
+            if (ok) {
+                const int t = (r / a.W / FT) * a.TX + (r % a.W) / FT;
+                a.stamp[(size_t)f * a.nt + t] = 1;
+                a.list[0][atomicAdd(a.ctr, 1)] = f * a.nt + t;
+            }
+        }
+    }
+}
+
+// chip-wide round r: one wavefront per queued (field, tile), grid-stride over the list
+__global__ __launch_bounds__(64) void field_round_kernel(field_args a, int r) {
+    const int n = a.ctr[r];
+    const int32_t* cur = a.list[r & 1];
+    int32_t* nxt = a.list[(r + 1) & 1];
+    int32_t* nctr = a.ctr + r + 1;
+    const int lane = threadIdx.x;
+    for (int i = blockIdx.x; i < n; i += gridDim.x) {
+        const int e = cur[i];
+        const int f = e / a.nt, t = e % a.nt;
+        visit_tile(a, f, t % a.TX, t / a.TX, [&](int ux, int uy) {
+            if (lane == 0) {
+                const int u = f * a.nt + uy * a.TX + ux;
+                if (atomicMax(a.stamp + u, r + 2) < r + 2) nxt[atomicAdd(nctr, 1)] = u;
+            }
+        });
+    }
+}
+
+// finisher: one workgroup per field completes the tiles still queued after `rounds` chip-wide rounds
+__global__ __launch_bounds__(64 * FIN_WAVES) void field_finish_kernel(field_args a, int rounds) {
+    __shared__ uint32_t dirty[FIN_MAX_TILES / 32];
+    __shared__ uint16_t work[FIN_MAX_TILES];
+    __shared__ int count;
+    const int f = blockIdx.x;
+    if (!a.ok[f]) return;
+    const int nt = a.nt, nw = (nt + 31) / 32;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    for (int w = tid; w < nw; w += blockDim.x) {
+        uint32_t b = 0;
+        for (int k = 0; k < 32 && w * 32 + k < nt; ++k) b |= (uint32_t)(a.stamp[(size_t)f * nt + w * 32 + k] == rounds + 1) << k;
+        dirty[w] = b;
+    }
+    __syncthreads();
+    for (;;) {
+        if (tid == 0) count = 0;
+        __syncthreads();
+        for (int w = tid; w < nw; w += blockDim.x) {
+            uint32_t b = dirty[w];
+            if (b) {
+                dirty[w] = 0;
+                int p = atomicAdd(&count, __popc(b));
+                while (b) {
+                    const int k = __ffs(b) - 1;
+                    b &= b - 1;
+                    work[p++] = (uint16_t)(w * 32 + k);
+                }
+            }
+        }
+        __syncthreads();
+        const int n = count;
+        if (n == 0) break;
+        for (int i = wave; i < n; i += FIN_WAVES) {
+            const int t = work[i];
+            visit_tile(a, f, t % a.TX, t / a.TX, [&](int ux, int uy) {
+                if (lane == 0) {
+                    const int u = uy * a.TX + ux;
+                    atomicOr(&dirty[u >> 5], 1u << (u & 31));
+                }
+            });
+        }
+        __syncthreads();
+    }
+}
+
+// ---- read-out ------------------------------------------------------------------------------------------------------
+struct paths_args {
+    const int32_t* d2;
+    const int32_t* fgrid;
+    const int32_t* g;
+    const int32_t* root;
+    const int32_t* qfield;
+    const int32_t* target;
+    int G, W, H, F, Q, Lmax, to_root;
+    int32_t thr;
+    int32_t *path, *len, *cost, *status;
+};
+
+__constant__ int RP_DX[8] = {1, -1, 0, 0, 1, -1, 1, -1};
+__constant__ int RP_DY[8] = {0, 0, 1, -1, 1, 1, -1, -1};
+
+__global__ __launch_bounds__(64 * RP_WAVES) void field_paths_kernel(paths_args a) {
+    __shared__ uint32_t win_all[RP_WAVES][RP_WIN * RP_WIN];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int q = blockIdx.x * RP_WAVES + wave;
+    if (q >= a.Q) return;
+    uint32_t* win = win_all[wave];
+    const int W = a.W, H = a.H;
+    const long long n = (long long)W * H;
+    const int fq = a.qfield[q];
+    const int gi = (fq >= 0 && fq < a.F) ? (a.fgrid ? a.fgrid[fq] : 0) : -1;
+    const int r = fq >= 0 && fq < a.F ? a.root[fq] : -1;
+    const int t = a.target[q];
+    const bool ok = gi >= 0 && gi < a.G && r >= 0 && r < n && t >= 0 && t < n && a.d2[(size_t)gi * n + r] >= a.thr &&
+                    a.d2[(size_t)gi * n + t] >= a.thr;
+    if (!ok) {
+        if (lane == 0) { a.len[q] = 0; a.cost[q] = -1; a.status[q] = SC_Q_BAD_ENDPOINT; }
+        return;
+    }
+    const int32_t* G = a.g + (size_t)fq * n;
+    const uint32_t gt = (uint32_t)G[t];
+    if (gt >= FINF) {
+        if (lane == 0) { a.len[q] = 0; a.cost[q] = -1; a.status[q] = SC_Q_NO_PATH; }
+        return;
+    }
+    int32_t* P = a.path + (size_t)q * a.Lmax;
+    const int rx = r % W, ry = r / W;
+    int cx = t % W, cy = t / W;
+    uint32_t gc = gt;
+    long long L = 1;
+    if (lane == 0) P[0] = t;
+    bool fail = false;
+    while (!(cx == rx && cy == ry)) {
+        // window placed so that the walk, which heads for the root, has room in the root's direction
+        const int ox = cx - (rx < cx ? RP_WIN - 3 : (rx > cx ? 2 : RP_WIN / 2));
+        const int oy = cy - (ry < cy ? RP_WIN - 3 : (ry > cy ? 2 : RP_WIN / 2));
+#pragma unroll
+        for (int k = 0; k < RP_WIN * RP_WIN / 64; ++k) {
+            const int i = k * 64 + lane, wx = ox + (i % RP_WIN), wy = oy + (i / RP_WIN);
+            win[i] = (wx >= 0 && wx < W && wy >= 0 && wy < H) ? (uint32_t)G[(size_t)wy * W + wx] : FINF;
+        }
+        wave_lds_sync();
+        // parent rule inside the window (c and its 8 neighbours must lie in it)
+        while (!(cx == rx && cy == ry) && cx - ox >= 1 && cx - ox <= RP_WIN - 2 && cy - oy >= 1 && cy - oy <= RP_WIN - 2) {
+            const int lx = cx - ox, ly = cy - oy;
+            int d = 0;
+            for (; d < 8; ++d) {
+                const int px = cx - RP_DX[d], py = cy - RP_DY[d];
+                if (px < 0 || py < 0 || px >= W || py >= H) continue;
+                const uint32_t gp = win[(ly - RP_DY[d]) * RP_WIN + lx - RP_DX[d]];
+                if (gp >= FINF || gp + (d < 4 ? 10u : 14u) != gc) continue;
+                // side cells of a diagonal: reachable <=> traversable next to a reachable cell
+                if (d >= 4 && (win[ly * RP_WIN + lx - RP_DX[d]] >= FINF || win[(ly - RP_DY[d]) * RP_WIN + lx] >= FINF)) continue;
+                break;
+            }
+            if (d == 8 || L >= n) { fail = true; break; }
+            cx -= RP_DX[d]; cy -= RP_DY[d];
+            gc -= d < 4 ? 10u : 14u;
+            if (lane == 0 && L < a.Lmax) P[L] = cy * W + cx;
+            ++L;
+        }
+        wave_lds_sync();
+        if (fail) break;
+    }
+    if (fail) {
+        if (lane == 0) { a.len[q] = 0; a.cost[q] = -1; a.status[q] = SC_Q_NO_PATH; }
+        return;
+    }
+    const int Li = (int)L;
+    if (Li <= a.Lmax && !a.to_root) {
+        __threadfence_block();   // lane 0 wrote the walk; every lane reverses it
+        for (int i = lane; i < Li / 2; i += 64) {
+            const int32_t u = P[i], v = P[Li - 1 - i];
+            P[i] = v;
+            P[Li - 1 - i] = u;
+        }
+    }
+    if (lane == 0) { a.len[q] = Li; a.cost[q] = (int32_t)gt; a.status[q] = Li <= a.Lmax ? SC_Q_OK : SC_Q_TRUNCATED; }
+}
+
+int field_default_rounds(int TX, int TY) { return 2 * (TX + TY) + 16; }
+
+}  // namespace
+
+extern "C" int sc_cost_field_batch(sc_ctx* ctx, const int32_t* d2, int G, const int32_t* fgrid, int W, int H, int32_t r2_clear,
+                                   const int32_t* root, int F, int rounds, int32_t* g, int32_t* fstatus) {
+    if (!ctx || !d2 || !root || !g || G <= 0 || F <= 0 || W <= 0 || H <= 0 || W > SC_MAX_DIM || H > SC_MAX_DIM || (!fgrid && G != 1))
+        return SC_ERR_INVALID;
+    SC_HIP(ctx, hipSetDevice(ctx->device));
+    const int TX = (W + FT - 1) / FT, TY = (H + FT - 1) / FT, nt = TX * TY;
+    if ((long long)F * nt > 0x7FFFFFFF / 2) return SC_ERR_INVALID;
+    if (rounds < 0) rounds = field_default_rounds(TX, TY);
+    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t mask_b = (size_t)G * TY * W * 8;
+    const size_t o_ok = 0, o_stamp = al((size_t)F * 4), o_l0 = o_stamp + al((size_t)F * nt * 4), o_l1 = o_l0 + al((size_t)F * nt * 4),
+                 o_ctr = o_l1 + al((size_t)F * nt * 4), total = o_ctr + al((size_t)(rounds + 1) * 4);
+    int r = sc_scratch_reserve(ctx, &ctx->fld_mask, mask_b);
+    if (r == SC_OK) r = sc_scratch_reserve(ctx, &ctx->fld_state, total);
+    if (r != SC_OK) return r;
+    char* b = (char*)ctx->fld_state.p;
+    field_args a;
+    a.mask = (const uint64_t*)ctx->fld_mask.p; a.d2 = d2; a.fgrid = fgrid; a.root = root; a.g = g;
+    a.ok = (int32_t*)(b + o_ok); a.stamp = (int32_t*)(b + o_stamp);
+    a.list[0] = (int32_t*)(b + o_l0); a.list[1] = (int32_t*)(b + o_l1); a.ctr = (int32_t*)(b + o_ctr);
+    a.G = G; a.W = W; a.H = H; a.F = F; a.TX = TX; a.TY = TY; a.nt = nt;
+    a.thr = r2_clear > 1 ? r2_clear : 1;
+    int tk = sc_time_begin(ctx, SC_K_ASTAR);
+    SC_HIP(ctx, hipMemsetAsync(b + o_stamp, 0, (size_t)F * nt * 4, ctx->stream));
+    SC_HIP(ctx, hipMemsetAsync(b + o_ctr, 0, (size_t)(rounds + 1) * 4, ctx->stream));
+    {
+        const size_t nm = (size_t)G * TY * W;
+        hipLaunchKernelGGL(field_mask_kernel, dim3((unsigned)((nm + 255) / 256)), dim3(256), 0, ctx->stream, d2, G, W, H, TY, a.thr,
+                           (uint64_t*)ctx->fld_mask.p);
+    }
+    {
+        const size_t n = (size_t)W * H;
+        unsigned bx = (unsigned)((n + 1023) / 1024);
+        if (bx > 1024) bx = 1024;
+        hipLaunchKernelGGL(field_init_kernel, dim3(bx, F < 65535 ? F : 65535), dim3(1024), 0, ctx->stream, a, fstatus);
+    }
+    if (rounds > 0) {
+        if (!ctx->cu_count) {
+            int cu = 0;
+            SC_HIP(ctx, hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, ctx->device));
+            ctx->cu_count = cu > 0 ? cu : 1;
+        }
+        const long long cap = (long long)ctx->cu_count * 8;
+        const unsigned blocks = (unsigned)((long long)F * nt < cap ? (long long)F * nt : cap);
+        for (int k = 0; k < rounds; ++k) hipLaunchKernelGGL(field_round_kernel, dim3(blocks), dim3(64), 0, ctx->stream, a, k);
+    }
+    hipLaunchKernelGGL(field_finish_kernel, dim3(F), dim3(64 * FIN_WAVES), 0, ctx->stream, a, rounds);
+    sc_time_end(ctx, tk);
+    SC_HIP(ctx, hipGetLastError());
+    return SC_OK;
+}
+
+extern "C" int sc_field_paths_batch(sc_ctx* ctx, const int32_t* d2, int G, const int32_t* fgrid, int W, int H, int32_t r2_clear,
+                                    const int32_t* g, const int32_t* root, int F, const int32_t* qfield, const int32_t* target, int Q,
+                                    int Lmax, int to_root, int32_t* path, int32_t* len, int32_t* cost, int32_t* status) {
+    if (!ctx || !d2 || !g || !root || !qfield || !target || !path || !len || !cost || !status || G <= 0 || F <= 0 || W <= 0 || H <= 0 ||
+        W > SC_MAX_DIM || H > SC_MAX_DIM || Q < 0 || Lmax <= 0 || (!fgrid && G != 1))
+        return SC_ERR_INVALID;
+    if (Q == 0) return SC_OK;
+    SC_HIP(ctx, hipSetDevice(ctx->device));
+    paths_args a{d2, fgrid, g, root, qfield, target, G, W, H, F, Q, Lmax, to_root ? 1 : 0, r2_clear > 1 ? r2_clear : 1, path, len, cost, status};
+    int tk = sc_time_begin(ctx, SC_K_ASTAR);
+    hipLaunchKernelGGL(field_paths_kernel, dim3((unsigned)((Q + RP_WAVES - 1) / RP_WAVES)), dim3(64 * RP_WAVES), 0, ctx->stream, a);
+    sc_time_end(ctx, tk);
+    SC_HIP(ctx, hipGetLastError());
+    return SC_OK;
+}
+
+extern "C" int sc_cost_field_batch_host(sc_ctx* ctx, const int32_t* d2, int G, const int32_t* fgrid, int W, int H, int32_t r2_clear,
+                                        const int32_t* root, int F, int rounds, int32_t* g, int32_t* fstatus) {
+    if (!ctx || !d2 || !root || !g || G <= 0 || F <= 0 || W <= 0 || H <= 0 || W > SC_MAX_DIM || H > SC_MAX_DIM || (!fgrid && G != 1))
+        return SC_ERR_INVALID;
+    SC_HIP(ctx, hipSetDevice(ctx->device));
+    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t n = (size_t)W * H;
+    const size_t o_d2 = 0, o_fg = al((size_t)G * n * 4), o_rt = o_fg + al((size_t)F * 4), o_g = o_rt + al((size_t)F * 4),
+                 o_st = o_g + al((size_t)F * n * 4), total = o_st + al((size_t)F * 4);
+    int r = sc_scratch_reserve(ctx, &ctx->fld_stage, total);
+    if (r != SC_OK) return r;
+    char* b = (char*)ctx->fld_stage.p;
+    SC_HIP(ctx, hipMemcpyAsync(b + o_d2, d2, (size_t)G * n * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (fgrid) SC_HIP(ctx, hipMemcpyAsync(b + o_fg, fgrid, (size_t)F * 4, hipMemcpyHostToDevice, ctx->stream));
+    SC_HIP(ctx, hipMemcpyAsync(b + o_rt, root, (size_t)F * 4, hipMemcpyHostToDevice, ctx->stream));
+    r = sc_cost_field_batch(ctx, (const int32_t*)(b + o_d2), G, fgrid ? (const int32_t*)(b + o_fg) : nullptr, W, H, r2_clear,
+                            (const int32_t*)(b + o_rt), F, rounds, (int32_t*)(b + o_g), (int32_t*)(b + o_st));
+    if (r != SC_OK) return r;
+    SC_HIP(ctx, hipMemcpyAsync(g, b + o_g, (size_t)F * n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (fstatus) SC_HIP(ctx, hipMemcpyAsync(fstatus, b + o_st, (size_t)F * 4, hipMemcpyDeviceToHost, ctx->stream));
+    return sc_ctx_synchronize(ctx);
+}
+
+extern "C" int sc_field_paths_batch_host(sc_ctx* ctx, const int32_t* d2, int G, const int32_t* fgrid, int W, int H, int32_t r2_clear,
+                                         const int32_t* g, const int32_t* root, int F, const int32_t* qfield, const int32_t* target, int Q,
+                                         int Lmax, int to_root, int32_t* path, int32_t* len, int32_t* cost, int32_t* status) {
+    if (!ctx || !d2 || !g || !root || !qfield || !target || !path || !len || !cost || !status || G <= 0 || F <= 0 || W <= 0 || H <= 0 ||
+        W > SC_MAX_DIM || H > SC_MAX_DIM || Q < 0 || Lmax <= 0 || (!fgrid && G != 1))
+        return SC_ERR_INVALID;
+    if (Q == 0) return SC_OK;
+    // data contract: every g value is a cost or SC_FIELD_INF
+    const size_t n = (size_t)W * H;
+    for (size_t i = 0; i < (size_t)F * n; ++i)
+        if (g[i] < 0) return SC_ERR_INVALID;
+    SC_HIP(ctx, hipSetDevice(ctx->device));
+    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t qb = al((size_t)Q * 4);
+    const size_t o_d2 = 0, o_fg = al((size_t)G * n * 4), o_g = o_fg + al((size_t)F * 4), o_rt = o_g + al((size_t)F * n * 4),
+                 o_qf = o_rt + al((size_t)F * 4), o_t = o_qf + qb, o_p = o_t + qb, o_len = o_p + al((size_t)Q * Lmax * 4),
+                 o_c = o_len + qb, o_s = o_c + qb, total = o_s + qb;
+    int r = sc_scratch_reserve(ctx, &ctx->fld_stage, total);
+    if (r != SC_OK) return r;
+    char* b = (char*)ctx->fld_stage.p;
+    SC_HIP(ctx, hipMemcpyAsync(b + o_d2, d2, (size_t)G * n * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (fgrid) SC_HIP(ctx, hipMemcpyAsync(b + o_fg, fgrid, (size_t)F * 4, hipMemcpyHostToDevice, ctx->stream));
+    SC_HIP(ctx, hipMemcpyAsync(b + o_g, g, (size_t)F * n * 4, hipMemcpyHostToDevice, ctx->stream));
+    SC_HIP(ctx, hipMemcpyAsync(b + o_rt, root, (size_t)F * 4, hipMemcpyHostToDevice, ctx->stream));
+    SC_HIP(ctx, hipMemcpyAsync(b + o_qf, qfield, (size_t)Q * 4, hipMemcpyHostToDevice, ctx->stream));
+    SC_HIP(ctx, hipMemcpyAsync(b + o_t, target, (size_t)Q * 4, hipMemcpyHostToDevice, ctx->stream));
+    r = sc_field_paths_batch(ctx, (const int32_t*)(b + o_d2), G, fgrid ? (const int32_t*)(b + o_fg) : nullptr, W, H, r2_clear,
+                             (const int32_t*)(b + o_g), (const int32_t*)(b + o_rt), F, (const int32_t*)(b + o_qf), (const int32_t*)(b + o_t),
+                             Q, Lmax, to_root, (int32_t*)(b + o_p), (int32_t*)(b + o_len), (int32_t*)(b + o_c), (int32_t*)(b + o_s));
+    if (r != SC_OK) return r;
+    SC_HIP(ctx, hipMemcpyAsync(path, b + o_p, (size_t)Q * Lmax * 4, hipMemcpyDeviceToHost, ctx->stream));
+    SC_HIP(ctx, hipMemcpyAsync(len, b + o_len, (size_t)Q * 4, hipMemcpyDeviceToHost, ctx->stream));
+    SC_HIP(ctx, hipMemcpyAsync(cost, b + o_c, (size_t)Q * 4, hipMemcpyDeviceToHost, ctx->stream));
+    SC_HIP(ctx, hipMemcpyAsync(status, b + o_s, (size_t)Q * 4, hipMemcpyDeviceToHost, ctx->stream));
+    return sc_ctx_synchronize(ctx);
+}

@@ -54,6 +54,9 @@ struct sc_ctx {
     sc_scratch sm_stage;    // smoothing: sc_smooth_paths_batch_host's device copies
     sc_scratch occ_prep;    // polygon occupancy: float4 box [n_obs] | int2 cell-row range [n_obs] of every obstacle
     sc_scratch occ_stage;   // polygon occupancy: sc_occ_from_polygons_host's device copies
+    sc_scratch fld_mask;    // cost fields: uint64 [G][tile rows][W] traversability of 64 rows per column
+    sc_scratch fld_state;   // cost fields: per-field ok [F] | tile stamps [F][tiles] | two tile lists [F * tiles] | round counts
+    sc_scratch fld_stage;   // cost fields: the _host forms' device copies
     sc_scratch staging[9];  // _host wrappers
     int astar_cap = 1 << 16;          // ring entries per bucket (power of two)
     size_t astar_slot_budget = (size_t)96 << 30;  // bytes of g + bitmap + ring scratch this context may take (SC_ASTAR_SLOT_GB), further bounded by what the device has free; 4096^2: 96 GiB = 1966 slots measured best (48: -34 %, 160: -17 %)

@@ -18,6 +18,7 @@ LIB_PATH = os.environ.get("SC_LIB_PATH") or os.path.join(NATIVE_DIR, "libsea_cur
 HEADER_PATH = os.path.join(REPO_ROOT, "include", "sea_current_hip.h")
 
 EDT_INF = 2**31 - 1
+FIELD_INF = 2**31 - 1
 Q_OK, Q_NO_PATH, Q_BAD_ENDPOINT, Q_TRUNCATED, Q_RING_OVERFLOW, Q_BAD_PATH = 0, 1, 2, 3, 4, 5
 K_EDT_COLBITS, K_EDT_BAND, K_MOVES, K_ASTAR, K_TOPPRA, K_TOPPRA_SAMPLE, K_BEZIER, K_ARCLENGTH, K_RESAMPLE, K_OCC, K_NEAREST, K_FMT, K_GATHER = range(13)
 K_WAYPOINTS = 13
@@ -65,6 +66,10 @@ _SIGNATURES = {
     "sc_astar_gfield": (_i, [_vp, _vp, _i, _i, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp]),
     "sc_path_waypoints_batch": (_i, [_vp, _vp, _i, _i, C.c_int32, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "sc_path_waypoints_batch_host": (_i, [_vp, _vp, _i, _i, C.c_int32, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "sc_cost_field_batch": (_i, [_vp, _vp, _i, _vp, _i, _i, C.c_int32, _vp, _i, _i, _vp, _vp]),
+    "sc_cost_field_batch_host": (_i, [_vp, _vp, _i, _vp, _i, _i, C.c_int32, _vp, _i, _i, _vp, _vp]),
+    "sc_field_paths_batch": (_i, [_vp, _vp, _i, _vp, _i, _i, C.c_int32, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "sc_field_paths_batch_host": (_i, [_vp, _vp, _i, _vp, _i, _i, C.c_int32, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "sc_toppra_hermite_batch": (_i, [_vp, _i, _i, _i] + [_vp] * 6 + [_i, _vp, _vp, _d, _d] + [_vp] * 5),
     "sc_toppra_hermite_batch_host": (_i, [_vp, _i, _i, _i] + [_vp] * 6 + [_i, _vp, _vp, _d, _d] + [_vp] * 5),
     "sc_toppra_sample_batch": (_i, [_vp, _i, _i, _i] + [_vp] * 6 + [_d, _i] + [_vp] * 5),
@@ -241,6 +246,36 @@ class Context:
                        cost=torch.empty(Q, dtype=torch.int32, device=dev), status=torch.empty(Q, dtype=torch.int32, device=dev))
         self._ck(self._l.sc_astar_batch_multi(self._h, _ptr(d2), G, _ptr(qgrid), W, H, r2, _ptr(start), _ptr(goal), Q, Lmax,
                                               _ptr(out["path"]), _ptr(out["len"]), _ptr(out["cost"]), _ptr(out["status"])), "sc_astar_batch_multi")
+        return out
+
+    def cost_fields(self, d2, roots, r2=0, fgrid=None, rounds=-1, out=None):
+        """Cost-to-come fields (sc_cost_field_batch).  d2 int32 [H,W] or [G,H,W], roots int32 [F], fgrid int32 [F] (the grid
+        of every field; None only with one grid), all on the GPU.  Returns dict(g int32 [F,H,W], status int32 [F])."""
+        import torch
+        G, H, W = (1,) + tuple(d2.shape) if d2.dim() == 2 else tuple(d2.shape)
+        F = roots.shape[0]
+        dev = d2.device
+        if out is None:
+            out = dict(g=torch.empty((F, H, W), dtype=torch.int32, device=dev), status=torch.empty(F, dtype=torch.int32, device=dev))
+        self._ck(self._l.sc_cost_field_batch(self._h, _ptr(d2), G, _ptr(fgrid), W, H, r2, _ptr(roots), F, rounds, _ptr(out["g"]),
+                                             _ptr(out["status"])), "sc_cost_field_batch")
+        return out
+
+    def field_paths(self, d2, g, roots, qfield, targets, r2=0, Lmax=4096, to_root=False, fgrid=None, out=None):
+        """Paths read from cost fields (sc_field_paths_batch): query q follows field qfield[q] (g int32 [F,H,W] and roots [F]
+        as cost_fields took and returned them) to targets[q].  Returns astar_batch's dict of GPU tensors; to_root=True
+        writes every path target..root."""
+        import torch
+        G, H, W = (1,) + tuple(d2.shape) if d2.dim() == 2 else tuple(d2.shape)
+        F = roots.shape[0]
+        Q = targets.shape[0]
+        dev = d2.device
+        if out is None:
+            out = dict(path=torch.empty((Q, Lmax), dtype=torch.int32, device=dev), len=torch.empty(Q, dtype=torch.int32, device=dev),
+                       cost=torch.empty(Q, dtype=torch.int32, device=dev), status=torch.empty(Q, dtype=torch.int32, device=dev))
+        self._ck(self._l.sc_field_paths_batch(self._h, _ptr(d2), G, _ptr(fgrid), W, H, r2, _ptr(g), _ptr(roots), F, _ptr(qfield),
+                                              _ptr(targets), Q, Lmax, int(bool(to_root)), _ptr(out["path"]), _ptr(out["len"]),
+                                              _ptr(out["cost"]), _ptr(out["status"])), "sc_field_paths_batch")
         return out
 
     def path_waypoints(self, d2, res, r2=0, Wmax=None, out=None):
@@ -630,6 +665,33 @@ class Context:
         self._ck(self._l.sc_astar_batch_host(self._h, _ptr(d2), W, H, r2, _ptr(start), _ptr(goal), Q, Lmax,
                                              _ptr(out["path"]), _ptr(out["len"]), _ptr(out["cost"]),
                                              _ptr(out["status"])), "sc_astar_batch_host")
+        return out
+
+    def cost_fields_host(self, d2, roots, r2=0, fgrid=None, rounds=-1):
+        """Host form of cost_fields (numpy in, numpy out)."""
+        d2 = np.ascontiguousarray(d2, dtype=np.int32)
+        roots = np.ascontiguousarray(roots, dtype=np.int32)
+        fgrid = None if fgrid is None else np.ascontiguousarray(fgrid, dtype=np.int32)
+        G, H, W = (1,) + d2.shape if d2.ndim == 2 else d2.shape
+        F = roots.shape[0]
+        out = dict(g=np.zeros((F, H, W), np.int32), status=np.zeros(F, np.int32))
+        self._ck(self._l.sc_cost_field_batch_host(self._h, _ptr(d2), G, _ptr(fgrid), W, H, r2, _ptr(roots), F, rounds, _ptr(out["g"]),
+                                                  _ptr(out["status"])), "sc_cost_field_batch_host")
+        return out
+
+    def field_paths_host(self, d2, g, roots, qfield, targets, r2=0, Lmax=4096, to_root=False, fgrid=None):
+        """Host form of field_paths (numpy in, numpy out)."""
+        d2 = np.ascontiguousarray(d2, dtype=np.int32)
+        g = np.ascontiguousarray(g, dtype=np.int32)
+        roots, qfield, targets = (np.ascontiguousarray(a, dtype=np.int32) for a in (roots, qfield, targets))
+        fgrid = None if fgrid is None else np.ascontiguousarray(fgrid, dtype=np.int32)
+        G, H, W = (1,) + d2.shape if d2.ndim == 2 else d2.shape
+        F, Q = roots.shape[0], targets.shape[0]
+        out = dict(path=np.full((Q, Lmax), -1, dtype=np.int32), len=np.zeros(Q, np.int32), cost=np.zeros(Q, np.int32),
+                   status=np.zeros(Q, np.int32))
+        self._ck(self._l.sc_field_paths_batch_host(self._h, _ptr(d2), G, _ptr(fgrid), W, H, r2, _ptr(g), _ptr(roots), F, _ptr(qfield),
+                                                   _ptr(targets), Q, Lmax, int(bool(to_root)), _ptr(out["path"]), _ptr(out["len"]),
+                                                   _ptr(out["cost"]), _ptr(out["status"])), "sc_field_paths_batch_host")
         return out
 
     def path_waypoints_host(self, d2, path, lens, status=None, r2=0, Wmax=None):

@@ -23,6 +23,7 @@
 //   (new) occupancy_grid::waypoints_batch, planning_space::simplify_paths: A* cell paths -> line-of-sight waypoints
 //   (new) smooth_paths_batch: from_path -> arclength -> gen_vel_prof<1> -> resample(nudge) -> ang_vel for many paths, one call
 //   (new) occupancy_grid::rasterize(obstacles, ctx), planning_space::make_grid(ctx): the polygon rasteriser on the GPU
+//   (new) occupancy_grid::cost_fields / field_paths, planning_space::plan_from / plan_to: one search per shared endpoint
 //
 // Differences that are deliberate: obstacle::closed is initialised (the reference leaves it
 // uninitialised, :197); library code never prints or calls std::exit (SC_ASSERT throws in DEBUG);
@@ -400,6 +401,44 @@ public:
                                       r.path.data(), r.len.data(), r.cost.data(), r.status.data()), "sc_astar_batch_host");
         return r;
     }
+    // Cost-to-come fields (sc_cost_field_batch): g[f] = the optimal A* cost from roots[f] to every cell, SC_FIELD_INF where
+    // there is none; status[f] SC_Q_OK or SC_Q_BAD_ENDPOINT.  rounds < 0: the library default.
+    struct field_result {
+        std::vector<int32_t> g, status, roots;  // g is [F][H][W]
+        int32_t r2 = 0;
+    };
+    field_result cost_fields(const std::vector<int32_t>& roots, int32_t r2_clear = 0, int rounds = -1,
+                             gpu_context& ctx = default_context()) {
+        if (d2.size() != occ.size()) edt(ctx);
+        field_result r;
+        const int F = (int)roots.size();
+        r.roots = roots;
+        r.r2 = r2_clear;
+        r.g.assign((size_t)F * W * H, SC_FIELD_INF); r.status.assign(F, SC_Q_BAD_ENDPOINT);
+        if (F == 0) return r;
+        ctx.check(sc_cost_field_batch_host(ctx.get(), d2.data(), 1, nullptr, W, H, r2_clear, roots.data(), F, rounds, r.g.data(),
+                                           r.status.data()),
+                  "sc_cost_field_batch_host");
+        return r;
+    }
+    // Paths read from fields (sc_field_paths_batch): query q follows field qfield[q] to targets[q].  Equal to astar_batch
+    // with start roots[qfield[q]] and goal targets[q] (to_root = false), or to its paths reversed (to_root = true).
+    batch_result field_paths(const field_result& fr, const std::vector<int32_t>& qfield, const std::vector<int32_t>& targets,
+                             int Lmax = 0, bool to_root = false, gpu_context& ctx = default_context()) {
+        if (d2.size() != occ.size()) edt(ctx);
+        batch_result r;
+        const int Q = (int)targets.size(), F = (int)fr.roots.size();
+        if (qfield.size() != targets.size()) throw std::invalid_argument("occupancy_grid::field_paths: qfield and targets differ in size");
+        r.Lmax = Lmax > 0 ? Lmax : 4 * (W + H);
+        r.path.assign((size_t)Q * r.Lmax, -1); r.len.assign(Q, 0); r.cost.assign(Q, -1); r.status.assign(Q, SC_Q_NO_PATH);
+        if (Q == 0) return r;
+        if (F == 0) { r.status.assign(Q, SC_Q_BAD_ENDPOINT); return r; }
+        ctx.check(sc_field_paths_batch_host(ctx.get(), d2.data(), 1, nullptr, W, H, fr.r2, fr.g.data(), fr.roots.data(), F, qfield.data(),
+                                            targets.data(), Q, r.Lmax, to_root ? 1 : 0, r.path.data(), r.len.data(), r.cost.data(),
+                                            r.status.data()),
+                  "sc_field_paths_batch_host");
+        return r;
+    }
     struct waypoint_result {
         std::vector<int32_t> wp, n, status;  // wp is [Q][Wmax] cell indices, start..goal; n / status [Q]
         int Wmax = 0;
@@ -614,16 +653,55 @@ public:
         g.edt(ctx);
         std::vector<int32_t> s(starts.size()), t(goals.size());
         for (size_t i = 0; i < starts.size(); ++i) { s[i] = g.cell_of(starts[i]); t[i] = g.cell_of(goals[i]); }
-        const float cc = clearance / g.resolution;
-        const int32_t r2 = (int32_t)std::ceil(cc * cc);
+        const int32_t r2 = clearance_r2(g);
         auto br = g.astar_batch(s, t, r2, 0, ctx);
+        return to_points(g, br, r2, starts, goals, "plan_batch", ctx);
+    }
+    // One start, many goals (ranking candidate goals): one cost field rooted at the start's cell instead of one A* search
+    // per goal.  Returns exactly plan_batch(std::vector<Vector2f>(goals.size(), start), goals, ctx).
+    std::vector<std::optional<std::vector<Vector2f>>> plan_from(const Vector2f& start, const std::vector<Vector2f>& goals,
+                                                                gpu_context& ctx = default_context()) {
+        occupancy_grid g = make_grid(ctx);
+        g.edt(ctx);
+        std::vector<int32_t> t(goals.size()), qf(goals.size(), 0);
+        for (size_t i = 0; i < goals.size(); ++i) t[i] = g.cell_of(goals[i]);
+        const int32_t r2 = clearance_r2(g);
+        auto fr = g.cost_fields({g.cell_of(start)}, r2, -1, ctx);
+        auto br = g.field_paths(fr, qf, t, 0, false, ctx);
+        return to_points(g, br, r2, std::vector<Vector2f>(goals.size(), start), goals, "plan_from", ctx);
+    }
+    // Many starts, one goal (a fleet heading to one goal): one cost field rooted at the goal's cell.  Entry q runs
+    // starts[q]..goal; with simplify_paths off it is plan_batch({goal}, {starts[q]})[0] reversed, with it on the waypoints
+    // of that start..goal cell path.
+    std::vector<std::optional<std::vector<Vector2f>>> plan_to(const std::vector<Vector2f>& starts, const Vector2f& goal,
+                                                              gpu_context& ctx = default_context()) {
+        occupancy_grid g = make_grid(ctx);
+        g.edt(ctx);
+        std::vector<int32_t> s(starts.size()), qf(starts.size(), 0);
+        for (size_t i = 0; i < starts.size(); ++i) s[i] = g.cell_of(starts[i]);
+        const int32_t r2 = clearance_r2(g);
+        auto fr = g.cost_fields({g.cell_of(goal)}, r2, -1, ctx);
+        auto br = g.field_paths(fr, qf, s, 0, true, ctx);
+        return to_points(g, br, r2, starts, std::vector<Vector2f>(starts.size(), goal), "plan_to", ctx);
+    }
+
+private:
+    int32_t clearance_r2(const occupancy_grid& g) const {
+        const float cc = clearance / g.resolution;
+        return (int32_t)std::ceil(cc * cc);
+    }
+    // cell paths (astar_batch's layout) -> the exact endpoints around the centres of the interior cells or waypoints
+    std::vector<std::optional<std::vector<Vector2f>>> to_points(occupancy_grid& g, const occupancy_grid::batch_result& br, int32_t r2,
+                                                                const std::vector<Vector2f>& starts, const std::vector<Vector2f>& goals,
+                                                                const char* who, gpu_context& ctx) const {
         occupancy_grid::waypoint_result wr;
         if (simplify_paths) wr = g.waypoints_batch(br, r2, ctx);
         std::vector<std::optional<std::vector<Vector2f>>> out(starts.size());
         for (size_t q = 0; q < starts.size(); ++q) {
             if (br.status[q] != SC_Q_OK) continue;
             if (simplify_paths && wr.status[q] != SC_Q_OK)
-                throw std::runtime_error("planning_space::plan_batch: waypoints of an A* path: status " + std::to_string(wr.status[q]));
+                throw std::runtime_error(std::string("planning_space::") + who + ": waypoints of an A* path: status " +
+                                         std::to_string(wr.status[q]));
             const int32_t* cells = simplify_paths ? &wr.wp[(size_t)q * wr.Wmax] : &br.path[(size_t)q * br.Lmax];
             const int n = simplify_paths ? wr.n[q] : br.len[q];
             std::vector<Vector2f> wp;
