@@ -1229,9 +1229,9 @@ extern "C" int sc_astar_gfield(sc_ctx* ctx, const int32_t* d2, int W, int H, int
     SC_HIP(ctx, hipSetDevice(ctx->device));
     const size_t cells = (size_t)W * H;
     // scratch: start, goal, len, path(1)
-    int r = sc_scratch_reserve(ctx, &ctx->staging[7], 64);
+    int r = sc_scratch_reserve(ctx, &ctx->astar_ends, 64);
     if (r != SC_OK) return r;
-    int32_t* sg = (int32_t*)ctx->staging[7].p;
+    int32_t* sg = (int32_t*)ctx->astar_ends.p;
     int32_t h[2] = {start, goal};
     SC_HIP(ctx, hipMemcpyAsync(sg, h, 8, hipMemcpyHostToDevice, ctx->stream));
     SC_HIP(ctx, hipStreamSynchronize(ctx->stream));

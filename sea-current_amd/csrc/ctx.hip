@@ -35,12 +35,6 @@ extern "C" int sc_ctx_create(int device, sc_ctx** out) {
     return SC_OK;
 }
 
-static void free_scratch(sc_scratch* s) {
-    if (s->p) (void)hipFree(s->p);
-    s->p = nullptr;
-    s->bytes = 0;
-}
-
 extern "C" int sc_ctx_destroy(sc_ctx* ctx) {
     if (!ctx) return SC_ERR_INVALID;
     (void)hipSetDevice(ctx->device);
@@ -49,13 +43,8 @@ extern "C" int sc_ctx_destroy(sc_ctx* ctx) {
     for (auto& p : ctx->pending) { if (!p.shared_a) (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     for (auto e : ctx->ev_pool) (void)hipEventDestroy(e);
     if (ctx->wait_ev) (void)hipEventDestroy(ctx->wait_ev);
-    free_scratch(&ctx->colbits); free_scratch(&ctx->updown); free_scratch(&ctx->edt_fault); free_scratch(&ctx->fmt_nbr); free_scratch(&ctx->edt_flags); free_scratch(&ctx->moves); free_scratch(&ctx->gslots);
-    free_scratch(&ctx->buckets); free_scratch(&ctx->qstats); free_scratch(&ctx->closed); free_scratch(&ctx->actr); free_scratch(&ctx->bez_tang); free_scratch(&ctx->bez_gl); free_scratch(&ctx->bez_seginfo); free_scratch(&ctx->cheb_a); free_scratch(&ctx->gather_msg); free_scratch(&ctx->wp_spill);
-    free_scratch(&ctx->sm_ctrl); free_scratch(&ctx->sm_cum); free_scratch(&ctx->sm_tp); free_scratch(&ctx->sm_int); free_scratch(&ctx->sm_smp); free_scratch(&ctx->sm_stage); free_scratch(&ctx->occ_prep); free_scratch(&ctx->occ_stage);
-    free_scratch(&ctx->fld_mask); free_scratch(&ctx->fld_state); free_scratch(&ctx->fld_stage);
-    for (auto& s : ctx->staging) free_scratch(&s);
     (void)hipStreamDestroy(ctx->own_stream);
-    delete ctx;
+    delete ctx;   // the scratch buffers free themselves
     return SC_OK;
 }
 
@@ -120,23 +109,40 @@ int sc_scratch_reserve(sc_ctx* ctx, sc_scratch* s, size_t bytes) {
     if (s->p) {
         SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
         SC_HIP(ctx, hipFree(s->p));
+        ctx->scratch_total -= s->bytes;
         s->p = nullptr;
         s->bytes = 0;
     }
     SC_HIP(ctx, hipMalloc(&s->p, bytes));
     s->bytes = bytes;
+    ctx->scratch_total += bytes;
     return SC_OK;
 }
 
 extern "C" int sc_ctx_scratch_bytes(sc_ctx* ctx, int64_t* bytes) {
     if (!ctx || !bytes) return SC_ERR_INVALID;
-    size_t b = ctx->colbits.bytes + ctx->updown.bytes + ctx->edt_fault.bytes + ctx->edt_flags.bytes + ctx->moves.bytes + ctx->gslots.bytes + ctx->closed.bytes + ctx->buckets.bytes +
-               ctx->qstats.bytes + ctx->actr.bytes + ctx->bez_tang.bytes + ctx->bez_gl.bytes + ctx->bez_seginfo.bytes + ctx->cheb_a.bytes + ctx->gather_msg.bytes + ctx->fmt_nbr.bytes + ctx->wp_spill.bytes +
-               ctx->sm_ctrl.bytes + ctx->sm_cum.bytes + ctx->sm_tp.bytes + ctx->sm_int.bytes + ctx->sm_smp.bytes + ctx->sm_stage.bytes + ctx->occ_prep.bytes + ctx->occ_stage.bytes +
-               ctx->fld_mask.bytes + ctx->fld_state.bytes + ctx->fld_stage.bytes;
-    for (auto& s : ctx->staging) b += s.bytes;
-    *bytes = (int64_t)b;
+    *bytes = (int64_t)ctx->scratch_total;
     return SC_OK;
+}
+
+int sc_stage::upload() {
+    const int r = sc_scratch_reserve(ctx_, &ctx_->host_stage, end_);
+    if (r != SC_OK) return r;
+    for (const copy& c : up_) SC_HIP(ctx_, hipMemcpyAsync(dev<char>(c.slot), c.host, c.bytes, hipMemcpyHostToDevice, ctx_->stream));
+    up_.clear();
+    return SC_OK;
+}
+
+int sc_stage::finish(int r) {
+    auto download = [&]() -> int {
+        for (const copy& c : down_) SC_HIP(ctx_, hipMemcpyAsync(c.host, dev<char>(c.slot), c.bytes, hipMemcpyDeviceToHost, ctx_->stream));
+        return SC_OK;
+    };
+    if (r == SC_OK) r = download();
+    down_.clear();
+    if (r == SC_OK) return sc_ctx_synchronize(ctx_);
+    (void)hipStreamSynchronize(ctx_->stream);
+    return r;
 }
 
 // ---- timing ---------------------------------------------------------------
@@ -215,26 +221,16 @@ extern "C" int sc_ctx_get_timing(sc_ctx* ctx, int kid, double* total_ms, int64_t
     return SC_OK;
 }
 
-// ---- host wrappers ---------------------------------------------------------
-#define STAGE(i, bytes)                                                        \
-    do {                                                                       \
-        int r_ = sc_scratch_reserve(ctx, &ctx->staging[i], (bytes));           \
-        if (r_ != SC_OK) return r_;                                            \
-    } while (0)
-#define H2D(i, src, bytes) SC_HIP(ctx, hipMemcpyAsync(ctx->staging[i].p, (src), (bytes), hipMemcpyHostToDevice, ctx->stream))
-#define D2H(dst, i, bytes) SC_HIP(ctx, hipMemcpyAsync((dst), ctx->staging[i].p, (bytes), hipMemcpyDeviceToHost, ctx->stream))
-
+// ---- host wrappers: argument checks, then sc_stage (sc_internal.h) around the device form ---------------------------
 extern "C" int sc_edt_u8_i32_host(sc_ctx* ctx, const uint8_t* occ, int W, int H, int batch, int32_t* d2) {
     if (!ctx || !occ || !d2 || W <= 0 || H <= 0 || batch <= 0) return SC_ERR_INVALID;
     SC_HIP(ctx, hipSetDevice(ctx->device));
-    size_t n = (size_t)W * H * batch;
-    STAGE(0, n);
-    STAGE(1, n * 4);
-    H2D(0, occ, n);
-    int r = sc_edt_u8_i32(ctx, (const uint8_t*)ctx->staging[0].p, W, H, batch, (int32_t*)ctx->staging[1].p);
-    if (r != SC_OK) return r;
-    D2H(d2, 1, n * 4);
-    return sc_ctx_synchronize(ctx);
+    const size_t n = (size_t)W * H * batch;
+    sc_stage st(ctx);
+    const int i_occ = st.in(occ, n), o_d2 = st.out(d2, n * 4);
+    int r = st.upload();
+    if (r == SC_OK) r = sc_edt_u8_i32(ctx, st.dev<const uint8_t>(i_occ), W, H, batch, st.dev<int32_t>(o_d2));
+    return st.finish(r);
 }
 
 extern "C" int sc_astar_batch_host(sc_ctx* ctx, const int32_t* d2, int W, int H, int32_t r2,
@@ -244,16 +240,15 @@ extern "C" int sc_astar_batch_host(sc_ctx* ctx, const int32_t* d2, int W, int H,
         return SC_ERR_INVALID;
     if (Q == 0) return SC_OK;
     SC_HIP(ctx, hipSetDevice(ctx->device));
-    size_t n = (size_t)W * H;
-    STAGE(0, n * 4); STAGE(1, (size_t)Q * 4); STAGE(2, (size_t)Q * 4);
-    STAGE(3, (size_t)Q * Lmax * 4); STAGE(4, (size_t)Q * 4); STAGE(5, (size_t)Q * 4); STAGE(6, (size_t)Q * 4);
-    H2D(0, d2, n * 4); H2D(1, start, (size_t)Q * 4); H2D(2, goal, (size_t)Q * 4);
-    int r = sc_astar_batch(ctx, (const int32_t*)ctx->staging[0].p, W, H, r2, (const int32_t*)ctx->staging[1].p,
-                           (const int32_t*)ctx->staging[2].p, Q, Lmax, (int32_t*)ctx->staging[3].p,
-                           (int32_t*)ctx->staging[4].p, (int32_t*)ctx->staging[5].p, (int32_t*)ctx->staging[6].p);
-    if (r != SC_OK) return r;
-    D2H(path, 3, (size_t)Q * Lmax * 4); D2H(len, 4, (size_t)Q * 4); D2H(cost, 5, (size_t)Q * 4); D2H(status, 6, (size_t)Q * 4);
-    return sc_ctx_synchronize(ctx);
+    const size_t n = (size_t)W * H, qb = (size_t)Q * 4;
+    sc_stage st(ctx);
+    const int i_d2 = st.in(d2, n * 4), i_s = st.in(start, qb), i_g = st.in(goal, qb);
+    const int o_path = st.out(path, qb * Lmax), o_len = st.out(len, qb), o_cost = st.out(cost, qb), o_st = st.out(status, qb);
+    int r = st.upload();
+    if (r == SC_OK)
+        r = sc_astar_batch(ctx, st.dev<const int32_t>(i_d2), W, H, r2, st.dev<const int32_t>(i_s), st.dev<const int32_t>(i_g), Q, Lmax,
+                           st.dev<int32_t>(o_path), st.dev<int32_t>(o_len), st.dev<int32_t>(o_cost), st.dev<int32_t>(o_st));
+    return st.finish(r);
 }
 
 extern "C" int sc_path_waypoints_batch_host(sc_ctx* ctx, const int32_t* d2, int W, int H, int32_t r2_clear, const int32_t* path,
@@ -263,24 +258,16 @@ extern "C" int sc_path_waypoints_batch_host(sc_ctx* ctx, const int32_t* d2, int 
         return SC_ERR_INVALID;
     if (Q == 0) return SC_OK;
     SC_HIP(ctx, hipSetDevice(ctx->device));
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t n = (size_t)W * H, qb = al((size_t)Q * 4);
-    const size_t o_d2 = 0, o_p = al(n * 4), o_len = o_p + al((size_t)Q * Lmax * 4), o_as = o_len + qb, o_wp = o_as + qb,
-                 o_n = o_wp + al((size_t)Q * Wmax * 4), o_st = o_n + qb, total = o_st + qb;
-    STAGE(8, total);
-    char* b = (char*)ctx->staging[8].p;
-    SC_HIP(ctx, hipMemcpyAsync(b + o_d2, d2, n * 4, hipMemcpyHostToDevice, ctx->stream));
-    SC_HIP(ctx, hipMemcpyAsync(b + o_p, path, (size_t)Q * Lmax * 4, hipMemcpyHostToDevice, ctx->stream));
-    SC_HIP(ctx, hipMemcpyAsync(b + o_len, len, (size_t)Q * 4, hipMemcpyHostToDevice, ctx->stream));
-    if (astar_status) SC_HIP(ctx, hipMemcpyAsync(b + o_as, astar_status, (size_t)Q * 4, hipMemcpyHostToDevice, ctx->stream));
-    int r = sc_path_waypoints_batch(ctx, (const int32_t*)(b + o_d2), W, H, r2_clear, (const int32_t*)(b + o_p), (const int32_t*)(b + o_len),
-                                    astar_status ? (const int32_t*)(b + o_as) : nullptr, Q, Lmax, Wmax, (int32_t*)(b + o_wp),
-                                    (int32_t*)(b + o_n), (int32_t*)(b + o_st));
-    if (r != SC_OK) return r;
-    SC_HIP(ctx, hipMemcpyAsync(wp, b + o_wp, (size_t)Q * Wmax * 4, hipMemcpyDeviceToHost, ctx->stream));
-    SC_HIP(ctx, hipMemcpyAsync(n_wp, b + o_n, (size_t)Q * 4, hipMemcpyDeviceToHost, ctx->stream));
-    SC_HIP(ctx, hipMemcpyAsync(status, b + o_st, (size_t)Q * 4, hipMemcpyDeviceToHost, ctx->stream));
-    return sc_ctx_synchronize(ctx);
+    const size_t n = (size_t)W * H, qb = (size_t)Q * 4;
+    sc_stage st(ctx);
+    const int i_d2 = st.in(d2, n * 4), i_p = st.in(path, qb * Lmax), i_len = st.in(len, qb), i_as = st.in(astar_status, qb);
+    const int o_wp = st.out(wp, qb * Wmax), o_n = st.out(n_wp, qb), o_st = st.out(status, qb);
+    int r = st.upload();
+    if (r == SC_OK)
+        r = sc_path_waypoints_batch(ctx, st.dev<const int32_t>(i_d2), W, H, r2_clear, st.dev<const int32_t>(i_p), st.dev<const int32_t>(i_len),
+                                    astar_status ? st.dev<const int32_t>(i_as) : nullptr, Q, Lmax, Wmax, st.dev<int32_t>(o_wp),
+                                    st.dev<int32_t>(o_n), st.dev<int32_t>(o_st));
+    return st.finish(r);
 }
 
 extern "C" int sc_toppra_hermite_batch_host(sc_ctx* ctx, int P, int dof, int N,
@@ -293,29 +280,19 @@ extern "C" int sc_toppra_hermite_batch_host(sc_ctx* ctx, int P, int dof, int N,
         !alim_hi || !K || !x || !u || !t || !status)
         return SC_ERR_INVALID;
     SC_HIP(ctx, hipSetDevice(ctx->device));
-    size_t pd = (size_t)P * dof * 8, vl = vlim_per_stage ? pd * (N + 1) : pd;
-    // one staging block: inputs then outputs
-    size_t off_in[8] = {0, pd, 2 * pd, 3 * pd, 4 * pd, 4 * pd + vl, 4 * pd + 2 * vl, 5 * pd + 2 * vl};
-    size_t in_bytes = 6 * pd + 2 * vl;
-    size_t oK = in_bytes, ox = oK + (size_t)P * (N + 1) * 16, ou = ox + (size_t)P * (N + 1) * 8,
-           ot = ou + (size_t)P * N * 8, os = ot + (size_t)P * (N + 1) * 8, total = os + (size_t)P * 4;
-    STAGE(0, total);
-    char* b = (char*)ctx->staging[0].p;
-    const void* src[8] = {p0, p1, v0, v1, vlim_lo, vlim_hi, alim_lo, alim_hi};
-    size_t sz[8] = {pd, pd, pd, pd, vl, vl, pd, pd};
-    for (int i = 0; i < 8; ++i) SC_HIP(ctx, hipMemcpyAsync(b + off_in[i], src[i], sz[i], hipMemcpyHostToDevice, ctx->stream));
-    int r = sc_toppra_hermite_batch(ctx, P, dof, N, (double*)(b + off_in[0]), (double*)(b + off_in[1]),
-                                    (double*)(b + off_in[2]), (double*)(b + off_in[3]), (double*)(b + off_in[4]),
-                                    (double*)(b + off_in[5]), vlim_per_stage, (double*)(b + off_in[6]),
-                                    (double*)(b + off_in[7]), sd_start, sd_end, (double*)(b + oK), (double*)(b + ox),
-                                    (double*)(b + ou), (double*)(b + ot), (int32_t*)(b + os));
-    if (r != SC_OK) return r;
-    SC_HIP(ctx, hipMemcpyAsync(K, b + oK, (size_t)P * (N + 1) * 16, hipMemcpyDeviceToHost, ctx->stream));
-    SC_HIP(ctx, hipMemcpyAsync(x, b + ox, (size_t)P * (N + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
-    SC_HIP(ctx, hipMemcpyAsync(u, b + ou, (size_t)P * N * 8, hipMemcpyDeviceToHost, ctx->stream));
-    SC_HIP(ctx, hipMemcpyAsync(t, b + ot, (size_t)P * (N + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
-    SC_HIP(ctx, hipMemcpyAsync(status, b + os, (size_t)P * 4, hipMemcpyDeviceToHost, ctx->stream));
-    return sc_ctx_synchronize(ctx);
+    const size_t pd = (size_t)P * dof * 8, vl = vlim_per_stage ? pd * (N + 1) : pd, kb = (size_t)P * (N + 1) * 8;
+    sc_stage st(ctx);
+    const int i_p0 = st.in(p0, pd), i_p1 = st.in(p1, pd), i_v0 = st.in(v0, pd), i_v1 = st.in(v1, pd), i_vlo = st.in(vlim_lo, vl),
+              i_vhi = st.in(vlim_hi, vl), i_alo = st.in(alim_lo, pd), i_ahi = st.in(alim_hi, pd);
+    const int o_K = st.out(K, 2 * kb), o_x = st.out(x, kb), o_u = st.out(u, (size_t)P * N * 8), o_t = st.out(t, kb),
+              o_st = st.out(status, (size_t)P * 4);
+    int r = st.upload();
+    if (r == SC_OK)
+        r = sc_toppra_hermite_batch(ctx, P, dof, N, st.dev<const double>(i_p0), st.dev<const double>(i_p1), st.dev<const double>(i_v0),
+                                    st.dev<const double>(i_v1), st.dev<const double>(i_vlo), st.dev<const double>(i_vhi), vlim_per_stage,
+                                    st.dev<const double>(i_alo), st.dev<const double>(i_ahi), sd_start, sd_end, st.dev<double>(o_K),
+                                    st.dev<double>(o_x), st.dev<double>(o_u), st.dev<double>(o_t), st.dev<int32_t>(o_st));
+    return st.finish(r);
 }
 
 extern "C" int sc_toppra_sample_batch_host(sc_ctx* ctx, int P, int dof, int N,
@@ -326,59 +303,42 @@ extern "C" int sc_toppra_sample_batch_host(sc_ctx* ctx, int P, int dof, int N,
         !vel || !acc || !times || !length)
         return SC_ERR_INVALID;
     SC_HIP(ctx, hipSetDevice(ctx->device));
-    size_t pd = (size_t)P * dof * 8, xs = (size_t)P * (N + 1) * 8;
-    size_t o[6] = {0, pd, 2 * pd, 3 * pd, 4 * pd, 4 * pd + xs};
-    size_t in_bytes = 4 * pd + 2 * xs;
-    size_t fb = (size_t)P * dof * max_len * 4;
-    size_t opos = in_bytes, ovel = opos + fb, oacc = ovel + fb, otim = oacc + fb, olen = otim + (size_t)P * max_len * 8,
-           total = olen + (size_t)P * 4;
-    STAGE(1, total);
-    char* b = (char*)ctx->staging[1].p;
-    const void* src[6] = {p0, p1, v0, v1, x, t};
-    size_t sz[6] = {pd, pd, pd, pd, xs, xs};
-    for (int i = 0; i < 6; ++i) SC_HIP(ctx, hipMemcpyAsync(b + o[i], src[i], sz[i], hipMemcpyHostToDevice, ctx->stream));
-    int r = sc_toppra_sample_batch(ctx, P, dof, N, (double*)(b + o[0]), (double*)(b + o[1]), (double*)(b + o[2]),
-                                   (double*)(b + o[3]), (double*)(b + o[4]), (double*)(b + o[5]), dt, max_len,
-                                   (float*)(b + opos), (float*)(b + ovel), (float*)(b + oacc), (double*)(b + otim),
-                                   (int32_t*)(b + olen));
-    if (r != SC_OK) return r;
-    SC_HIP(ctx, hipMemcpyAsync(pos, b + opos, fb, hipMemcpyDeviceToHost, ctx->stream));
-    SC_HIP(ctx, hipMemcpyAsync(vel, b + ovel, fb, hipMemcpyDeviceToHost, ctx->stream));
-    SC_HIP(ctx, hipMemcpyAsync(acc, b + oacc, fb, hipMemcpyDeviceToHost, ctx->stream));
-    SC_HIP(ctx, hipMemcpyAsync(times, b + otim, (size_t)P * max_len * 8, hipMemcpyDeviceToHost, ctx->stream));
-    SC_HIP(ctx, hipMemcpyAsync(length, b + olen, (size_t)P * 4, hipMemcpyDeviceToHost, ctx->stream));
-    return sc_ctx_synchronize(ctx);
+    const size_t pd = (size_t)P * dof * 8, xs = (size_t)P * (N + 1) * 8, fb = (size_t)P * dof * max_len * 4;
+    sc_stage st(ctx);
+    const int i_p0 = st.in(p0, pd), i_p1 = st.in(p1, pd), i_v0 = st.in(v0, pd), i_v1 = st.in(v1, pd), i_x = st.in(x, xs), i_t = st.in(t, xs);
+    const int o_pos = st.out(pos, fb), o_vel = st.out(vel, fb), o_acc = st.out(acc, fb), o_tim = st.out(times, (size_t)P * max_len * 8),
+              o_len = st.out(length, (size_t)P * 4);
+    int r = st.upload();
+    if (r == SC_OK)
+        r = sc_toppra_sample_batch(ctx, P, dof, N, st.dev<const double>(i_p0), st.dev<const double>(i_p1), st.dev<const double>(i_v0),
+                                   st.dev<const double>(i_v1), st.dev<const double>(i_x), st.dev<const double>(i_t), dt, max_len,
+                                   st.dev<float>(o_pos), st.dev<float>(o_vel), st.dev<float>(o_acc), st.dev<double>(o_tim),
+                                   st.dev<int32_t>(o_len));
+    return st.finish(r);
 }
 
 extern "C" int sc_bezier_from_path_batch_host(sc_ctx* ctx, const float* path, const int32_t* npts, int P, int n_max, float start_angle,
                                               const float* lines, int nlines, float* ctrl) {
     if (!ctx || !path || !npts || !ctrl || P <= 0 || n_max < 2 || nlines < 0 || (nlines > 0 && !lines)) return SC_ERR_INVALID;
     SC_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t pb = (size_t)P * n_max * 2 * 4, nb = (size_t)P * 4, lb = (size_t)nlines * 16, cb = (size_t)P * (n_max - 1) * 32;
-    STAGE(2, pb + nb + lb + cb + 64);
-    char* b = (char*)ctx->staging[2].p;
-    SC_HIP(ctx, hipMemcpyAsync(b, path, pb, hipMemcpyHostToDevice, ctx->stream));
-    SC_HIP(ctx, hipMemcpyAsync(b + pb, npts, nb, hipMemcpyHostToDevice, ctx->stream));
-    if (lb) SC_HIP(ctx, hipMemcpyAsync(b + pb + nb, lines, lb, hipMemcpyHostToDevice, ctx->stream));
-    int r = sc_bezier_from_path_batch(ctx, (const float*)b, (const int32_t*)(b + pb), P, n_max, start_angle,
-                                      lb ? (const float*)(b + pb + nb) : nullptr, nlines, (float*)(b + pb + nb + lb));
-    if (r != SC_OK) return r;
-    SC_HIP(ctx, hipMemcpyAsync(ctrl, b + pb + nb + lb, cb, hipMemcpyDeviceToHost, ctx->stream));
-    return sc_ctx_synchronize(ctx);
+    sc_stage st(ctx);
+    const int i_path = st.in(path, (size_t)P * n_max * 8), i_npts = st.in(npts, (size_t)P * 4), i_l = st.in(lines, (size_t)nlines * 16);
+    const int o_ctrl = st.out(ctrl, (size_t)P * (n_max - 1) * 32);
+    int r = st.upload();
+    if (r == SC_OK)
+        r = sc_bezier_from_path_batch(ctx, st.dev<const float>(i_path), st.dev<const int32_t>(i_npts), P, n_max, start_angle,
+                                      nlines ? st.dev<const float>(i_l) : nullptr, nlines, st.dev<float>(o_ctrl));
+    return st.finish(r);
 }
 
 extern "C" int sc_bezier_arclength_batch_host(sc_ctx* ctx, const float* ctrl, int S, int nsub, float* cum, float* seg_len) {
     if (!ctx || !ctrl || !cum || !seg_len || S <= 0 || nsub <= 0) return SC_ERR_INVALID;
     SC_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t cb = (size_t)S * 32, ub = (size_t)S * (nsub + 1) * 4, sb = (size_t)S * 4;
-    STAGE(3, cb + ub + sb);
-    char* b = (char*)ctx->staging[3].p;
-    SC_HIP(ctx, hipMemcpyAsync(b, ctrl, cb, hipMemcpyHostToDevice, ctx->stream));
-    int r = sc_bezier_arclength_batch(ctx, (const float*)b, S, nsub, (float*)(b + cb), (float*)(b + cb + ub));
-    if (r != SC_OK) return r;
-    SC_HIP(ctx, hipMemcpyAsync(cum, b + cb, ub, hipMemcpyDeviceToHost, ctx->stream));
-    SC_HIP(ctx, hipMemcpyAsync(seg_len, b + cb + ub, sb, hipMemcpyDeviceToHost, ctx->stream));
-    return sc_ctx_synchronize(ctx);
+    sc_stage st(ctx);
+    const int i_ctrl = st.in(ctrl, (size_t)S * 32), o_cum = st.out(cum, (size_t)S * (nsub + 1) * 4), o_len = st.out(seg_len, (size_t)S * 4);
+    int r = st.upload();
+    if (r == SC_OK) r = sc_bezier_arclength_batch(ctx, st.dev<const float>(i_ctrl), S, nsub, st.dev<float>(o_cum), st.dev<float>(o_len));
+    return st.finish(r);
 }
 
 extern "C" int sc_bezier_resample_batch_host(sc_ctx* ctx, const float* ctrl, const float* cum, const float* arclength,
@@ -388,33 +348,20 @@ extern "C" int sc_bezier_resample_batch_host(sc_ctx* ctx, const float* ctrl, con
         return SC_ERR_INVALID;
     if (seg_off[B] != S || seg_off[0] != 0 || prof_off[0] != 0 || prof_off[B] < 0) return SC_ERR_INVALID;
     SC_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t M = (size_t)prof_off[B];
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t o_ctrl = 0, o_cum = o_ctrl + al((size_t)S * 32), o_al = o_cum + al((size_t)S * (nsub + 1) * 4), o_so = o_al + al((size_t)B * 4),
-                 o_po = o_so + al((size_t)(B + 1) * 4), o_pp = o_po + al((size_t)(B + 1) * 4), o_pts = o_pp + al(M * 4), o_t = o_pts + al(M * 8),
-                 o_sg = o_t + al(M * 4), o_cv = o_sg + al(M * 4), o_st = o_cv + al(M * 4), total = o_st + al((size_t)B * 4);
-    STAGE(4, total);
-    char* b = (char*)ctx->staging[4].p;
-    SC_HIP(ctx, hipMemcpyAsync(b + o_ctrl, ctrl, (size_t)S * 32, hipMemcpyHostToDevice, ctx->stream));
-    SC_HIP(ctx, hipMemcpyAsync(b + o_cum, cum, (size_t)S * (nsub + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-    SC_HIP(ctx, hipMemcpyAsync(b + o_al, arclength, (size_t)B * 4, hipMemcpyHostToDevice, ctx->stream));
-    SC_HIP(ctx, hipMemcpyAsync(b + o_so, seg_off, (size_t)(B + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-    SC_HIP(ctx, hipMemcpyAsync(b + o_po, prof_off, (size_t)(B + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-    if (M) SC_HIP(ctx, hipMemcpyAsync(b + o_pp, profile_pos, M * 4, hipMemcpyHostToDevice, ctx->stream));
-    int r = sc_bezier_resample_batch(ctx, (const float*)(b + o_ctrl), (const float*)(b + o_cum), (const float*)(b + o_al),
-                                     (const int32_t*)(b + o_so), B, S, nsub, (float*)(b + o_pp), (const int32_t*)(b + o_po), nudge,
-                                     pts ? (float*)(b + o_pts) : nullptr, tpar ? (float*)(b + o_t) : nullptr,
-                                     seg ? (int32_t*)(b + o_sg) : nullptr, curvature ? (float*)(b + o_cv) : nullptr, (int32_t*)(b + o_st));
-    if (r != SC_OK) return r;
-    if (M) {
-        SC_HIP(ctx, hipMemcpyAsync(profile_pos, b + o_pp, M * 4, hipMemcpyDeviceToHost, ctx->stream));
-        if (pts) SC_HIP(ctx, hipMemcpyAsync(pts, b + o_pts, M * 8, hipMemcpyDeviceToHost, ctx->stream));
-        if (tpar) SC_HIP(ctx, hipMemcpyAsync(tpar, b + o_t, M * 4, hipMemcpyDeviceToHost, ctx->stream));
-        if (seg) SC_HIP(ctx, hipMemcpyAsync(seg, b + o_sg, M * 4, hipMemcpyDeviceToHost, ctx->stream));
-        if (curvature) SC_HIP(ctx, hipMemcpyAsync(curvature, b + o_cv, M * 4, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    SC_HIP(ctx, hipMemcpyAsync(status, b + o_st, (size_t)B * 4, hipMemcpyDeviceToHost, ctx->stream));
-    return sc_ctx_synchronize(ctx);
+    const size_t M = (size_t)prof_off[B], bb = (size_t)B * 4;
+    sc_stage st(ctx);
+    const int i_ctrl = st.in(ctrl, (size_t)S * 32), i_cum = st.in(cum, (size_t)S * (nsub + 1) * 4), i_al = st.in(arclength, bb),
+              i_so = st.in(seg_off, bb + 4), i_po = st.in(prof_off, bb + 4), io_pp = st.in(profile_pos, M * 4);
+    st.back(io_pp, profile_pos, M * 4);
+    const int o_pts = st.out(pts, M * 8), o_t = st.out(tpar, M * 4), o_sg = st.out(seg, M * 4), o_cv = st.out(curvature, M * 4),
+              o_st = st.out(status, bb);
+    int r = st.upload();
+    if (r == SC_OK)
+        r = sc_bezier_resample_batch(ctx, st.dev<const float>(i_ctrl), st.dev<const float>(i_cum), st.dev<const float>(i_al),
+                                     st.dev<const int32_t>(i_so), B, S, nsub, st.dev<float>(io_pp), st.dev<const int32_t>(i_po), nudge,
+                                     pts ? st.dev<float>(o_pts) : nullptr, tpar ? st.dev<float>(o_t) : nullptr,
+                                     seg ? st.dev<int32_t>(o_sg) : nullptr, curvature ? st.dev<float>(o_cv) : nullptr, st.dev<int32_t>(o_st));
+    return st.finish(r);
 }
 
 extern "C" int sc_bezier_eval_batch_host(sc_ctx* ctx, const float* ctrl, int S, const int32_t* seg, const float* t, int M, int order,
@@ -423,59 +370,43 @@ extern "C" int sc_bezier_eval_batch_host(sc_ctx* ctx, const float* ctrl, int S, 
     for (int i = 0; i < M; ++i)
         if (seg[i] < 0 || seg[i] >= S) return SC_ERR_INVALID;
     SC_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t cb = ((size_t)S * 32 + 255) & ~(size_t)255, mb = ((size_t)M * 4 + 255) & ~(size_t)255;
-    STAGE(5, cb + 2 * mb + (size_t)M * 8);
-    char* b = (char*)ctx->staging[5].p;
-    SC_HIP(ctx, hipMemcpyAsync(b, ctrl, (size_t)S * 32, hipMemcpyHostToDevice, ctx->stream));
-    SC_HIP(ctx, hipMemcpyAsync(b + cb, seg, (size_t)M * 4, hipMemcpyHostToDevice, ctx->stream));
-    SC_HIP(ctx, hipMemcpyAsync(b + cb + mb, t, (size_t)M * 4, hipMemcpyHostToDevice, ctx->stream));
-    int r = sc_bezier_eval_batch(ctx, (const float*)b, (const int32_t*)(b + cb), (const float*)(b + cb + mb), M, order,
-                                 (float*)(b + cb + 2 * mb));
-    if (r != SC_OK) return r;
-    SC_HIP(ctx, hipMemcpyAsync(out, b + cb + 2 * mb, (size_t)M * 8, hipMemcpyDeviceToHost, ctx->stream));
-    return sc_ctx_synchronize(ctx);
+    sc_stage st(ctx);
+    const int i_ctrl = st.in(ctrl, (size_t)S * 32), i_seg = st.in(seg, (size_t)M * 4), i_t = st.in(t, (size_t)M * 4), o = st.out(out, (size_t)M * 8);
+    int r = st.upload();
+    if (r == SC_OK)
+        r = sc_bezier_eval_batch(ctx, st.dev<const float>(i_ctrl), st.dev<const int32_t>(i_seg), st.dev<const float>(i_t), M, order, st.dev<float>(o));
+    return st.finish(r);
 }
 
 extern "C" int sc_bezier_shrink_tangent_batch_host(sc_ctx* ctx, const float* T, const float* Wp, int M, float k, const float* lines, int nlines,
                                                    float* out) {
     if (!ctx || !T || !Wp || !out || M <= 0 || nlines < 0 || (nlines > 0 && !lines)) return SC_ERR_INVALID;
     SC_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t mb = ((size_t)M * 8 + 255) & ~(size_t)255, lb = ((size_t)nlines * 16 + 255) & ~(size_t)255;
-    STAGE(5, 3 * mb + lb);
-    char* b = (char*)ctx->staging[5].p;
-    SC_HIP(ctx, hipMemcpyAsync(b, T, (size_t)M * 8, hipMemcpyHostToDevice, ctx->stream));
-    SC_HIP(ctx, hipMemcpyAsync(b + mb, Wp, (size_t)M * 8, hipMemcpyHostToDevice, ctx->stream));
-    if (nlines) SC_HIP(ctx, hipMemcpyAsync(b + 2 * mb, lines, (size_t)nlines * 16, hipMemcpyHostToDevice, ctx->stream));
-    int r = sc_bezier_shrink_tangent_batch(ctx, (const float*)b, (const float*)(b + mb), M, k, nlines ? (const float*)(b + 2 * mb) : nullptr, nlines,
-                                           (float*)(b + 2 * mb + lb));
-    if (r != SC_OK) return r;
-    SC_HIP(ctx, hipMemcpyAsync(out, b + 2 * mb + lb, (size_t)M * 8, hipMemcpyDeviceToHost, ctx->stream));
-    return sc_ctx_synchronize(ctx);
+    sc_stage st(ctx);
+    const int i_T = st.in(T, (size_t)M * 8), i_W = st.in(Wp, (size_t)M * 8), i_l = st.in(lines, (size_t)nlines * 16), o = st.out(out, (size_t)M * 8);
+    int r = st.upload();
+    if (r == SC_OK)
+        r = sc_bezier_shrink_tangent_batch(ctx, st.dev<const float>(i_T), st.dev<const float>(i_W), M, k,
+                                           nlines ? st.dev<const float>(i_l) : nullptr, nlines, st.dev<float>(o));
+    return st.finish(r);
 }
 
 extern "C" int sc_fmt_star_batch_host(sc_ctx* ctx, const float* samples, int n, const float* starts, const float* goals, int Q, float rn,
                                       const float* lines, int E, int Lmax, float* path, int32_t* len, float* cost, int32_t* status) {
-    if (!ctx || !samples || !starts || !goals || !path || !len || !cost || !status || n < 0 || Q < 0 || E < 0 || Lmax <= 0) return SC_ERR_INVALID;
+    if (!ctx || !samples || !starts || !goals || !path || !len || !cost || !status || n < 0 || Q < 0 || E < 0 || (E > 0 && !lines) ||
+        Lmax <= 0)
+        return SC_ERR_INVALID;
     if (Q == 0) return SC_OK;
     SC_HIP(ctx, hipSetDevice(ctx->device));
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t o_s = 0, o_st = o_s + al((size_t)(n > 0 ? n : 1) * 8), o_g = o_st + al((size_t)Q * 8), o_l = o_g + al((size_t)Q * 8),
-                 o_p = o_l + al((size_t)(E > 0 ? E : 1) * 16), o_len = o_p + al((size_t)Q * Lmax * 8), o_c = o_len + al((size_t)Q * 4),
-                 o_status = o_c + al((size_t)Q * 4), total = o_status + al((size_t)Q * 4);
-    STAGE(6, total);
-    char* b = (char*)ctx->staging[6].p;
-    if (n) SC_HIP(ctx, hipMemcpyAsync(b + o_s, samples, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-    SC_HIP(ctx, hipMemcpyAsync(b + o_st, starts, (size_t)Q * 8, hipMemcpyHostToDevice, ctx->stream));
-    SC_HIP(ctx, hipMemcpyAsync(b + o_g, goals, (size_t)Q * 8, hipMemcpyHostToDevice, ctx->stream));
-    if (E) SC_HIP(ctx, hipMemcpyAsync(b + o_l, lines, (size_t)E * 16, hipMemcpyHostToDevice, ctx->stream));
-    int r = sc_fmt_star_batch(ctx, (const float*)(b + o_s), n, (const float*)(b + o_st), (const float*)(b + o_g), Q, rn, (const float*)(b + o_l), E,
-                              Lmax, (float*)(b + o_p), (int32_t*)(b + o_len), (float*)(b + o_c), (int32_t*)(b + o_status));
-    if (r != SC_OK) return r;
-    SC_HIP(ctx, hipMemcpyAsync(path, b + o_p, (size_t)Q * Lmax * 8, hipMemcpyDeviceToHost, ctx->stream));
-    SC_HIP(ctx, hipMemcpyAsync(len, b + o_len, (size_t)Q * 4, hipMemcpyDeviceToHost, ctx->stream));
-    SC_HIP(ctx, hipMemcpyAsync(cost, b + o_c, (size_t)Q * 4, hipMemcpyDeviceToHost, ctx->stream));
-    SC_HIP(ctx, hipMemcpyAsync(status, b + o_status, (size_t)Q * 4, hipMemcpyDeviceToHost, ctx->stream));
-    return sc_ctx_synchronize(ctx);
+    const size_t qb = (size_t)Q * 4;
+    sc_stage st(ctx);
+    const int i_s = st.in(samples, (size_t)n * 8), i_st = st.in(starts, 2 * qb), i_g = st.in(goals, 2 * qb), i_l = st.in(lines, (size_t)E * 16);
+    const int o_p = st.out(path, 2 * qb * Lmax), o_len = st.out(len, qb), o_c = st.out(cost, qb), o_st = st.out(status, qb);
+    int r = st.upload();
+    if (r == SC_OK)
+        r = sc_fmt_star_batch(ctx, st.dev<const float>(i_s), n, st.dev<const float>(i_st), st.dev<const float>(i_g), Q, rn, st.dev<const float>(i_l),
+                              E, Lmax, st.dev<float>(o_p), st.dev<int32_t>(o_len), st.dev<float>(o_c), st.dev<int32_t>(o_st));
+    return st.finish(r);
 }
 
 extern "C" int sc_bezier_curve_batch_host(sc_ctx* ctx, const float* ctrl, int S, int degree, const int32_t* seg, const float* t, int M, float* out) {
@@ -483,37 +414,27 @@ extern "C" int sc_bezier_curve_batch_host(sc_ctx* ctx, const float* ctrl, int S,
     for (int i = 0; i < M; ++i)
         if (seg[i] < 0 || seg[i] >= S) return SC_ERR_INVALID;
     SC_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t cbytes = (size_t)S * (degree + 1) * 8;
-    const size_t cb = (cbytes + 255) & ~(size_t)255, mb = ((size_t)M * 4 + 255) & ~(size_t)255;
-    STAGE(5, cb + 2 * mb + (size_t)M * 8);
-    char* b = (char*)ctx->staging[5].p;
-    SC_HIP(ctx, hipMemcpyAsync(b, ctrl, cbytes, hipMemcpyHostToDevice, ctx->stream));
-    SC_HIP(ctx, hipMemcpyAsync(b + cb, seg, (size_t)M * 4, hipMemcpyHostToDevice, ctx->stream));
-    SC_HIP(ctx, hipMemcpyAsync(b + cb + mb, t, (size_t)M * 4, hipMemcpyHostToDevice, ctx->stream));
-    int r = sc_bezier_curve_batch(ctx, (const float*)b, degree, (const int32_t*)(b + cb), (const float*)(b + cb + mb), M, (float*)(b + cb + 2 * mb));
-    if (r != SC_OK) return r;
-    SC_HIP(ctx, hipMemcpyAsync(out, b + cb + 2 * mb, (size_t)M * 8, hipMemcpyDeviceToHost, ctx->stream));
-    return sc_ctx_synchronize(ctx);
+    sc_stage st(ctx);
+    const int i_ctrl = st.in(ctrl, (size_t)S * (degree + 1) * 8), i_seg = st.in(seg, (size_t)M * 4), i_t = st.in(t, (size_t)M * 4),
+              o = st.out(out, (size_t)M * 8);
+    int r = st.upload();
+    if (r == SC_OK)
+        r = sc_bezier_curve_batch(ctx, st.dev<const float>(i_ctrl), degree, st.dev<const int32_t>(i_seg), st.dev<const float>(i_t), M, st.dev<float>(o));
+    return st.finish(r);
 }
 
 extern "C" int sc_chebfit_batch_host(sc_ctx* ctx, const float* x, const float* y, const int32_t* off, int B, int degree, float* coef, float* xrange) {
     if (!ctx || !x || !y || !off || !coef || !xrange || B <= 0 || degree < 1 || degree > SC_CHEB_MAX_DEGREE || off[0] != 0 || off[B] <= 0) return SC_ERR_INVALID;
     SC_HIP(ctx, hipSetDevice(ctx->device));
     const size_t n = (size_t)off[B];
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t o_x = 0, o_y = al(n * 4), o_off = o_y + al(n * 4), o_c = o_off + al((size_t)(B + 1) * 4), o_r = o_c + al((size_t)B * degree * 4),
-                 total = o_r + al((size_t)B * 8);
-    STAGE(6, total);
-    char* b = (char*)ctx->staging[6].p;
-    SC_HIP(ctx, hipMemcpyAsync(b + o_x, x, n * 4, hipMemcpyHostToDevice, ctx->stream));
-    SC_HIP(ctx, hipMemcpyAsync(b + o_y, y, n * 4, hipMemcpyHostToDevice, ctx->stream));
-    SC_HIP(ctx, hipMemcpyAsync(b + o_off, off, (size_t)(B + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-    int r = sc_chebfit_batch(ctx, (const float*)(b + o_x), (const float*)(b + o_y), (const int32_t*)(b + o_off), B, (int)n, degree, (float*)(b + o_c),
-                             (float*)(b + o_r));
-    if (r != SC_OK) return r;
-    SC_HIP(ctx, hipMemcpyAsync(coef, b + o_c, (size_t)B * degree * 4, hipMemcpyDeviceToHost, ctx->stream));
-    SC_HIP(ctx, hipMemcpyAsync(xrange, b + o_r, (size_t)B * 8, hipMemcpyDeviceToHost, ctx->stream));
-    return sc_ctx_synchronize(ctx);
+    sc_stage st(ctx);
+    const int i_x = st.in(x, n * 4), i_y = st.in(y, n * 4), i_off = st.in(off, (size_t)(B + 1) * 4);
+    const int o_c = st.out(coef, (size_t)B * degree * 4), o_r = st.out(xrange, (size_t)B * 8);
+    int r = st.upload();
+    if (r == SC_OK)
+        r = sc_chebfit_batch(ctx, st.dev<const float>(i_x), st.dev<const float>(i_y), st.dev<const int32_t>(i_off), B, (int)n, degree,
+                             st.dev<float>(o_c), st.dev<float>(o_r));
+    return st.finish(r);
 }
 
 extern "C" int sc_chebeval_batch_host(sc_ctx* ctx, const float* x, const int32_t* off, int B, int degree, const float* coef, const float* xrange,
@@ -521,18 +442,12 @@ extern "C" int sc_chebeval_batch_host(sc_ctx* ctx, const float* x, const int32_t
     if (!ctx || !x || !off || !coef || !xrange || !y || B <= 0 || degree < 1 || degree > SC_CHEB_MAX_DEGREE || off[0] != 0 || off[B] <= 0) return SC_ERR_INVALID;
     SC_HIP(ctx, hipSetDevice(ctx->device));
     const size_t n = (size_t)off[B];
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t o_x = 0, o_y = al(n * 4), o_off = o_y + al(n * 4), o_c = o_off + al((size_t)(B + 1) * 4), o_r = o_c + al((size_t)B * degree * 4),
-                 total = o_r + al((size_t)B * 8);
-    STAGE(6, total);
-    char* b = (char*)ctx->staging[6].p;
-    SC_HIP(ctx, hipMemcpyAsync(b + o_x, x, n * 4, hipMemcpyHostToDevice, ctx->stream));
-    SC_HIP(ctx, hipMemcpyAsync(b + o_off, off, (size_t)(B + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-    SC_HIP(ctx, hipMemcpyAsync(b + o_c, coef, (size_t)B * degree * 4, hipMemcpyHostToDevice, ctx->stream));
-    SC_HIP(ctx, hipMemcpyAsync(b + o_r, xrange, (size_t)B * 8, hipMemcpyHostToDevice, ctx->stream));
-    int r = sc_chebeval_batch(ctx, (const float*)(b + o_x), (const int32_t*)(b + o_off), B, degree, (const float*)(b + o_c), (const float*)(b + o_r),
-                              (float*)(b + o_y));
-    if (r != SC_OK) return r;
-    SC_HIP(ctx, hipMemcpyAsync(y, b + o_y, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    return sc_ctx_synchronize(ctx);
+    sc_stage st(ctx);
+    const int i_x = st.in(x, n * 4), i_off = st.in(off, (size_t)(B + 1) * 4), i_c = st.in(coef, (size_t)B * degree * 4),
+              i_r = st.in(xrange, (size_t)B * 8), o_y = st.out(y, n * 4);
+    int r = st.upload();
+    if (r == SC_OK)
+        r = sc_chebeval_batch(ctx, st.dev<const float>(i_x), st.dev<const int32_t>(i_off), B, degree, st.dev<const float>(i_c),
+                              st.dev<const float>(i_r), st.dev<float>(o_y));
+    return st.finish(r);
 }

@@ -404,18 +404,29 @@ int field_default_rounds(int TX, int TY) { return 2 * (TX + TY) + 16; }
 
 }  // namespace
 
+// the argument checks of the device and _host forms
+static bool cost_field_args_ok(const sc_ctx* ctx, const int32_t* d2, int G, const int32_t* fgrid, int W, int H, const int32_t* root, int F,
+                               const int32_t* g) {
+    return ctx && d2 && root && g && G > 0 && F > 0 && W > 0 && H > 0 && W <= SC_MAX_DIM && H <= SC_MAX_DIM && (fgrid || G == 1);
+}
+
+static bool field_paths_args_ok(const sc_ctx* ctx, const int32_t* d2, int G, const int32_t* fgrid, int W, int H, const int32_t* g,
+                                const int32_t* root, int F, const int32_t* qfield, const int32_t* target, int Q, int Lmax, const int32_t* path,
+                                const int32_t* len, const int32_t* cost, const int32_t* status) {
+    return ctx && d2 && g && root && qfield && target && path && len && cost && status && G > 0 && F > 0 && W > 0 && H > 0 &&
+           W <= SC_MAX_DIM && H <= SC_MAX_DIM && Q >= 0 && Lmax > 0 && (fgrid || G == 1);
+}
+
 extern "C" int sc_cost_field_batch(sc_ctx* ctx, const int32_t* d2, int G, const int32_t* fgrid, int W, int H, int32_t r2_clear,
                                    const int32_t* root, int F, int rounds, int32_t* g, int32_t* fstatus) {
-    if (!ctx || !d2 || !root || !g || G <= 0 || F <= 0 || W <= 0 || H <= 0 || W > SC_MAX_DIM || H > SC_MAX_DIM || (!fgrid && G != 1))
-        return SC_ERR_INVALID;
+    if (!cost_field_args_ok(ctx, d2, G, fgrid, W, H, root, F, g)) return SC_ERR_INVALID;
     SC_HIP(ctx, hipSetDevice(ctx->device));
     const int TX = (W + FT - 1) / FT, TY = (H + FT - 1) / FT, nt = TX * TY;
     if ((long long)F * nt > 0x7FFFFFFF / 2) return SC_ERR_INVALID;
     if (rounds < 0) rounds = field_default_rounds(TX, TY);
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
     const size_t mask_b = (size_t)G * TY * W * 8;
-    const size_t o_ok = 0, o_stamp = al((size_t)F * 4), o_l0 = o_stamp + al((size_t)F * nt * 4), o_l1 = o_l0 + al((size_t)F * nt * 4),
-                 o_ctr = o_l1 + al((size_t)F * nt * 4), total = o_ctr + al((size_t)(rounds + 1) * 4);
+    const size_t o_ok = 0, o_stamp = al256((size_t)F * 4), o_l0 = o_stamp + al256((size_t)F * nt * 4), o_l1 = o_l0 + al256((size_t)F * nt * 4),
+                 o_ctr = o_l1 + al256((size_t)F * nt * 4), total = o_ctr + al256((size_t)(rounds + 1) * 4);
     int r = sc_scratch_reserve(ctx, &ctx->fld_mask, mask_b);
     if (r == SC_OK) r = sc_scratch_reserve(ctx, &ctx->fld_state, total);
     if (r != SC_OK) return r;
@@ -459,9 +470,7 @@ extern "C" int sc_cost_field_batch(sc_ctx* ctx, const int32_t* d2, int G, const 
 extern "C" int sc_field_paths_batch(sc_ctx* ctx, const int32_t* d2, int G, const int32_t* fgrid, int W, int H, int32_t r2_clear,
                                     const int32_t* g, const int32_t* root, int F, const int32_t* qfield, const int32_t* target, int Q,
                                     int Lmax, int to_root, int32_t* path, int32_t* len, int32_t* cost, int32_t* status) {
-    if (!ctx || !d2 || !g || !root || !qfield || !target || !path || !len || !cost || !status || G <= 0 || F <= 0 || W <= 0 || H <= 0 ||
-        W > SC_MAX_DIM || H > SC_MAX_DIM || Q < 0 || Lmax <= 0 || (!fgrid && G != 1))
-        return SC_ERR_INVALID;
+    if (!field_paths_args_ok(ctx, d2, G, fgrid, W, H, g, root, F, qfield, target, Q, Lmax, path, len, cost, status)) return SC_ERR_INVALID;
     if (Q == 0) return SC_OK;
     SC_HIP(ctx, hipSetDevice(ctx->device));
     paths_args a{d2, fgrid, g, root, qfield, target, G, W, H, F, Q, Lmax, to_root ? 1 : 0, r2_clear > 1 ? r2_clear : 1, path, len, cost, status};
@@ -474,60 +483,38 @@ extern "C" int sc_field_paths_batch(sc_ctx* ctx, const int32_t* d2, int G, const
 
 extern "C" int sc_cost_field_batch_host(sc_ctx* ctx, const int32_t* d2, int G, const int32_t* fgrid, int W, int H, int32_t r2_clear,
                                         const int32_t* root, int F, int rounds, int32_t* g, int32_t* fstatus) {
-    if (!ctx || !d2 || !root || !g || G <= 0 || F <= 0 || W <= 0 || H <= 0 || W > SC_MAX_DIM || H > SC_MAX_DIM || (!fgrid && G != 1))
-        return SC_ERR_INVALID;
+    if (!cost_field_args_ok(ctx, d2, G, fgrid, W, H, root, F, g)) return SC_ERR_INVALID;
     SC_HIP(ctx, hipSetDevice(ctx->device));
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t n = (size_t)W * H;
-    const size_t o_d2 = 0, o_fg = al((size_t)G * n * 4), o_rt = o_fg + al((size_t)F * 4), o_g = o_rt + al((size_t)F * 4),
-                 o_st = o_g + al((size_t)F * n * 4), total = o_st + al((size_t)F * 4);
-    int r = sc_scratch_reserve(ctx, &ctx->fld_stage, total);
-    if (r != SC_OK) return r;
-    char* b = (char*)ctx->fld_stage.p;
-    SC_HIP(ctx, hipMemcpyAsync(b + o_d2, d2, (size_t)G * n * 4, hipMemcpyHostToDevice, ctx->stream));
-    if (fgrid) SC_HIP(ctx, hipMemcpyAsync(b + o_fg, fgrid, (size_t)F * 4, hipMemcpyHostToDevice, ctx->stream));
-    SC_HIP(ctx, hipMemcpyAsync(b + o_rt, root, (size_t)F * 4, hipMemcpyHostToDevice, ctx->stream));
-    r = sc_cost_field_batch(ctx, (const int32_t*)(b + o_d2), G, fgrid ? (const int32_t*)(b + o_fg) : nullptr, W, H, r2_clear,
-                            (const int32_t*)(b + o_rt), F, rounds, (int32_t*)(b + o_g), (int32_t*)(b + o_st));
-    if (r != SC_OK) return r;
-    SC_HIP(ctx, hipMemcpyAsync(g, b + o_g, (size_t)F * n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (fstatus) SC_HIP(ctx, hipMemcpyAsync(fstatus, b + o_st, (size_t)F * 4, hipMemcpyDeviceToHost, ctx->stream));
-    return sc_ctx_synchronize(ctx);
+    const size_t n = (size_t)W * H, fb = (size_t)F * 4;
+    sc_stage st(ctx);
+    const int i_d2 = st.in(d2, (size_t)G * n * 4), i_fg = st.in(fgrid, fb), i_rt = st.in(root, fb);
+    const int o_g = st.out(g, fb * n), o_st = st.out(fstatus, fb);
+    int r = st.upload();
+    if (r == SC_OK)
+        r = sc_cost_field_batch(ctx, st.dev<const int32_t>(i_d2), G, fgrid ? st.dev<const int32_t>(i_fg) : nullptr, W, H, r2_clear,
+                                st.dev<const int32_t>(i_rt), F, rounds, st.dev<int32_t>(o_g), st.dev<int32_t>(o_st));
+    return st.finish(r);
 }
 
 extern "C" int sc_field_paths_batch_host(sc_ctx* ctx, const int32_t* d2, int G, const int32_t* fgrid, int W, int H, int32_t r2_clear,
                                          const int32_t* g, const int32_t* root, int F, const int32_t* qfield, const int32_t* target, int Q,
                                          int Lmax, int to_root, int32_t* path, int32_t* len, int32_t* cost, int32_t* status) {
-    if (!ctx || !d2 || !g || !root || !qfield || !target || !path || !len || !cost || !status || G <= 0 || F <= 0 || W <= 0 || H <= 0 ||
-        W > SC_MAX_DIM || H > SC_MAX_DIM || Q < 0 || Lmax <= 0 || (!fgrid && G != 1))
-        return SC_ERR_INVALID;
+    if (!field_paths_args_ok(ctx, d2, G, fgrid, W, H, g, root, F, qfield, target, Q, Lmax, path, len, cost, status)) return SC_ERR_INVALID;
     if (Q == 0) return SC_OK;
     // data contract: every g value is a cost or SC_FIELD_INF
     const size_t n = (size_t)W * H;
     for (size_t i = 0; i < (size_t)F * n; ++i)
         if (g[i] < 0) return SC_ERR_INVALID;
     SC_HIP(ctx, hipSetDevice(ctx->device));
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t qb = al((size_t)Q * 4);
-    const size_t o_d2 = 0, o_fg = al((size_t)G * n * 4), o_g = o_fg + al((size_t)F * 4), o_rt = o_g + al((size_t)F * n * 4),
-                 o_qf = o_rt + al((size_t)F * 4), o_t = o_qf + qb, o_p = o_t + qb, o_len = o_p + al((size_t)Q * Lmax * 4),
-                 o_c = o_len + qb, o_s = o_c + qb, total = o_s + qb;
-    int r = sc_scratch_reserve(ctx, &ctx->fld_stage, total);
-    if (r != SC_OK) return r;
-    char* b = (char*)ctx->fld_stage.p;
-    SC_HIP(ctx, hipMemcpyAsync(b + o_d2, d2, (size_t)G * n * 4, hipMemcpyHostToDevice, ctx->stream));
-    if (fgrid) SC_HIP(ctx, hipMemcpyAsync(b + o_fg, fgrid, (size_t)F * 4, hipMemcpyHostToDevice, ctx->stream));
-    SC_HIP(ctx, hipMemcpyAsync(b + o_g, g, (size_t)F * n * 4, hipMemcpyHostToDevice, ctx->stream));
-    SC_HIP(ctx, hipMemcpyAsync(b + o_rt, root, (size_t)F * 4, hipMemcpyHostToDevice, ctx->stream));
-    SC_HIP(ctx, hipMemcpyAsync(b + o_qf, qfield, (size_t)Q * 4, hipMemcpyHostToDevice, ctx->stream));
-    SC_HIP(ctx, hipMemcpyAsync(b + o_t, target, (size_t)Q * 4, hipMemcpyHostToDevice, ctx->stream));
-    r = sc_field_paths_batch(ctx, (const int32_t*)(b + o_d2), G, fgrid ? (const int32_t*)(b + o_fg) : nullptr, W, H, r2_clear,
-                             (const int32_t*)(b + o_g), (const int32_t*)(b + o_rt), F, (const int32_t*)(b + o_qf), (const int32_t*)(b + o_t),
-                             Q, Lmax, to_root, (int32_t*)(b + o_p), (int32_t*)(b + o_len), (int32_t*)(b + o_c), (int32_t*)(b + o_s));
-    if (r != SC_OK) return r;
-    SC_HIP(ctx, hipMemcpyAsync(path, b + o_p, (size_t)Q * Lmax * 4, hipMemcpyDeviceToHost, ctx->stream));
-    SC_HIP(ctx, hipMemcpyAsync(len, b + o_len, (size_t)Q * 4, hipMemcpyDeviceToHost, ctx->stream));
-    SC_HIP(ctx, hipMemcpyAsync(cost, b + o_c, (size_t)Q * 4, hipMemcpyDeviceToHost, ctx->stream));
-    SC_HIP(ctx, hipMemcpyAsync(status, b + o_s, (size_t)Q * 4, hipMemcpyDeviceToHost, ctx->stream));
-    return sc_ctx_synchronize(ctx);
+    const size_t fb = (size_t)F * 4, qb = (size_t)Q * 4;
+    sc_stage st(ctx);
+    const int i_d2 = st.in(d2, (size_t)G * n * 4), i_fg = st.in(fgrid, fb), i_g = st.in(g, fb * n), i_rt = st.in(root, fb),
+              i_qf = st.in(qfield, qb), i_t = st.in(target, qb);
+    const int o_p = st.out(path, qb * Lmax), o_len = st.out(len, qb), o_c = st.out(cost, qb), o_s = st.out(status, qb);
+    int r = st.upload();
+    if (r == SC_OK)
+        r = sc_field_paths_batch(ctx, st.dev<const int32_t>(i_d2), G, fgrid ? st.dev<const int32_t>(i_fg) : nullptr, W, H, r2_clear,
+                                 st.dev<const int32_t>(i_g), st.dev<const int32_t>(i_rt), F, st.dev<const int32_t>(i_qf), st.dev<const int32_t>(i_t),
+                                 Q, Lmax, to_root, st.dev<int32_t>(o_p), st.dev<int32_t>(o_len), st.dev<int32_t>(o_c), st.dev<int32_t>(o_s));
+    return st.finish(r);
 }

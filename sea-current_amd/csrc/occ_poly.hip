@@ -188,12 +188,11 @@ extern "C" int sc_occ_from_polygons(sc_ctx* ctx, const uint8_t* base, int G, int
     if (!occ_args_ok(ctx, G, W, H, x_min, y_min, res_x, res_y, lines, n_lines, obs_off, n_obs, grid_off, occ)) return SC_ERR_INVALID;
     SC_HIP(ctx, hipSetDevice(ctx->device));
     if (n_obs > 0) {
-        const size_t bb = ((size_t)n_obs * 16 + 255) & ~(size_t)255;
-        const int r = sc_scratch_reserve(ctx, &ctx->occ_prep, bb + (size_t)n_obs * 8);
+        const int r = sc_scratch_reserve(ctx, &ctx->occ_prep, al256((size_t)n_obs * 16) + (size_t)n_obs * 8);
         if (r != SC_OK) return r;
     }
     float4* pbox = (float4*)ctx->occ_prep.p;
-    int2* prow = n_obs > 0 ? (int2*)((char*)ctx->occ_prep.p + (((size_t)n_obs * 16 + 255) & ~(size_t)255)) : nullptr;
+    int2* prow = n_obs > 0 ? (int2*)((char*)ctx->occ_prep.p + al256((size_t)n_obs * 16)) : nullptr;
     int tk = sc_time_begin(ctx, SC_K_OCC);
     if (n_obs > 0)
         hipLaunchKernelGGL(occ_poly_prep_kernel, dim3((unsigned)min(n_obs, 65536)), dim3(64), 0, ctx->stream, (const float4*)lines,
@@ -250,25 +249,17 @@ extern "C" int sc_occ_from_polygons_host(sc_ctx* ctx, const uint8_t* base, int G
         !occ_contract_ok(G, W, H, x_min, y_min, res_x, res_y, lines, n_lines, obs_off, n_obs, obs_box, grid_off))
         return SC_ERR_INVALID;
     SC_HIP(ctx, hipSetDevice(ctx->device));
-    enum { S_OCC, S_LINES, S_OFF, S_BOX, S_CLOSED, S_GRID, NB };
     const size_t cells = (size_t)G * H * W;
-    const size_t sz[NB] = {cells, (size_t)n_lines * 16, n_obs > 0 ? (size_t)(n_obs + 1) * 4 : 0, obs_box ? (size_t)n_obs * 16 : 0,
-                           obs_closed ? (size_t)n_obs : 0, grid_off ? (size_t)(G + 1) * 4 : 0};
-    size_t off[NB + 1];
-    off[0] = 0;
-    for (int i = 0; i < NB; ++i) off[i + 1] = off[i] + ((sz[i] + 255) & ~(size_t)255);
-    int r = sc_scratch_reserve(ctx, &ctx->occ_stage, off[NB]);
-    if (r != SC_OK) return r;
-    char* b = (char*)ctx->occ_stage.p;
-    auto dp = [&](int i) -> void* { return sz[i] ? (void*)(b + off[i]) : nullptr; };
-    const void* src[NB] = {base, lines, obs_off, obs_box, obs_closed, grid_off};
-    for (int i = 0; i < NB; ++i)
-        if (sz[i] && src[i]) SC_HIP(ctx, hipMemcpyAsync(dp(i), src[i], sz[i], hipMemcpyHostToDevice, ctx->stream));
-    uint8_t* docc = (uint8_t*)dp(S_OCC);
-    r = sc_occ_from_polygons(ctx, base ? docc : nullptr, G, W, H, x_min, y_min, res_x, res_y, (const float*)dp(S_LINES), n_lines,
-                             (const int32_t*)dp(S_OFF), n_obs, (const float*)dp(S_BOX), (const uint8_t*)dp(S_CLOSED),
-                             (const int32_t*)dp(S_GRID), docc);
-    if (r != SC_OK) return r;
-    SC_HIP(ctx, hipMemcpyAsync(occ, docc, cells, hipMemcpyDeviceToHost, ctx->stream));
-    return sc_ctx_synchronize(ctx);
+    const bool obs = n_obs > 0;
+    sc_stage st(ctx);
+    const int io_occ = st.in(base, cells), i_l = st.in(lines, (size_t)n_lines * 16), i_off = st.in(obs_off, obs ? (size_t)(n_obs + 1) * 4 : 0),
+              i_box = st.in(obs_box, (size_t)n_obs * 16), i_cl = st.in(obs_closed, (size_t)n_obs), i_g = st.in(grid_off, (size_t)(G + 1) * 4);
+    st.back(io_occ, occ, cells);
+    int r = st.upload();
+    if (r == SC_OK)
+        r = sc_occ_from_polygons(ctx, base ? st.dev<const uint8_t>(io_occ) : nullptr, G, W, H, x_min, y_min, res_x, res_y,
+                                 n_lines > 0 ? st.dev<const float>(i_l) : nullptr, n_lines, obs ? st.dev<const int32_t>(i_off) : nullptr, n_obs,
+                                 obs && obs_box ? st.dev<const float>(i_box) : nullptr, obs && obs_closed ? st.dev<const uint8_t>(i_cl) : nullptr,
+                                 grid_off ? st.dev<const int32_t>(i_g) : nullptr, st.dev<uint8_t>(io_occ));
+    return st.finish(r);
 }

@@ -10,12 +10,20 @@
 
 #include "../../include/sea_current_hip.h"
 
+// a grow-only device buffer of a context (sc_scratch_reserve); freed with the context
 struct sc_scratch {
     void* p = nullptr;
     size_t bytes = 0;
+    sc_scratch() = default;
+    sc_scratch(const sc_scratch&) = delete;
+    sc_scratch& operator=(const sc_scratch&) = delete;
+    ~sc_scratch() { if (p) (void)hipFree(p); }
 };
 
-struct sc_ctx {
+static inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// hidden: the library's own types; their (inline) members are not part of the exported symbols
+struct __attribute__((visibility("hidden"))) sc_ctx {
     int device = 0;
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;
@@ -28,7 +36,10 @@ struct sc_ctx {
     std::vector<hipEvent_t> ev_pool;
     double t_ms[SC_K_COUNT] = {0};
     int64_t t_n[SC_K_COUNT] = {0};
-    // scratch (grow-only)
+    // scratch: grow-only, reserved through sc_scratch_reserve (which keeps scratch_total), freed by the destructors
+    size_t scratch_total = 0;
+    sc_scratch host_stage;  // the _host wrappers' device copies (sc_stage), one call at a time
+    sc_scratch astar_ends;  // sc_astar_gfield: int32 start, goal, len, path[1] of its one query
     sc_scratch colbits;     // EDT: uint32 [batch][nb][W]
     sc_scratch updown;      // EDT, rows wider than 1024: uint32 [batch][nb][W], rows to the nearest obstacle in the bands above / below
     sc_scratch edt_fault;   // EDT, rows wider than 1024: int32 [1], set by a wavefront whose bounded wait ran out (read by sc_ctx_synchronize)
@@ -51,13 +62,9 @@ struct sc_ctx {
     sc_scratch sm_tp;       // smoothing: fp64 TOPP-RA inputs p0 p1 v0 v1 vlo vhi alo ahi [P] | K [P][N+1][2] x t [P][N+1] u [P][N]
     sc_scratch sm_int;      // smoothing: int32 npts [P] | TOPP-RA status [P] | resample status [P] | resample offsets [P+1]
     sc_scratch sm_smp;      // smoothing: float vel | curvature [capacity] when the caller wants ang_vel without them
-    sc_scratch sm_stage;    // smoothing: sc_smooth_paths_batch_host's device copies
     sc_scratch occ_prep;    // polygon occupancy: float4 box [n_obs] | int2 cell-row range [n_obs] of every obstacle
-    sc_scratch occ_stage;   // polygon occupancy: sc_occ_from_polygons_host's device copies
     sc_scratch fld_mask;    // cost fields: uint64 [G][tile rows][W] traversability of 64 rows per column
     sc_scratch fld_state;   // cost fields: per-field ok [F] | tile stamps [F][tiles] | two tile lists [F * tiles] | round counts
-    sc_scratch fld_stage;   // cost fields: the _host forms' device copies
-    sc_scratch staging[9];  // _host wrappers
     int astar_cap = 1 << 16;          // ring entries per bucket (power of two)
     size_t astar_slot_budget = (size_t)96 << 30;  // bytes of g + bitmap + ring scratch this context may take (SC_ASTAR_SLOT_GB), further bounded by what the device has free; 4096^2: 96 GiB = 1966 slots measured best (48: -34 %, 160: -17 %)
     int last_Q = 0;
@@ -87,6 +94,49 @@ struct sc_ctx {
     } while (0)
 
 int sc_scratch_reserve(sc_ctx* ctx, sc_scratch* s, size_t bytes);
+
+// The device copies of one `_host` call: slots laid out 256-byte aligned in ctx->host_stage.
+//   sc_stage st(ctx);
+//   const int i = st.in(src, bytes), o = st.out(dst, bytes);   // src / dst null: slot only, no copy
+//   int r = st.upload();                                       // reserve, enqueue the uploads
+//   if (r == SC_OK) r = sc_device_form(ctx, st.dev<const T>(i), ..., st.dev<T>(o));
+//   return st.finish(r);                                       // ok: downloads + sc_ctx_synchronize
+// Every slot, an empty one included, owns at least 256 bytes, so dev() is never null: a wrapper that hands the device
+// form a null pointer says so at the call site.  finish() with an error waits for the stream (ignoring the outcome of
+// the wait) and returns the error: no copy or kernel is left using the buffer when the next call reuses it.
+class __attribute__((visibility("hidden"))) sc_stage {
+  public:
+    explicit sc_stage(sc_ctx* ctx) : ctx_(ctx) {}
+    int in(const void* src, size_t bytes) {
+        const int i = slot(bytes);
+        if (src && bytes) up_.push_back({i, const_cast<void*>(src), bytes});
+        return i;
+    }
+    int out(void* dst, size_t bytes) {
+        const int i = slot(bytes);
+        back(i, dst, bytes);
+        return i;
+    }
+    // download `bytes` of slot i to dst at the next finish(); dst null or bytes 0: nothing
+    void back(int i, void* dst, size_t bytes) {
+        if (dst && bytes) down_.push_back({i, dst, bytes});
+    }
+    int upload();
+    template <class T> T* dev(int i) const { return (T*)((char*)ctx_->host_stage.p + off_[i]); }
+    int finish(int r);
+
+  private:
+    struct copy { int slot; void* host; size_t bytes; };
+    int slot(size_t bytes) {
+        off_.push_back(end_);
+        end_ += al256(bytes ? bytes : 1);
+        return (int)off_.size() - 1;
+    }
+    sc_ctx* ctx_;
+    size_t end_ = 0;
+    std::vector<size_t> off_;
+    std::vector<copy> up_, down_;
+};
 
 // RAII-free timing bracket: t = sc_time_begin(ctx, kid); launch...; sc_time_end(ctx, t)
 int sc_time_begin(sc_ctx* ctx, int kid);

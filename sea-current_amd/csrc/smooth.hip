@@ -184,8 +184,6 @@ smooth_finish_kernel(const int32_t* __restrict__ rstat, const int32_t* __restric
     for (int i = gid; i < M; i += gridDim.x * 256) ang_vel[i] = vel[i] * curv[i];
 }
 
-static size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 extern "C" int sc_smooth_paths_batch(sc_ctx* ctx, const float* path, const int32_t* npts, int P, int n_max, const double* limits,
                                      float start_angle, const float* lines, int nlines, float dt, int N, int nsub, int64_t sample_capacity,
                                      float* ctrl, int32_t* seg_off, float* arclength, int32_t* length, int32_t* offsets, int32_t* status,
@@ -271,54 +269,37 @@ extern "C" int sc_smooth_paths_batch_host(sc_ctx* ctx, const float* path, const 
         sample_capacity < 0 || sample_capacity > INT32_MAX)
         return SC_ERR_INVALID;
     SC_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t S = (size_t)P * (n_max - 1), M = sample_capacity > 0 ? (size_t)sample_capacity : 1;
-    // one staging block: inputs, per-path outputs, per-sample outputs (each 256-byte aligned)
-    enum { I_PATH, I_NPTS, I_LIM, I_LINES, O_CTRL, O_SEGOFF, O_AL, O_LEN, O_OFF, O_ST, O_NEED, O_TIME, O_POS, O_VEL, O_ACC, O_PTS, O_CURV,
-           O_ANG, O_TPAR, O_SEG, NB };
-    const void* host_out[NB] = {};
-    host_out[O_TIME] = time; host_out[O_VEL] = vel; host_out[O_ACC] = acc; host_out[O_CURV] = curvature; host_out[O_ANG] = ang_vel;
-    host_out[O_TPAR] = tpar; host_out[O_SEG] = seg;
-    size_t sz[NB] = {(size_t)P * n_max * 8, (size_t)P * 4, (size_t)P * 32, (size_t)nlines * 16, S * 32, (size_t)(P + 1) * 4, (size_t)P * 4,
-                     (size_t)P * 4, (size_t)(P + 1) * 4, (size_t)P * 4, 8, M * 8, M * 4, M * 4, M * 4, M * 8, M * 4, M * 4, M * 4, M * 4};
-    for (int i = O_TIME; i < NB; ++i)
-        if (i != O_POS && i != O_PTS && !host_out[i]) sz[i] = 0;
-    size_t off[NB + 1];
-    off[0] = 0;
-    for (int i = 0; i < NB; ++i) off[i + 1] = off[i] + al256(sz[i]);
-    int r = sc_scratch_reserve(ctx, &ctx->sm_stage, off[NB]);
-    if (r != SC_OK) return r;
-    char* b = (char*)ctx->sm_stage.p;
-    auto dp = [&](int i) -> void* { return sz[i] ? (void*)(b + off[i]) : nullptr; };
-    SC_HIP(ctx, hipMemcpyAsync(dp(I_PATH), path, sz[I_PATH], hipMemcpyHostToDevice, ctx->stream));
-    SC_HIP(ctx, hipMemcpyAsync(dp(I_NPTS), npts, sz[I_NPTS], hipMemcpyHostToDevice, ctx->stream));
-    SC_HIP(ctx, hipMemcpyAsync(dp(I_LIM), limits, sz[I_LIM], hipMemcpyHostToDevice, ctx->stream));
-    if (nlines > 0) SC_HIP(ctx, hipMemcpyAsync(dp(I_LINES), lines, sz[I_LINES], hipMemcpyHostToDevice, ctx->stream));
-    r = sc_smooth_paths_batch(ctx, (const float*)dp(I_PATH), (const int32_t*)dp(I_NPTS), P, n_max, (const double*)dp(I_LIM), start_angle,
-                              (const float*)dp(I_LINES), nlines, dt, N, nsub, sample_capacity, (float*)dp(O_CTRL), (int32_t*)dp(O_SEGOFF),
-                              (float*)dp(O_AL), (int32_t*)dp(O_LEN), (int32_t*)dp(O_OFF), (int32_t*)dp(O_ST), (int64_t*)dp(O_NEED),
-                              (double*)dp(O_TIME), (float*)dp(O_POS), (float*)dp(O_VEL), (float*)dp(O_ACC), (float*)dp(O_PTS),
-                              (float*)dp(O_CURV), (float*)dp(O_ANG), (float*)dp(O_TPAR), (int32_t*)dp(O_SEG));
-    if (r != SC_OK) return r;
-    SC_HIP(ctx, hipMemcpyAsync(seg_off, dp(O_SEGOFF), sz[O_SEGOFF], hipMemcpyDeviceToHost, ctx->stream));
-    SC_HIP(ctx, hipMemcpyAsync(arclength, dp(O_AL), sz[O_AL], hipMemcpyDeviceToHost, ctx->stream));
-    SC_HIP(ctx, hipMemcpyAsync(length, dp(O_LEN), sz[O_LEN], hipMemcpyDeviceToHost, ctx->stream));
-    SC_HIP(ctx, hipMemcpyAsync(offsets, dp(O_OFF), sz[O_OFF], hipMemcpyDeviceToHost, ctx->stream));
-    SC_HIP(ctx, hipMemcpyAsync(status, dp(O_ST), sz[O_ST], hipMemcpyDeviceToHost, ctx->stream));
-    SC_HIP(ctx, hipMemcpyAsync(needed, dp(O_NEED), 8, hipMemcpyDeviceToHost, ctx->stream));
-    r = sc_ctx_synchronize(ctx);
+    const size_t S = (size_t)P * (n_max - 1), M = sample_capacity > 0 ? (size_t)sample_capacity : 1, pb = (size_t)P * 4;
+    sc_stage st(ctx);
+    const int i_path = st.in(path, (size_t)P * n_max * 8), i_npts = st.in(npts, pb), i_lim = st.in(limits, pb * 8),
+              i_l = st.in(lines, (size_t)nlines * 16);
+    const int o_ctrl = st.out(nullptr, S * 32), o_so = st.out(seg_off, pb + 4), o_al = st.out(arclength, pb), o_len = st.out(length, pb),
+              o_off = st.out(offsets, pb + 4), o_st = st.out(status, pb), o_need = st.out(needed, 8);
+    // per-sample outputs (room only for those the caller wants), downloaded once the counts are known
+    auto smp = [&](const void* h, size_t elem) { return st.out(nullptr, h ? M * elem : 0); };
+    const int o_time = smp(time, 8), o_pos = smp(pos, 4), o_vel = smp(vel, 4), o_acc = smp(acc, 4), o_pts = smp(pts, 8), o_cv = smp(curvature, 4),
+              o_ang = smp(ang_vel, 4), o_tpar = smp(tpar, 4), o_seg = smp(seg, 4);
+    int r = st.upload();
+    if (r == SC_OK)
+        r = sc_smooth_paths_batch(ctx, st.dev<const float>(i_path), st.dev<const int32_t>(i_npts), P, n_max, st.dev<const double>(i_lim), start_angle,
+                                  nlines > 0 ? st.dev<const float>(i_l) : nullptr, nlines, dt, N, nsub, sample_capacity, st.dev<float>(o_ctrl),
+                                  st.dev<int32_t>(o_so), st.dev<float>(o_al), st.dev<int32_t>(o_len), st.dev<int32_t>(o_off), st.dev<int32_t>(o_st),
+                                  st.dev<int64_t>(o_need), time ? st.dev<double>(o_time) : nullptr, st.dev<float>(o_pos),
+                                  vel ? st.dev<float>(o_vel) : nullptr, acc ? st.dev<float>(o_acc) : nullptr, st.dev<float>(o_pts),
+                                  curvature ? st.dev<float>(o_cv) : nullptr, ang_vel ? st.dev<float>(o_ang) : nullptr,
+                                  tpar ? st.dev<float>(o_tpar) : nullptr, seg ? st.dev<int32_t>(o_seg) : nullptr);
+    r = st.finish(r);
     if (r != SC_OK) return r;
     // the samples written: up to the first truncated path
     size_t Mw = (size_t)offsets[P];
     for (int p = 0; p < P; ++p)
         if (status[p] == SC_SMOOTH_TRUNCATED) { Mw = (size_t)offsets[p]; break; }
     if (Mw > (size_t)sample_capacity) Mw = (size_t)sample_capacity;
-    SC_HIP(ctx, hipMemcpyAsync(ctrl, dp(O_CTRL), (size_t)seg_off[P] * 32, hipMemcpyDeviceToHost, ctx->stream));
-    void* dst[NB] = {};
-    dst[O_TIME] = time; dst[O_POS] = pos; dst[O_VEL] = vel; dst[O_ACC] = acc; dst[O_PTS] = pts; dst[O_CURV] = curvature; dst[O_ANG] = ang_vel;
-    dst[O_TPAR] = tpar; dst[O_SEG] = seg;
-    for (int i = O_TIME; i < NB; ++i)
-        if (dst[i] && Mw) SC_HIP(ctx, hipMemcpyAsync(dst[i], dp(i), Mw * (sz[i] / M), hipMemcpyDeviceToHost, ctx->stream));
-    return sc_ctx_synchronize(ctx);
+    st.back(o_ctrl, ctrl, (size_t)seg_off[P] * 32);
+    st.back(o_time, time, Mw * 8); st.back(o_pos, pos, Mw * 4); st.back(o_vel, vel, Mw * 4); st.back(o_acc, acc, Mw * 4);
+    st.back(o_pts, pts, Mw * 8); st.back(o_cv, curvature, Mw * 4); st.back(o_ang, ang_vel, Mw * 4); st.back(o_tpar, tpar, Mw * 4);
+    st.back(o_seg, seg, Mw * 4);
+    return st.finish(SC_OK);
 }
 
 // cells of sc_path_waypoints_batch -> float points (occupancy_grid::centre_of), one thread per (path, point)

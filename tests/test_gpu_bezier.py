@@ -250,3 +250,121 @@ def test_resample_table_sizes(ctx, oracle, nsub):
         assert np.array_equal(got["seg"][sl], ref["seg"]), b
         assert np.abs(got["t"][sl] - ref["t"]).max() < 5e-7, b
         assert np.abs(got["pts"][sl] - ref["pts"]).max() < 1e-5, b
+
+
+# ---- the _host forms (numpy through ctypes) against the device forms (Context, torch) on the same inputs: every output
+# ---- byte-equal where the device form writes it
+
+def _host(name, *args):
+    import sea_current_amd as sc
+    st = getattr(sc.lib(), "sc_%s_host" % name)(*[sc._ptr(a) if isinstance(a, np.ndarray) else a for a in args])
+    assert st == 0, name
+
+
+def _cu(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def _same(ctx, dev, host):
+    ctx.synchronize()
+    d = dev.cpu().numpy()
+    assert d.dtype == host.dtype and d.shape == host.shape and d.tobytes() == host.tobytes()
+
+
+def test_from_path_and_arclength_host_forms(ctx):
+    rng = np.random.default_rng(31)
+    P, n_max, nsub = 13, 7, 40
+    npts = rng.integers(2, n_max + 1, P).astype(np.int32)
+    path = np.cumsum(rng.uniform(0.3, 2.0, (P, n_max, 2)) * rng.choice([-1, 1], (P, n_max, 2)), axis=1).astype(np.float32)
+    lines = rng.uniform(-5, 5, (6, 4)).astype(np.float32)
+    for ln in (lines, None):
+        nl = 0 if ln is None else ln.shape[0]
+        dev = ctx.bezier_from_path(_cu(path), _cu(npts), lines=None if ln is None else _cu(ln))
+        host = np.empty((P, n_max - 1, 4, 2), np.float32)
+        _host("bezier_from_path_batch", ctx._h, path, npts, P, n_max, float("nan"), ln, nl, host)
+        _same(ctx, dev, host)
+    S = P * (n_max - 1)
+    cum, seg_len = ctx.bezier_arclength(dev, nsub)
+    hc, hs = np.empty((S, nsub + 1), np.float32), np.empty(S, np.float32)
+    _host("bezier_arclength_batch", ctx._h, host, S, nsub, hc, hs)
+    _same(ctx, cum, hc)
+    _same(ctx, seg_len, hs)
+
+
+@pytest.mark.parametrize("nudge", [0, 1])
+def test_resample_host_form(ctx, oracle, nudge):
+    """With all four optional outputs and with none; profile_pos is in-out (nudged in place)."""
+    rng = np.random.default_rng(41 + nudge)
+    B, nsub = 9, 32
+    ctrls, cums, als, pps, seg_off, prof_off = [], [], [], [], [0], [0]
+    for b in range(B):
+        nwp = int(rng.integers(2, 6))
+        path = np.cumsum(rng.uniform(0.5, 3.0, (nwp, 2)) * rng.choice([-1, 1], (nwp, 2)), axis=0).astype(np.float32)
+        c = oracle.bezier_from_path(path)
+        cum = oracle.bezier_arclength(c, nsub)[1].astype(np.float32)
+        AL = np.float32(cum[:, -1].sum(dtype=np.float32))
+        n = int(rng.integers(40 * (nwp - 1), 300))
+        pp = (np.sort(rng.uniform(0, 1, n)) * AL).astype(np.float32)
+        if b % 2:
+            k = rng.choice(np.arange(1, n - 1), max(1, n // 30), replace=False)
+            pp[k] += rng.normal(0, 0.05 * AL, k.size).astype(np.float32)
+        ctrls.append(c); cums.append(cum); als.append(AL); pps.append(pp)
+        seg_off.append(seg_off[-1] + nwp - 1); prof_off.append(prof_off[-1] + n)
+    ctrl, cum, al = np.concatenate(ctrls), np.concatenate(cums), np.array(als, np.float32)
+    so, po, pp = np.array(seg_off, np.int32), np.array(prof_off, np.int32), np.concatenate(pps)
+    S, M = ctrl.shape[0], pp.shape[0]
+    tpp = _cu(pp)
+    dev = ctx.bezier_resample(_cu(ctrl), _cu(cum), _cu(al), _cu(so), tpp, _cu(po), nudge=bool(nudge))
+    ctx.synchronize()
+    d = {k: v.cpu().numpy() for k, v in dev.items()}
+    for want in (True, False):
+        hpp = pp.copy()
+        h = dict(pts=np.zeros((M, 2), np.float32), t=np.zeros(M, np.float32), seg=np.zeros(M, np.int32), curvature=np.zeros(M, np.float32))
+        st = np.empty(B, np.int32)
+        outs = [h[k] if want else None for k in ("pts", "t", "seg", "curvature")]
+        _host("bezier_resample_batch", ctx._h, ctrl, cum, al, so, B, S, nsub, hpp, po, nudge, *outs, st)
+        _same(ctx, tpp, hpp)
+        assert d["status"].tobytes() == st.tobytes()
+        assert (st == 0).any()
+        if want:
+            for b in np.flatnonzero(st == 0):
+                sl = slice(po[b], po[b + 1])
+                for k in h:
+                    assert d[k][sl].tobytes() == h[k][sl].tobytes(), (b, k)
+        else:
+            assert not any(v.any() for v in h.values())
+
+
+def test_eval_and_curve_host_forms(ctx):
+    rng = np.random.default_rng(51)
+    S, M = 11, 300
+    ctrl = rng.uniform(-3, 3, (S, 4, 2)).astype(np.float32)
+    seg = rng.integers(0, S, M).astype(np.int32)
+    t = rng.uniform(0, 1, M).astype(np.float32)
+    for order in (0, 1, 2):
+        host = np.empty((M, 2), np.float32)
+        _host("bezier_eval_batch", ctx._h, ctrl, S, seg, t, M, order, host)
+        _same(ctx, ctx.bezier_eval(_cu(ctrl), _cu(seg), _cu(t), order), host)
+    for degree in (2, 5):
+        c = rng.uniform(-3, 3, (S, degree + 1, 2)).astype(np.float32)
+        host = np.empty((M, 2), np.float32)
+        _host("bezier_curve_batch", ctx._h, c, S, degree, seg, t, M, host)
+        _same(ctx, ctx.bezier_curve(_cu(c), _cu(seg), _cu(t)), host)
+
+
+def test_chebfit_chebeval_host_forms(ctx):
+    rng = np.random.default_rng(61)
+    degree, sizes = 6, [5, 40, 300]
+    off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+    B = len(sizes)
+    x = rng.uniform(-2, 3, off[-1]).astype(np.float32)
+    y = (np.sin(x) + rng.normal(0, 0.01, x.size)).astype(np.float32)
+    coef, xr = ctx.chebfit(_cu(x), _cu(y), _cu(off), degree)
+    hc, hr = np.empty((B, degree), np.float32), np.empty((B, 2), np.float32)
+    _host("chebfit_batch", ctx._h, x, y, off, B, degree, hc, hr)
+    _same(ctx, coef, hc)
+    _same(ctx, xr, hr)
+    hy = np.empty_like(x)
+    _host("chebeval_batch", ctx._h, x, off, B, degree, hc, hr, hy)
+    _same(ctx, ctx.chebeval(_cu(x), _cu(off), coef, xr), hy)

@@ -40,3 +40,31 @@ def test_invalid_arguments_are_status_codes():
     torch.cuda.synchronize()
     assert res["status"].tolist() == [2, 2, 2]
     ctx.close()
+
+
+def test_host_forms_allocate_nothing_in_steady_state():
+    """The header promises no allocation in steady state: a fixed sequence of _host calls (one staging buffer serves them all)
+    run twice leaves scratch_bytes() where the first pass left it."""
+    import sea_current_amd as sc
+    from sea_current_amd import synth
+    ctx = sc.Context(0)
+    occ = synth.salt_grid(192, 128, 0.1, seed=3)
+    wp = np.cumsum(np.full((8, 6, 2), 0.7, np.float32), axis=1)
+    T = np.ones((50, 2), np.float32)
+
+    def one_pass():
+        d2 = ctx.edt_host(occ)
+        s, g = synth.queries(d2 >= 1, 24, seed=3)
+        res = ctx.astar_batch_host(d2, s, g, Lmax=1024)
+        ctx.path_waypoints_host(d2, res["path"], res["len"], res["status"])
+        f = ctx.cost_fields_host(d2, s[:3])
+        ctx.field_paths_host(d2, f["g"], s[:3], np.zeros(8, np.int32), g[:8])
+        out = np.empty((50, 2), np.float32)
+        assert ctx._l.sc_bezier_shrink_tangent_batch_host(ctx._h, sc._ptr(T), sc._ptr(T), 50, 0.5, None, 0, sc._ptr(out)) == 0
+        ctx.smooth_paths_host(wp, np.full(8, 6, np.int32), (-1.0, 1.0, -0.5, 0.5), 4096)
+
+    one_pass()
+    b1 = ctx.scratch_bytes()
+    one_pass()
+    assert ctx.scratch_bytes() == b1 > 0
+    ctx.close()

@@ -74,3 +74,34 @@ def test_fmt_star_random_polygons_and_truncation(oracle):
             if ref["status"] == 0:
                 assert got["cost"][q] == np.float32(ref["cost"]) and np.array_equal(got["path"][q, :ref["len"]], ref["path"]), (Lmax, q)
     ctx.close()
+
+
+@pytest.mark.parametrize("E0", [True, False])
+def test_fmt_star_host_form(oracle, E0):
+    """sc_fmt_star_batch_host (numpy through ctypes) against the device form on the same inputs, with E = 0 and E > 0: len, cost,
+    status byte-equal, and the path of every query that found one."""
+    import torch
+    import sea_current_amd as sc
+    ctx = sc.Context(0)
+    lines, off = _world(EXAMPLE)
+    samples, _ = oracle.sample_free(300, (-1, 1, -1, 1), lines, off)
+    rng = np.random.default_rng(77)
+    starts = np.array([(-0.5, 1.0)] + [tuple(samples[i]) for i in rng.integers(1, 300, 9)] + [(-0.9, -0.9)], np.float32)
+    goals = np.array([(1.0, -1.0)] + [tuple(samples[i]) for i in rng.integers(1, 300, 9)] + [(0.5, 0.5)], np.float32)
+    Q, Lmax, rn = starts.shape[0], 128, 0.6
+    ln = None if E0 else lines
+    E = 0 if E0 else lines.shape[0]
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32)).cuda()
+    dev = ctx.fmt_star(t(samples), t(starts), t(goals), rn, None if E0 else t(lines), Lmax=Lmax)
+    ctx.synchronize()
+    d = {k: v.cpu().numpy() for k, v in dev.items()}
+    h = dict(path=np.zeros((Q, Lmax, 2), np.float32), len=np.zeros(Q, np.int32), cost=np.zeros(Q, np.float32), status=np.zeros(Q, np.int32))
+    p = sc._ptr
+    assert sc.lib().sc_fmt_star_batch_host(ctx._h, p(samples), samples.shape[0], p(starts), p(goals), Q, rn, p(ln), E, Lmax,
+                                           *[p(h[k]) for k in ("path", "len", "cost", "status")]) == 0
+    for k in ("len", "cost", "status"):
+        assert d[k].tobytes() == h[k].tobytes(), k
+    assert (h["status"] == 0).sum() >= Q // 2
+    for q in np.flatnonzero(h["status"] == 0):
+        assert d["path"][q, :h["len"][q]].tobytes() == h["path"][q, :h["len"][q]].tobytes(), q
+    ctx.close()

@@ -304,3 +304,43 @@ def test_cells_to_points_is_centre_of(ctx):
                 e[0], e[exp_n - 1] = starts[q], goals[q]
             assert np.array_equal(path[q, :exp_n], e), q
             assert (path[q, exp_n:] == 0).all(), q
+
+
+def test_host_form_equals_device_form(ctx, bench_wp):
+    """sc_smooth_paths_batch_host against Context.smooth_paths on the same inputs, (a) with a capacity that truncates a path and
+    (b) with the optional outputs null: the per-path outputs byte-equal, the samples byte-equal as far as they are written,
+    and nothing copied back past them."""
+    import sea_current_amd as sc
+    wp = np.ascontiguousarray(bench_wp[:256], dtype=np.float32)
+    P, n_max, _ = wp.shape
+    npts = np.full(P, n_max, np.int32)
+    lim = (-1.0, 1.0, -0.5, 0.5)
+    full = _smooth(ctx, wp)
+    need = int(full["needed"][0])
+    cap = need // 2
+    dev = _smooth(ctx, wp, capacity=cap)
+    assert (dev["status"] == 4).any() and (dev["status"] == 0).any()
+    host = ctx.smooth_paths_host(wp, npts, lim, cap)
+    written = int(dev["offsets"][np.argmax(dev["status"] == 4)])
+
+    def same(d, h, keys, n):
+        for k in ("seg_off", "arclength", "length", "offsets", "status", "needed"):
+            assert d[k].tobytes() == h[k].tobytes(), k
+        L = int(h["seg_off"][P])
+        assert d["ctrl"][:L].tobytes() == h["ctrl"][:L].tobytes() and not h["ctrl"][L:].any()
+        for k in keys:
+            assert d[k][:n].tobytes() == h[k][:n].tobytes(), k
+            assert not h[k][n:].any(), k
+
+    same(dev, host, SAMPLE_KEYS, written)
+    # (b) time, vel, acc, curvature, ang_vel, tpar, seg null; room for every sample
+    o = dict(ctrl=np.zeros((P * (n_max - 1), 4, 2), np.float32), seg_off=np.zeros(P + 1, np.int32), arclength=np.zeros(P, np.float32),
+             length=np.zeros(P, np.int32), offsets=np.zeros(P + 1, np.int32), status=np.zeros(P, np.int32), needed=np.zeros(1, np.int64),
+             pos=np.zeros(need + 5, np.float32), pts=np.zeros((need + 5, 2), np.float32))
+    p = sc._ptr
+    limits = np.ascontiguousarray(np.broadcast_to(np.array(lim), (P, 4)))
+    assert sc.lib().sc_smooth_paths_batch_host(ctx._h, p(wp), p(npts), P, n_max, p(limits), float("nan"), None, 0, 0.02, 100, 100, need + 5,
+                                               *[p(o.get(k)) for k in ("ctrl", "seg_off", "arclength", "length", "offsets", "status",
+                                                                       "needed", "time", "pos", "vel", "acc", "pts", "curvature",
+                                                                       "ang_vel", "tpar", "seg")]) == 0
+    same(full, o, ("pos", "pts"), need)

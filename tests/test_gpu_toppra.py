@@ -96,6 +96,45 @@ def test_toppra_per_stage_limits(ctx, oracle, N):
         assert np.allclose(out["t"][p].cpu().numpy(), r["t"], rtol=1e-9, atol=1e-12)
 
 
+@pytest.mark.parametrize("per_stage", [0, 1])
+def test_toppra_host_forms_equal_device_forms(ctx, per_stage):
+    """sc_toppra_hermite_batch_host and sc_toppra_sample_batch_host (numpy through ctypes) give the bytes of the device forms
+    on the same inputs: K, x, u, t and status whole, the samples as far as they are written (min(length, max_len))."""
+    import sea_current_amd as sc
+    from sea_current_amd import synth
+    P, dof, N, L, dt = 12, 3, 60, 120, 0.02   # 67 .. 174 samples per plan
+    pl = synth.toppra_plans(P, dof=dof)
+    vlim = pl["vlim"]
+    if per_stage:
+        vlim = vlim[:, None, :] * (0.5 + np.abs(np.sin(3 * np.arange(N + 1) / N)))[None, :, None]
+    a = lambda v: np.ascontiguousarray(v, dtype=np.float64)
+    ends = [a(pl["p0"]), a(pl["p1"]), a(pl["v0"]), a(pl["v1"])]
+    vl, al = [a(-vlim), a(vlim)], [a(-pl["alim"]), a(pl["alim"])]
+    dev = ctx.toppra(*map(_t, ends + vl + al), N=N)
+    ctx.synchronize()
+    p = sc._ptr
+    host = dict(K=np.empty((P, N + 1, 2)), x=np.empty((P, N + 1)), u=np.empty((P, N)), t=np.empty((P, N + 1)), status=np.empty(P, np.int32))
+    assert sc.lib().sc_toppra_hermite_batch_host(ctx._h, P, dof, N, *map(p, ends + vl), per_stage, *map(p, al), 0.0, 0.0,
+                                                 *[p(host[k]) for k in ("K", "x", "u", "t", "status")]) == 0
+    for k in host:
+        assert dev[k].cpu().numpy().tobytes() == host[k].tobytes(), k
+    assert (host["status"] == 0).all()
+    smp = ctx.toppra_sample(*map(_t, ends), dev["x"], dev["t"], dt, L)
+    ctx.synchronize()
+    ds = {k: v.cpu().numpy() for k, v in smp.items()}
+    hs = dict(pos=np.empty((P, dof, L), np.float32), vel=np.empty((P, dof, L), np.float32), acc=np.empty((P, dof, L), np.float32),
+              time=np.empty((P, L)), length=np.empty(P, np.int32))
+    assert sc.lib().sc_toppra_sample_batch_host(ctx._h, P, dof, N, *map(p, ends), p(host["x"]), p(host["t"]), dt, L,
+                                                *[p(hs[k]) for k in ("pos", "vel", "acc", "time", "length")]) == 0
+    assert ds["length"].tobytes() == hs["length"].tobytes()
+    assert (hs["length"] > L).any() and (hs["length"] < L).any()      # plans cut at max_len and plans that end before it
+    for q in range(P):
+        n = min(int(hs["length"][q]), L)
+        for k in ("pos", "vel", "acc"):
+            assert ds[k][q, :, :n].tobytes() == hs[k][q, :, :n].tobytes(), (q, k)
+        assert ds["time"][q, :n].tobytes() == hs["time"][q, :n].tobytes(), q
+
+
 def test_toppra_statuses_match_oracle(ctx, oracle):
     """Plans the sweeps give up on (status 1: no controllable set; status 2: the start state is outside K[0]) next to
     solvable ones in one batch: statuses equal the oracle's, and whatever the oracle wrote before it stopped is there."""
