@@ -443,6 +443,81 @@ int sc_cells_to_points_batch(sc_ctx* ctx, const int32_t* wp, const int32_t* n_wp
                              float x_min, float y_min, float res_x, float res_y, const float* starts, const float* goals, float* path,
                              int32_t* npts);
 
+/* ---- per-stage speed limits from curvature and clearance ------------------------------------------------------
+ * The reference's gen_vel_prof takes a vel_lim_func, a limit that varies along the path (examples/test.cpp:194-209);
+ * sc_toppra_hermite_batch takes it as vlim_per_stage = 1.  These calls compute such a limit for curves that have legs
+ * and arclength tables, and sc_smooth_paths_limited_batch puts it between the arclength and TOPP-RA of
+ * sc_smooth_paths_batch.  Curves are not moved or shrunk: only the speed is limited.
+ *
+ * Per path: ctrl float [ns][4][2] (its legs), cum float [ns][nsub+1] (sc_bezier_arclength_batch), seg_len[j] = cum[j][nsub],
+ * AL = arclength (float), limits fp64 (vel_min, vel_max, acc_min, acc_max), dyn fp64 [4] = (omega_max, alat_max, clear_floor,
+ * clear_gain), optionally a grid d2 int32 [H][W] in the frame (W, H, x_min, y_min, res_x, res_y) of
+ * sc_cells_to_points_batch and sc_occ_from_polygons.  All arithmetic is fp64 on the float32 inputs.
+ *   Stage i of N: s_i = i / N, a_i = (double)AL * (3 s_i^2 - 2 s_i^3), the TOPP-RA path of gen_vel_prof<1>(AL, 0, 0, 0, ..)
+ *     at gridpoint i, where the limit of stage i applies.
+ *   Window: TOPP-RA enforces limits at gridpoints only (up to 1.5 AL / N apart), so a stage answers for the curve half
+ *     way to its neighbours: lo_i = a_0 for i = 0, else (a_{i-1} + a_i) / 2; hi_i = a_N for i = N, else (a_i + a_{i+1}) / 2;
+ *     samples j = -J .. J at x = a_i + (j/J) (a_i - lo_i) for j < 0, a_i + (j/J) (hi_i - a_i) for j >= 0.  1 <= J <= SC_SPEED_MAX_J.
+ *   Position -> (leg, t): B_0 = 0, B_{j+1} = B_j + (double)seg_len[j] in leg order; x clamped to [0, AL]; leg j = the last with
+ *     B_j <= x, at most ns-1; r = clamp(x - B_j, 0, seg_len[j]); k = the last index with cum[j][k] <= r, at most nsub-1;
+ *     t = clamp((k + f) / nsub, 0, 1), f = (r - c_k) / (c_{k+1} - c_k), or 0 when that denominator is <= 0.
+ *   Curvature: kappa = |x'y'' - y'x''| / (x'^2 + y'^2)^1.5 from the hodograph and the second derivative at t (the formula of
+ *     the resample's curvature output); a kappa that is not finite counts as 0.
+ *   Clearance (only with a grid and a finite clear_floor): fx = clamp((x - x_min) / res_x - 0.5, 0, W-1), ix = min((int)fx,
+ *     max(W-2, 0)), ux = fx - ix (W == 1: the second column is the first), the same in y; c = the bilinear interpolation of
+ *     min(res_x, res_y) * sqrt((double)d2[cell]) over the four cell centres.  Bilinear on purpose: the limit is continuous in
+ *     the position.  It can overestimate the true clearance by a fraction of a cell (d2 is the distance between cell
+ *     centres, and the interpolant of a distance field lies above it between samples of a convex stretch).
+ *   Limit of a sample: v = vel_max; kappa > 0: v = min(v, omega_max / kappa, sqrt(alat_max / kappa)); clearance on:
+ *     v = min(v, clear_floor + clear_gain * c).  vhi[i] = the minimum over the 2J+1 samples, vlo[i] = vel_min.
+ *     min_clear = the minimum of c over every sample of the path (float), +inf when the clearance is off.
+ * Contract of dyn: omega_max > 0, alat_max > 0 (+inf switches the term off), clear_floor >= 0 or +inf (off), clear_gain >= 0
+ * and finite, no NaN.  A path whose dyn breaks it gets SC_SMOOTH_BAD_INPUT, decided on the device; the _host forms return
+ * SC_ERR_INVALID for such data (and for a NaN in limits) before any launch.  With clear_floor = 0 a curve through a
+ * spot of zero clearance has limit 0 there, and no profile passes a stage of limit 0 in finite time.  The parametriser
+ * would not say so (like the reference's, it gives an interval of zero speed 5 s), so the limits kernel decides it: a
+ * path with a term-made limit of 0 at an interior stage (0 < i < N) reports SC_SMOOTH_TOPPRA_FAILED, vhi and min_clear
+ * hold what was computed, and the other paths are not affected.  A positive clear_floor is the crawl speed that avoids it.
+ *
+ * sc_speed_limits_batch: P curves; curve p owns legs seg_off[p] .. seg_off[p+1]-1 of ctrl and cum, arclength float [P],
+ * limits and dyn fp64 [P][4]; status int32 [P] may be NULL (all SC_SMOOTH_OK); d2 NULL = no grid (the frame is then
+ * ignored).  vhi fp64 [P][N+1]; min_clear float [P] and status_out int32 [P] may be NULL.  status_out[p] = status[p] when
+ * that is not OK, else SC_SMOOTH_BAD_INPUT (dyn, or no leg), SC_SMOOTH_NONFINITE (arclength), SC_SMOOTH_TOPPRA_FAILED (a
+ * limit of 0 inside, see above) or SC_SMOOTH_OK; a path with one of the first three gets vhi = 1 and min_clear = 0.  Device pointers; enqueues one kernel (timed under SC_K_SMOOTH), no host
+ * synchronisation, no device-to-host copy; the launch is sized by P and reads the leg counts from seg_off on the device.
+ * Errors: SC_ERR_INVALID for NULL pointers, P outside 1..SC_SMOOTH_MAX_PATHS, nsub outside 1..SC_RESAMPLE_MAX_NSUB, N <= 0,
+ * J outside 1..SC_SPEED_MAX_J, and with a grid W or H outside 1..SC_MAX_DIM or a frame that is not finite with res > 0. */
+#define SC_SPEED_MAX_J 32
+int sc_speed_limits_batch(sc_ctx* ctx, const float* ctrl, const float* cum, const int32_t* seg_off, const float* arclength,
+                          const int32_t* status, int P, int nsub, int N, int J, const double* limits, const double* dyn,
+                          const int32_t* d2, int W, int H, float x_min, float y_min, float res_x, float res_y, double* vhi,
+                          float* min_clear, int32_t* status_out);
+/* host pointers; S = seg_off[P] legs (seg_off must not decrease) */
+int sc_speed_limits_batch_host(sc_ctx* ctx, const float* ctrl, const float* cum, const int32_t* seg_off, const float* arclength,
+                               const int32_t* status, int P, int nsub, int N, int J, const double* limits, const double* dyn,
+                               const int32_t* d2, int W, int H, float x_min, float y_min, float res_x, float res_y, double* vhi,
+                               float* min_clear, int32_t* status_out);
+/* sc_smooth_paths_batch with these limits between the arclength and TOPP-RA: the same arguments in the same order, then
+ * dyn fp64 [P][4], J, the grid (d2 NULL = none) and two more outputs, vmax_stage fp64 [P][N+1] (the vhi TOPP-RA ran with)
+ * and min_clear float [P], each may be NULL.  TOPP-RA runs with vlim_per_stage = 1 on (vel_min replicated, vhi); every
+ * other step is the one of sc_smooth_paths_batch, so with every term off (omega_max = alat_max = clear_floor = +inf) all
+ * outputs are bit-identical to that call.  A path whose dyn breaks the contract reports SC_SMOOTH_BAD_INPUT (it keeps its
+ * legs, length 0).  Chains behind sc_cells_to_points_batch on one stream like that call; scratch grows by
+ * 2 * P * (N+1) doubles. */
+int sc_smooth_paths_limited_batch(sc_ctx* ctx, const float* path, const int32_t* npts, int P, int n_max, const double* limits,
+                                  float start_angle, const float* lines, int nlines, float dt, int N, int nsub, int64_t sample_capacity,
+                                  float* ctrl, int32_t* seg_off, float* arclength, int32_t* length, int32_t* offsets, int32_t* status,
+                                  int64_t* needed, double* time, float* pos, float* vel, float* acc, float* pts, float* curvature,
+                                  float* ang_vel, float* tpar, int32_t* seg, const double* dyn, int J, const int32_t* d2, int W, int H,
+                                  float x_min, float y_min, float res_x, float res_y, double* vmax_stage, float* min_clear);
+int sc_smooth_paths_limited_batch_host(sc_ctx* ctx, const float* path, const int32_t* npts, int P, int n_max, const double* limits,
+                                       float start_angle, const float* lines, int nlines, float dt, int N, int nsub,
+                                       int64_t sample_capacity, float* ctrl, int32_t* seg_off, float* arclength, int32_t* length,
+                                       int32_t* offsets, int32_t* status, int64_t* needed, double* time, float* pos, float* vel,
+                                       float* acc, float* pts, float* curvature, float* ang_vel, float* tpar, int32_t* seg,
+                                       const double* dyn, int J, const int32_t* d2, int W, int H, float x_min, float y_min, float res_x,
+                                       float res_y, double* vmax_stage, float* min_clear);
+
 /* ---- the reference's own planner, batched -----------------------------------------------
  * planning_space::fast_marching_trees (sea_current.hpp:1339-1407) with near (:1328-1337), cost (:1315-1326) and
  * intersects (:142-178): FMT* from starts[q] to goals[q] (float [Q][2]) over n shared free samples (float [n][2], e.g.

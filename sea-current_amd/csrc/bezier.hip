@@ -104,19 +104,6 @@ bezier_ctrl_kernel(const float* __restrict__ path, const int32_t* __restrict__ n
     c[6] = w[2]; c[7] = w[3];
 }
 
-__device__ __forceinline__ void bez_eval(const float* c, double s, int order, double& ox, double& oy) {
-    const double r = 1 - s;
-    double o[2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a) {
-        const double p0 = c[a], p1 = c[2 + a], p2 = c[4 + a], p3 = c[6 + a];
-        if (order == 0) o[a] = r * r * r * p0 + 3 * r * r * s * p1 + 3 * r * s * s * p2 + s * s * s * p3;
-        else if (order == 1) o[a] = 3 * (r * r * (p1 - p0) + 2 * r * s * (p2 - p1) + s * s * (p3 - p2));
-        else o[a] = 6 * (r * (p2 - 2 * p1 + p0) + s * (p3 - 2 * p2 + p1));
-    }
-    ox = o[0]; oy = o[1];
-}
-
 __global__ void __launch_bounds__(256)
 bezier_eval_kernel(const float* __restrict__ ctrl, const int32_t* __restrict__ seg, const float* __restrict__ t, int M, int order,
                    float* __restrict__ out) {

@@ -62,6 +62,7 @@ struct __attribute__((visibility("hidden"))) sc_ctx {
     sc_scratch sm_tp;       // smoothing: fp64 TOPP-RA inputs p0 p1 v0 v1 vlo vhi alo ahi [P] | K [P][N+1][2] x t [P][N+1] u [P][N]
     sc_scratch sm_int;      // smoothing: int32 npts [P] | TOPP-RA status [P] | resample status [P] | resample offsets [P+1]
     sc_scratch sm_smp;      // smoothing: float vel | curvature [capacity] when the caller wants ang_vel without them
+    sc_scratch sm_vlim;     // smoothing with per-stage limits: fp64 vlo [P][N+1] | vhi [P][N+1]
     sc_scratch occ_prep;    // polygon occupancy: float4 box [n_obs] | int2 cell-row range [n_obs] of every obstacle
     sc_scratch fld_mask;    // cost fields: uint64 [G][tile rows][W] traversability of 64 rows per column
     sc_scratch fld_state;   // cost fields: per-field ok [F] | tile stamps [F][tiles] | two tile lists [F * tiles] | round counts
@@ -151,6 +152,22 @@ int sc_launch_arclength(sc_ctx* ctx, const float* ctrl, int S, int nsub, float* 
 int sc_launch_resample(sc_ctx* ctx, const float* ctrl, const float* cum, const float* arclength, const int32_t* seg_off, int B, int S,
                        int nsub, float* profile_pos, const int32_t* prof_off, int nudge, float* pts, float* tpar, int32_t* seg,
                        float* curvature, int32_t* status, const int32_t* S_dev);
+// per-stage speed limits (speed.hip); the grid of one call: d2 NULL = none
+struct sc_speed_frame {
+    const int32_t* d2;
+    int W, H;
+    float x_min, y_min, res_x, res_y;
+};
+// ns_bound: an upper bound of the legs of one path (sizes the LDS the kernel stages a path's tables in), <= 0: not known.
+// vlo (may be NULL) receives vel_min per stage, vhi_copy (may be NULL) a second copy of vhi.
+int sc_launch_speed_limits(sc_ctx* ctx, const float* ctrl, const float* cum, const int32_t* seg_off, const float* arclength,
+                           const int32_t* status, int P, int nsub, int N, int J, const double* limits, const double* dyn,
+                           const sc_speed_frame& fr, int ns_bound, double* vlo, double* vhi, double* vhi_copy, float* min_clear,
+                           int32_t* status_out);
+// argument checks shared by the entry points that take dyn, J and a grid
+int sc_speed_args_ok(int J, const double* dyn, const sc_speed_frame& fr);
+// the contract of dyn [P][4] on the host (the _host forms refuse what the kernel would mark SC_SMOOTH_BAD_INPUT)
+int sc_speed_dyn_ok(const double* dyn, int P);
 int sc_launch_toppra_sample_packed(sc_ctx* ctx, int P, int dof, int N, const double* p0, const double* p1, const double* v0,
                                    const double* v1, const double* x, const double* t, double dt, const int32_t* offsets,
                                    const int32_t* plen, const int32_t* skip, float* pos, float* vel, float* acc, double* times);
@@ -169,5 +186,19 @@ __device__ __forceinline__ void wave_lds_sync() {
     // LDS operations of one wave execute in issue order; only the compiler must not reorder them.
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
+}
+
+// point (order 0), hodograph (1) or second derivative (2) of the cubic Bezier c [4][2] at parameter s, in fp64
+__device__ __forceinline__ void bez_eval(const float* c, double s, int order, double& ox, double& oy) {
+    const double r = 1 - s;
+    double o[2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+        const double p0 = c[a], p1 = c[2 + a], p2 = c[4 + a], p3 = c[6 + a];
+        if (order == 0) o[a] = r * r * r * p0 + 3 * r * r * s * p1 + 3 * r * s * s * p2 + s * s * s * p3;
+        else if (order == 1) o[a] = 3 * (r * r * (p1 - p0) + 2 * r * s * (p2 - p1) + s * s * (p3 - p2));
+        else o[a] = 6 * (r * (p2 - 2 * p1 + p0) + s * (p3 - 2 * p2 + p1));
+    }
+    ox = o[0]; oy = o[1];
 }
 #endif

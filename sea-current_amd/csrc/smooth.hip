@@ -184,16 +184,26 @@ smooth_finish_kernel(const int32_t* __restrict__ rstat, const int32_t* __restric
     for (int i = gid; i < M; i += gridDim.x * 256) ang_vel[i] = vel[i] * curv[i];
 }
 
-extern "C" int sc_smooth_paths_batch(sc_ctx* ctx, const float* path, const int32_t* npts, int P, int n_max, const double* limits,
-                                     float start_angle, const float* lines, int nlines, float dt, int N, int nsub, int64_t sample_capacity,
-                                     float* ctrl, int32_t* seg_off, float* arclength, int32_t* length, int32_t* offsets, int32_t* status,
-                                     int64_t* needed, double* time, float* pos, float* vel, float* acc, float* pts, float* curvature,
-                                     float* ang_vel, float* tpar, int32_t* seg) {
+// what sc_smooth_paths_limited_batch adds to the sequence: per-stage limits between the arclength and TOPP-RA
+struct sm_limited {
+    const double* dyn;
+    int J;
+    sc_speed_frame fr;
+    double* vmax_stage;
+    float* min_clear;
+};
+
+// the sequence of both entry points; lt NULL: one constant limit per path
+static int smooth_run(sc_ctx* ctx, const float* path, const int32_t* npts, int P, int n_max, const double* limits, float start_angle,
+                      const float* lines, int nlines, float dt, int N, int nsub, int64_t sample_capacity, float* ctrl, int32_t* seg_off,
+                      float* arclength, int32_t* length, int32_t* offsets, int32_t* status, int64_t* needed, double* time, float* pos,
+                      float* vel, float* acc, float* pts, float* curvature, float* ang_vel, float* tpar, int32_t* seg, const sm_limited* lt) {
     if (!ctx || !path || !npts || !limits || !ctrl || !seg_off || !arclength || !length || !offsets || !status || !needed || !pos || !pts ||
         P <= 0 || P > SC_SMOOTH_MAX_PATHS || n_max < 2 || (long long)P * (n_max - 1) > INT32_MAX / 8 || nlines < 0 || (nlines > 0 && !lines) ||
         !(dt > 0.f) || !isfinite(dt) || N <= 0 || nsub <= 0 || nsub > SC_RESAMPLE_MAX_NSUB || sample_capacity < 0 ||
         sample_capacity > INT32_MAX)
         return SC_ERR_INVALID;
+    if (lt && (!sc_speed_args_ok(lt->J, lt->dyn, lt->fr) || (long long)P * ((long long)N + 1) > INT32_MAX)) return SC_ERR_INVALID;
     SC_HIP(ctx, hipSetDevice(ctx->device));
     const int Smax = P * (n_max - 1);
     const long long cap = sample_capacity;
@@ -205,6 +215,7 @@ extern "C" int sc_smooth_paths_batch(sc_ctx* ctx, const float* path, const int32
     if (r == SC_OK) r = sc_scratch_reserve(ctx, &ctx->sm_int, (size_t)(4 * P + 1) * 4);
     const bool need_vel = ang_vel && !vel, need_curv = ang_vel && !curvature;
     if (r == SC_OK && (need_vel || need_curv)) r = sc_scratch_reserve(ctx, &ctx->sm_smp, (size_t)2 * (cap > 0 ? cap : 1) * 4);
+    if (r == SC_OK && lt) r = sc_scratch_reserve(ctx, &ctx->sm_vlim, (size_t)2 * P * (N + 1) * 8);
     if (r != SC_OK) return r;
     float* padded = (float*)ctx->sm_ctrl.p;
     float* cum = (float*)ctx->sm_cum.p;
@@ -235,8 +246,19 @@ extern "C" int sc_smooth_paths_batch(sc_ctx* ctx, const float* path, const int32
     sc_time_end(ctx, tk);
     SC_HIP(ctx, hipGetLastError());
     const double *p0 = tp, *p1 = tp + P, *v0 = tp + 2 * (size_t)P, *v1 = tp + 3 * (size_t)P;
-    r = sc_toppra_hermite_batch(ctx, P, 1, N, p0, p1, v0, v1, tp + 4 * (size_t)P, tp + 5 * (size_t)P, 0, tp + 6 * (size_t)P,
-                                tp + 7 * (size_t)P, 0.0, 0.0, tp + oK, tp + ox, tp + ou, tp + ot, tstat);
+    if (lt) {
+        // status is read and written in place: every thread of a path's workgroup derives the same value from what it reads,
+        // before or after the one store
+        double* vlo = (double*)ctx->sm_vlim.p;
+        double* vhi = vlo + (size_t)P * (N + 1);
+        r = sc_launch_speed_limits(ctx, ctrl, cum, seg_off, arclength, status, P, nsub, N, lt->J, limits, lt->dyn, lt->fr, n_max - 1, vlo, vhi,
+                                   lt->vmax_stage, lt->min_clear, status);
+        if (r != SC_OK) return r;
+        r = sc_toppra_hermite_batch(ctx, P, 1, N, p0, p1, v0, v1, vlo, vhi, 1, tp + 6 * (size_t)P, tp + 7 * (size_t)P, 0.0, 0.0, tp + oK,
+                                    tp + ox, tp + ou, tp + ot, tstat);
+    } else
+        r = sc_toppra_hermite_batch(ctx, P, 1, N, p0, p1, v0, v1, tp + 4 * (size_t)P, tp + 5 * (size_t)P, 0, tp + 6 * (size_t)P,
+                                    tp + 7 * (size_t)P, 0.0, 0.0, tp + oK, tp + ox, tp + ou, tp + ot, tstat);
     if (r != SC_OK) return r;
     tk = sc_time_begin(ctx, SC_K_SMOOTH);
     hipLaunchKernelGGL(smooth_count_scan_kernel, dim3(1), dim3(SM_THREADS), 0, ctx->stream, (const double*)(tp + ot), (const int32_t*)tstat, P, N,
@@ -259,18 +281,47 @@ extern "C" int sc_smooth_paths_batch(sc_ctx* ctx, const float* path, const int32
     return SC_OK;
 }
 
-extern "C" int sc_smooth_paths_batch_host(sc_ctx* ctx, const float* path, const int32_t* npts, int P, int n_max, const double* limits,
-                                          float start_angle, const float* lines, int nlines, float dt, int N, int nsub,
-                                          int64_t sample_capacity, float* ctrl, int32_t* seg_off, float* arclength, int32_t* length,
-                                          int32_t* offsets, int32_t* status, int64_t* needed, double* time, float* pos, float* vel,
-                                          float* acc, float* pts, float* curvature, float* ang_vel, float* tpar, int32_t* seg) {
+extern "C" int sc_smooth_paths_batch(sc_ctx* ctx, const float* path, const int32_t* npts, int P, int n_max, const double* limits,
+                                     float start_angle, const float* lines, int nlines, float dt, int N, int nsub, int64_t sample_capacity,
+                                     float* ctrl, int32_t* seg_off, float* arclength, int32_t* length, int32_t* offsets, int32_t* status,
+                                     int64_t* needed, double* time, float* pos, float* vel, float* acc, float* pts, float* curvature,
+                                     float* ang_vel, float* tpar, int32_t* seg) {
+    return smooth_run(ctx, path, npts, P, n_max, limits, start_angle, lines, nlines, dt, N, nsub, sample_capacity, ctrl, seg_off, arclength,
+                      length, offsets, status, needed, time, pos, vel, acc, pts, curvature, ang_vel, tpar, seg, nullptr);
+}
+
+extern "C" int sc_smooth_paths_limited_batch(sc_ctx* ctx, const float* path, const int32_t* npts, int P, int n_max, const double* limits,
+                                             float start_angle, const float* lines, int nlines, float dt, int N, int nsub,
+                                             int64_t sample_capacity, float* ctrl, int32_t* seg_off, float* arclength, int32_t* length,
+                                             int32_t* offsets, int32_t* status, int64_t* needed, double* time, float* pos, float* vel,
+                                             float* acc, float* pts, float* curvature, float* ang_vel, float* tpar, int32_t* seg,
+                                             const double* dyn, int J, const int32_t* d2, int W, int H, float x_min, float y_min, float res_x,
+                                             float res_y, double* vmax_stage, float* min_clear) {
+    const sm_limited lt{dyn, J, {d2, W, H, x_min, y_min, res_x, res_y}, vmax_stage, min_clear};
+    return smooth_run(ctx, path, npts, P, n_max, limits, start_angle, lines, nlines, dt, N, nsub, sample_capacity, ctrl, seg_off, arclength,
+                      length, offsets, status, needed, time, pos, vel, acc, pts, curvature, ang_vel, tpar, seg, &lt);
+}
+
+// the host form of both; lt (host pointers) NULL: sc_smooth_paths_batch_host
+static int smooth_run_host(sc_ctx* ctx, const float* path, const int32_t* npts, int P, int n_max, const double* limits, float start_angle,
+                           const float* lines, int nlines, float dt, int N, int nsub, int64_t sample_capacity, float* ctrl,
+                           int32_t* seg_off, float* arclength, int32_t* length, int32_t* offsets, int32_t* status, int64_t* needed,
+                           double* time, float* pos, float* vel, float* acc, float* pts, float* curvature, float* ang_vel, float* tpar,
+                           int32_t* seg, const sm_limited* lt) {
     if (!ctx || !path || !npts || !limits || !ctrl || !seg_off || !arclength || !length || !offsets || !status || !needed || !pos || !pts ||
         P <= 0 || P > SC_SMOOTH_MAX_PATHS || n_max < 2 || (long long)P * (n_max - 1) > INT32_MAX / 8 || nlines < 0 || (nlines > 0 && !lines) ||
         sample_capacity < 0 || sample_capacity > INT32_MAX)
         return SC_ERR_INVALID;
+    if (lt && (N <= 0 || (long long)P * ((long long)N + 1) > INT32_MAX || !sc_speed_args_ok(lt->J, lt->dyn, lt->fr) ||
+               !sc_speed_dyn_ok(lt->dyn, P)))
+        return SC_ERR_INVALID;
     SC_HIP(ctx, hipSetDevice(ctx->device));
     const size_t S = (size_t)P * (n_max - 1), M = sample_capacity > 0 ? (size_t)sample_capacity : 1, pb = (size_t)P * 4;
     sc_stage st(ctx);
+    const bool grid = lt && lt->fr.d2;
+    const int i_dyn = st.in(lt ? lt->dyn : nullptr, lt ? pb * 8 : 0), i_d2 = st.in(grid ? lt->fr.d2 : nullptr, grid ? (size_t)lt->fr.W * lt->fr.H * 4 : 0),
+              o_vs = st.out(lt ? lt->vmax_stage : nullptr, lt && lt->vmax_stage ? (size_t)P * (N + 1) * 8 : 0),
+              o_mc = st.out(lt ? lt->min_clear : nullptr, lt && lt->min_clear ? pb : 0);
     const int i_path = st.in(path, (size_t)P * n_max * 8), i_npts = st.in(npts, pb), i_lim = st.in(limits, pb * 8),
               i_l = st.in(lines, (size_t)nlines * 16);
     const int o_ctrl = st.out(nullptr, S * 32), o_so = st.out(seg_off, pb + 4), o_al = st.out(arclength, pb), o_len = st.out(length, pb),
@@ -280,14 +331,22 @@ extern "C" int sc_smooth_paths_batch_host(sc_ctx* ctx, const float* path, const 
     const int o_time = smp(time, 8), o_pos = smp(pos, 4), o_vel = smp(vel, 4), o_acc = smp(acc, 4), o_pts = smp(pts, 8), o_cv = smp(curvature, 4),
               o_ang = smp(ang_vel, 4), o_tpar = smp(tpar, 4), o_seg = smp(seg, 4);
     int r = st.upload();
+    sm_limited dl{};
+    if (lt) {
+        dl = *lt;
+        dl.dyn = st.dev<const double>(i_dyn);
+        dl.fr.d2 = grid ? st.dev<const int32_t>(i_d2) : nullptr;
+        dl.vmax_stage = lt->vmax_stage ? st.dev<double>(o_vs) : nullptr;
+        dl.min_clear = lt->min_clear ? st.dev<float>(o_mc) : nullptr;
+    }
     if (r == SC_OK)
-        r = sc_smooth_paths_batch(ctx, st.dev<const float>(i_path), st.dev<const int32_t>(i_npts), P, n_max, st.dev<const double>(i_lim), start_angle,
+        r = smooth_run(ctx, st.dev<const float>(i_path), st.dev<const int32_t>(i_npts), P, n_max, st.dev<const double>(i_lim), start_angle,
                                   nlines > 0 ? st.dev<const float>(i_l) : nullptr, nlines, dt, N, nsub, sample_capacity, st.dev<float>(o_ctrl),
                                   st.dev<int32_t>(o_so), st.dev<float>(o_al), st.dev<int32_t>(o_len), st.dev<int32_t>(o_off), st.dev<int32_t>(o_st),
                                   st.dev<int64_t>(o_need), time ? st.dev<double>(o_time) : nullptr, st.dev<float>(o_pos),
                                   vel ? st.dev<float>(o_vel) : nullptr, acc ? st.dev<float>(o_acc) : nullptr, st.dev<float>(o_pts),
                                   curvature ? st.dev<float>(o_cv) : nullptr, ang_vel ? st.dev<float>(o_ang) : nullptr,
-                                  tpar ? st.dev<float>(o_tpar) : nullptr, seg ? st.dev<int32_t>(o_seg) : nullptr);
+                                  tpar ? st.dev<float>(o_tpar) : nullptr, seg ? st.dev<int32_t>(o_seg) : nullptr, lt ? &dl : nullptr);
     r = st.finish(r);
     if (r != SC_OK) return r;
     // the samples written: up to the first truncated path
@@ -300,6 +359,27 @@ extern "C" int sc_smooth_paths_batch_host(sc_ctx* ctx, const float* path, const 
     st.back(o_pts, pts, Mw * 8); st.back(o_cv, curvature, Mw * 4); st.back(o_ang, ang_vel, Mw * 4); st.back(o_tpar, tpar, Mw * 4);
     st.back(o_seg, seg, Mw * 4);
     return st.finish(SC_OK);
+}
+
+extern "C" int sc_smooth_paths_batch_host(sc_ctx* ctx, const float* path, const int32_t* npts, int P, int n_max, const double* limits,
+                                          float start_angle, const float* lines, int nlines, float dt, int N, int nsub,
+                                          int64_t sample_capacity, float* ctrl, int32_t* seg_off, float* arclength, int32_t* length,
+                                          int32_t* offsets, int32_t* status, int64_t* needed, double* time, float* pos, float* vel,
+                                          float* acc, float* pts, float* curvature, float* ang_vel, float* tpar, int32_t* seg) {
+    return smooth_run_host(ctx, path, npts, P, n_max, limits, start_angle, lines, nlines, dt, N, nsub, sample_capacity, ctrl, seg_off,
+                           arclength, length, offsets, status, needed, time, pos, vel, acc, pts, curvature, ang_vel, tpar, seg, nullptr);
+}
+
+extern "C" int sc_smooth_paths_limited_batch_host(sc_ctx* ctx, const float* path, const int32_t* npts, int P, int n_max, const double* limits,
+                                                  float start_angle, const float* lines, int nlines, float dt, int N, int nsub,
+                                                  int64_t sample_capacity, float* ctrl, int32_t* seg_off, float* arclength, int32_t* length,
+                                                  int32_t* offsets, int32_t* status, int64_t* needed, double* time, float* pos, float* vel,
+                                                  float* acc, float* pts, float* curvature, float* ang_vel, float* tpar, int32_t* seg,
+                                                  const double* dyn, int J, const int32_t* d2, int W, int H, float x_min, float y_min,
+                                                  float res_x, float res_y, double* vmax_stage, float* min_clear) {
+    const sm_limited lt{dyn, J, {d2, W, H, x_min, y_min, res_x, res_y}, vmax_stage, min_clear};
+    return smooth_run_host(ctx, path, npts, P, n_max, limits, start_angle, lines, nlines, dt, N, nsub, sample_capacity, ctrl, seg_off,
+                           arclength, length, offsets, status, needed, time, pos, vel, acc, pts, curvature, ang_vel, tpar, seg, &lt);
 }
 
 // cells of sc_path_waypoints_batch -> float points (occupancy_grid::centre_of), one thread per (path, point)

@@ -99,6 +99,12 @@ _SIGNATURES = {
     "sc_smooth_paths_batch": (_i, [_vp, _vp, _vp, _i, _i, _vp, C.c_float, _vp, _i, C.c_float, _i, _i, C.c_int64] + [_vp] * 16),
     "sc_smooth_paths_batch_host": (_i, [_vp, _vp, _vp, _i, _i, _vp, C.c_float, _vp, _i, C.c_float, _i, _i, C.c_int64] + [_vp] * 16),
     "sc_cells_to_points_batch": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, C.c_float, C.c_float, C.c_float, C.c_float, _vp, _vp, _vp, _vp]),
+    "sc_speed_limits_batch": (_i, [_vp] * 6 + [_i] * 4 + [_vp] * 3 + [_i, _i] + [C.c_float] * 4 + [_vp] * 3),
+    "sc_speed_limits_batch_host": (_i, [_vp] * 6 + [_i] * 4 + [_vp] * 3 + [_i, _i] + [C.c_float] * 4 + [_vp] * 3),
+    "sc_smooth_paths_limited_batch": (_i, [_vp, _vp, _vp, _i, _i, _vp, C.c_float, _vp, _i, C.c_float, _i, _i, C.c_int64] + [_vp] * 16 +
+                                      [_vp, _i, _vp, _i, _i] + [C.c_float] * 4 + [_vp, _vp]),
+    "sc_smooth_paths_limited_batch_host": (_i, [_vp, _vp, _vp, _i, _i, _vp, C.c_float, _vp, _i, C.c_float, _i, _i, C.c_int64] + [_vp] * 16 +
+                                           [_vp, _i, _vp, _i, _i] + [C.c_float] * 4 + [_vp, _vp]),
     "sc_rank_range": (None, [_i, _i, _i, C.POINTER(_i), C.POINTER(_i)]),
     "sc_comm_unique_id": (_i, [_vp]),
     "sc_comm_init": (_i, [_vp, _vp, _i, _i]),
@@ -324,17 +330,76 @@ class Context:
         est = torch.where(torch.isfinite(T), (T / dt * 1.25).clamp(max=1e6).floor() + 64, torch.full_like(T, 64.0))
         return int(est.sum().item())
 
-    def smooth_paths(self, wp, npts, limits, dt=0.02, N=100, nsub=100, start_angle=float("nan"), lines=None, capacity=None, out=None):
+    @staticmethod
+    def _frame(d2, frame):
+        """(W, H, x_min, y_min, res_x, res_y) of a grid argument; frame = (x_min, y_min, res_x, res_y)."""
+        if d2 is None:
+            return (0, 0, 0.0, 0.0, 0.0, 0.0)
+        if frame is None:
+            raise ValueError("d2 needs frame=(x_min, y_min, res_x, res_y)")
+        H, W = d2.shape
+        return (W, H) + tuple(float(v) for v in frame)
+
+    def speed_limits(self, ctrl, cum, seg_off, arclength, limits, dyn, N=100, J=4, status=None, d2=None, frame=None):
+        """Per-stage speed limits of P curves from curvature and clearance (sc_speed_limits_batch; the definition is in
+        include/sea_current_hip.h).  GPU tensors: ctrl float32 [S,4,2], cum float32 [S,nsub+1], seg_off int32 [P+1], arclength
+        float32 [P], limits / dyn float64 [P,4] or 4 numbers for every curve, dyn = (omega_max, alat_max, clear_floor,
+        clear_gain), status int32 [P] or None, d2 int32 [H,W] with frame = (x_min, y_min, res_x, res_y) or None.  Returns
+        dict(vhi float64 [P,N+1], min_clear float32 [P], status int32 [P])."""
+        import torch
+        P = arclength.shape[0]
+        dev = arclength.device
+        f4 = lambda v: (v if torch.is_tensor(v) else torch.tensor([list(map(float, v))] * P, dtype=torch.float64, device=dev)) \
+            .to(torch.float64).expand(P, 4).contiguous()
+        limits, dyn = f4(limits), f4(dyn)
+        out = dict(vhi=torch.empty((P, N + 1), dtype=torch.float64, device=dev), min_clear=torch.empty(P, dtype=torch.float32, device=dev),
+                   status=torch.empty(P, dtype=torch.int32, device=dev))
+        self._ck(self._l.sc_speed_limits_batch(self._h, _ptr(ctrl), _ptr(cum), _ptr(seg_off), _ptr(arclength), _ptr(status), P,
+                                               cum.shape[-1] - 1, N, J, _ptr(limits), _ptr(dyn), _ptr(d2), *self._frame(d2, frame),
+                                               _ptr(out["vhi"]), _ptr(out["min_clear"]), _ptr(out["status"])), "sc_speed_limits_batch")
+        return out
+
+    def speed_limits_host(self, ctrl, cum, seg_off, arclength, limits, dyn, N=100, J=4, status=None, d2=None, frame=None):
+        """Host form of speed_limits (numpy in, numpy out; sc_speed_limits_batch_host checks the contract of dyn first)."""
+        ctrl = np.ascontiguousarray(ctrl, dtype=np.float32)
+        cum = np.ascontiguousarray(cum, dtype=np.float32)
+        seg_off = np.ascontiguousarray(seg_off, dtype=np.int32)
+        arclength = np.ascontiguousarray(arclength, dtype=np.float32)
+        P = arclength.shape[0]
+        limits = np.ascontiguousarray(np.broadcast_to(np.asarray(limits, dtype=np.float64), (P, 4)))
+        dyn = np.ascontiguousarray(np.broadcast_to(np.asarray(dyn, dtype=np.float64), (P, 4)))
+        status = None if status is None else np.ascontiguousarray(status, dtype=np.int32)
+        d2 = None if d2 is None else np.ascontiguousarray(d2, dtype=np.int32)
+        out = dict(vhi=np.zeros((P, N + 1)), min_clear=np.zeros(P, np.float32), status=np.zeros(P, np.int32))
+        self._ck(self._l.sc_speed_limits_batch_host(self._h, _ptr(ctrl), _ptr(cum), _ptr(seg_off), _ptr(arclength), _ptr(status), P,
+                                                    cum.shape[-1] - 1, N, J, _ptr(limits), _ptr(dyn), _ptr(d2), *self._frame(d2, frame),
+                                                    _ptr(out["vhi"]), _ptr(out["min_clear"]), _ptr(out["status"])),
+                 "sc_speed_limits_batch_host")
+        return out
+
+    def smooth_paths(self, wp, npts, limits, dt=0.02, N=100, nsub=100, start_angle=float("nan"), lines=None, capacity=None, out=None,
+                     dyn=None, J=4, d2=None, frame=None):
         """The post-planner sequence for a batch of paths in one call (sc_smooth_paths_batch).  wp float32 [P,n_max,2],
         npts int32 [P], limits float64 [P,4] (vel_min, vel_max, acc_min, acc_max) or 4 numbers for every path, lines float32
         [E,4] or None; all on the GPU.  capacity=None: room for an estimate of the samples, the call repeated once with the
         exact count if that was short (reads `needed`: synchronises), and the per-sample outputs cut to `needed`.  With a
         capacity the call only enqueues.  `out`: the dict of an earlier call with the same P, n_max and capacity, reused.
         Returns dict(ctrl [P*(n_max-1),4,2], seg_off, arclength, length, offsets, status, needed [1], and per sample time,
-        pos, vel, acc, pts [M,2], curvature, ang_vel, tpar, seg)."""
+        pos, vel, acc, pts [M,2], curvature, ang_vel, tpar, seg).
+        dyn (float64 [P,4] or 4 numbers: omega_max, alat_max, clear_floor, clear_gain) asks for per-stage speed limits from
+        curvature and, with d2 int32 [H,W] and frame = (x_min, y_min, res_x, res_y), clearance (sc_smooth_paths_limited_batch,
+        J samples to each side of a stage); the dict then also holds vmax_stage float64 [P,N+1] and min_clear float32 [P].
+        With dyn None the call is sc_smooth_paths_batch as before."""
         import torch
         P, n_max, _ = wp.shape
         dev = wp.device
+        if dyn is None and d2 is not None:
+            raise ValueError("d2 without dyn: the grid only enters through the speed limits")
+        if dyn is not None:
+            if not torch.is_tensor(dyn):
+                dyn = torch.tensor([list(map(float, dyn))] * P, dtype=torch.float64, device=dev)
+            dyn = dyn.to(torch.float64).expand(P, 4).contiguous()
+            fr = self._frame(d2, frame)
         if not torch.is_tensor(limits):
             limits = torch.tensor([list(map(float, limits))] * P, dtype=torch.float64, device=dev)
         limits = limits.to(torch.float64).expand(P, 4).contiguous()
@@ -349,10 +414,17 @@ class Context:
                 o = dict(ctrl=f(P * (n_max - 1), 4, 2), seg_off=i(P + 1), arclength=f(P), length=i(P), offsets=i(P + 1), status=i(P),
                          needed=torch.empty(1, dtype=torch.int64, device=dev), time=torch.empty(cap, dtype=torch.float64, device=dev),
                          pos=f(cap), vel=f(cap), acc=f(cap), pts=f(cap, 2), curvature=f(cap), ang_vel=f(cap), tpar=f(cap), seg=i(cap))
-            self._ck(self._l.sc_smooth_paths_batch(
-                self._h, _ptr(wp), _ptr(npts), P, n_max, _ptr(limits), start_angle, _ptr(lines) if nl else None, nl, dt, N, nsub, cap,
-                *[_ptr(o[k]) for k in ("ctrl", "seg_off", "arclength", "length", "offsets", "status", "needed", "time", "pos", "vel", "acc",
-                                       "pts", "curvature", "ang_vel", "tpar", "seg")]), "sc_smooth_paths_batch")
+            args = [self._h, _ptr(wp), _ptr(npts), P, n_max, _ptr(limits), start_angle, _ptr(lines) if nl else None, nl, dt, N, nsub, cap,
+                    *[_ptr(o[k]) for k in ("ctrl", "seg_off", "arclength", "length", "offsets", "status", "needed", "time", "pos", "vel", "acc",
+                                           "pts", "curvature", "ang_vel", "tpar", "seg")]]
+            if dyn is None:
+                self._ck(self._l.sc_smooth_paths_batch(*args), "sc_smooth_paths_batch")
+                return o
+            if "vmax_stage" not in o or o["vmax_stage"].shape != (P, N + 1):
+                o["vmax_stage"] = torch.empty((P, N + 1), dtype=torch.float64, device=dev)
+                o["min_clear"] = torch.empty(P, dtype=torch.float32, device=dev)
+            self._ck(self._l.sc_smooth_paths_limited_batch(*args, _ptr(dyn), J, _ptr(d2), *fr, _ptr(o["vmax_stage"]), _ptr(o["min_clear"])),
+                     "sc_smooth_paths_limited_batch")
             return o
 
         o = run(cap, out)
@@ -363,8 +435,10 @@ class Context:
             o = run(need, None)
         return {k: (v[:need] if k in ("time", "pos", "vel", "acc", "pts", "curvature", "ang_vel", "tpar", "seg") else v) for k, v in o.items()}
 
-    def smooth_paths_host(self, wp, npts, limits, capacity, dt=0.02, N=100, nsub=100, start_angle=float("nan"), lines=None):
-        """Host form (numpy in, numpy out) of smooth_paths with room for `capacity` samples (sc_smooth_paths_batch_host)."""
+    def smooth_paths_host(self, wp, npts, limits, capacity, dt=0.02, N=100, nsub=100, start_angle=float("nan"), lines=None, dyn=None, J=4,
+                          d2=None, frame=None):
+        """Host form (numpy in, numpy out) of smooth_paths with room for `capacity` samples (sc_smooth_paths_batch_host; with
+        dyn sc_smooth_paths_limited_batch_host, which adds vmax_stage and min_clear)."""
         wp = np.ascontiguousarray(wp, dtype=np.float32)
         npts = np.ascontiguousarray(npts, dtype=np.int32)
         P, n_max, _ = wp.shape
@@ -377,10 +451,20 @@ class Context:
                  time=np.zeros(cap), pos=np.zeros(cap, np.float32), vel=np.zeros(cap, np.float32), acc=np.zeros(cap, np.float32),
                  pts=np.zeros((cap, 2), np.float32), curvature=np.zeros(cap, np.float32), ang_vel=np.zeros(cap, np.float32),
                  tpar=np.zeros(cap, np.float32), seg=np.zeros(cap, np.int32))
-        self._ck(self._l.sc_smooth_paths_batch_host(
-            self._h, _ptr(wp), _ptr(npts), P, n_max, _ptr(limits), start_angle, _ptr(lines) if nl else None, nl, dt, N, nsub, cap,
-            *[_ptr(o[k]) for k in ("ctrl", "seg_off", "arclength", "length", "offsets", "status", "needed", "time", "pos", "vel", "acc",
-                                   "pts", "curvature", "ang_vel", "tpar", "seg")]), "sc_smooth_paths_batch_host")
+        args = [self._h, _ptr(wp), _ptr(npts), P, n_max, _ptr(limits), start_angle, _ptr(lines) if nl else None, nl, dt, N, nsub, cap,
+                *[_ptr(o[k]) for k in ("ctrl", "seg_off", "arclength", "length", "offsets", "status", "needed", "time", "pos", "vel", "acc",
+                                       "pts", "curvature", "ang_vel", "tpar", "seg")]]
+        if dyn is None:
+            if d2 is not None:
+                raise ValueError("d2 without dyn: the grid only enters through the speed limits")
+            self._ck(self._l.sc_smooth_paths_batch_host(*args), "sc_smooth_paths_batch_host")
+            return o
+        dyn = np.ascontiguousarray(np.broadcast_to(np.asarray(dyn, dtype=np.float64), (P, 4)))
+        d2 = None if d2 is None else np.ascontiguousarray(d2, dtype=np.int32)
+        o["vmax_stage"] = np.zeros((P, N + 1))
+        o["min_clear"] = np.zeros(P, np.float32)
+        self._ck(self._l.sc_smooth_paths_limited_batch_host(*args, _ptr(dyn), J, _ptr(d2), *self._frame(d2, frame), _ptr(o["vmax_stage"]),
+                                                            _ptr(o["min_clear"])), "sc_smooth_paths_limited_batch_host")
         return o
 
     # ---- multi-GPU gather (RCCL through the C ABI) ----

@@ -49,6 +49,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <limits>
 #include <optional>
 #include <stdexcept>
 #include <string>
@@ -1141,9 +1142,19 @@ velocity_profile gen_vel_prof(const VectorNd<N>& pos_end, const VectorNd<N>& pos
 // resampled spline (ctrl_pts, pts, positions), the profile, the arclength (the tables are not returned) and ang_vel =
 // vel * curvature (the curvature of the resample kernel; bezier_spline::curvature goes through the hodograph on the host,
 // so the two agree to rounding).  status is an sc_smooth_status; the other members are empty unless it is SC_SMOOTH_OK.
+//
+// Per-stage speed limits (sc_smooth_paths_limited_batch; the definition is in sea_current_hip.h): a request may bound the
+// angular velocity (v <= omega_max / |kappa|), the lateral acceleration (v <= sqrt(alat_max / |kappa|)) and, in the overload
+// that takes an occupancy_grid with its d2, the speed near obstacles (v <= clear_floor + clear_gain * clearance).  +inf
+// switches a term off; with every term off and no grid the call is sc_smooth_paths_batch_host as before.  vmax_stage then
+// holds the limit TOPP-RA ran with at each of its SC_TOPPRA_GRID + 1 stages, min_clear the smallest sampled clearance.
 struct smooth_request {
     std::vector<Vector2f> path;
     double vel_min, vel_max, acc_min, acc_max;
+    double omega_max = std::numeric_limits<double>::infinity();
+    double alat_max = std::numeric_limits<double>::infinity();
+    double clear_floor = std::numeric_limits<double>::infinity();
+    double clear_gain = 0.0;
 };
 struct smooth_result {
     int status = SC_SMOOTH_BAD_INPUT;
@@ -1151,9 +1162,12 @@ struct smooth_result {
     velocity_profile profile{{}, {}, {}, toppra_compat::Vector()};
     arclength_data arclength;
     std::vector<float> ang_vel;
+    std::vector<double> vmax_stage;   // [SC_TOPPRA_GRID + 1] when limits were asked for, else empty
+    float min_clear = std::numeric_limits<float>::infinity();
 };
-inline std::vector<smooth_result> smooth_paths_batch(const std::vector<smooth_request>& requests, const planning_space& space,
-                                                     float dt = 0.02f, float precision = 0.01f, gpu_context& ctx = default_context()) {
+constexpr int SC_SPEED_SAMPLES = 4;   // J: samples to each side of a stage
+inline std::vector<smooth_result> smooth_paths_batch_impl(const std::vector<smooth_request>& requests, const planning_space& space,
+                                                          const occupancy_grid* grid, float dt, float precision, gpu_context& ctx) {
     const int P = (int)requests.size();
     std::vector<smooth_result> out(P);
     if (P == 0) return out;
@@ -1161,10 +1175,15 @@ inline std::vector<smooth_result> smooth_paths_batch(const std::vector<smooth_re
     for (const auto& r : requests) n_max = std::max(n_max, (int)r.path.size());
     std::vector<float> xy((size_t)P * n_max * 2, 0.f), lines;
     std::vector<int32_t> npts(P);
-    std::vector<double> lim((size_t)P * 4);
+    std::vector<double> lim((size_t)P * 4), dyn((size_t)P * 4), vstage;
+    std::vector<float> min_clear;
+    bool limited = grid != nullptr;
     int64_t cap = 0;
     for (int p = 0; p < P; ++p) {
         const auto& r = requests[p];
+        const double inf = std::numeric_limits<double>::infinity();
+        dyn[4 * (size_t)p] = r.omega_max; dyn[4 * (size_t)p + 1] = r.alat_max; dyn[4 * (size_t)p + 2] = r.clear_floor; dyn[4 * (size_t)p + 3] = r.clear_gain;
+        limited = limited || r.omega_max != inf || r.alat_max != inf || r.clear_floor != inf;
         npts[p] = (int32_t)r.path.size();
         float poly = 0;
         for (size_t i = 0; i < r.path.size(); ++i) {
@@ -1184,15 +1203,28 @@ inline std::vector<smooth_result> smooth_paths_batch(const std::vector<smooth_re
     std::vector<int32_t> seg_off(P + 1), length(P), offsets(P + 1), status(P), seg;
     std::vector<double> times;
     int64_t needed = 0;
+    if (limited) { vstage.resize((size_t)P * (SC_TOPPRA_GRID + 1)); min_clear.resize(P); }
+    if (grid) { SC_ASSERT(grid->d2.size() == grid->occ.size() && !grid->d2.empty(), "the grid's d2 is missing: call edt() first"); }
     for (int attempt = 0; attempt < 2; ++attempt) {
         cap = std::min<int64_t>(std::max<int64_t>(cap, 1), INT32_MAX);
         pos.resize(cap); vel.resize(cap); acc.resize(cap); pts.resize(2 * (size_t)cap); ang.resize(cap); tpar.resize(cap); seg.resize(cap);
         times.resize(cap);
-        ctx.check(sc_smooth_paths_batch_host(ctx.get(), xy.data(), npts.data(), P, n_max, lim.data(), NAN, lines.empty() ? nullptr : lines.data(),
-                                             (int)(lines.size() / 4), dt, SC_TOPPRA_GRID, nsub, cap, ctrl.data(), seg_off.data(), al.data(),
-                                             length.data(), offsets.data(), status.data(), &needed, times.data(), pos.data(), vel.data(),
-                                             acc.data(), pts.data(), nullptr, ang.data(), tpar.data(), seg.data()),
-                  "sc_smooth_paths_batch_host");
+        if (!limited)
+            ctx.check(sc_smooth_paths_batch_host(ctx.get(), xy.data(), npts.data(), P, n_max, lim.data(), NAN, lines.empty() ? nullptr : lines.data(),
+                                                 (int)(lines.size() / 4), dt, SC_TOPPRA_GRID, nsub, cap, ctrl.data(), seg_off.data(), al.data(),
+                                                 length.data(), offsets.data(), status.data(), &needed, times.data(), pos.data(), vel.data(),
+                                                 acc.data(), pts.data(), nullptr, ang.data(), tpar.data(), seg.data()),
+                      "sc_smooth_paths_batch_host");
+        else
+            ctx.check(sc_smooth_paths_limited_batch_host(
+                          ctx.get(), xy.data(), npts.data(), P, n_max, lim.data(), NAN, lines.empty() ? nullptr : lines.data(),
+                          (int)(lines.size() / 4), dt, SC_TOPPRA_GRID, nsub, cap, ctrl.data(), seg_off.data(), al.data(), length.data(),
+                          offsets.data(), status.data(), &needed, times.data(), pos.data(), vel.data(), acc.data(), pts.data(), nullptr,
+                          ang.data(), tpar.data(), seg.data(), dyn.data(), SC_SPEED_SAMPLES, grid ? grid->d2.data() : nullptr,
+                          grid ? grid->W : 0, grid ? grid->H : 0, grid ? grid->bound_rect.x_min : 0.f, grid ? grid->bound_rect.y_min : 0.f,
+                          grid ? grid->resolution : 0.f, grid ? (grid->bound_rect.y_max - grid->bound_rect.y_min) / (float)grid->H : 0.f,
+                          vstage.data(), min_clear.data()),
+                      "sc_smooth_paths_limited_batch_host");
         if (needed <= cap) break;
         cap = needed;
     }
@@ -1200,6 +1232,10 @@ inline std::vector<smooth_result> smooth_paths_batch(const std::vector<smooth_re
         smooth_result& res = out[p];
         res.status = status[p];
         res.arclength.arclength = al[p];
+        if (limited) {
+            res.vmax_stage.assign(vstage.begin() + (size_t)p * (SC_TOPPRA_GRID + 1), vstage.begin() + (size_t)(p + 1) * (SC_TOPPRA_GRID + 1));
+            res.min_clear = min_clear[p];
+        }
         if (status[p] != SC_SMOOTH_OK) continue;
         const int s0 = seg_off[p], ns = seg_off[p + 1] - s0, o = offsets[p], L = length[p];
         bezier_spline& bs = res.spline;
@@ -1222,6 +1258,50 @@ inline std::vector<smooth_result> smooth_paths_batch(const std::vector<smooth_re
         res.ang_vel.assign(ang.begin() + o, ang.begin() + o + L);
     }
     return out;
+}
+inline std::vector<smooth_result> smooth_paths_batch(const std::vector<smooth_request>& requests, const planning_space& space,
+                                                     float dt = 0.02f, float precision = 0.01f, gpu_context& ctx = default_context()) {
+    return smooth_paths_batch_impl(requests, space, nullptr, dt, precision, ctx);
+}
+// the same with a grid (its d2 filled by edt()): the clearance term of every request that has a finite clear_floor reads it
+inline std::vector<smooth_result> smooth_paths_batch(const std::vector<smooth_request>& requests, const planning_space& space,
+                                                     const occupancy_grid& grid, float dt = 0.02f, float precision = 0.01f,
+                                                     gpu_context& ctx = default_context()) {
+    return smooth_paths_batch_impl(requests, space, &grid, dt, precision, ctx);
+}
+
+// The same limits through the reference's own hook: a vel_lim_func for gen_vel_prof<1>(ad.arclength, 0, 0, 0, f, ..) along
+// `spline` (its legs) with the tables `ad` of spline.arclength().  sc_speed_limits_batch_host runs once, here; the function
+// answers s with the limit of stage round(s * SC_TOPPRA_GRID).  `rq` gives vel_min, vel_max and the four terms (its path
+// is not read).  Throws when rq breaks the contract of the terms.
+inline vel_lim_func speed_limit_func(const bezier_spline& spline, const arclength_data& ad, const smooth_request& rq,
+                                     const occupancy_grid* grid = nullptr, int J = SC_SPEED_SAMPLES, gpu_context& ctx = default_context()) {
+    const int ns = spline.n_segments(), N = SC_TOPPRA_GRID;
+    SC_ASSERT(ns >= 1 && (int)ad.segments.size() == ns, "the tables must be those of the spline");
+    const int nsub = (int)ad.segments[0].size() - 1;
+    std::vector<float> ctrl((size_t)ns * 8), cum((size_t)ns * (nsub + 1));
+    for (int i = 0; i < ns; ++i) {
+        SC_ASSERT((int)ad.segments[i].size() == nsub + 1 && spline.ctrl_pts[i].size() == 4, "cubic legs with equal tables");
+        for (int k = 0; k < 4; ++k) { ctrl[(size_t)i * 8 + 2 * k] = spline.ctrl_pts[i][k].x(); ctrl[(size_t)i * 8 + 2 * k + 1] = spline.ctrl_pts[i][k].y(); }
+        for (int k = 0; k <= nsub; ++k) cum[(size_t)i * (nsub + 1) + k] = ad.segments[i](k);
+    }
+    if (grid) { SC_ASSERT(grid->d2.size() == grid->occ.size() && !grid->d2.empty(), "the grid's d2 is missing: call edt() first"); }
+    const int32_t seg_off[2] = {0, ns};
+    const double lim[4] = {rq.vel_min, rq.vel_max, rq.acc_min, rq.acc_max}, dyn[4] = {rq.omega_max, rq.alat_max, rq.clear_floor, rq.clear_gain};
+    std::vector<double> vhi(N + 1);
+    ctx.check(sc_speed_limits_batch_host(ctx.get(), ctrl.data(), cum.data(), seg_off, &ad.arclength, nullptr, 1, nsub, N, J, lim, dyn,
+                                         grid ? grid->d2.data() : nullptr, grid ? grid->W : 0, grid ? grid->H : 0,
+                                         grid ? grid->bound_rect.x_min : 0.f, grid ? grid->bound_rect.y_min : 0.f, grid ? grid->resolution : 0.f,
+                                         grid ? (grid->bound_rect.y_max - grid->bound_rect.y_min) / (float)grid->H : 0.f, vhi.data(), nullptr,
+                                         nullptr),
+              "sc_speed_limits_batch_host");
+    const double vel_min = rq.vel_min;
+    return [vhi = std::move(vhi), vel_min, N](value_type s) {
+        const int i = std::clamp((int)std::lround((double)s * N), 0, N);
+        toppra_compat::Vector lo(1), hi(1);
+        lo(0) = vel_min; hi(0) = vhi[i];
+        return std::make_tuple(lo, hi);
+    };
 }
 
 // ---- wire formats of the example service ---------------------------------------------------
