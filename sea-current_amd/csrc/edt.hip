@@ -6,30 +6,107 @@
 //
 // Data flow (HBM bytes per cell):
 //   occ  u8 [batch][H][W]   --edt_colbits-->  colbits u32 [batch][nb][W]   (1 read, 1/8 write)
-//   colbits                 --edt_band---->   d2 i32 [batch][H][W]         (1/8 + look-back read, 4 write)
+//   colbits                 --band kernel-->  d2 i32 [batch][H][W]         (1/8 + look-back read, 4 write)
 // colbits[b][x] bit i = occ[32 b + i][x] != 0: a bit-transposed copy of the grid, one word per
 // column per 32-row band.  It is at once the compressed occupancy and the band summary that lets a
 // band find the nearest obstacle above/below it (clz/ffs on neighbouring bands' words) without
 // touching rows outside the band.
 //
-// edt_band: one 256-thread workgroup per (grid, band); each wave owns whole rows.
-// Row pass = exact cascade of 3-point parabolic erosions.  Because k^2 = 1 + 3 + ... + (2k-1),
+// Every band kernel runs the same row pass, an exact cascade of 3-point parabolic erosions.  Because
+// k^2 = 1 + 3 + ... + (2k-1),
 //     F_j(x) = min(F_{j-1}(x), min(F_{j-1}(x-1), F_{j-1}(x+1)) + (2j-1)),   F_0(x) = g(x)^2
 // equals  min_{|k|<=j} g(x+k)^2 + k^2  exactly (g = vertical distance), and F_j is final once
-// (j+1)^2 >= max_x F_j(x).  Lane l keeps PPL consecutive pixels of the row in registers, packed two
-// per VGPR as u16 pairs (pixel j with pixel j + PPL/2, so the left/right neighbour vectors of
-// register j are simply registers j-1 / j+1); only the two pixels at the lane's ends come from the
-// adjacent lanes (one wave_shr and one wave_shl DPP move per iteration).  An iteration over a whole
-// row costs 3 packed VALU ops per two pixels and touches no memory.  Saturating u16 adds commute
-// with clipping at 65535, so the packed F_j equals min(65535, exact F_j): every pixel that ends
-// below 65535 is exact; a row with a pixel still at 65535 (d2 >= 65535: a very sparse grid) is redone
-// with 32-bit registers.  Rows are contiguous in HBM: occupancy reads and d2 writes are coalesced.
+// (j+1)^2 >= max_x F_j(x).  A wave owns whole rows; lane l keeps PPL consecutive pixels in registers,
+// packed two per VGPR as u16 pairs (pixel j with pixel j + PPL/2), and only the two pixels at the
+// lane's ends come from the adjacent lanes (DPP).  Packed values saturate, so every pixel that ends
+// below the kernel's packed limit is exact; rows with a pixel at the limit (very sparse grids) are
+// redone in 32 bits.  Rows are contiguous in HBM: occupancy reads and d2 writes are coalesced.
+//
+// Which kernel serves which width (sc_launch_edt at the end of the file is the table; DESIGN.md 4.1
+// has the measurements behind each choice):
+//   all W        edt_colbits_kernel (W % 4 == 0) / edt_colbits_generic_kernel
+//   W <=  256    edt_band_kernel<2 | 4>: the general kernel, 256 threads per band, closed-form vertical
+//                distances; few pixels per lane, so set-up cost does not matter
+//   W <=  512    edt_band_g8_kernel<8>: 512 threads per band, all 32 x W vertical distances by a packed
+//                recurrence into LDS bytes first
+//   W <= 1024    edt_band_k16_kernel: the headline width.  g8's structure with the add + min3 step
+//                (pk_min3_f16bits); its OPEN twin adds a site search for open space and runs, with
+//                edt_updown_kernel in front, while the context is in open-space mode (g_edt_open,
+//                sc_edt_open_mode_update)
+//   W <= 4096    edt_updown_kernel, then edt_band_wide_kernel: whole rows of up to four
+//                1024-pixel stretches in registers, one persistent workgroup per CU
+//   W <= 8192    launch_band_windows: 1024-column windows through edt_band_g8_kernel<16, true, TILED>,
+//                twice, then edt_band_kernel<128> for the bands the windows gave up on
+// The legal-move kernels that read d2 are in moves.hip.
+//
+// One translation unit on purpose.  The band kernels share edt_gdist_global (__noinline__) and g_edt_open (the library
+// is built without relocatable device code).  And what else is in the unit changes the code of a kernel: compiled in a
+// unit without edt_updown_kernel, every band kernel, edt_band_wide_kernel included, comes out different (the clz of the
+// device library loses its guard for a zero input, and the schedule around it moves).  So compare the assembly kernel by
+// kernel before and after moving one out of this file; the benchmark's kernels are touchy that way.
 #include "sc_internal.h"
-#include <stdlib.h>
 
 #define EDT_G_INF 0x7FFF                       // "no obstacle in this column"
 #define EDT_F_INF (EDT_G_INF * EDT_G_INF)      // > any real d2 for dims <= 8192
 
+// d2 is written once and not read again by this library: non-temporal stores keep the 256 MiB of output
+// from lingering as dirty lines whose write-back would otherwise slow whatever runs next (measured:
+// the following colbits launch drops from ~25 us to ~10 us, the read floor for 64 MiB).
+typedef int v4i_t __attribute__((ext_vector_type(4)));
+#define EDT_STORE4(p, v) __builtin_nontemporal_store(v4i_t{(v).x, (v).y, (v).z, (v).w}, reinterpret_cast<v4i_t*>(p))
+
+// ---- packed helpers: two u16 per VGPR ----
+typedef unsigned short us2_t __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint32_t pk_min(uint32_t a, uint32_t b) {
+    return __builtin_bit_cast(uint32_t, __builtin_elementwise_min(__builtin_bit_cast(us2_t, a), __builtin_bit_cast(us2_t, b)));
+}
+__device__ __forceinline__ uint32_t pk_max(uint32_t a, uint32_t b) {
+    return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(us2_t, a), __builtin_bit_cast(us2_t, b)));
+}
+__device__ __forceinline__ uint32_t pk_add_sat(uint32_t a, uint32_t b) {
+    return __builtin_bit_cast(uint32_t, __builtin_elementwise_add_sat(__builtin_bit_cast(us2_t, a), __builtin_bit_cast(us2_t, b)));
+}
+__device__ __forceinline__ uint32_t pk_mul_lo(uint32_t a, uint32_t b) {
+    return __builtin_bit_cast(uint32_t, __builtin_bit_cast(us2_t, a) * __builtin_bit_cast(us2_t, b));
+}
+__device__ __forceinline__ uint32_t pk_add_wrap(uint32_t a, uint32_t b) {
+    return __builtin_bit_cast(uint32_t, __builtin_bit_cast(us2_t, a) + __builtin_bit_cast(us2_t, b));
+}
+__device__ __forceinline__ uint32_t pk_mad_u16(uint32_t a, uint32_t b, uint32_t c) {
+    return __builtin_bit_cast(uint32_t, (us2_t)(__builtin_bit_cast(us2_t, a) * __builtin_bit_cast(us2_t, b) + __builtin_bit_cast(us2_t, c)));
+}
+
+// ---- the add + min3 cascade step of edt_band_k16_kernel and edt_band_wide_kernel ----
+// v_pk_minimum3_f16 on bit patterns 0 .. 0x7C00 (non-negative f16, denormals included): the f16 order is the integer order
+// (tools/microbench/min3_mb.hip checks the instruction on 32 M triples), so the cascade step is two packed instructions per
+// register -- T = P + (2 it - 1), P = min3(P, T[left], T[right]) -- instead of three.  To stay below the NaN patterns the
+// distance bytes are clamped at 177 (packed values below 177^2 = 31329 are exact) and the cascade stops after 175 steps
+// (T <= 31329 + 349 < 0x7C00); rows that need more (very sparse grids) are redone in 32 bits.
+#define EDT_W_GCAP 177u
+#define EDT_W_ITMAX 175
+__device__ __forceinline__ uint32_t pk_min3_f16bits(uint32_t a, uint32_t b, uint32_t c) {
+    uint32_t r;
+    asm("v_pk_minimum3_f16 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+    return r;
+}
+
+// lane l <- lane l-1, lane 0 <- lane 63 / lane l <- lane l+1, lane 63 <- lane 0
+__device__ __forceinline__ uint32_t wave_ror1(uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x13C /*wave_ror:1*/, 0xF, 0xF, true);   // every lane is written: no old value
+}
+__device__ __forceinline__ uint32_t wave_rol1(uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x134 /*wave_rol:1*/, 0xF, 0xF, true);
+}
+
+// lane l <- lane l-1 (lane 0 keeps `fill`) / lane l <- lane l+1 (lane 63 keeps `fill`)
+__device__ __forceinline__ uint32_t from_lane_below(uint32_t v, uint32_t fill) {
+    return (uint32_t)__builtin_amdgcn_update_dpp((int)fill, (int)v, 0x138 /*wave_shr:1*/, 0xF, 0xF, false);
+}
+__device__ __forceinline__ uint32_t from_lane_above(uint32_t v, uint32_t fill) {
+    return (uint32_t)__builtin_amdgcn_update_dpp((int)fill, (int)v, 0x130 /*wave_shl:1*/, 0xF, 0xF, false);
+}
+
+// ---- edt_colbits: occupancy bytes -> column words ----
 __device__ __forceinline__ uint32_t nonzero_bytes_hi(uint32_t v) {
     // bit 7 of every non-zero byte
     return (((v & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | v) & 0x80808080u;
@@ -105,33 +182,6 @@ edt_colbits_generic_kernel(const uint8_t* __restrict__ occ, int W, int H, int nb
     uint32_t w = 0;
     for (int i = 0; i < rows; ++i) w |= (uint32_t)(base[(size_t)i * W] != 0) << i;
     colbits[((size_t)g * nb + b) * W + x] = w;
-}
-
-// d2 is written once and not read again by this library: non-temporal stores keep the 256 MiB of output
-// from lingering as dirty lines whose write-back would otherwise slow whatever runs next (measured:
-// the following colbits launch drops from ~25 us to ~10 us, the read floor for 64 MiB).
-typedef int v4i_t __attribute__((ext_vector_type(4)));
-#define EDT_STORE4(p, v) __builtin_nontemporal_store(v4i_t{(v).x, (v).y, (v).z, (v).w}, reinterpret_cast<v4i_t*>(p))
-
-typedef unsigned short us2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t pk_min(uint32_t a, uint32_t b) {
-    return __builtin_bit_cast(uint32_t, __builtin_elementwise_min(__builtin_bit_cast(us2_t, a), __builtin_bit_cast(us2_t, b)));
-}
-__device__ __forceinline__ uint32_t pk_max(uint32_t a, uint32_t b) {
-    return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(us2_t, a), __builtin_bit_cast(us2_t, b)));
-}
-__device__ __forceinline__ uint32_t pk_add_sat(uint32_t a, uint32_t b) {
-    return __builtin_bit_cast(uint32_t, __builtin_elementwise_add_sat(__builtin_bit_cast(us2_t, a), __builtin_bit_cast(us2_t, b)));
-}
-__device__ __forceinline__ uint32_t pk_mul_lo(uint32_t a, uint32_t b) {
-    return __builtin_bit_cast(uint32_t, __builtin_bit_cast(us2_t, a) * __builtin_bit_cast(us2_t, b));
-}
-// lane l <- lane l-1 (lane 0 keeps `fill`) / lane l <- lane l+1 (lane 63 keeps `fill`)
-__device__ __forceinline__ uint32_t from_lane_below(uint32_t v, uint32_t fill) {
-    return (uint32_t)__builtin_amdgcn_update_dpp((int)fill, (int)v, 0x138 /*wave_shr:1*/, 0xF, 0xF, false);
-}
-__device__ __forceinline__ uint32_t from_lane_above(uint32_t v, uint32_t fill) {
-    return (uint32_t)__builtin_amdgcn_update_dpp((int)fill, (int)v, 0x130 /*wave_shl:1*/, 0xF, 0xF, false);
 }
 
 template <int PPL, bool FULL>
@@ -307,14 +357,6 @@ edt_band_kernel(const uint32_t* __restrict__ colbits, int W, int H, int nb, int3
             for (int j = 0; j < PPL; ++j) V[j] = V[j] >= (uint32_t)EDT_F_INF ? (uint32_t)INT32_MAX : V[j];
             done = true;
         }
-#ifdef EDT_DIRECT_STORE
-        if (done && FULL && PPL % 4 == 0) {
-            // each lane stores its own PPL consecutive pixels as 16-byte pieces
-#pragma unroll
-            for (int j = 0; j < PPL; j += 4)
-                *reinterpret_cast<int4*>(out + PPL * lane + j) = make_int4((int)V[j], (int)V[j + 1], (int)V[j + 2], (int)V[j + 3]);
-        } else
-#endif
         if (done) {
             // ---- transpose through LDS so that global stores are lane-contiguous ----
 #pragma unroll
@@ -371,7 +413,7 @@ edt_band_kernel(const uint32_t* __restrict__ colbits, int W, int H, int nb, int3
     }
 }
 
-// ---- edt_band_g8_kernel: the W <= 1024 fast path -------------------------------------------------
+// ---- edt_band_g8_kernel: 257 .. 512 columns (PPL = 8) and the 1024-column windows of rows wider than 4096 (PPL = 16, TILED) ----
 // Same cascade, leaner set-up.  Phase 1 turns the band's column words into ALL 32 x W vertical
 // distances with a packed-u16 recurrence (two columns per VGPR:  gu_i = bit_i ? 0 : gu_{i-1} + 1
 // top-down, gd bottom-up, g = min(gu, gd, 255)), ~5 VALU ops per pixel instead of ~16 for the
@@ -399,12 +441,12 @@ __device__ __noinline__ uint32_t edt_gdist_global(const uint32_t* cb, int W, int
     return min(gg, (uint32_t)EDT_G_INF);
 }
 
-// TILED (rows wider than 1024, PPL == 16): a workgroup handles a window of 1024 columns of its band -- a core of
+// TILED (rows wider than 4096, PPL == 16): a workgroup handles a window of 1024 columns of its band -- a core of
 // 1024 - 2 halo columns plus `halo` on either side.  After `it` cascade steps a core pixel has seen every site
 // within `it` columns, all of them inside the window, so the usual stopping rule holds as long as it <= halo;
 // only the core is tested and stored.  A row that needs more steps (or leaves the packed range) raises its band's flag and
 // the whole-row kernel redoes that band afterwards.
-#define EDT_TILE_HALO_MIN 32   // the halo is a multiple of 16 (whole lanes) chosen per width: see launch_band_g8_tiled
+#define EDT_TILE_HALO_MIN 32   // the halo is a multiple of 16 (whole lanes) chosen per width: see launch_band_windows
 template <int PPL, bool FULL, bool TILED = false>
 __global__ void __launch_bounds__(512, 8)
 edt_band_g8_kernel(const uint32_t* __restrict__ colbits, int W, int H, int nb, int32_t* __restrict__ d2, int tiles, int halo,
@@ -432,10 +474,6 @@ edt_band_g8_kernel(const uint32_t* __restrict__ colbits, int W, int H, int nb, i
     const int xw0 = TILED ? tile * tcore - halo : 0;                    // global column of the window's first pixel
     const uint32_t* cb = colbits + (size_t)g * nb * W;
 
-#ifdef EDT_ABLATE_PHASE1   // timing-only: no look-back / recurrence, constant distances
-    for (int q = threadIdx.x; q < 32 * WP / 4; q += WAVES * 64) smem[q] = 0x03020302u + (cb[(size_t)b * W + (q & (W - 1))] & 1u);
-    if (false)
-#endif
     // ---- phase 1: two adjacent columns per thread -> 32 rows of 2 distance bytes ----
     for (int q = threadIdx.x; q < WP / 2; q += WAVES * 64) {
         uint32_t nw[2];
@@ -527,10 +565,6 @@ edt_band_g8_kernel(const uint32_t* __restrict__ colbits, int W, int H, int nb, i
         tr = trs + (size_t)wave * 256;
         trb = smem + (size_t)wave * (WP / 4) - 256;   // so that trb[8 * lane + r] with lane >= 32 lands in row `wave`
     }
-#ifdef EDT_ABLATE_ROWS   // timing-only: phase 1 alone (one store keeps it alive)
-    if (threadIdx.x == 0) d2[((size_t)g * H + y0) * W] = g8[lane];
-    if (true) return;
-#endif
     int chk_from = 2;   // first cascade step after which this wave tests for convergence (adapted row by row)
     for (int i = wave; i < nrows; i += WAVES) {
         int32_t* out = d2 + ((size_t)g * H + y0 + i) * W;
@@ -705,33 +739,6 @@ edt_band_g8_kernel(const uint32_t* __restrict__ colbits, int W, int H, int nb, i
             }
         }
     }
-}
-
-// ---- packed helpers shared by the 1024-wide and the wide-row kernels ----
-// v_pk_minimum3_f16 on bit patterns 0 .. 0x7C00 (non-negative f16, denormals included): the f16 order is the integer order
-// (tools/microbench/min3_mb.hip checks the instruction on 32 M triples), so the cascade step is two packed instructions per
-// register -- T = P + (2 it - 1), P = min3(P, T[left], T[right]) -- instead of three.  To stay below the NaN patterns the
-// distance bytes are clamped at 177 (packed values below 177^2 = 31329 are exact) and the cascade stops after 175 steps
-// (T <= 31329 + 349 < 0x7C00); rows that need more (very sparse grids) are redone in 32 bits.
-#define EDT_W_GCAP 177u
-#define EDT_W_ITMAX 175
-__device__ __forceinline__ uint32_t pk_min3_f16bits(uint32_t a, uint32_t b, uint32_t c) {
-    uint32_t r;
-    asm("v_pk_minimum3_f16 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    return r;
-}
-__device__ __forceinline__ uint32_t pk_add_wrap(uint32_t a, uint32_t b) {
-    return __builtin_bit_cast(uint32_t, __builtin_bit_cast(us2_t, a) + __builtin_bit_cast(us2_t, b));
-}
-__device__ __forceinline__ uint32_t pk_mad_u16(uint32_t a, uint32_t b, uint32_t c) {
-    return __builtin_bit_cast(uint32_t, (us2_t)(__builtin_bit_cast(us2_t, a) * __builtin_bit_cast(us2_t, b) + __builtin_bit_cast(us2_t, c)));
-}
-// lane l <- lane l-1, lane 0 <- lane 63 / lane l <- lane l+1, lane 63 <- lane 0
-__device__ __forceinline__ uint32_t wave_ror1(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x13C /*wave_ror:1*/, 0xF, 0xF, true);   // every lane is written: no old value
-}
-__device__ __forceinline__ uint32_t wave_rol1(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x134 /*wave_rol:1*/, 0xF, 0xF, true);
 }
 
 // ---- edt_updown_kernel: per (band, column), rows to the nearest obstacle in the bands above / below -----------
@@ -1201,41 +1208,6 @@ edt_band_wide_kernel(const uint32_t* __restrict__ colbits, const uint32_t* __res
     }
 }
 
-template <int TILES, bool FULL>
-static int launch_band_wide(sc_ctx* ctx, const uint32_t* colbits, int W, int H, int nb, int batch, int32_t* d2) {
-    const int nsb = (H + 15) / 16;
-    const int ngroups = nsb * batch;
-    const size_t lds = (size_t)2 * 16 * 1024 * TILES;
-    {
-        int r_ = sc_allow_big_lds(ctx, reinterpret_cast<const void*>(edt_band_wide_kernel<TILES, FULL>), (int)lds);
-        if (r_ != SC_OK) return r_;
-    }
-    if (ctx->cu_count <= 0) {
-        hipDeviceProp_t prop;
-        ctx->cu_count = (hipGetDeviceProperties(&prop, ctx->device) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-    }
-    // one workgroup (16 wavefronts) per CU, each with a strided set of row groups
-    const int nwg = min(ngroups, ctx->cu_count);
-    int tk = ctx->edt_open_token;   // opened in front of the updown launch (-1: timing off)
-    ctx->edt_open_token = -1;
-    if (!ctx->edt_fault.p) {
-        int r_ = sc_scratch_reserve(ctx, &ctx->edt_fault, sizeof(int32_t));
-        if (r_ != SC_OK) return r_;
-        SC_HIP(ctx, hipMemsetAsync(ctx->edt_fault.p, 0, sizeof(int32_t), ctx->stream));
-    }
-    hipLaunchKernelGGL((edt_band_wide_kernel<TILES, FULL>), dim3((unsigned)nwg), dim3(1024), lds, ctx->stream, colbits,
-                       (const uint32_t*)ctx->updown.p, W, H, nb, nsb, ngroups, d2, (int32_t*)ctx->edt_fault.p);
-    sc_time_end(ctx, tk);
-    SC_HIP(ctx, hipGetLastError());
-    return SC_OK;
-}
-
-template <int TILES>
-static int launch_band_wide_t(sc_ctx* ctx, const uint32_t* colbits, int W, int H, int nb, int batch, int32_t* d2) {
-    return W == 1024 * TILES ? launch_band_wide<TILES, true>(ctx, colbits, W, H, nb, batch, d2)
-                             : launch_band_wide<TILES, false>(ctx, colbits, W, H, nb, batch, d2);
-}
-
 // Open space at widths up to 1024 (a hint between launches, per device): [0] a row of edt_band_k16_kernel<.., false> took the
 // 32-bit fallback; [1] a row of its OPEN build took the site search.  sc_ctx_synchronize reads and clears them: a context
 // that has seen [0] runs the OPEN build (with edt_updown_kernel in front) until a launch of it leaves [1] clear.
@@ -1345,7 +1317,7 @@ __device__ __forceinline__ int edt_k16_site_row(const uint32_t* __restrict__ cbr
 }
 
 // ---- edt_band_k16_kernel: rows of 513 .. 1024 pixels (the headline width) -------------------------------------
-// edt_band_g8_kernel<16> with three changes (measured on the wide-row kernel first, whose LDS traffic was its bound):
+// edt_band_g8_kernel with 16 pixels per lane and three changes (measured on the wide-row kernel first, whose LDS traffic was its bound):
 //  * the cascade step is add + min3 (two packed instructions per register instead of three, see pk_min3_f16bits);
 //  * the vertical pass is one packed multiply-add per row and direction (gu = free ? gu + 1 : 0 is (gu + 1) * free), the
 //    32 rows in two halves so that the running values stay in registers, and pairs of lanes exchange their 2 x 2 bytes so
@@ -1634,16 +1606,25 @@ edt_band_k16_kernel(const uint32_t* __restrict__ colbits, int W, int H, int nb, 
     }
 }
 
+// ---- host side: one launcher per band kernel, then sc_launch_edt, the table that picks one by width --------------------
+// Timing.  The band bracket of an EDT chains onto its colbits bracket (token cb_tk >= 0): the event that ends colbits is
+// the one that starts the band, one record between back-to-back kernels.  Without a colbits bracket (timing off, or the
+// later passes of the window route: cb_tk < 0) it is an ordinary bracket.  Tokens index ctx->pending, so they live in
+// locals and arguments of one call only.
+static int edt_band_time_begin(sc_ctx* ctx, int cb_tk) {
+    return cb_tk >= 0 ? sc_time_chain(ctx, cb_tk, SC_K_EDT_BAND) : sc_time_begin(ctx, SC_K_EDT_BAND);
+}
+
+// 513 .. 1024 columns
 template <bool FULL>
-static int launch_band_k16(sc_ctx* ctx, const uint32_t* colbits, int W, int H, int nb, int batch, int32_t* d2) {
+static int launch_band_k16(sc_ctx* ctx, const uint32_t* colbits, int W, int H, int nb, int batch, int32_t* d2, int cb_tk) {
     const size_t lds = (size_t)32 * 1024 + 8 * 1024;
     ctx->edt_k16_launched = true;
     if (ctx->edt_open_mode) {
         // open space seen on this context (sc_ctx_synchronize): the up / down words first, then the build with the site search
         int r_ = sc_scratch_reserve(ctx, &ctx->updown, (size_t)batch * nb * W * sizeof(uint32_t));
         if (r_ != SC_OK) return r_;
-        int tk = ctx->edt_chain_token >= 0 ? sc_time_chain(ctx, ctx->edt_chain_token, SC_K_EDT_BAND) : sc_time_begin(ctx, SC_K_EDT_BAND);
-        ctx->edt_chain_token = -1;
+        const int tk = edt_band_time_begin(ctx, cb_tk);
         launch_updown(ctx, colbits, W, nb, batch, (uint32_t*)ctx->updown.p);
         hipLaunchKernelGGL((edt_band_k16_kernel<FULL, true>), dim3((unsigned)(nb * batch)), dim3(512), lds, ctx->stream, colbits, W, H, nb, d2,
                            (const uint32_t*)ctx->updown.p);
@@ -1652,8 +1633,7 @@ static int launch_band_k16(sc_ctx* ctx, const uint32_t* colbits, int W, int H, i
         SC_HIP(ctx, hipGetLastError());
         return SC_OK;
     }
-    int tk = ctx->edt_chain_token >= 0 ? sc_time_chain(ctx, ctx->edt_chain_token, SC_K_EDT_BAND) : sc_time_begin(ctx, SC_K_EDT_BAND);
-    ctx->edt_chain_token = -1;
+    const int tk = edt_band_time_begin(ctx, cb_tk);
     hipLaunchKernelGGL((edt_band_k16_kernel<FULL, false>), dim3((unsigned)(nb * batch)), dim3(512), lds, ctx->stream, colbits, W, H, nb, d2,
                        (const uint32_t*)nullptr);
     sc_time_end(ctx, tk);
@@ -1677,16 +1657,16 @@ int sc_edt_open_mode_update(sc_ctx* ctx) {
     return SC_OK;
 }
 
-template <int PPL, bool FULL>
-static int launch_band_g8(sc_ctx* ctx, const uint32_t* colbits, int W, int H, int nb, int batch, int32_t* d2) {
-    constexpr int WP = 64 * PPL;
-    const size_t lds = PPL == 16 ? (size_t)32 * WP + 8 * 1024 : (size_t)32 * WP + (size_t)8 * 64 * (PPL / 2 + 1) * sizeof(uint32_t);
+// 257 .. 512 columns: edt_band_g8_kernel with 8 pixels per lane
+template <bool FULL>
+static int launch_band_g8(sc_ctx* ctx, const uint32_t* colbits, int W, int H, int nb, int batch, int32_t* d2, int cb_tk) {
+    constexpr int PPL = 8, WP = 64 * PPL;
+    const size_t lds = (size_t)32 * WP + (size_t)8 * 64 * (PPL / 2 + 1) * sizeof(uint32_t);   // distance bytes + a transposition buffer per wave
     {
         int r_ = sc_allow_big_lds(ctx, reinterpret_cast<const void*>(edt_band_g8_kernel<PPL, FULL>), 160 * 1024);
         if (r_ != SC_OK) return r_;
     }
-    int tk = ctx->edt_chain_token >= 0 ? sc_time_chain(ctx, ctx->edt_chain_token, SC_K_EDT_BAND) : sc_time_begin(ctx, SC_K_EDT_BAND);
-    ctx->edt_chain_token = -1;
+    const int tk = edt_band_time_begin(ctx, cb_tk);
     hipLaunchKernelGGL((edt_band_g8_kernel<PPL, FULL>), dim3((unsigned)(nb * batch)), dim3(512), lds, ctx->stream,
                        colbits, W, H, nb, d2, 1, 0, (int32_t*)nullptr, (const int32_t*)nullptr);
     sc_time_end(ctx, tk);
@@ -1694,14 +1674,10 @@ static int launch_band_g8(sc_ctx* ctx, const uint32_t* colbits, int W, int H, in
     return SC_OK;
 }
 
-template <int PPL>
-static int launch_band_g8_ppl(sc_ctx* ctx, const uint32_t* colbits, int W, int H, int nb, int batch, int32_t* d2) {
-    return W == 64 * PPL ? launch_band_g8<PPL, true>(ctx, colbits, W, H, nb, batch, d2)
-                         : launch_band_g8<PPL, false>(ctx, colbits, W, H, nb, batch, d2);
-}
-
+// The general kernel, 64 * PPL >= W.  `flags` (may be null) concerns edt_band_kernel<128> only, the last pass of the window
+// route: int32 [batch][nb], a band is computed where its flag is non-zero.
 template <int PPL, bool FULL>
-static int launch_band(sc_ctx* ctx, const uint32_t* colbits, int W, int H, int nb, int batch, int32_t* d2, const int32_t* flags = nullptr) {
+static int launch_band(sc_ctx* ctx, const uint32_t* colbits, int W, int H, int nb, int batch, int32_t* d2, const int32_t* flags, int cb_tk) {
     constexpr int G = PPL < 16 ? PPL : 16;
     constexpr int WP = 64 * PPL;
     constexpr int TRN = (64 * (G + 1) > WP / 2 ? 64 * (G + 1) : WP / 2);
@@ -1710,8 +1686,7 @@ static int launch_band(sc_ctx* ctx, const uint32_t* colbits, int W, int H, int n
         int r_ = sc_allow_big_lds(ctx, reinterpret_cast<const void*>(edt_band_kernel<PPL, FULL>), 160 * 1024);
         if (r_ != SC_OK) return r_;
     }
-    int tk = ctx->edt_chain_token >= 0 ? sc_time_chain(ctx, ctx->edt_chain_token, SC_K_EDT_BAND) : sc_time_begin(ctx, SC_K_EDT_BAND);
-    ctx->edt_chain_token = -1;
+    const int tk = edt_band_time_begin(ctx, cb_tk);
     hipLaunchKernelGGL((edt_band_kernel<PPL, FULL>), dim3((unsigned)(nb * batch)), dim3(256), lds, ctx->stream,
                        colbits, W, H, nb, d2, flags);
     sc_time_end(ctx, tk);
@@ -1720,16 +1695,63 @@ static int launch_band(sc_ctx* ctx, const uint32_t* colbits, int W, int H, int n
 }
 
 template <int PPL>
-static int launch_band_ppl(sc_ctx* ctx, const uint32_t* colbits, int W, int H, int nb, int batch, int32_t* d2, const int32_t* flags = nullptr) {
-    return W == 64 * PPL ? launch_band<PPL, true>(ctx, colbits, W, H, nb, batch, d2, flags)
-                         : launch_band<PPL, false>(ctx, colbits, W, H, nb, batch, d2, flags);
+static int launch_band_ppl(sc_ctx* ctx, const uint32_t* colbits, int W, int H, int nb, int batch, int32_t* d2, const int32_t* flags, int cb_tk) {
+    return W == 64 * PPL ? launch_band<PPL, true>(ctx, colbits, W, H, nb, batch, d2, flags, cb_tk)
+                         : launch_band<PPL, false>(ctx, colbits, W, H, nb, batch, d2, flags, cb_tk);
 }
 
-// Rows wider than 1024: windows of 1024 columns through the fast kernel; flags[grid][band] != 0 where it gave up.
-// `halo` columns on either side of a window's core bound the cascade steps (= the largest distance) a row may need;
-// `only`: process just the bands an earlier pass flagged.
+// edt_band_wide_kernel alone: ctx->updown has been written on the stream and the caller holds the timing bracket
+template <int TILES, bool FULL>
+static int launch_band_wide(sc_ctx* ctx, const uint32_t* colbits, int W, int H, int nb, int batch, int32_t* d2) {
+    const int nsb = (H + 15) / 16;
+    const int ngroups = nsb * batch;
+    const size_t lds = (size_t)2 * 16 * 1024 * TILES;
+    {
+        int r_ = sc_allow_big_lds(ctx, reinterpret_cast<const void*>(edt_band_wide_kernel<TILES, FULL>), (int)lds);
+        if (r_ != SC_OK) return r_;
+    }
+    if (ctx->cu_count <= 0) {
+        hipDeviceProp_t prop;
+        ctx->cu_count = (hipGetDeviceProperties(&prop, ctx->device) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
+    }
+    // one workgroup (16 wavefronts) per CU, each with a strided set of row groups
+    const int nwg = min(ngroups, ctx->cu_count);
+    if (!ctx->edt_fault.p) {
+        int r_ = sc_scratch_reserve(ctx, &ctx->edt_fault, sizeof(int32_t));
+        if (r_ != SC_OK) return r_;
+        SC_HIP(ctx, hipMemsetAsync(ctx->edt_fault.p, 0, sizeof(int32_t), ctx->stream));
+    }
+    hipLaunchKernelGGL((edt_band_wide_kernel<TILES, FULL>), dim3((unsigned)nwg), dim3(1024), lds, ctx->stream, colbits,
+                       (const uint32_t*)ctx->updown.p, W, H, nb, nsb, ngroups, d2, (int32_t*)ctx->edt_fault.p);
+    SC_HIP(ctx, hipGetLastError());
+    return SC_OK;
+}
+
+template <int TILES>
+static int launch_band_wide_t(sc_ctx* ctx, const uint32_t* colbits, int W, int H, int nb, int batch, int32_t* d2) {
+    return W == 1024 * TILES ? launch_band_wide<TILES, true>(ctx, colbits, W, H, nb, batch, d2)
+                             : launch_band_wide<TILES, false>(ctx, colbits, W, H, nb, batch, d2);
+}
+
+// 1025 .. 4096 columns: the up / down words, then whole rows in registers.  One band bracket around both: the look-up
+// table of the band kernel counts as band time.
+static int launch_band_wide_rows(sc_ctx* ctx, const uint32_t* colbits, int W, int H, int nb, int batch, int32_t* d2, int cb_tk) {
+    int r = sc_scratch_reserve(ctx, &ctx->updown, (size_t)batch * nb * W * sizeof(uint32_t));
+    if (r != SC_OK) return r;
+    const int tk = edt_band_time_begin(ctx, cb_tk);
+    launch_updown(ctx, colbits, W, nb, batch, (uint32_t*)ctx->updown.p);
+    if (W <= 2048) r = launch_band_wide_t<2>(ctx, colbits, W, H, nb, batch, d2);
+    else if (W <= 3072) r = launch_band_wide_t<3>(ctx, colbits, W, H, nb, batch, d2);
+    else r = launch_band_wide_t<4>(ctx, colbits, W, H, nb, batch, d2);
+    sc_time_end(ctx, tk);
+    return r;
+}
+
+// One pass of 1024-column windows (edt_band_g8_kernel's TILED build); flags[grid][band] != 0 where it gave up.  `halo`
+// columns on either side of a window's core bound the cascade steps (= the largest distance) a row may need; `only`
+// (may be null): process just the bands an earlier pass flagged.
 static int launch_band_g8_tiled(sc_ctx* ctx, const uint32_t* colbits, int W, int H, int nb, int batch, int32_t* d2, int halo, int32_t* flags,
-                                const int32_t* only, bool first) {
+                                const int32_t* only, int cb_tk) {
     const int tiles = (W + (1024 - 2 * halo) - 1) / (1024 - 2 * halo);
     const size_t lds = (size_t)32 * 1024 + 8 * 1024;
     {
@@ -1737,16 +1759,34 @@ static int launch_band_g8_tiled(sc_ctx* ctx, const uint32_t* colbits, int W, int
         if (r_ != SC_OK) return r_;
     }
     SC_HIP(ctx, hipMemsetAsync(flags, 0, (size_t)batch * nb * sizeof(int32_t), ctx->stream));
-    int tk = -1;
-    if (first) {
-        tk = ctx->edt_chain_token >= 0 ? sc_time_chain(ctx, ctx->edt_chain_token, SC_K_EDT_BAND) : sc_time_begin(ctx, SC_K_EDT_BAND);
-        ctx->edt_chain_token = -1;
-    } else tk = sc_time_begin(ctx, SC_K_EDT_BAND);
+    const int tk = edt_band_time_begin(ctx, cb_tk);
     hipLaunchKernelGGL((edt_band_g8_kernel<16, true, true>), dim3((unsigned)((size_t)nb * batch * tiles)), dim3(512), lds, ctx->stream,
                        colbits, W, H, nb, d2, tiles, halo, flags, only);
     sc_time_end(ctx, tk);
     SC_HIP(ctx, hipGetLastError());
     return SC_OK;
+}
+
+// 4097 .. 8192 columns: three launches, each a band bracket of its own.
+//   1. Windows with as few of them as the minimal halo allows (5 .. 9), the halo as wide as that number leaves room for
+//      in whole lanes of 16 pixels: 32 .. 96 columns for these widths.  Settles every row whose distances stay below the
+//      halo, i.e. all of an ordinary map.
+//   2. Only the bands in which some row needed more steps (flags of pass 1): windows with a halo of 256 columns, which
+//      covers every distance the packed cascade can represent.
+//   3. Only the bands still open (flags of pass 2: grids so sparse that distances exceed 255): edt_band_kernel<128>, whole
+//      rows, with its 32-bit fallback.
+static int launch_band_windows(sc_ctx* ctx, const uint32_t* colbits, int W, int H, int nb, int batch, int32_t* d2, int cb_tk) {
+    int r = sc_scratch_reserve(ctx, &ctx->edt_flags, (size_t)2 * batch * nb * sizeof(int32_t));
+    if (r != SC_OK) return r;
+    int32_t* f1 = (int32_t*)ctx->edt_flags.p;
+    int32_t* f2 = f1 + (size_t)batch * nb;
+    const int tiles = (W + (1024 - 2 * EDT_TILE_HALO_MIN) - 1) / (1024 - 2 * EDT_TILE_HALO_MIN);
+    const int halo = ((1024 - (W + tiles - 1) / tiles) / 2) / 16 * 16;   // >= EDT_TILE_HALO_MIN by the choice of `tiles`
+    r = launch_band_g8_tiled(ctx, colbits, W, H, nb, batch, d2, halo, f1, nullptr, cb_tk);
+    if (r != SC_OK) return r;
+    r = launch_band_g8_tiled(ctx, colbits, W, H, nb, batch, d2, 256, f2, f1, -1);
+    if (r != SC_OK) return r;
+    return launch_band_ppl<128>(ctx, colbits, W, H, nb, batch, d2, f2, -1);
 }
 
 int sc_launch_edt(sc_ctx* ctx, const uint8_t* occ, int W, int H, int batch, int32_t* d2) {
@@ -1756,11 +1796,8 @@ int sc_launch_edt(sc_ctx* ctx, const uint8_t* occ, int W, int H, int batch, int3
     uint32_t* colbits = (uint32_t*)ctx->colbits.p;
     if (batch > 65535 || nb > 65535) return SC_ERR_INVALID;
 
-    static const char* only = getenv("SC_EDT_ONLY");  // debug/profiling: run a single kernel of the pair
-    const bool skip_colbits = only && only[0] == 'b', skip_band = only && only[0] == 'c';
-    int tk = sc_time_begin(ctx, SC_K_EDT_COLBITS);
-    if (skip_colbits) {
-    } else if (W % 16 == 0 && ((uintptr_t)occ & 15) == 0) {
+    const int cb_tk = sc_time_begin(ctx, SC_K_EDT_COLBITS);   // ended by the band launcher (edt_band_time_begin)
+    if (W % 16 == 0 && ((uintptr_t)occ & 15) == 0) {
         hipLaunchKernelGGL(edt_colbits_kernel<true>, dim3((W + 1023) / 1024, nb, batch), dim3(64, 4), 0, ctx->stream,
                            occ, W, H, nb, colbits);
     } else if (W % 4 == 0 && ((uintptr_t)occ & 3) == 0) {
@@ -1771,198 +1808,17 @@ int sc_launch_edt(sc_ctx* ctx, const uint8_t* occ, int W, int H, int batch, int3
         hipLaunchKernelGGL(edt_colbits_generic_kernel, grid, dim3(256), 0, ctx->stream, occ, W, H, nb, colbits);
     }
     SC_HIP(ctx, hipGetLastError());
-    if (skip_band) { sc_time_end(ctx, tk); return SC_OK; }
-    ctx->edt_chain_token = tk;
-    // pixels per lane: smallest power of two with 64 * PPL >= W
-    if (W <= 128) return launch_band_ppl<2>(ctx, colbits, W, H, nb, batch, d2);
-    if (W <= 256) return launch_band_ppl<4>(ctx, colbits, W, H, nb, batch, d2);
-#ifndef EDT_NO_G8
-    if (W > 256 && W <= 512) return launch_band_g8_ppl<8>(ctx, colbits, W, H, nb, batch, d2);
-    if (W > 512 && W <= 1024) {
-        static const bool old16 = getenv("SC_EDT_OLD16") && atoi(getenv("SC_EDT_OLD16"));   // A/B against edt_band_g8_kernel<16>
-        if (old16) return launch_band_g8_ppl<16>(ctx, colbits, W, H, nb, batch, d2);
-        return W == 1024 ? launch_band_k16<true>(ctx, colbits, W, H, nb, batch, d2) : launch_band_k16<false>(ctx, colbits, W, H, nb, batch, d2);
-    }
-#endif
-    if (W <= 512) return launch_band_ppl<8>(ctx, colbits, W, H, nb, batch, d2);
-    if (W <= 1024) return launch_band_ppl<16>(ctx, colbits, W, H, nb, batch, d2);
-#ifndef EDT_NO_WIDE
-    // rows of up to 4096 pixels: whole rows in registers, 16 rows per workgroup
-    if ((size_t)((H + 15) / 16) * batch <= 0x7FFFFFFFu) {
-        r = sc_scratch_reserve(ctx, &ctx->updown, (size_t)batch * nb * W * sizeof(uint32_t));
-        if (r != SC_OK) return r;
-        colbits = (uint32_t*)ctx->colbits.p;
-        // timing: the look-up table of the band kernel counts as band time (the colbits bracket ends here)
-        if (ctx->edt_chain_token >= 0) ctx->edt_open_token = sc_time_chain(ctx, ctx->edt_chain_token, SC_K_EDT_BAND);
-        ctx->edt_chain_token = -1;
-        launch_updown(ctx, colbits, W, nb, batch, (uint32_t*)ctx->updown.p);
-        if (W <= 2048) return launch_band_wide_t<2>(ctx, colbits, W, H, nb, batch, d2);
-        if (W <= 3072) return launch_band_wide_t<3>(ctx, colbits, W, H, nb, batch, d2);
-        if (W <= 4096) return launch_band_wide_t<4>(ctx, colbits, W, H, nb, batch, d2);
-    }
-#endif
-    // wider rows still: 1024-column windows through the fast kernel first, then the whole-row kernel for the grids (if
-    // any) in which some row did not settle within the window's halo
-    const int32_t* flags = nullptr;
-#ifndef EDT_NO_G8
-    {
-        // Pass 1: as few windows as the minimal halo allows, with the halo as wide as that number of windows leaves room
-        // for (whole lanes of 16 pixels): at W = 4096 five windows either way, with a halo of 96 columns instead of 32.
-        // Pass 2, only for the bands in which some row needed more steps than that (block-type maps: a tenth of the bands
-        // at 4096^2): windows with a halo of 256 columns, which covers every distance the packed cascade can represent.
-        // Pass 3: the whole-row kernel for what is still open (grids so sparse that distances exceed 255).
-        r = sc_scratch_reserve(ctx, &ctx->edt_flags, (size_t)2 * batch * nb * sizeof(int32_t));
-        if (r != SC_OK) return r;
-        int32_t* f1 = (int32_t*)ctx->edt_flags.p;
-        int32_t* f2 = f1 + (size_t)batch * nb;
-        const int tiles = (W + (1024 - 2 * EDT_TILE_HALO_MIN) - 1) / (1024 - 2 * EDT_TILE_HALO_MIN);
-        int halo = ((1024 - (W + tiles - 1) / tiles) / 2) / 16 * 16;
-        if (halo < EDT_TILE_HALO_MIN) halo = EDT_TILE_HALO_MIN;
-        r = launch_band_g8_tiled(ctx, colbits, W, H, nb, batch, d2, halo, f1, nullptr, true);
-        if (r != SC_OK) return r;
-        flags = f1;
-        if (halo < 256) {
-            r = launch_band_g8_tiled(ctx, colbits, W, H, nb, batch, d2, 256, f2, f1, false);
-            if (r != SC_OK) return r;
-            flags = f2;
-        }
-    }
-#endif
-    if (W <= 2048) return launch_band_ppl<32>(ctx, colbits, W, H, nb, batch, d2, flags);
-    if (W <= 4096) return launch_band_ppl<64>(ctx, colbits, W, H, nb, batch, d2, flags);
-    return launch_band_ppl<128>(ctx, colbits, W, H, nb, batch, d2, flags);
+
+    if (W <= 128) return launch_band_ppl<2>(ctx, colbits, W, H, nb, batch, d2, nullptr, cb_tk);
+    if (W <= 256) return launch_band_ppl<4>(ctx, colbits, W, H, nb, batch, d2, nullptr, cb_tk);
+    if (W <= 512) return W == 512 ? launch_band_g8<true>(ctx, colbits, W, H, nb, batch, d2, cb_tk) : launch_band_g8<false>(ctx, colbits, W, H, nb, batch, d2, cb_tk);
+    if (W <= 1024) return W == 1024 ? launch_band_k16<true>(ctx, colbits, W, H, nb, batch, d2, cb_tk) : launch_band_k16<false>(ctx, colbits, W, H, nb, batch, d2, cb_tk);
+    if (W <= 4096) return launch_band_wide_rows(ctx, colbits, W, H, nb, batch, d2, cb_tk);
+    return launch_band_windows(ctx, colbits, W, H, nb, batch, d2, cb_tk);
 }
 
 extern "C" int sc_edt_u8_i32(sc_ctx* ctx, const uint8_t* occ, int W, int H, int batch, int32_t* d2) {
     if (!ctx || !occ || !d2 || W <= 0 || H <= 0 || batch <= 0 || W > SC_MAX_DIM || H > SC_MAX_DIM) return SC_ERR_INVALID;
     SC_HIP(ctx, hipSetDevice(ctx->device));
     return sc_launch_edt(ctx, occ, W, H, batch, d2);
-}
-
-// ---- legal-move mask --------------------------------------------------------------------------
-__global__ void __launch_bounds__(256)
-moves_kernel(const int32_t* __restrict__ d2, int W, int Hall, int H, int32_t rmin, uint8_t* __restrict__ moves) {
-    // Hall = G * H rows: G grids of H rows stacked; a cell's neighbours are looked up inside its own grid only
-    const int x = blockIdx.x * 256 + threadIdx.x;
-    const int yall = blockIdx.y;
-    if (x >= W) return;
-    const int y = yall % H;
-    const int32_t* r1 = d2 + (size_t)yall * W;
-    bool t[3][3];
-#pragma unroll
-    for (int j = -1; j <= 1; ++j)
-#pragma unroll
-        for (int i = -1; i <= 1; ++i) {
-            int xx = x + i, yy = y + j;
-            t[j + 1][i + 1] = xx >= 0 && xx < W && yy >= 0 && yy < H && r1[(ptrdiff_t)j * W + xx] >= rmin;
-        }
-    uint32_t m = 0;
-    if (t[1][1]) {
-        // d: dx = {1,-1,0,0,1,-1,1,-1}, dy = {0,0,1,-1,1,1,-1,-1}
-        m |= (uint32_t)t[1][2] << 0;
-        m |= (uint32_t)t[1][0] << 1;
-        m |= (uint32_t)t[2][1] << 2;
-        m |= (uint32_t)t[0][1] << 3;
-        m |= (uint32_t)(t[2][2] && t[1][2] && t[2][1]) << 4;
-        m |= (uint32_t)(t[2][0] && t[1][0] && t[2][1]) << 5;
-        m |= (uint32_t)(t[0][2] && t[1][2] && t[0][1]) << 6;
-        m |= (uint32_t)(t[0][0] && t[1][0] && t[0][1]) << 7;
-    }
-    moves[(size_t)yall * W + x] = (uint8_t)m;
-}
-
-// The same, four cells per thread (W a multiple of 4, rows 16-byte aligned): the three rows come in as 16-byte loads plus
-// the two cells beside them, the four masks leave as one dword -- the one-cell form moves 5 B/cell at 0.8 TB/s (a byte per
-// thread and store), this one is bound by the d2 reads.
-__global__ void __launch_bounds__(256)
-moves4_kernel(const int32_t* __restrict__ d2, int W, int Hall, int H, int32_t rmin, uint8_t* __restrict__ moves) {
-    const int x = 4 * (blockIdx.x * 256 + threadIdx.x);
-    const int yall = blockIdx.y;
-    if (x >= W) return;
-    const int y = yall % H;
-    const int32_t* r1 = d2 + (size_t)yall * W;
-    uint32_t t[3] = {0u, 0u, 0u};          // bit i + 1 of t[j + 1]: cell (x + i, y + j) is traversable, i = -1 .. 4
-#pragma unroll
-    for (int j = -1; j <= 1; ++j) {
-        const int yy = y + j;
-        if (yy < 0 || yy >= H) continue;
-        const int32_t* r = r1 + (ptrdiff_t)j * W;
-        const int4 v = *reinterpret_cast<const int4*>(r + x);
-        const int32_t l = x > 0 ? r[x - 1] : 0, q = x + 4 < W ? r[x + 4] : 0;      // 0 < rmin: outside the grid is blocked
-        t[j + 1] = (uint32_t)(l >= rmin) | (uint32_t)(v.x >= rmin) << 1 | (uint32_t)(v.y >= rmin) << 2 | (uint32_t)(v.z >= rmin) << 3 |
-                   (uint32_t)(v.w >= rmin) << 4 | (uint32_t)(q >= rmin) << 5;
-    }
-    uint32_t out = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const uint32_t a = t[0] >> i, c = t[1] >> i, b = t[2] >> i;   // rows y - 1, y, y + 1; bit 0 = x - 1, bit 1 = x, bit 2 = x + 1
-        uint32_t m = 0;
-        if (c & 2u) {
-            // d: dx = {1,-1,0,0,1,-1,1,-1}, dy = {0,0,1,-1,1,1,-1,-1}
-            const uint32_t E = (c >> 2) & 1u, Wt = c & 1u, S = (b >> 1) & 1u, N = (a >> 1) & 1u;
-            m = E | Wt << 1 | S << 2 | N << 3 | (((b >> 2) & 1u) & E & S) << 4 | ((b & 1u) & Wt & S) << 5 | (((a >> 2) & 1u) & E & N) << 6 |
-                ((a & 1u) & Wt & N) << 7;
-        }
-        out |= m << (8 * i);
-    }
-    *reinterpret_cast<uint32_t*>(moves + (size_t)yall * W + x) = out;
-}
-
-// ... and four rows per thread as well (H a multiple of 4: a block of rows stays inside its grid): six rows read for four
-// written instead of twelve.
-__global__ void __launch_bounds__(256)
-moves4x4_kernel(const int32_t* __restrict__ d2, int W, int Hall, int H, int32_t rmin, uint8_t* __restrict__ moves) {
-    const int x = 4 * (blockIdx.x * 256 + threadIdx.x);
-    const int yall0 = 4 * blockIdx.y;
-    if (x >= W) return;
-    const int y0 = yall0 % H;
-    const int32_t* r1 = d2 + (size_t)yall0 * W;
-    uint32_t t[6];                          // rows y0 - 1 .. y0 + 4; bit i + 1: cell x + i is traversable, i = -1 .. 4
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-        const int yy = y0 + j - 1;
-        t[j] = 0u;
-        if (yy < 0 || yy >= H) continue;
-        const int32_t* r = r1 + (ptrdiff_t)(j - 1) * W;
-        const int4 v = *reinterpret_cast<const int4*>(r + x);
-        const int32_t l = x > 0 ? r[x - 1] : 0, q = x + 4 < W ? r[x + 4] : 0;
-        t[j] = (uint32_t)(l >= rmin) | (uint32_t)(v.x >= rmin) << 1 | (uint32_t)(v.y >= rmin) << 2 | (uint32_t)(v.z >= rmin) << 3 |
-               (uint32_t)(v.w >= rmin) << 4 | (uint32_t)(q >= rmin) << 5;
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        uint32_t out = 0;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const uint32_t a = t[k] >> i, c = t[k + 1] >> i, b = t[k + 2] >> i;
-            uint32_t m = 0;
-            if (c & 2u) {
-                const uint32_t E = (c >> 2) & 1u, Wt = c & 1u, S = (b >> 1) & 1u, N = (a >> 1) & 1u;
-                m = E | Wt << 1 | S << 2 | N << 3 | (((b >> 2) & 1u) & E & S) << 4 | ((b & 1u) & Wt & S) << 5 | (((a >> 2) & 1u) & E & N) << 6 |
-                    ((a & 1u) & Wt & N) << 7;
-            }
-            out |= m << (8 * i);
-        }
-        *reinterpret_cast<uint32_t*>(moves + (size_t)(yall0 + k) * W + x) = out;
-    }
-}
-
-int sc_launch_moves(sc_ctx* ctx, const int32_t* d2, int W, int Hall, int H, int32_t r2, uint8_t* moves) {
-    int32_t rmin = r2 > 1 ? r2 : 1;
-    int tk = sc_time_begin(ctx, SC_K_MOVES);
-    if (W % 4 == 0 && H % 4 == 0 && ((uintptr_t)d2 & 15) == 0 && ((uintptr_t)moves & 3) == 0)
-        hipLaunchKernelGGL(moves4x4_kernel, dim3((W / 4 + 255) / 256, Hall / 4), dim3(256), 0, ctx->stream, d2, W, Hall, H, rmin, moves);
-    else if (W % 4 == 0 && ((uintptr_t)d2 & 15) == 0 && ((uintptr_t)moves & 3) == 0)
-        hipLaunchKernelGGL(moves4_kernel, dim3((W / 4 + 255) / 256, Hall), dim3(256), 0, ctx->stream, d2, W, Hall, H, rmin, moves);
-    else
-    hipLaunchKernelGGL(moves_kernel, dim3((W + 255) / 256, Hall), dim3(256), 0, ctx->stream, d2, W, Hall, H, rmin, moves);
-    sc_time_end(ctx, tk);
-    SC_HIP(ctx, hipGetLastError());
-    return SC_OK;
-}
-
-extern "C" int sc_moves_i32_u8(sc_ctx* ctx, const int32_t* d2, int W, int H, int32_t r2_clear, uint8_t* moves) {
-    if (!ctx || !d2 || !moves || W <= 0 || H <= 0 || W > SC_MAX_DIM || H > SC_MAX_DIM) return SC_ERR_INVALID;
-    SC_HIP(ctx, hipSetDevice(ctx->device));
-    return sc_launch_moves(ctx, d2, W, H, H, r2_clear, moves);
 }

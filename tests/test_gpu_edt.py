@@ -118,11 +118,14 @@ def test_edt_nearest_matches_oracle(ctx, oracle):
         assert np.array_equal(nb[k], oracle.edt_nearest(ob[k].cpu().numpy(), d2b[k].cpu().numpy()))
 
 
-@pytest.mark.parametrize("W,H", [(1025, 40), (1984, 33), (2049, 70), (3000, 64), (3073, 17), (4095, 31), (4096, 50), (5000, 40)])
+@pytest.mark.parametrize("W,H", [(1025, 40), (1984, 33), (2049, 70), (3000, 64), (3073, 17), (4095, 31), (4096, 50), (5000, 40),
+                                 (4097, 33), (6145, 17), (8192, 33)])
 def test_edt_wide_rows(ctx, oracle, W, H):
     """Rows of 1025 .. 4096 pixels run whole in registers (edt_band_wide_kernel: 16-row groups, producer / consumer
     wavefronts); rows its packed cascade cannot settle (distances beyond 175 columns) are redone in 32 bits inside the same
-    launch; wider rows still go through 1024-column windows.  One batch mixes dense, sparse, seam and empty grids."""
+    launch; wider rows still go through 1024-column windows (the last four shapes: the narrowest such width, an odd one,
+    and the full width with a partial second band, whose whole-row pass is edt_band_kernel<128, true>).  One batch mixes
+    dense, sparse, seam and empty grids, which between them need all three passes of the window route."""
     import torch
     rng = np.random.default_rng(W)
     dense = (rng.random((H, W)) < 0.2).astype(np.uint8)
@@ -135,6 +138,39 @@ def test_edt_wide_rows(ctx, oracle, W, H):
     got = d2.cpu().numpy()
     for b in range(occ.shape[0]):
         assert np.array_equal(got[b], oracle.edt(occ[b])), b
+
+
+@pytest.mark.parametrize("W", [100, 300, 1000, 2000, 5000])
+def test_edt_timing_brackets(oracle, W):
+    """Launch timing of one EDT on a fresh context, on every route of the dispatch: one colbits bracket and one band bracket
+    (edt_updown_kernel counts as band time), three band brackets for rows wider than 4096 (two window passes and the
+    whole-row pass).  With timing switched off again, further EDTs -- the routes that open their bracket ahead of a second
+    launch included -- add nothing and raise nothing."""
+    import torch
+    import sea_current_amd as sc
+    from sea_current_amd import synth
+    H = 40
+    occ = synth.salt_grid(W, H, 0.1, seed=W)
+    c = sc.Context(0)
+    c.set_timing(True)
+    d2 = c.edt(torch.from_numpy(occ).cuda())
+    c.synchronize()
+    ms_c, n_c = c.get_timing(sc.K_EDT_COLBITS)
+    ms_b, n_b = c.get_timing(sc.K_EDT_BAND)
+    print(f"W={W}: colbits {n_c} x, {ms_c:.4f} ms; band {n_b} x, {ms_b:.4f} ms")
+    assert n_c == 1
+    assert n_b == (3 if W > 4096 else 1)
+    assert ms_c > 0 and ms_b > 0
+    assert np.array_equal(d2.cpu().numpy(), oracle.edt(occ))
+    c.set_timing(False)
+    for W2 in (2000, 5000):
+        occ2 = synth.salt_grid(W2, H, 0.1, seed=W2)
+        d2 = c.edt(torch.from_numpy(occ2).cuda())
+        c.synchronize()
+        assert np.array_equal(d2.cpu().numpy(), oracle.edt(occ2))
+    assert c.get_timing(sc.K_EDT_COLBITS) == (ms_c, n_c)
+    assert c.get_timing(sc.K_EDT_BAND) == (ms_b, n_b)
+    c.close()
 
 
 @pytest.mark.parametrize("W", [2048, 3100, 4096])

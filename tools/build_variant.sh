@@ -11,10 +11,8 @@ unit=${VARIANT_UNIT:-astar}     # which source is rebuilt with the macros (astar
 src=csrc/$unit.hip
 [ $unit = astar ] && src=${ASTAR_SRC:-csrc/astar.hip}
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-function "$@" -c $src -o variants/$name.$unit.o
-objs=""
-for o in ctx edt astar toppra bezier grid fmt gather; do
-  if [ $o = $unit ]; then objs="$objs variants/$name.$unit.o"; else objs="$objs csrc/$o.o"; fi
-done
+# the Makefile's object list, with the rebuilt unit swapped in
+objs=$(make -s print-objs | sed "s#csrc/$unit\.o#variants/$name.$unit.o#")
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o variants/$name.so $objs -ldl
 rm -f variants/$name.$unit.o
 echo built variants/$name.so
