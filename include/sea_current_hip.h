@@ -57,9 +57,9 @@ typedef enum {
 typedef enum {
     SC_K_EDT_COLBITS = 0, /* occupancy bytes -> transposed per-band column bit words */
     SC_K_EDT_BAND = 1,    /* per 32-row band: vertical distances + exact row envelope -> d2 */
-    SC_K_MOVES = 2,       /* d2 + clearance -> legal-move byte per cell */
+    SC_K_MOVES = 2,       /* d2 + clearance -> legal-move byte per cell; also sc_clearance_penalty_u8 */
     SC_K_ASTAR = 3,       /* batched A*: two wavefronts per query (prep + search + retry launches); also the cost fields and
-                           * their read-out (sc_cost_field_batch, sc_field_paths_batch) */
+                           * their read-out (sc_cost_field_batch, sc_field_paths_batch and the weighted forms) */
     SC_K_TOPPRA = 4,      /* batched TOPP-RA: computeParams + backward + forward sweep */
     SC_K_TOPPRA_SAMPLE = 5,
     SC_K_BEZIER = 6,      /* tangents + control points, curve evaluation */
@@ -253,6 +253,57 @@ int sc_field_paths_batch(sc_ctx* ctx, const int32_t* d2, int G, const int32_t* f
 int sc_field_paths_batch_host(sc_ctx* ctx, const int32_t* d2, int G, const int32_t* fgrid, int W, int H, int32_t r2_clear,
                               const int32_t* g, const int32_t* root, int F, const int32_t* qfield, const int32_t* target, int Q,
                               int Lmax, int to_root, int32_t* path, int32_t* len, int32_t* cost, int32_t* status);
+
+/* ---- clearance-weighted cost fields ------------------------------------------------------------------
+ * The cost fields above with a per-cell entry cost: an inflation layer.  Paths keep their distance from obstacles where
+ * there is room and still pass where there is none, instead of scraping every corner (small r2_clear) or losing the
+ * narrow passages (large r2_clear).  DESIGN.md section 14.
+ *   Costmap: pen uint8 [G][H][W], indexed like d2: any entry cost of the caller's (clearance, terrain, traffic).  pen_cap
+ *     in 0..255; the effective penalty of cell c is min(pen[c], pen_cap).
+ *   Graph: that of the cost fields -- the same 8 moves in the same order, the same T(c) <=> d2[c] >= max(r2_clear, 1), the
+ *     same no-corner-cutting rule.  The move n -> c in direction d costs w_d + min(pen[c], pen_cap), w_d = 10 for d < 4
+ *     and 14 otherwise: the penalty is paid on entering a cell, and the root's own penalty is never paid.
+ *   Field: g[c] = the exact optimal cost from the root, SC_FIELD_INF when c is unreachable or not traversable; a bad
+ *     root as in sc_cost_field_batch.
+ *   Overflow contract: the device forms return SC_ERR_INVALID before any launch or allocation unless 0 <= pen_cap <= 255
+ *     and (14 + pen_cap) * (W*H - 1) <= INT32_MAX - 1 (64-bit arithmetic).  A simple path enters each cell at most once,
+ *     so every finite cost stays below SC_FIELD_INF: every cap passes up to 2048^2, caps up to 114 at 4096^2, up to 18 at
+ *     8192^2.  Inside a tile the kernels add at most the entry costs of 63 cells of a row to a value in uint32, and
+ *     INF + 63 * (10 + 255) < 2^32, so nothing wraps.
+ *   Parent rule: parent(c) = the smallest d such that n = c - (dx_d, dy_d), the move n -> c is legal and
+ *     g[n] + w_d + min(pen[c], pen_cap) == g[c].  Outputs, statuses, to_root, Lmax and truncation, qfield and fgrid out of
+ *     range: those of sc_field_paths_batch; cost[q] = g[target].
+ *   Asymmetry: the cost r -> t and the cost t -> r differ by pen[t] - pen[r] (each enters the other's end cell), and by
+ *     nothing else: the optimal cell sequences are the same reversed, so to_root keeps its meaning.
+ *   Anchor: with pen_cap == 0 (whatever pen holds) or pen all zero, g, fstatus and every read-out output are bit-identical
+ *     to sc_cost_field_batch / sc_field_paths_batch on the same inputs, hence equal to sc_astar_batch.
+ * sc_clearance_penalty_u8: the costmap from d2 [batch][H][W], integer arithmetic only.  thr = max(r2_clear, 1), isqrt =
+ *   the exact floor square root, s10 = isqrt(100 * r2_soft); pen[c] = 0 if d2[c] < thr or d2[c] >= r2_soft, else
+ *   (pen_max * (s10 - isqrt(100 * d2[c]))) / s10 (floor): it falls linearly with the distance, in tenths of a cell (the
+ *   unit of the 10 / 14 move costs), and reaches 0 at the soft radius.  SC_ERR_INVALID for pen_max outside 0..255,
+ *   r2_soft < 1, batch <= 0, W or H outside 1..SC_MAX_DIM, NULL pointers.  One kernel, timed as SC_K_MOVES.
+ * The device forms only enqueue (no host synchronisation, no device-to-host copy): sc_edt_u8_i32 ->
+ *   sc_clearance_penalty_u8 -> sc_cost_field_weighted_batch -> sc_field_paths_weighted_batch -> sc_path_waypoints_batch ->
+ *   sc_cells_to_points_batch -> sc_smooth_paths_batch runs on one stream.  Arguments, errors and scratch otherwise as
+ *   sc_cost_field_batch / sc_field_paths_batch (pen NULL: SC_ERR_INVALID); the _host forms copy pen as well.  The two
+ *   field entries are timed as SC_K_ASTAR. */
+int sc_clearance_penalty_u8(sc_ctx* ctx, const int32_t* d2, int W, int H, int batch, int32_t r2_clear, int32_t r2_soft, int pen_max,
+                            uint8_t* pen);
+int sc_clearance_penalty_u8_host(sc_ctx* ctx, const int32_t* d2, int W, int H, int batch, int32_t r2_clear, int32_t r2_soft,
+                                 int pen_max, uint8_t* pen);
+int sc_cost_field_weighted_batch(sc_ctx* ctx, const int32_t* d2, const uint8_t* pen, int pen_cap, int G, const int32_t* fgrid, int W,
+                                 int H, int32_t r2_clear, const int32_t* root, int F, int rounds, int32_t* g, int32_t* fstatus);
+int sc_cost_field_weighted_batch_host(sc_ctx* ctx, const int32_t* d2, const uint8_t* pen, int pen_cap, int G, const int32_t* fgrid,
+                                      int W, int H, int32_t r2_clear, const int32_t* root, int F, int rounds, int32_t* g,
+                                      int32_t* fstatus);
+int sc_field_paths_weighted_batch(sc_ctx* ctx, const int32_t* d2, const uint8_t* pen, int pen_cap, int G, const int32_t* fgrid, int W,
+                                  int H, int32_t r2_clear, const int32_t* g, const int32_t* root, int F, const int32_t* qfield,
+                                  const int32_t* target, int Q, int Lmax, int to_root, int32_t* path, int32_t* len, int32_t* cost,
+                                  int32_t* status);
+int sc_field_paths_weighted_batch_host(sc_ctx* ctx, const int32_t* d2, const uint8_t* pen, int pen_cap, int G, const int32_t* fgrid,
+                                       int W, int H, int32_t r2_clear, const int32_t* g, const int32_t* root, int F,
+                                       const int32_t* qfield, const int32_t* target, int Q, int Lmax, int to_root, int32_t* path,
+                                       int32_t* len, int32_t* cost, int32_t* status);
 
 /* ---- line-of-sight waypoints of A* paths ---------------------------------------------------------------
  * Shortcuts every cell path of sc_astar_batch to the cells where it has to turn, the short waypoint list the

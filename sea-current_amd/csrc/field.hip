@@ -18,6 +18,14 @@
 //   8 wavefronts claiming tiles from an LDS bitmap between barriers, until no tile is queued.  Values only fall and a tile
 //   is queued only when a value fell, so it terminates; what it returns is the unique fixed point.
 // Read-out: one wavefront per query walks the parent rule from the target, 32 x 32 cells of g at a time in LDS.
+//
+// Weighted fields (sc_cost_field_weighted_batch, sc_field_paths_weighted_batch): the move into cell
+// c costs w_d + min(pen[c], pen_cap).  The same kernels, built a second time with WEIGHTED = true: a visit also holds
+// its column's 64 capped penalties, four to a register; every move it relaxes enters one of its own cells, so it needs
+// no penalty of a halo cell.  The row closing becomes a min-scan over prefix sums of the entry costs (close_row).  The
+// unweighted builds take the `if constexpr` branches they always had.
+#include <type_traits>
+
 #include "sc_internal.h"
 
 namespace {
@@ -25,6 +33,7 @@ namespace {
 constexpr int FT = 64;                     // tile edge (= wavefront width: lane = column)
 constexpr uint32_t FINF = 0x7FFFFFFFu;     // SC_FIELD_INF; INF + 640 still fits in uint32, so sums need no saturation
 constexpr int FIN_WAVES = 8;               // wavefronts of a finisher workgroup
+constexpr int FIN_WAVES_W = 4;             // ... of the weighted finisher: its visit needs more than the 256 VGPRs 8 would leave
 constexpr int FIN_MAX_TILES = (SC_MAX_DIM / FT) * (SC_MAX_DIM / FT);
 constexpr int RP_WIN = 32;                 // read-out window edge
 constexpr int RP_WAVES = 4;
@@ -43,6 +52,11 @@ struct field_args {
     int32_t thr;
 };
 
+struct field_args_w : field_args {
+    const uint8_t* pen;      // [G][H][W] entry penalty of every cell
+    uint32_t cap;            // pen_cap
+};
+
 __device__ __forceinline__ uint32_t shup(uint32_t v, int s) { return (uint32_t)__shfl_up((int)v, s, 64); }
 __device__ __forceinline__ uint32_t shdn(uint32_t v, int s) { return (uint32_t)__shfl_down((int)v, s, 64); }
 __device__ __forceinline__ uint64_t shup64(uint64_t v) {
@@ -59,28 +73,58 @@ __device__ __forceinline__ bool tbit(uint64_t m, uint32_t ex, int y) {
 }
 
 // close row values v across the lanes: segmented min-plus scans left-to-right then right-to-left over runs of traversable
-// lanes (tmask = ballot of T in this row)
-__device__ __forceinline__ uint32_t close_row(uint32_t v, uint64_t tmask, bool tc, int lane) {
+// lanes (tmask = ballot of T in this row).
+// WEIGHTED: c = the entry cost 10 + penalty of this lane's cell.  Going right from k to x costs c[k+1] + .. + c[x] =
+// S[k] - S[x] with the suffix sums S[x] = c[x+1] + .. + c[63], so g'[x] = min over the run's k <= x of (g[k] + S[k]) - S[x];
+// going left costs Q[k] - Q[x] with the prefix sums Q[x] = c[0] + .. + c[x-1].  Both are min-scans with the shuffles of
+// the uniform form, and S, Q <= 63 * 265, so INF + S does not wrap.  k = x is in every minimum: a value never rises.
+template <bool WEIGHTED>
+__device__ __forceinline__ uint32_t close_row(uint32_t v, uint64_t tmask, bool tc, int lane, uint32_t c) {
     const uint64_t blocked = ~tmask;
     const uint64_t below = blocked & ((1ull << lane) - 1ull);
     const int rs = below ? 64 - __clzll((long long)below) : 0;
     const uint64_t above = lane == 63 ? 0ull : (blocked & (~0ull << (lane + 1)));
     const int re = above ? __ffsll((long long)above) - 2 : 63;
+    if constexpr (WEIGHTED) {
+        uint32_t P = c;                      // inclusive prefix sum of c over the 64 lanes
 #pragma unroll
-    for (int s = 1; s < 64; s <<= 1) {
-        const uint32_t o = shup(v, s) + 10u * s;
-        if (tc && lane - s >= rs) v = min(v, o);
-    }
+        for (int s = 1; s < 64; s <<= 1) {
+            const uint32_t o = shup(P, s);
+            if (lane >= s) P += o;
+        }
+        const uint32_t Q = P - c, S = rdl(P, 63) - P;
+        uint32_t u = v + S;
 #pragma unroll
-    for (int s = 1; s < 64; s <<= 1) {
-        const uint32_t o = shdn(v, s) + 10u * s;
-        if (tc && lane + s <= re) v = min(v, o);
+        for (int s = 1; s < 64; s <<= 1) {
+            const uint32_t o = shup(u, s);
+            if (tc && lane - s >= rs) u = min(u, o);
+        }
+        u = u - S + Q;
+#pragma unroll
+        for (int s = 1; s < 64; s <<= 1) {
+            const uint32_t o = shdn(u, s);
+            if (tc && lane + s <= re) u = min(u, o);
+        }
+        return u - Q;
+    } else {
+#pragma unroll
+        for (int s = 1; s < 64; s <<= 1) {
+            const uint32_t o = shup(v, s) + 10u * s;
+            if (tc && lane - s >= rs) v = min(v, o);
+        }
+#pragma unroll
+        for (int s = 1; s < 64; s <<= 1) {
+            const uint32_t o = shdn(v, s) + 10u * s;
+            if (tc && lane + s <= re) v = min(v, o);
+        }
+        return v;
     }
-    return v;
 }
 
+template <bool WEIGHTED>
 struct tile_state {
     uint32_t g[FT];          // column `lane`, rows 0..63
+    uint32_t pc[WEIGHTED ? FT / 4 : 1];   // WEIGHTED: the column's capped penalties, row y in byte y % 4 of pc[y / 4]
     uint64_t m, mL, mR;      // T of this column and of the columns to the left / right, rows 0..63
     uint32_t ex, exL, exR;   // the same for rows -1 and 64
     uint32_t gu, gd;         // g of rows -1 and 64 in this column
@@ -88,12 +132,14 @@ struct tile_state {
     uint64_t chg;            // rows changed in this visit
 };
 
-__device__ __forceinline__ uint32_t HL(const tile_state& s, int y) { return y + 1 < 64 ? rdl(s.hla, y + 1) : rdl(s.hlb, y - 63); }
-__device__ __forceinline__ uint32_t HR(const tile_state& s, int y) { return y + 1 < 64 ? rdl(s.hra, y + 1) : rdl(s.hrb, y - 63); }
+template <bool WT> __device__ __forceinline__ uint32_t HL(const tile_state<WT>& s, int y) { return y + 1 < 64 ? rdl(s.hla, y + 1) : rdl(s.hlb, y - 63); }
+template <bool WT> __device__ __forceinline__ uint32_t HR(const tile_state<WT>& s, int y) { return y + 1 < 64 ? rdl(s.hra, y + 1) : rdl(s.hrb, y - 63); }
 
 // one row step of a sweep: row y takes the moves from row yp = y -/+ 1, then closes; returns whether it changed.  Called
 // from fully unrolled loops only, so every g index is a constant and the column stays in registers.
-__device__ __forceinline__ bool row_step(tile_state& s, int y, int yp, int lane, bool force) {
+// WEIGHTED: every move here enters cell (lane, y), so the cheapest of them pays that cell's penalty once.
+template <bool WEIGHTED>
+__device__ __forceinline__ bool row_step(tile_state<WEIGHTED>& s, int y, int yp, int lane, bool force) {
     const uint32_t pv = yp < 0 ? s.gu : (yp >= FT ? s.gd : s.g[yp]);
     uint32_t pl = shup(pv, 1), pr = shdn(pv, 1);
     if (lane == 0) pl = HL(s, yp);
@@ -102,22 +148,48 @@ __device__ __forceinline__ bool row_step(tile_state& s, int y, int yp, int lane,
     const bool tl = tbit(s.mL, s.exL, y), tr = tbit(s.mR, s.exR, y);
     const uint32_t old = s.g[y];
     uint32_t v = old;
-    if (tc) {
-        v = min(v, pv + 10u);
-        if (tl && tcp) v = min(v, pl + 14u);
-        if (tr && tcp) v = min(v, pr + 14u);
-        if (lane == 0) v = min(v, HL(s, y) + 10u);
-        if (lane == 63) v = min(v, HR(s, y) + 10u);
+    uint32_t c = 10u;
+    if constexpr (WEIGHTED) {
+        const uint32_t p = (s.pc[y >> 2] >> (8 * (y & 3))) & 0xFFu;
+        c += p;
+        if (tc) {
+            uint32_t m = pv + 10u;
+            if (tl && tcp) m = min(m, pl + 14u);
+            if (tr && tcp) m = min(m, pr + 14u);
+            if (lane == 0) m = min(m, HL(s, y) + 10u);
+            if (lane == 63) m = min(m, HR(s, y) + 10u);
+            v = min(v, m + p);
+        }
+    } else {
+        if (tc) {
+            v = min(v, pv + 10u);
+            if (tl && tcp) v = min(v, pl + 14u);
+            if (tr && tcp) v = min(v, pr + 14u);
+            if (lane == 0) v = min(v, HL(s, y) + 10u);
+            if (lane == 63) v = min(v, HR(s, y) + 10u);
+        }
     }
-    if ((__ballot(v < old) != 0ull || force) && __ballot(v < FINF) != 0ull) v = close_row(v, __ballot(tc), tc, lane);
+    if ((__ballot(v < old) != 0ull || force) && __ballot(v < FINF) != 0ull) v = close_row<WEIGHTED>(v, __ballot(tc), tc, lane, c);
     s.g[y] = v;
     if (v < old) s.chg |= 1ull << y;
     return __ballot(v < old) != 0ull;
 }
 
-__device__ __forceinline__ bool sweep(tile_state& s, bool down, int lane, bool force) {
+// the weighted row step is past the size at which `#pragma unroll` still unrolls 64 of them, and a loop left standing
+// would index g dynamically and send it to scratch: its sweeps unroll by recursion instead
+template <int Y, bool DOWN>
+__device__ __forceinline__ void sweep_rows_w(tile_state<true>& s, int lane, bool force, bool& c) {
+    c |= row_step(s, Y, DOWN ? Y - 1 : Y + 1, lane, force);
+    if constexpr (DOWN ? Y + 1 < FT : Y > 0) sweep_rows_w<DOWN ? Y + 1 : Y - 1, DOWN>(s, lane, force, c);
+}
+
+template <bool WT>
+__device__ __forceinline__ bool sweep(tile_state<WT>& s, bool down, int lane, bool force) {
     bool c = false;
-    if (down) {
+    if constexpr (WT) {
+        if (down) sweep_rows_w<0, true>(s, lane, force, c);
+        else sweep_rows_w<FT - 1, false>(s, lane, force, c);
+    } else if (down) {
 #pragma unroll
         for (int y = 0; y < FT; ++y) c |= row_step(s, y, y - 1, lane, force);
     } else {
@@ -128,8 +200,8 @@ __device__ __forceinline__ bool sweep(tile_state& s, bool down, int lane, bool f
 }
 
 // Visit tile (tx, ty) of field f with one wavefront; mark(tx', ty') queues a neighbour (called by every lane, uniform).
-template <class Mark>
-__device__ __forceinline__ void visit_tile(const field_args& a, int f, int tx, int ty, Mark mark) {
+template <bool WEIGHTED, class Args, class Mark>
+__device__ __forceinline__ void visit_tile(const Args& a, int f, int tx, int ty, Mark mark) {
     const int lane = threadIdx.x & 63;
     const int W = a.W, H = a.H;
     const int gi = a.fgrid ? a.fgrid[f] : 0;
@@ -139,7 +211,7 @@ __device__ __forceinline__ void visit_tile(const field_args& a, int f, int tx, i
     const int tw = min(FT, W - x0), th = min(FT, H - y0);
     const int cx = x0 + lane;
     const bool colin = lane < tw;
-    tile_state s;
+    tile_state<WEIGHTED> s;
     s.m = colin ? M[(size_t)ty * W + cx] : 0ull;
     s.ex = 0;
     if (colin && ty > 0) s.ex |= (uint32_t)(M[(size_t)(ty - 1) * W + cx] >> 63);
@@ -166,6 +238,20 @@ __device__ __forceinline__ void visit_tile(const field_args& a, int f, int tx, i
         s.hra = (va && x0 + FT < W) ? (uint32_t)G[(size_t)ra * W + x0 + FT] : FINF;
         s.hlb = (vb && x0 > 0) ? (uint32_t)G[(size_t)rb * W + x0 - 1] : FINF;
         s.hrb = (vb && x0 + FT < W) ? (uint32_t)G[(size_t)rb * W + x0 + FT] : FINF;
+    }
+    if constexpr (WEIGHTED) {
+        const uint8_t* Pn = a.pen + (size_t)gi * W * H;
+#pragma unroll
+        for (int k = 0; k < FT / 4; ++k) {
+            uint32_t w = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int y = 4 * k + j;
+                const uint32_t b = (colin && y < th) ? min((uint32_t)Pn[(size_t)(y0 + y) * W + cx], a.cap) : 0u;
+                w |= b << (8 * j);
+            }
+            s.pc[k] = w;
+        }
     }
     s.chg = 0;
     // the root's tile starts with rows that are not closed (0 at the root, INF beside it): its first sweep closes every row
@@ -241,7 +327,8 @@ __global__ void field_init_kernel(field_args a, int32_t* fstatus) {
 }
 
 // chip-wide round r: one wavefront per queued (field, tile), grid-stride over the list
-__global__ __launch_bounds__(64) void field_round_kernel(field_args a, int r) {
+template <bool WEIGHTED>
+__global__ __launch_bounds__(64) void field_round_kernel(std::conditional_t<WEIGHTED, field_args_w, field_args> a, int r) {
     const int n = a.ctr[r];
     const int32_t* cur = a.list[r & 1];
     int32_t* nxt = a.list[(r + 1) & 1];
@@ -250,7 +337,7 @@ __global__ __launch_bounds__(64) void field_round_kernel(field_args a, int r) {
     for (int i = blockIdx.x; i < n; i += gridDim.x) {
         const int e = cur[i];
         const int f = e / a.nt, t = e % a.nt;
-        visit_tile(a, f, t % a.TX, t / a.TX, [&](int ux, int uy) {
+        visit_tile<WEIGHTED>(a, f, t % a.TX, t / a.TX, [&](int ux, int uy) {
             if (lane == 0) {
                 const int u = f * a.nt + uy * a.TX + ux;
                 if (atomicMax(a.stamp + u, r + 2) < r + 2) nxt[atomicAdd(nctr, 1)] = u;
@@ -260,7 +347,8 @@ __global__ __launch_bounds__(64) void field_round_kernel(field_args a, int r) {
 }
 
 // finisher: one workgroup per field completes the tiles still queued after `rounds` chip-wide rounds
-__global__ __launch_bounds__(64 * FIN_WAVES) void field_finish_kernel(field_args a, int rounds) {
+template <bool WEIGHTED, int WAVES>
+__global__ __launch_bounds__(64 * WAVES) void field_finish_kernel(std::conditional_t<WEIGHTED, field_args_w, field_args> a, int rounds) {
     __shared__ uint32_t dirty[FIN_MAX_TILES / 32];
     __shared__ uint16_t work[FIN_MAX_TILES];
     __shared__ int count;
@@ -292,9 +380,9 @@ __global__ __launch_bounds__(64 * FIN_WAVES) void field_finish_kernel(field_args
         __syncthreads();
         const int n = count;
         if (n == 0) break;
-        for (int i = wave; i < n; i += FIN_WAVES) {
+        for (int i = wave; i < n; i += WAVES) {
             const int t = work[i];
-            visit_tile(a, f, t % a.TX, t / a.TX, [&](int ux, int uy) {
+            visit_tile<WEIGHTED>(a, f, t % a.TX, t / a.TX, [&](int ux, int uy) {
                 if (lane == 0) {
                     const int u = uy * a.TX + ux;
                     atomicOr(&dirty[u >> 5], 1u << (u & 31));
@@ -318,15 +406,25 @@ struct paths_args {
     int32_t *path, *len, *cost, *status;
 };
 
+struct paths_args_w : paths_args {
+    const uint8_t* pen;
+    uint32_t cap;
+};
+
 __constant__ int RP_DX[8] = {1, -1, 0, 0, 1, -1, 1, -1};
 __constant__ int RP_DY[8] = {0, 0, 1, -1, 1, 1, -1, -1};
 
-__global__ __launch_bounds__(64 * RP_WAVES) void field_paths_kernel(paths_args a) {
+// WEIGHTED: a second window holds the capped penalties.  The step into the current cell c cost w_d + penalty(c), so the
+// parent test and the cost walked back both add the penalty of c.
+template <bool WEIGHTED>
+__global__ __launch_bounds__(64 * RP_WAVES) void field_paths_kernel(std::conditional_t<WEIGHTED, paths_args_w, paths_args> a) {
     __shared__ uint32_t win_all[RP_WAVES][RP_WIN * RP_WIN];
+    __shared__ uint8_t winp_all[WEIGHTED ? RP_WAVES : 1][WEIGHTED ? RP_WIN * RP_WIN : 1];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int q = blockIdx.x * RP_WAVES + wave;
     if (q >= a.Q) return;
     uint32_t* win = win_all[wave];
+    [[maybe_unused]] uint8_t* winp = winp_all[WEIGHTED ? wave : 0];
     const int W = a.W, H = a.H;
     const long long n = (long long)W * H;
     const int fq = a.qfield[q];
@@ -360,17 +458,26 @@ __global__ __launch_bounds__(64 * RP_WAVES) void field_paths_kernel(paths_args a
         for (int k = 0; k < RP_WIN * RP_WIN / 64; ++k) {
             const int i = k * 64 + lane, wx = ox + (i % RP_WIN), wy = oy + (i / RP_WIN);
             win[i] = (wx >= 0 && wx < W && wy >= 0 && wy < H) ? (uint32_t)G[(size_t)wy * W + wx] : FINF;
+            if constexpr (WEIGHTED)
+                winp[i] = (wx >= 0 && wx < W && wy >= 0 && wy < H)
+                              ? (uint8_t)min((uint32_t)a.pen[(size_t)gi * n + (size_t)wy * W + wx], a.cap) : (uint8_t)0;
         }
         wave_lds_sync();
         // parent rule inside the window (c and its 8 neighbours must lie in it)
         while (!(cx == rx && cy == ry) && cx - ox >= 1 && cx - ox <= RP_WIN - 2 && cy - oy >= 1 && cy - oy <= RP_WIN - 2) {
             const int lx = cx - ox, ly = cy - oy;
+            [[maybe_unused]] uint32_t pc = 0;
+            if constexpr (WEIGHTED) pc = winp[ly * RP_WIN + lx];
             int d = 0;
             for (; d < 8; ++d) {
                 const int px = cx - RP_DX[d], py = cy - RP_DY[d];
                 if (px < 0 || py < 0 || px >= W || py >= H) continue;
                 const uint32_t gp = win[(ly - RP_DY[d]) * RP_WIN + lx - RP_DX[d]];
-                if (gp >= FINF || gp + (d < 4 ? 10u : 14u) != gc) continue;
+                if constexpr (WEIGHTED) {
+                    if (gp >= FINF || gp + (d < 4 ? 10u : 14u) + pc != gc) continue;
+                } else {
+                    if (gp >= FINF || gp + (d < 4 ? 10u : 14u) != gc) continue;
+                }
                 // side cells of a diagonal: reachable <=> traversable next to a reachable cell
                 if (d >= 4 && (win[ly * RP_WIN + lx - RP_DX[d]] >= FINF || win[(ly - RP_DY[d]) * RP_WIN + lx] >= FINF)) continue;
                 break;
@@ -378,6 +485,7 @@ __global__ __launch_bounds__(64 * RP_WAVES) void field_paths_kernel(paths_args a
             if (d == 8 || L >= n) { fail = true; break; }
             cx -= RP_DX[d]; cy -= RP_DY[d];
             gc -= d < 4 ? 10u : 14u;
+            if constexpr (WEIGHTED) gc -= pc;
             if (lane == 0 && L < a.Lmax) P[L] = cy * W + cx;
             ++L;
         }
@@ -417,9 +525,15 @@ static bool field_paths_args_ok(const sc_ctx* ctx, const int32_t* d2, int G, con
            W <= SC_MAX_DIM && H <= SC_MAX_DIM && Q >= 0 && Lmax > 0 && (fgrid || G == 1);
 }
 
-extern "C" int sc_cost_field_batch(sc_ctx* ctx, const int32_t* d2, int G, const int32_t* fgrid, int W, int H, int32_t r2_clear,
-                                   const int32_t* root, int F, int rounds, int32_t* g, int32_t* fstatus) {
-    if (!cost_field_args_ok(ctx, d2, G, fgrid, W, H, root, F, g)) return SC_ERR_INVALID;
+// the overflow contract of the weighted entries: a simple path enters each of the other W*H - 1 cells at most once
+static bool weighted_args_ok(const uint8_t* pen, int pen_cap, int W, int H) {
+    if (!pen || pen_cap < 0 || pen_cap > 255) return false;
+    return (long long)(14 + pen_cap) * ((long long)W * H - 1) <= (long long)INT32_MAX - 1;
+}
+
+// both field entries; pen NULL: the unweighted kernels
+static int cost_field_launch(sc_ctx* ctx, const int32_t* d2, const uint8_t* pen, int pen_cap, int G, const int32_t* fgrid, int W, int H,
+                             int32_t r2_clear, const int32_t* root, int F, int rounds, int32_t* g, int32_t* fstatus) {
     SC_HIP(ctx, hipSetDevice(ctx->device));
     const int TX = (W + FT - 1) / FT, TY = (H + FT - 1) / FT, nt = TX * TY;
     if ((long long)F * nt > 0x7FFFFFFF / 2) return SC_ERR_INVALID;
@@ -431,7 +545,8 @@ extern "C" int sc_cost_field_batch(sc_ctx* ctx, const int32_t* d2, int G, const 
     if (r == SC_OK) r = sc_scratch_reserve(ctx, &ctx->fld_state, total);
     if (r != SC_OK) return r;
     char* b = (char*)ctx->fld_state.p;
-    field_args a;
+    field_args_w a;
+    a.pen = pen; a.cap = (uint32_t)pen_cap;
     a.mask = (const uint64_t*)ctx->fld_mask.p; a.d2 = d2; a.fgrid = fgrid; a.root = root; a.g = g;
     a.ok = (int32_t*)(b + o_ok); a.stamp = (int32_t*)(b + o_stamp);
     a.list[0] = (int32_t*)(b + o_l0); a.list[1] = (int32_t*)(b + o_l1); a.ctr = (int32_t*)(b + o_ctr);
@@ -449,7 +564,7 @@ extern "C" int sc_cost_field_batch(sc_ctx* ctx, const int32_t* d2, int G, const 
         const size_t n = (size_t)W * H;
         unsigned bx = (unsigned)((n + 1023) / 1024);
         if (bx > 1024) bx = 1024;
-        hipLaunchKernelGGL(field_init_kernel, dim3(bx, F < 65535 ? F : 65535), dim3(1024), 0, ctx->stream, a, fstatus);
+        hipLaunchKernelGGL(field_init_kernel, dim3(bx, F < 65535 ? F : 65535), dim3(1024), 0, ctx->stream, (field_args)a, fstatus);
     }
     if (rounds > 0) {
         if (!ctx->cu_count) {
@@ -459,12 +574,29 @@ extern "C" int sc_cost_field_batch(sc_ctx* ctx, const int32_t* d2, int G, const 
         }
         const long long cap = (long long)ctx->cu_count * 8;
         const unsigned blocks = (unsigned)((long long)F * nt < cap ? (long long)F * nt : cap);
-        for (int k = 0; k < rounds; ++k) hipLaunchKernelGGL(field_round_kernel, dim3(blocks), dim3(64), 0, ctx->stream, a, k);
+        for (int k = 0; k < rounds; ++k) {
+            if (pen) hipLaunchKernelGGL(field_round_kernel<true>, dim3(blocks), dim3(64), 0, ctx->stream, a, k);
+            else hipLaunchKernelGGL(field_round_kernel<false>, dim3(blocks), dim3(64), 0, ctx->stream, (field_args)a, k);
+        }
     }
-    hipLaunchKernelGGL(field_finish_kernel, dim3(F), dim3(64 * FIN_WAVES), 0, ctx->stream, a, rounds);
+    if (pen) hipLaunchKernelGGL((field_finish_kernel<true, FIN_WAVES_W>), dim3(F), dim3(64 * FIN_WAVES_W), 0, ctx->stream, a, rounds);
+    else hipLaunchKernelGGL((field_finish_kernel<false, FIN_WAVES>), dim3(F), dim3(64 * FIN_WAVES), 0, ctx->stream, (field_args)a, rounds);
     sc_time_end(ctx, tk);
     SC_HIP(ctx, hipGetLastError());
     return SC_OK;
+}
+
+extern "C" int sc_cost_field_batch(sc_ctx* ctx, const int32_t* d2, int G, const int32_t* fgrid, int W, int H, int32_t r2_clear,
+                                   const int32_t* root, int F, int rounds, int32_t* g, int32_t* fstatus) {
+    if (!cost_field_args_ok(ctx, d2, G, fgrid, W, H, root, F, g)) return SC_ERR_INVALID;
+    return cost_field_launch(ctx, d2, nullptr, 0, G, fgrid, W, H, r2_clear, root, F, rounds, g, fstatus);
+}
+
+extern "C" int sc_cost_field_weighted_batch(sc_ctx* ctx, const int32_t* d2, const uint8_t* pen, int pen_cap, int G, const int32_t* fgrid,
+                                            int W, int H, int32_t r2_clear, const int32_t* root, int F, int rounds, int32_t* g,
+                                            int32_t* fstatus) {
+    if (!cost_field_args_ok(ctx, d2, G, fgrid, W, H, root, F, g) || !weighted_args_ok(pen, pen_cap, W, H)) return SC_ERR_INVALID;
+    return cost_field_launch(ctx, d2, pen, pen_cap, G, fgrid, W, H, r2_clear, root, F, rounds, g, fstatus);
 }
 
 extern "C" int sc_field_paths_batch(sc_ctx* ctx, const int32_t* d2, int G, const int32_t* fgrid, int W, int H, int32_t r2_clear,
@@ -475,7 +607,27 @@ extern "C" int sc_field_paths_batch(sc_ctx* ctx, const int32_t* d2, int G, const
     SC_HIP(ctx, hipSetDevice(ctx->device));
     paths_args a{d2, fgrid, g, root, qfield, target, G, W, H, F, Q, Lmax, to_root ? 1 : 0, r2_clear > 1 ? r2_clear : 1, path, len, cost, status};
     int tk = sc_time_begin(ctx, SC_K_ASTAR);
-    hipLaunchKernelGGL(field_paths_kernel, dim3((unsigned)((Q + RP_WAVES - 1) / RP_WAVES)), dim3(64 * RP_WAVES), 0, ctx->stream, a);
+    hipLaunchKernelGGL(field_paths_kernel<false>, dim3((unsigned)((Q + RP_WAVES - 1) / RP_WAVES)), dim3(64 * RP_WAVES), 0, ctx->stream, a);
+    sc_time_end(ctx, tk);
+    SC_HIP(ctx, hipGetLastError());
+    return SC_OK;
+}
+
+extern "C" int sc_field_paths_weighted_batch(sc_ctx* ctx, const int32_t* d2, const uint8_t* pen, int pen_cap, int G, const int32_t* fgrid,
+                                             int W, int H, int32_t r2_clear, const int32_t* g, const int32_t* root, int F,
+                                             const int32_t* qfield, const int32_t* target, int Q, int Lmax, int to_root, int32_t* path,
+                                             int32_t* len, int32_t* cost, int32_t* status) {
+    if (!field_paths_args_ok(ctx, d2, G, fgrid, W, H, g, root, F, qfield, target, Q, Lmax, path, len, cost, status) ||
+        !weighted_args_ok(pen, pen_cap, W, H))
+        return SC_ERR_INVALID;
+    if (Q == 0) return SC_OK;
+    SC_HIP(ctx, hipSetDevice(ctx->device));
+    paths_args_w a;
+    (paths_args&)a = paths_args{d2, fgrid, g, root, qfield, target, G, W, H, F, Q, Lmax, to_root ? 1 : 0, r2_clear > 1 ? r2_clear : 1,
+                                path, len, cost, status};
+    a.pen = pen; a.cap = (uint32_t)pen_cap;
+    int tk = sc_time_begin(ctx, SC_K_ASTAR);
+    hipLaunchKernelGGL(field_paths_kernel<true>, dim3((unsigned)((Q + RP_WAVES - 1) / RP_WAVES)), dim3(64 * RP_WAVES), 0, ctx->stream, a);
     sc_time_end(ctx, tk);
     SC_HIP(ctx, hipGetLastError());
     return SC_OK;
@@ -516,5 +668,49 @@ extern "C" int sc_field_paths_batch_host(sc_ctx* ctx, const int32_t* d2, int G, 
         r = sc_field_paths_batch(ctx, st.dev<const int32_t>(i_d2), G, fgrid ? st.dev<const int32_t>(i_fg) : nullptr, W, H, r2_clear,
                                  st.dev<const int32_t>(i_g), st.dev<const int32_t>(i_rt), F, st.dev<const int32_t>(i_qf), st.dev<const int32_t>(i_t),
                                  Q, Lmax, to_root, st.dev<int32_t>(o_p), st.dev<int32_t>(o_len), st.dev<int32_t>(o_c), st.dev<int32_t>(o_s));
+    return st.finish(r);
+}
+
+extern "C" int sc_cost_field_weighted_batch_host(sc_ctx* ctx, const int32_t* d2, const uint8_t* pen, int pen_cap, int G, const int32_t* fgrid,
+                                                 int W, int H, int32_t r2_clear, const int32_t* root, int F, int rounds, int32_t* g,
+                                                 int32_t* fstatus) {
+    if (!cost_field_args_ok(ctx, d2, G, fgrid, W, H, root, F, g) || !weighted_args_ok(pen, pen_cap, W, H)) return SC_ERR_INVALID;
+    SC_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t n = (size_t)W * H, fb = (size_t)F * 4;
+    sc_stage st(ctx);
+    const int i_d2 = st.in(d2, (size_t)G * n * 4), i_pen = st.in(pen, (size_t)G * n), i_fg = st.in(fgrid, fb), i_rt = st.in(root, fb);
+    const int o_g = st.out(g, fb * n), o_st = st.out(fstatus, fb);
+    int r = st.upload();
+    if (r == SC_OK)
+        r = sc_cost_field_weighted_batch(ctx, st.dev<const int32_t>(i_d2), st.dev<const uint8_t>(i_pen), pen_cap, G,
+                                         fgrid ? st.dev<const int32_t>(i_fg) : nullptr, W, H, r2_clear, st.dev<const int32_t>(i_rt), F,
+                                         rounds, st.dev<int32_t>(o_g), st.dev<int32_t>(o_st));
+    return st.finish(r);
+}
+
+extern "C" int sc_field_paths_weighted_batch_host(sc_ctx* ctx, const int32_t* d2, const uint8_t* pen, int pen_cap, int G,
+                                                  const int32_t* fgrid, int W, int H, int32_t r2_clear, const int32_t* g, const int32_t* root,
+                                                  int F, const int32_t* qfield, const int32_t* target, int Q, int Lmax, int to_root,
+                                                  int32_t* path, int32_t* len, int32_t* cost, int32_t* status) {
+    if (!field_paths_args_ok(ctx, d2, G, fgrid, W, H, g, root, F, qfield, target, Q, Lmax, path, len, cost, status) ||
+        !weighted_args_ok(pen, pen_cap, W, H))
+        return SC_ERR_INVALID;
+    if (Q == 0) return SC_OK;
+    // data contract: every g value is a cost or SC_FIELD_INF
+    const size_t n = (size_t)W * H;
+    for (size_t i = 0; i < (size_t)F * n; ++i)
+        if (g[i] < 0) return SC_ERR_INVALID;
+    SC_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t fb = (size_t)F * 4, qb = (size_t)Q * 4;
+    sc_stage st(ctx);
+    const int i_d2 = st.in(d2, (size_t)G * n * 4), i_pen = st.in(pen, (size_t)G * n), i_fg = st.in(fgrid, fb), i_g = st.in(g, fb * n),
+              i_rt = st.in(root, fb), i_qf = st.in(qfield, qb), i_t = st.in(target, qb);
+    const int o_p = st.out(path, qb * Lmax), o_len = st.out(len, qb), o_c = st.out(cost, qb), o_s = st.out(status, qb);
+    int r = st.upload();
+    if (r == SC_OK)
+        r = sc_field_paths_weighted_batch(ctx, st.dev<const int32_t>(i_d2), st.dev<const uint8_t>(i_pen), pen_cap, G,
+                                          fgrid ? st.dev<const int32_t>(i_fg) : nullptr, W, H, r2_clear, st.dev<const int32_t>(i_g),
+                                          st.dev<const int32_t>(i_rt), F, st.dev<const int32_t>(i_qf), st.dev<const int32_t>(i_t), Q, Lmax,
+                                          to_root, st.dev<int32_t>(o_p), st.dev<int32_t>(o_len), st.dev<int32_t>(o_c), st.dev<int32_t>(o_s));
     return st.finish(r);
 }

@@ -1,6 +1,6 @@
 // moves.hip -- legal-move masks for A* (gfx950): one byte per cell, bit d set where the step in direction d is allowed.
 // A cell is traversable where the EDT's d2 (edt.hip) is at least the squared clearance asked for; a diagonal step also
-// needs both cells beside it.
+// needs both cells beside it.  Also the clearance penalty of the weighted cost fields (sc_clearance_penalty_u8).
 #include "sc_internal.h"
 
 __global__ void __launch_bounds__(256)
@@ -128,4 +128,55 @@ extern "C" int sc_moves_i32_u8(sc_ctx* ctx, const int32_t* d2, int W, int H, int
     if (!ctx || !d2 || !moves || W <= 0 || H <= 0 || W > SC_MAX_DIM || H > SC_MAX_DIM) return SC_ERR_INVALID;
     SC_HIP(ctx, hipSetDevice(ctx->device));
     return sc_launch_moves(ctx, d2, W, H, H, r2_clear, moves);
+}
+
+// ---- clearance penalty (costmap of sc_cost_field_weighted_batch) ----------------------------------------------------
+// exact floor square root: fp64 sqrt is within one of it for v < 2^53, integer compares settle the rest
+__host__ __device__ static inline int64_t isqrt64(int64_t v) {
+    int64_t r = (int64_t)sqrt((double)v);
+    while (r * r > v) --r;
+    while ((r + 1) * (r + 1) <= v) ++r;
+    return r;
+}
+
+// pen = pen_max * (s10 - isqrt(100 d2)) / s10 for thr <= d2 < r2_soft, 0 elsewhere; one thread per cell
+__global__ void __launch_bounds__(256)
+clearance_penalty_kernel(const int32_t* __restrict__ d2, size_t n, int32_t thr, int32_t r2_soft, int64_t s10, int pen_max,
+                         uint8_t* __restrict__ pen) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int32_t d = d2[i];
+    uint8_t p = 0;
+    if (d >= thr && d < r2_soft) p = (uint8_t)(((int64_t)pen_max * (s10 - isqrt64(100ll * d))) / s10);
+    pen[i] = p;
+}
+
+extern "C" int sc_clearance_penalty_u8(sc_ctx* ctx, const int32_t* d2, int W, int H, int batch, int32_t r2_clear, int32_t r2_soft,
+                                       int pen_max, uint8_t* pen) {
+    if (!ctx || !d2 || !pen || W <= 0 || H <= 0 || W > SC_MAX_DIM || H > SC_MAX_DIM || batch <= 0 || pen_max < 0 || pen_max > 255 ||
+        r2_soft < 1)
+        return SC_ERR_INVALID;
+    SC_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t n = (size_t)batch * W * H;
+    if ((n + 255) / 256 > 0x7FFFFFFFull) return SC_ERR_INVALID;
+    int tk = sc_time_begin(ctx, SC_K_MOVES);
+    hipLaunchKernelGGL(clearance_penalty_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d2, n,
+                       r2_clear > 1 ? r2_clear : 1, r2_soft, isqrt64(100ll * r2_soft), pen_max, pen);
+    sc_time_end(ctx, tk);
+    SC_HIP(ctx, hipGetLastError());
+    return SC_OK;
+}
+
+extern "C" int sc_clearance_penalty_u8_host(sc_ctx* ctx, const int32_t* d2, int W, int H, int batch, int32_t r2_clear, int32_t r2_soft,
+                                            int pen_max, uint8_t* pen) {
+    if (!ctx || !d2 || !pen || W <= 0 || H <= 0 || W > SC_MAX_DIM || H > SC_MAX_DIM || batch <= 0 || pen_max < 0 || pen_max > 255 ||
+        r2_soft < 1)
+        return SC_ERR_INVALID;
+    SC_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t n = (size_t)batch * W * H;
+    sc_stage st(ctx);
+    const int i_d2 = st.in(d2, n * 4), o_pen = st.out(pen, n);
+    int r = st.upload();
+    if (r == SC_OK) r = sc_clearance_penalty_u8(ctx, st.dev<const int32_t>(i_d2), W, H, batch, r2_clear, r2_soft, pen_max, st.dev<uint8_t>(o_pen));
+    return st.finish(r);
 }

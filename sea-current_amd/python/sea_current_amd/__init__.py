@@ -70,6 +70,14 @@ _SIGNATURES = {
     "sc_cost_field_batch_host": (_i, [_vp, _vp, _i, _vp, _i, _i, C.c_int32, _vp, _i, _i, _vp, _vp]),
     "sc_field_paths_batch": (_i, [_vp, _vp, _i, _vp, _i, _i, C.c_int32, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "sc_field_paths_batch_host": (_i, [_vp, _vp, _i, _vp, _i, _i, C.c_int32, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "sc_clearance_penalty_u8": (_i, [_vp, _vp, _i, _i, _i, C.c_int32, C.c_int32, _i, _vp]),
+    "sc_clearance_penalty_u8_host": (_i, [_vp, _vp, _i, _i, _i, C.c_int32, C.c_int32, _i, _vp]),
+    "sc_cost_field_weighted_batch": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, C.c_int32, _vp, _i, _i, _vp, _vp]),
+    "sc_cost_field_weighted_batch_host": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, C.c_int32, _vp, _i, _i, _vp, _vp]),
+    "sc_field_paths_weighted_batch": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, C.c_int32, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp,
+                                           _vp]),
+    "sc_field_paths_weighted_batch_host": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, C.c_int32, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp,
+                                                _vp, _vp]),
     "sc_toppra_hermite_batch": (_i, [_vp, _i, _i, _i] + [_vp] * 6 + [_i, _vp, _vp, _d, _d] + [_vp] * 5),
     "sc_toppra_hermite_batch_host": (_i, [_vp, _i, _i, _i] + [_vp] * 6 + [_i, _vp, _vp, _d, _d] + [_vp] * 5),
     "sc_toppra_sample_batch": (_i, [_vp, _i, _i, _i] + [_vp] * 6 + [_d, _i] + [_vp] * 5),
@@ -254,23 +262,39 @@ class Context:
                                               _ptr(out["path"]), _ptr(out["len"]), _ptr(out["cost"]), _ptr(out["status"])), "sc_astar_batch_multi")
         return out
 
-    def cost_fields(self, d2, roots, r2=0, fgrid=None, rounds=-1, out=None):
+    def clearance_penalty(self, d2, r2=0, r2_soft=36, pen_max=40, out=None):
+        """The costmap of the weighted cost fields from d2 (sc_clearance_penalty_u8): d2 int32 [H,W] or [G,H,W] on the GPU ->
+        uint8 of the same shape, pen_max next to the hard clearance falling linearly to 0 at distance sqrt(r2_soft)."""
+        import torch
+        G, H, W = (1,) + tuple(d2.shape) if d2.dim() == 2 else tuple(d2.shape)
+        if out is None:
+            out = torch.empty(tuple(d2.shape), dtype=torch.uint8, device=d2.device)
+        self._ck(self._l.sc_clearance_penalty_u8(self._h, _ptr(d2), W, H, G, r2, r2_soft, pen_max, _ptr(out)), "sc_clearance_penalty_u8")
+        return out
+
+    def cost_fields(self, d2, roots, r2=0, fgrid=None, rounds=-1, out=None, pen=None, pen_cap=255):
         """Cost-to-come fields (sc_cost_field_batch).  d2 int32 [H,W] or [G,H,W], roots int32 [F], fgrid int32 [F] (the grid
-        of every field; None only with one grid), all on the GPU.  Returns dict(g int32 [F,H,W], status int32 [F])."""
+        of every field; None only with one grid), all on the GPU.  Returns dict(g int32 [F,H,W], status int32 [F]).
+        pen (uint8, shaped like d2): the weighted fields (sc_cost_field_weighted_batch), entering cell c costs
+        min(pen[c], pen_cap) more."""
         import torch
         G, H, W = (1,) + tuple(d2.shape) if d2.dim() == 2 else tuple(d2.shape)
         F = roots.shape[0]
         dev = d2.device
         if out is None:
             out = dict(g=torch.empty((F, H, W), dtype=torch.int32, device=dev), status=torch.empty(F, dtype=torch.int32, device=dev))
+        if pen is not None:
+            self._ck(self._l.sc_cost_field_weighted_batch(self._h, _ptr(d2), _ptr(pen), pen_cap, G, _ptr(fgrid), W, H, r2, _ptr(roots), F,
+                                                          rounds, _ptr(out["g"]), _ptr(out["status"])), "sc_cost_field_weighted_batch")
+            return out
         self._ck(self._l.sc_cost_field_batch(self._h, _ptr(d2), G, _ptr(fgrid), W, H, r2, _ptr(roots), F, rounds, _ptr(out["g"]),
                                              _ptr(out["status"])), "sc_cost_field_batch")
         return out
 
-    def field_paths(self, d2, g, roots, qfield, targets, r2=0, Lmax=4096, to_root=False, fgrid=None, out=None):
+    def field_paths(self, d2, g, roots, qfield, targets, r2=0, Lmax=4096, to_root=False, fgrid=None, out=None, pen=None, pen_cap=255):
         """Paths read from cost fields (sc_field_paths_batch): query q follows field qfield[q] (g int32 [F,H,W] and roots [F]
         as cost_fields took and returned them) to targets[q].  Returns astar_batch's dict of GPU tensors; to_root=True
-        writes every path target..root."""
+        writes every path target..root.  pen, pen_cap: those cost_fields computed g with (sc_field_paths_weighted_batch)."""
         import torch
         G, H, W = (1,) + tuple(d2.shape) if d2.dim() == 2 else tuple(d2.shape)
         F = roots.shape[0]
@@ -279,6 +303,12 @@ class Context:
         if out is None:
             out = dict(path=torch.empty((Q, Lmax), dtype=torch.int32, device=dev), len=torch.empty(Q, dtype=torch.int32, device=dev),
                        cost=torch.empty(Q, dtype=torch.int32, device=dev), status=torch.empty(Q, dtype=torch.int32, device=dev))
+        if pen is not None:
+            self._ck(self._l.sc_field_paths_weighted_batch(self._h, _ptr(d2), _ptr(pen), pen_cap, G, _ptr(fgrid), W, H, r2, _ptr(g),
+                                                           _ptr(roots), F, _ptr(qfield), _ptr(targets), Q, Lmax, int(bool(to_root)),
+                                                           _ptr(out["path"]), _ptr(out["len"]), _ptr(out["cost"]), _ptr(out["status"])),
+                     "sc_field_paths_weighted_batch")
+            return out
         self._ck(self._l.sc_field_paths_batch(self._h, _ptr(d2), G, _ptr(fgrid), W, H, r2, _ptr(g), _ptr(roots), F, _ptr(qfield),
                                               _ptr(targets), Q, Lmax, int(bool(to_root)), _ptr(out["path"]), _ptr(out["len"]),
                                               _ptr(out["cost"]), _ptr(out["status"])), "sc_field_paths_batch")
@@ -751,7 +781,16 @@ class Context:
                                              _ptr(out["status"])), "sc_astar_batch_host")
         return out
 
-    def cost_fields_host(self, d2, roots, r2=0, fgrid=None, rounds=-1):
+    def clearance_penalty_host(self, d2, r2=0, r2_soft=36, pen_max=40):
+        """Host form of clearance_penalty (numpy in, numpy out)."""
+        d2 = np.ascontiguousarray(d2, dtype=np.int32)
+        G, H, W = (1,) + d2.shape if d2.ndim == 2 else d2.shape
+        out = np.zeros(d2.shape, np.uint8)
+        self._ck(self._l.sc_clearance_penalty_u8_host(self._h, _ptr(d2), W, H, G, r2, r2_soft, pen_max, _ptr(out)),
+                 "sc_clearance_penalty_u8_host")
+        return out
+
+    def cost_fields_host(self, d2, roots, r2=0, fgrid=None, rounds=-1, pen=None, pen_cap=255):
         """Host form of cost_fields (numpy in, numpy out)."""
         d2 = np.ascontiguousarray(d2, dtype=np.int32)
         roots = np.ascontiguousarray(roots, dtype=np.int32)
@@ -759,11 +798,17 @@ class Context:
         G, H, W = (1,) + d2.shape if d2.ndim == 2 else d2.shape
         F = roots.shape[0]
         out = dict(g=np.zeros((F, H, W), np.int32), status=np.zeros(F, np.int32))
+        if pen is not None:
+            pen = np.ascontiguousarray(pen, dtype=np.uint8)
+            self._ck(self._l.sc_cost_field_weighted_batch_host(self._h, _ptr(d2), _ptr(pen), pen_cap, G, _ptr(fgrid), W, H, r2, _ptr(roots),
+                                                               F, rounds, _ptr(out["g"]), _ptr(out["status"])),
+                     "sc_cost_field_weighted_batch_host")
+            return out
         self._ck(self._l.sc_cost_field_batch_host(self._h, _ptr(d2), G, _ptr(fgrid), W, H, r2, _ptr(roots), F, rounds, _ptr(out["g"]),
                                                   _ptr(out["status"])), "sc_cost_field_batch_host")
         return out
 
-    def field_paths_host(self, d2, g, roots, qfield, targets, r2=0, Lmax=4096, to_root=False, fgrid=None):
+    def field_paths_host(self, d2, g, roots, qfield, targets, r2=0, Lmax=4096, to_root=False, fgrid=None, pen=None, pen_cap=255):
         """Host form of field_paths (numpy in, numpy out)."""
         d2 = np.ascontiguousarray(d2, dtype=np.int32)
         g = np.ascontiguousarray(g, dtype=np.int32)
@@ -773,6 +818,13 @@ class Context:
         F, Q = roots.shape[0], targets.shape[0]
         out = dict(path=np.full((Q, Lmax), -1, dtype=np.int32), len=np.zeros(Q, np.int32), cost=np.zeros(Q, np.int32),
                    status=np.zeros(Q, np.int32))
+        if pen is not None:
+            pen = np.ascontiguousarray(pen, dtype=np.uint8)
+            self._ck(self._l.sc_field_paths_weighted_batch_host(self._h, _ptr(d2), _ptr(pen), pen_cap, G, _ptr(fgrid), W, H, r2, _ptr(g),
+                                                                _ptr(roots), F, _ptr(qfield), _ptr(targets), Q, Lmax, int(bool(to_root)),
+                                                                _ptr(out["path"]), _ptr(out["len"]), _ptr(out["cost"]),
+                                                                _ptr(out["status"])), "sc_field_paths_weighted_batch_host")
+            return out
         self._ck(self._l.sc_field_paths_batch_host(self._h, _ptr(d2), G, _ptr(fgrid), W, H, r2, _ptr(g), _ptr(roots), F, _ptr(qfield),
                                                    _ptr(targets), Q, Lmax, int(bool(to_root)), _ptr(out["path"]), _ptr(out["len"]),
                                                    _ptr(out["cost"]), _ptr(out["status"])), "sc_field_paths_batch_host")

@@ -24,6 +24,8 @@
 //   (new) smooth_paths_batch: from_path -> arclength -> gen_vel_prof<1> -> resample(nudge) -> ang_vel for many paths, one call
 //   (new) occupancy_grid::rasterize(obstacles, ctx), planning_space::make_grid(ctx): the polygon rasteriser on the GPU
 //   (new) occupancy_grid::cost_fields / field_paths, planning_space::plan_from / plan_to: one search per shared endpoint
+//   (new) occupancy_grid::clearance_penalty, cost_fields / field_paths with a costmap, planning_space::soft_clearance /
+//         soft_penalty: clearance-weighted cost fields (an inflation layer) behind plan_from / plan_to
 //
 // Differences that are deliberate: obstacle::closed is initialised (the reference leaves it
 // uninitialised, :197); library code never prints or calls std::exit (SC_ASSERT throws in DEBUG);
@@ -407,6 +409,8 @@ public:
     struct field_result {
         std::vector<int32_t> g, status, roots;  // g is [F][H][W]
         int32_t r2 = 0;
+        std::vector<uint8_t> pen;               // the costmap of a weighted field ([H][W]), empty for an unweighted one:
+        int pen_cap = 0;                        // field_paths reads a field with what cost_fields computed it with
     };
     field_result cost_fields(const std::vector<int32_t>& roots, int32_t r2_clear = 0, int rounds = -1,
                              gpu_context& ctx = default_context()) {
@@ -422,8 +426,37 @@ public:
                   "sc_cost_field_batch_host");
         return r;
     }
+    // The costmap of the weighted fields from d2 (sc_clearance_penalty_u8): pen_max next to the hard clearance r2_clear,
+    // falling linearly with the distance to 0 at sqrt(r2_soft) cells.
+    std::vector<uint8_t> clearance_penalty(int32_t r2_clear, int32_t r2_soft, int pen_max, gpu_context& ctx = default_context()) {
+        if (d2.size() != occ.size()) edt(ctx);
+        std::vector<uint8_t> pen(occ.size(), 0);
+        ctx.check(sc_clearance_penalty_u8_host(ctx.get(), d2.data(), W, H, 1, r2_clear, r2_soft, pen_max, pen.data()),
+                  "sc_clearance_penalty_u8_host");
+        return pen;
+    }
+    // Weighted cost fields (sc_cost_field_weighted_batch): entering cell c costs min(pen[c], pen_cap) on top of the 10 / 14
+    // of the move; pen is [H][W].  The result remembers pen and pen_cap for field_paths.
+    field_result cost_fields(const std::vector<int32_t>& roots, const std::vector<uint8_t>& pen, int pen_cap, int32_t r2_clear = 0,
+                             int rounds = -1, gpu_context& ctx = default_context()) {
+        if (d2.size() != occ.size()) edt(ctx);
+        if (pen.size() != occ.size()) throw std::invalid_argument("occupancy_grid::cost_fields: pen is not [H][W]");
+        field_result r;
+        const int F = (int)roots.size();
+        r.roots = roots;
+        r.r2 = r2_clear;
+        r.pen = pen;
+        r.pen_cap = pen_cap;
+        r.g.assign((size_t)F * W * H, SC_FIELD_INF); r.status.assign(F, SC_Q_BAD_ENDPOINT);
+        if (F == 0) return r;
+        ctx.check(sc_cost_field_weighted_batch_host(ctx.get(), d2.data(), pen.data(), pen_cap, 1, nullptr, W, H, r2_clear, roots.data(), F,
+                                                    rounds, r.g.data(), r.status.data()),
+                  "sc_cost_field_weighted_batch_host");
+        return r;
+    }
     // Paths read from fields (sc_field_paths_batch): query q follows field qfield[q] to targets[q].  Equal to astar_batch
-    // with start roots[qfield[q]] and goal targets[q] (to_root = false), or to its paths reversed (to_root = true).
+    // with start roots[qfield[q]] and goal targets[q] (to_root = false), or to its paths reversed (to_root = true).  A
+    // weighted field is read with its own costmap (sc_field_paths_weighted_batch).
     batch_result field_paths(const field_result& fr, const std::vector<int32_t>& qfield, const std::vector<int32_t>& targets,
                              int Lmax = 0, bool to_root = false, gpu_context& ctx = default_context()) {
         if (d2.size() != occ.size()) edt(ctx);
@@ -434,6 +467,13 @@ public:
         r.path.assign((size_t)Q * r.Lmax, -1); r.len.assign(Q, 0); r.cost.assign(Q, -1); r.status.assign(Q, SC_Q_NO_PATH);
         if (Q == 0) return r;
         if (F == 0) { r.status.assign(Q, SC_Q_BAD_ENDPOINT); return r; }
+        if (!fr.pen.empty()) {
+            ctx.check(sc_field_paths_weighted_batch_host(ctx.get(), d2.data(), fr.pen.data(), fr.pen_cap, 1, nullptr, W, H, fr.r2, fr.g.data(),
+                                                         fr.roots.data(), F, qfield.data(), targets.data(), Q, r.Lmax, to_root ? 1 : 0,
+                                                         r.path.data(), r.len.data(), r.cost.data(), r.status.data()),
+                      "sc_field_paths_weighted_batch_host");
+            return r;
+        }
         ctx.check(sc_field_paths_batch_host(ctx.get(), d2.data(), 1, nullptr, W, H, fr.r2, fr.g.data(), fr.roots.data(), F, qfield.data(),
                                             targets.data(), Q, r.Lmax, to_root ? 1 : 0, r.path.data(), r.len.data(), r.cost.data(),
                                             r.status.data()),
@@ -518,6 +558,13 @@ public:
     halton_state y_state;
     int grid_cells = 256;       // cells along the longer side of bound_rect (new knob)
     float clearance = 0.0f;     // required obstacle clearance in world units (new knob)
+    // (new knobs, off by default) a soft margin for plan_from / plan_to: when both are positive, cells closer to an obstacle
+    // than soft_clearance (world units, converted like clearance) cost up to soft_penalty more to enter (tenths of a cell
+    // of detour; occupancy_grid::clearance_penalty), so paths keep their distance where there is room and still pass where
+    // there is none.  plan_batch and fast_marching_trees (A*) are unchanged: they minimise length only.  simplify_paths
+    // shortcuts by visibility under the hard clearance only, so it can straighten a path back towards a wall.
+    float soft_clearance = 0.0f;
+    int soft_penalty = 0;
     // (new knob) plan_batch / fast_marching_trees return the exact start, the centres of the path's line-of-sight waypoints
     // (occupancy_grid::waypoints_batch) and the exact goal instead of every cell centre: the short, non-collinear list the
     // reference's planner hands to bezier_spline::from_path (examples/test.cpp:284 -> :300).  Limits:
@@ -667,7 +714,7 @@ public:
         std::vector<int32_t> t(goals.size()), qf(goals.size(), 0);
         for (size_t i = 0; i < goals.size(); ++i) t[i] = g.cell_of(goals[i]);
         const int32_t r2 = clearance_r2(g);
-        auto fr = g.cost_fields({g.cell_of(start)}, r2, -1, ctx);
+        auto fr = fields_of(g, g.cell_of(start), r2, ctx);
         auto br = g.field_paths(fr, qf, t, 0, false, ctx);
         return to_points(g, br, r2, std::vector<Vector2f>(goals.size(), start), goals, "plan_from", ctx);
     }
@@ -681,7 +728,7 @@ public:
         std::vector<int32_t> s(starts.size()), qf(starts.size(), 0);
         for (size_t i = 0; i < starts.size(); ++i) s[i] = g.cell_of(starts[i]);
         const int32_t r2 = clearance_r2(g);
-        auto fr = g.cost_fields({g.cell_of(goal)}, r2, -1, ctx);
+        auto fr = fields_of(g, g.cell_of(goal), r2, ctx);
         auto br = g.field_paths(fr, qf, s, 0, true, ctx);
         return to_points(g, br, r2, starts, std::vector<Vector2f>(starts.size(), goal), "plan_to", ctx);
     }
@@ -690,6 +737,14 @@ private:
     int32_t clearance_r2(const occupancy_grid& g) const {
         const float cc = clearance / g.resolution;
         return (int32_t)std::ceil(cc * cc);
+    }
+    // the field of plan_from / plan_to: weighted when both soft knobs are positive, else today's
+    occupancy_grid::field_result fields_of(occupancy_grid& g, int32_t root, int32_t r2, gpu_context& ctx) const {
+        if (!(soft_clearance > 0.0f && soft_penalty > 0)) return g.cost_fields({root}, r2, -1, ctx);
+        const float sc = soft_clearance / g.resolution;
+        const int32_t r2_soft = std::max((int32_t)std::ceil(sc * sc), (int32_t)1);
+        const int pen_max = std::min(soft_penalty, 255);
+        return g.cost_fields({root}, g.clearance_penalty(r2, r2_soft, pen_max, ctx), pen_max, r2, -1, ctx);
     }
     // cell paths (astar_batch's layout) -> the exact endpoints around the centres of the interior cells or waypoints
     std::vector<std::optional<std::vector<Vector2f>>> to_points(occupancy_grid& g, const occupancy_grid::batch_result& br, int32_t r2,
