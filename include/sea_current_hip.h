@@ -57,7 +57,8 @@ typedef enum {
 typedef enum {
     SC_K_EDT_COLBITS = 0, /* occupancy bytes -> transposed per-band column bit words */
     SC_K_EDT_BAND = 1,    /* per 32-row band: vertical distances + exact row envelope -> d2 */
-    SC_K_MOVES = 2,       /* d2 + clearance -> legal-move byte per cell; also sc_clearance_penalty_u8 */
+    SC_K_MOVES = 2,       /* d2 + clearance -> legal-move byte per cell; also sc_clearance_penalty_u8, sc_components_batch,
+                           * sc_reachable_batch */
     SC_K_ASTAR = 3,       /* batched A*: two wavefronts per query (prep + search + retry launches); also the cost fields and
                            * their read-out (sc_cost_field_batch, sc_field_paths_batch and the weighted forms) */
     SC_K_TOPPRA = 4,      /* batched TOPP-RA: computeParams + backward + forward sweep */
@@ -304,6 +305,50 @@ int sc_field_paths_weighted_batch_host(sc_ctx* ctx, const int32_t* d2, const uin
                                        int W, int H, int32_t r2_clear, const int32_t* g, const int32_t* root, int F,
                                        const int32_t* qfield, const int32_t* target, int Q, int Lmax, int to_root, int32_t* path,
                                        int32_t* len, int32_t* cost, int32_t* status);
+
+/* ---- free-space components ---------------------------------------------------------------------------
+ * Labels the connected components of the traversable cells once, so that "is there a path from a to b" is answered
+ * without searching, connected start and goal cells can be handed out, and a hopeless query is refused in O(1) instead
+ * of expanding the start's whole component.  DESIGN.md section 15.
+ *   Definition: T(c) <=> d2[c] >= max(r2_clear, 1).  Two traversable cells are in one component iff a chain of orthogonal
+ *     moves through traversable cells joins them.  label[c] = the smallest linear index y*W + x of c's component, -1
+ *     where c is not traversable: unique and independent of any execution order.
+ *   This is exactly A*'s reachability: a diagonal move needs both orthogonal side cells traversable, so it can always be
+ *     replaced by two orthogonal moves, and 8-connected reachability under the no-corner-cutting rule equals 4-connected
+ *     reachability.  Two traversable cells have a path (SC_Q_OK or SC_Q_TRUNCATED from sc_astar_batch) iff their labels
+ *     are equal.
+ * sc_components_batch: d2 and label int32 [G][H][W].  size, ncomp and largest may each be NULL.  size int32 [G][H][W]:
+ *   the cell count of the component at its representative cell (label[c] == c), 0 everywhere else.  ncomp int32 [G]: the
+ *   number of components.  largest int32 [G]: the representative of the largest component, ties going to the smaller
+ *   index, -1 on a grid with no traversable cell.  Integer atomics only; every output is independent of execution order.
+ *   A constant number of kernels (at most five) and no host synchronisation.  Timed as SC_K_MOVES.  Scratch: G * 8 B, plus
+ *   G * W * H * 4 B when largest is asked for without size; grows only.
+ * sc_reachable_batch: status[q] = SC_Q_BAD_ENDPOINT if start[q] or goal[q] is out of range, qgrid[q] is out of range or a
+ *   label is negative; SC_Q_NO_PATH if the labels differ; SC_Q_OK otherwise -- the status sc_astar_batch returns for the
+ *   same query, SC_Q_OK standing for both SC_Q_OK and SC_Q_TRUNCATED.  qgrid int32 [Q] may be NULL only when G == 1.  One
+ *   kernel, timed as SC_K_MOVES.
+ * sc_astar_batch_screened: sc_astar_batch_multi (sc_astar_batch when G == 1 and qgrid is NULL) that never searches a query
+ *   whose endpoints lie in different components.  status, len, cost, and path wherever status is SC_Q_OK, are bit-identical
+ *   to the unscreened call on the same inputs.  label must be what sc_components_batch wrote for the same d2 and r2_clear
+ *   (the contract of g in sc_field_paths_batch).  A kernel writes the starts into context scratch with -1 where the labels
+ *   differ, the unscreened entry runs on those (such a query leaves at once as a bad endpoint: len 0, cost -1), a second
+ *   kernel sets their status to SC_Q_NO_PATH.  Only enqueues, like the call it wraps; timed as SC_K_ASTAR.
+ *   sc_astar_last_expansions then counts only the searches that ran.  Scratch: Q * 4 B on top of the search's.
+ * All three device forms only enqueue: sc_edt_u8_i32 -> sc_components_batch -> sc_astar_batch_screened ->
+ *   sc_path_waypoints_batch runs on one stream.
+ * Errors: SC_ERR_INVALID for NULL pointers (other than the optional ones), W or H outside 1..SC_MAX_DIM, G <= 0, Q < 0,
+ *   Lmax <= 0.  Q == 0 is a no-op.  The _host forms take host pointers, copy, run, copy back and synchronise. */
+int sc_components_batch(sc_ctx* ctx, const int32_t* d2, int G, int W, int H, int32_t r2_clear, int32_t* label, int32_t* size,
+                        int32_t* ncomp, int32_t* largest);
+int sc_components_batch_host(sc_ctx* ctx, const int32_t* d2, int G, int W, int H, int32_t r2_clear, int32_t* label, int32_t* size,
+                             int32_t* ncomp, int32_t* largest);
+int sc_reachable_batch(sc_ctx* ctx, const int32_t* label, int G, const int32_t* qgrid, int W, int H, const int32_t* start,
+                       const int32_t* goal, int Q, int32_t* status);
+int sc_reachable_batch_host(sc_ctx* ctx, const int32_t* label, int G, const int32_t* qgrid, int W, int H, const int32_t* start,
+                            const int32_t* goal, int Q, int32_t* status);
+int sc_astar_batch_screened(sc_ctx* ctx, const int32_t* d2, const int32_t* label, int G, const int32_t* qgrid, int W, int H,
+                            int32_t r2_clear, const int32_t* start, const int32_t* goal, int Q, int Lmax, int32_t* path, int32_t* len,
+                            int32_t* cost, int32_t* status);
 
 /* ---- line-of-sight waypoints of A* paths ---------------------------------------------------------------
  * Shortcuts every cell path of sc_astar_batch to the cells where it has to turn, the short waypoint list the

@@ -66,7 +66,9 @@ struct __attribute__((visibility("hidden"))) sc_ctx {
     sc_scratch occ_prep;    // polygon occupancy: float4 box [n_obs] | int2 cell-row range [n_obs] of every obstacle
     sc_scratch fld_mask;    // cost fields: uint64 [G][tile rows][W] traversability of 64 rows per column
     sc_scratch fld_state;   // cost fields: per-field ok [F] | tile stamps [F][tiles] | two tile lists [F * tiles] | round counts
-    int astar_cap = 1 << 16;          // ring entries per bucket (power of two)
+    sc_scratch cmp_state;   // components: int32 [G][H][W] sizes when the caller passes none | uint64 [G] largest keys
+    sc_scratch cmp_start;   // screened A*: int32 [Q] the starts, -1 where the endpoints lie in different components
+    int astar_cap = 1 << 16;         // ring entries per bucket (power of two)
     size_t astar_slot_budget = (size_t)96 << 30;  // bytes of g + bitmap + ring scratch this context may take (SC_ASTAR_SLOT_GB), further bounded by what the device has free; 4096^2: 96 GiB = 1966 slots measured best (48: -34 %, 160: -17 %)
     int last_Q = 0;
     void* comm = nullptr;           // ncclComm_t of sc_allgather_paths

@@ -78,6 +78,11 @@ _SIGNATURES = {
                                            _vp]),
     "sc_field_paths_weighted_batch_host": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, C.c_int32, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp,
                                                 _vp, _vp]),
+    "sc_components_batch": (_i, [_vp, _vp, _i, _i, _i, C.c_int32, _vp, _vp, _vp, _vp]),
+    "sc_components_batch_host": (_i, [_vp, _vp, _i, _i, _i, C.c_int32, _vp, _vp, _vp, _vp]),
+    "sc_reachable_batch": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _vp, _i, _vp]),
+    "sc_reachable_batch_host": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _vp, _i, _vp]),
+    "sc_astar_batch_screened": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, C.c_int32, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "sc_toppra_hermite_batch": (_i, [_vp, _i, _i, _i] + [_vp] * 6 + [_i, _vp, _vp, _d, _d] + [_vp] * 5),
     "sc_toppra_hermite_batch_host": (_i, [_vp, _i, _i, _i] + [_vp] * 6 + [_i, _vp, _vp, _d, _d] + [_vp] * 5),
     "sc_toppra_sample_batch": (_i, [_vp, _i, _i, _i] + [_vp] * 6 + [_d, _i] + [_vp] * 5),
@@ -234,8 +239,10 @@ class Context:
         self._ck(self._l.sc_moves_i32_u8(self._h, _ptr(d2), W, H, r2, _ptr(out)), "sc_moves_i32_u8")
         return out
 
-    def astar_batch(self, d2, start, goal, r2=0, Lmax=4096, out=None):
-        """d2 int32 [H,W]; start/goal int32 [Q] (GPU).  Returns dict of GPU tensors."""
+    def astar_batch(self, d2, start, goal, r2=0, Lmax=4096, out=None, label=None):
+        """d2 int32 [H,W]; start/goal int32 [Q] (GPU).  Returns dict of GPU tensors.  label (int32 [H,W], what components
+        returned for the same d2 and r2): the screened search (sc_astar_batch_screened), the same results without searching
+        the queries whose endpoints lie in different components."""
         import torch
         H, W = d2.shape
         Q = start.shape[0]
@@ -244,13 +251,19 @@ class Context:
                        len=torch.empty(Q, dtype=torch.int32, device=d2.device),
                        cost=torch.empty(Q, dtype=torch.int32, device=d2.device),
                        status=torch.empty(Q, dtype=torch.int32, device=d2.device))
+        if label is not None:
+            self._ck(self._l.sc_astar_batch_screened(self._h, _ptr(d2), _ptr(label), 1, None, W, H, r2, _ptr(start), _ptr(goal), Q, Lmax,
+                                                     _ptr(out["path"]), _ptr(out["len"]), _ptr(out["cost"]), _ptr(out["status"])),
+                     "sc_astar_batch_screened")
+            return out
         self._ck(self._l.sc_astar_batch(self._h, _ptr(d2), W, H, r2, _ptr(start), _ptr(goal), Q, Lmax,
                                         _ptr(out["path"]), _ptr(out["len"]), _ptr(out["cost"]), _ptr(out["status"])),
                  "sc_astar_batch")
         return out
 
-    def astar_batch_multi(self, d2, qgrid, start, goal, r2=0, Lmax=4096, out=None):
-        """Several grids in one launch: d2 int32 [G,H,W], qgrid int32 [Q] (grid of every query), start/goal int32 [Q]."""
+    def astar_batch_multi(self, d2, qgrid, start, goal, r2=0, Lmax=4096, out=None, label=None):
+        """Several grids in one launch: d2 int32 [G,H,W], qgrid int32 [Q] (grid of every query), start/goal int32 [Q].
+        label (int32 [G,H,W] from components): the screened search, as in astar_batch."""
         import torch
         G, H, W = d2.shape
         Q = start.shape[0]
@@ -258,9 +271,43 @@ class Context:
         if out is None:
             out = dict(path=torch.empty((Q, Lmax), dtype=torch.int32, device=dev), len=torch.empty(Q, dtype=torch.int32, device=dev),
                        cost=torch.empty(Q, dtype=torch.int32, device=dev), status=torch.empty(Q, dtype=torch.int32, device=dev))
+        if label is not None:
+            self._ck(self._l.sc_astar_batch_screened(self._h, _ptr(d2), _ptr(label), G, _ptr(qgrid), W, H, r2, _ptr(start), _ptr(goal), Q,
+                                                     Lmax, _ptr(out["path"]), _ptr(out["len"]), _ptr(out["cost"]), _ptr(out["status"])),
+                     "sc_astar_batch_screened")
+            return out
         self._ck(self._l.sc_astar_batch_multi(self._h, _ptr(d2), G, _ptr(qgrid), W, H, r2, _ptr(start), _ptr(goal), Q, Lmax,
                                               _ptr(out["path"]), _ptr(out["len"]), _ptr(out["cost"]), _ptr(out["status"])), "sc_astar_batch_multi")
         return out
+
+    def components(self, d2, r2=0, want_size=False, out=None):
+        """Connected components of the traversable cells (sc_components_batch).  d2 int32 [H,W] or [G,H,W] on the GPU.
+        Returns dict(label int32 shaped like d2: the smallest cell index of the cell's component, -1 where it is not
+        traversable; size int32 shaped like d2 (the cell count at every representative, 0 elsewhere) or None without
+        want_size; ncomp int32 [G]; largest int32 [G], -1 on a grid without a traversable cell).  `out`: the dict of an
+        earlier call with the same shapes, reused.  Only enqueues."""
+        import torch
+        G, H, W = (1,) + tuple(d2.shape) if d2.dim() == 2 else tuple(d2.shape)
+        dev = d2.device
+        if out is None:
+            out = dict(label=torch.empty(tuple(d2.shape), dtype=torch.int32, device=dev),
+                       size=torch.empty(tuple(d2.shape), dtype=torch.int32, device=dev) if want_size else None,
+                       ncomp=torch.empty(G, dtype=torch.int32, device=dev), largest=torch.empty(G, dtype=torch.int32, device=dev))
+        self._ck(self._l.sc_components_batch(self._h, _ptr(d2), G, W, H, r2, _ptr(out["label"]), _ptr(out.get("size")), _ptr(out["ncomp"]),
+                                             _ptr(out["largest"])), "sc_components_batch")
+        return out
+
+    def reachable(self, label, start, goal, qgrid=None):
+        """The status astar_batch would give every query, from the labels alone (sc_reachable_batch): label int32 [H,W] or
+        [G,H,W] from components, start / goal int32 [Q], qgrid int32 [Q] (None only with one grid), on the GPU.  Returns
+        int32 [Q]: Q_BAD_ENDPOINT, Q_NO_PATH, or Q_OK where A* returns Q_OK or Q_TRUNCATED."""
+        import torch
+        G, H, W = (1,) + tuple(label.shape) if label.dim() == 2 else tuple(label.shape)
+        Q = start.shape[0]
+        status = torch.empty(Q, dtype=torch.int32, device=label.device)
+        self._ck(self._l.sc_reachable_batch(self._h, _ptr(label), G, _ptr(qgrid), W, H, _ptr(start), _ptr(goal), Q, _ptr(status)),
+                 "sc_reachable_batch")
+        return status
 
     def clearance_penalty(self, d2, r2=0, r2_soft=36, pen_max=40, out=None):
         """The costmap of the weighted cost fields from d2 (sc_clearance_penalty_u8): d2 int32 [H,W] or [G,H,W] on the GPU ->
@@ -780,6 +827,29 @@ class Context:
                                              _ptr(out["path"]), _ptr(out["len"]), _ptr(out["cost"]),
                                              _ptr(out["status"])), "sc_astar_batch_host")
         return out
+
+    def components_host(self, d2, r2=0, want_size=False):
+        """Host form of components (numpy in, numpy out)."""
+        d2 = np.ascontiguousarray(d2, dtype=np.int32)
+        G, H, W = (1,) + d2.shape if d2.ndim == 2 else d2.shape
+        out = dict(label=np.zeros(d2.shape, np.int32), size=np.zeros(d2.shape, np.int32) if want_size else None,
+                   ncomp=np.zeros(G, np.int32), largest=np.zeros(G, np.int32))
+        self._ck(self._l.sc_components_batch_host(self._h, _ptr(d2), G, W, H, r2, _ptr(out["label"]), _ptr(out["size"]), _ptr(out["ncomp"]),
+                                                  _ptr(out["largest"])), "sc_components_batch_host")
+        return out
+
+    def reachable_host(self, label, start, goal, qgrid=None):
+        """Host form of reachable (numpy in, numpy out)."""
+        label = np.ascontiguousarray(label, dtype=np.int32)
+        start = np.ascontiguousarray(start, dtype=np.int32)
+        goal = np.ascontiguousarray(goal, dtype=np.int32)
+        qgrid = None if qgrid is None else np.ascontiguousarray(qgrid, dtype=np.int32)
+        G, H, W = (1,) + label.shape if label.ndim == 2 else label.shape
+        Q = start.shape[0]
+        status = np.zeros(Q, np.int32)
+        self._ck(self._l.sc_reachable_batch_host(self._h, _ptr(label), G, _ptr(qgrid), W, H, _ptr(start), _ptr(goal), Q, _ptr(status)),
+                 "sc_reachable_batch_host")
+        return status
 
     def clearance_penalty_host(self, d2, r2=0, r2_soft=36, pen_max=40):
         """Host form of clearance_penalty (numpy in, numpy out)."""

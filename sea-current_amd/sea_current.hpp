@@ -404,6 +404,57 @@ public:
                                       r.path.data(), r.len.data(), r.cost.data(), r.status.data()), "sc_astar_batch_host");
         return r;
     }
+    // Connected components of the traversable cells (sc_components_batch): label[c] = the smallest cell index of c's
+    // component, -1 where d2[c] < max(r2_clear, 1); size[c] = the cell count at every representative (label[c] == c), 0
+    // elsewhere; ncomp components; largest = the representative of the largest one (ties to the smaller index), -1 when no
+    // cell is traversable.  Two traversable cells have an A* path iff their labels are equal.
+    struct component_result {
+        std::vector<int32_t> label, size;  // [H][W]
+        int32_t ncomp = 0, largest = -1;
+        int32_t r2 = 0;
+    };
+    component_result components(int32_t r2_clear = 0, gpu_context& ctx = default_context()) {
+        if (d2.size() != occ.size()) edt(ctx);
+        component_result r;
+        r.r2 = r2_clear;
+        r.label.assign(occ.size(), -1); r.size.assign(occ.size(), 0);
+        if (occ.empty()) return r;
+        ctx.check(sc_components_batch_host(ctx.get(), d2.data(), 1, W, H, r2_clear, r.label.data(), r.size.data(), &r.ncomp, &r.largest),
+                  "sc_components_batch_host");
+        return r;
+    }
+    // The status astar_batch gives every query, from the labels alone (sc_reachable_batch): SC_Q_BAD_ENDPOINT, SC_Q_NO_PATH, or
+    // SC_Q_OK where A* returns SC_Q_OK or SC_Q_TRUNCATED.
+    std::vector<int32_t> reachable(const component_result& cr, const std::vector<int32_t>& start, const std::vector<int32_t>& goal,
+                                   gpu_context& ctx = default_context()) const {
+        if (start.size() != goal.size()) throw std::invalid_argument("occupancy_grid::reachable: start and goal differ in size");
+        std::vector<int32_t> st(start.size(), SC_Q_BAD_ENDPOINT);
+        if (start.empty() || cr.label.size() != occ.size() || occ.empty()) return st;
+        ctx.check(sc_reachable_batch_host(ctx.get(), cr.label.data(), 1, nullptr, W, H, start.data(), goal.data(), (int)start.size(), st.data()),
+                  "sc_reachable_batch_host");
+        return st;
+    }
+    // astar_batch that never searches a query whose endpoints lie in different components of `cr` (components() with the
+    // same r2_clear): the results are those of astar_batch.  The labels are on the host here, so the three steps of
+    // sc_astar_batch_screened are taken on the host: such a query's start becomes -1, the search leaves it at once as a bad
+    // endpoint (len 0, cost -1), and its status is set to SC_Q_NO_PATH.
+    batch_result astar_batch_screened(const component_result& cr, const std::vector<int32_t>& start, const std::vector<int32_t>& goal,
+                                      int Lmax = 0, gpu_context& ctx = default_context()) {
+        if (cr.label.size() != occ.size()) throw std::invalid_argument("occupancy_grid::astar_batch_screened: labels are not [H][W]");
+        const int32_t n = (int32_t)occ.size();
+        std::vector<int32_t> masked(start);
+        std::vector<char> cut(start.size(), 0);
+        for (size_t q = 0; q < start.size() && q < goal.size(); ++q) {
+            const int32_t s = start[q], t = goal[q];
+            if (s < 0 || t < 0 || s >= n || t >= n) continue;
+            const int32_t ls = cr.label[(size_t)s], lt = cr.label[(size_t)t];
+            if (ls >= 0 && lt >= 0 && ls != lt) { masked[q] = -1; cut[q] = 1; }
+        }
+        batch_result r = astar_batch(masked, goal, cr.r2, Lmax, ctx);
+        for (size_t q = 0; q < cut.size(); ++q)
+            if (cut[q]) r.status[q] = SC_Q_NO_PATH;
+        return r;
+    }
     // Cost-to-come fields (sc_cost_field_batch): g[f] = the optimal A* cost from roots[f] to every cell, SC_FIELD_INF where
     // there is none; status[f] SC_Q_OK or SC_Q_BAD_ENDPOINT.  rounds < 0: the library default.
     struct field_result {
@@ -694,16 +745,26 @@ public:
         }
         return out;
     }
-    // batched form: one grid, one EDT, Q queries in one GPU launch
+    // batched form: one grid, one EDT, Q queries in one GPU launch.  screen = true labels the grid's components once
+    // (occupancy_grid::components) and leaves the queries whose endpoints lie in different components unsearched
+    // (astar_batch_screened): the same results, without the cost of expanding a whole component for every hopeless query.
     std::vector<std::optional<std::vector<Vector2f>>> plan_batch(const std::vector<Vector2f>& starts, const std::vector<Vector2f>& goals,
-                                                                 gpu_context& ctx = default_context()) {
+                                                                 gpu_context& ctx = default_context(), bool screen = false) {
         occupancy_grid g = make_grid(ctx);
         g.edt(ctx);
         std::vector<int32_t> s(starts.size()), t(goals.size());
         for (size_t i = 0; i < starts.size(); ++i) { s[i] = g.cell_of(starts[i]); t[i] = g.cell_of(goals[i]); }
         const int32_t r2 = clearance_r2(g);
-        auto br = g.astar_batch(s, t, r2, 0, ctx);
+        auto br = screen ? g.astar_batch_screened(g.components(r2, ctx), s, t, 0, ctx) : g.astar_batch(s, t, r2, 0, ctx);
         return to_points(g, br, r2, starts, goals, "plan_batch", ctx);
+    }
+    // Is there a path between two world points?  Answered from the component labels, without a search: true iff
+    // plan_batch({a}, {b}) finds a path.  r2_clear < 0: the squared clearance in cells that `clearance` gives, as in plan_batch.
+    bool reachable(const Vector2f& a, const Vector2f& b, int32_t r2_clear = -1, gpu_context& ctx = default_context()) {
+        occupancy_grid g = make_grid(ctx);
+        g.edt(ctx);
+        const int32_t r2 = r2_clear < 0 ? clearance_r2(g) : r2_clear;
+        return g.reachable(g.components(r2, ctx), {g.cell_of(a)}, {g.cell_of(b)}, ctx)[0] == SC_Q_OK;
     }
     // One start, many goals (ranking candidate goals): one cost field rooted at the start's cell instead of one A* search
     // per goal.  Returns exactly plan_batch(std::vector<Vector2f>(goals.size(), start), goals, ctx).
