@@ -60,7 +60,7 @@ typedef enum {
     SC_K_MOVES = 2,       /* d2 + clearance -> legal-move byte per cell; also sc_clearance_penalty_u8, sc_components_batch,
                            * sc_reachable_batch */
     SC_K_ASTAR = 3,       /* batched A*: two wavefronts per query (prep + search + retry launches); also the cost fields and
-                           * their read-out (sc_cost_field_batch, sc_field_paths_batch and the weighted forms) */
+                           * their read-out (sc_cost_field_batch, sc_field_paths_batch, the weighted and the multi-source forms) */
     SC_K_TOPPRA = 4,      /* batched TOPP-RA: computeParams + backward + forward sweep */
     SC_K_TOPPRA_SAMPLE = 5,
     SC_K_BEZIER = 6,      /* tangents + control points, curve evaluation */
@@ -240,7 +240,7 @@ int sc_astar_gfield(sc_ctx* ctx, const int32_t* d2, int W, int H, int32_t r2_cle
  *   sc_occ_from_polygons / sc_occ_from_rects -> sc_edt_u8_i32 -> sc_cost_field_batch -> sc_field_paths_batch ->
  *   sc_path_waypoints_batch -> sc_cells_to_points_batch -> sc_smooth_paths_batch.
  * Errors: SC_ERR_INVALID for NULL pointers, W or H outside 1..SC_MAX_DIM, F <= 0, G <= 0, Q < 0, Lmax <= 0.  Q == 0 is a
- *   no-op.  Scratch: G * W * ceil(H/64) * 8 B of traversability masks and about 12 B per (field, 64 x 64 tile), grows
+ *   no-op.  Scratch: G * W * ceil(H/64) * 8 B of traversability masks and about 16 B per (field, 64 x 64 tile), grows
  *   only.  The _host forms take host pointers, check the data (sc_field_paths_batch_host: every g value >= 0) before any
  *   launch, copy, run, copy back and synchronise.  Timed as SC_K_ASTAR. */
 #define SC_FIELD_INF INT32_MAX
@@ -305,6 +305,67 @@ int sc_field_paths_weighted_batch_host(sc_ctx* ctx, const int32_t* d2, const uin
                                        int W, int H, int32_t r2_clear, const int32_t* g, const int32_t* root, int F,
                                        const int32_t* qfield, const int32_t* target, int Q, int Lmax, int to_root, int32_t* path,
                                        int32_t* len, int32_t* cost, int32_t* status);
+
+/* ---- multi-source cost fields -------------------------------------------------------------------------
+ * One field from many seeds: every cell's cost to the cheapest of K goals (docks, exits, chargers, frontier cells), each
+ * with an optional start cost of its own (queue time at a dock), and for every cell which seed that is.  One relaxation
+ * instead of K fields and a minimum over them.  DESIGN.md section 16.
+ *   Graph: that of the cost fields above -- the moves, their order, costs 10 / 14, T(c) <=> d2[c] >= max(r2_clear, 1), the
+ *     no-corner-cutting rule; with a costmap the move n -> c costs w_d + min(pen[c], pen_cap) as in the weighted fields.
+ *     pen == NULL: unweighted (pen_cap is ignored).
+ *   Seeds: field f owns seeds seed_off[f] .. seed_off[f+1] - 1 of seed int32 [n_seed] (cell indices on grid fgrid[f]) and
+ *     seed_cost int32 [n_seed] (NULL: all zero).  A seed is valid iff its cell is in range and traversable and
+ *     0 <= seed_cost <= SC_FIELD_SEED_COST_MAX (1 << 24, in the units of the move costs).  Invalid seeds are skipped.  A
+ *     field with no valid seed (an empty list, an out-of-range fgrid[f]) is all SC_FIELD_INF with fstatus
+ *     SC_Q_BAD_ENDPOINT.
+ *   Field: g[c] = min over f's valid seeds s of seed_cost[s] + dist(seed[s], c); SC_FIELD_INF where no seed reaches c or c
+ *     is not traversable.  A seed's own penalty is never paid, as for a root.  A seed may be dominated:
+ *     g[seed[s]] < seed_cost[s].
+ *   Overflow contract: the device forms return SC_ERR_INVALID before any launch unless
+ *     (14 + cap) * (W*H - 1) + SC_FIELD_SEED_COST_MAX <= INT32_MAX - 1 (64-bit arithmetic; cap = pen_cap in 0..255, or 0
+ *     when pen is NULL).  Unweighted it holds at every size up to 8192^2; every cap passes up to 2048^2, caps up to 113 at
+ *     4096^2, up to 17 at 8192^2.
+ *   Terminal and owner: cell c is terminal iff some valid seed s of the field has seed[s] == c and seed_cost[s] == g[c];
+ *     its owner is the smallest such s (an index into the call's seed array: seed[owner] is the cell).  A terminal cell is
+ *     terminal even when a parent would also satisfy the equality.  A finite non-terminal cell has owner[c] =
+ *     owner[parent(c)], parent being the rule of the fields above; owner[c] = -1 where g is SC_FIELD_INF.  g falls by at
+ *     least 10 per step and every finite non-terminal cell has a parent, so the owner is unique.
+ *   Read-out: query q walks the parent rule from target[q] on field qfield[q] to the first terminal cell.  which[q] = its
+ *     owner (-1 unless the status is SC_Q_OK or SC_Q_TRUNCATED); cost[q] = g[target], seed cost included.  to_seed = 0
+ *     writes seed..target, to_seed = 1 target..seed.  SC_Q_BAD_ENDPOINT: target out of range or not traversable, or a bad
+ *     qfield; SC_Q_NO_PATH: g is SC_FIELD_INF (every target of a field without a valid seed); SC_Q_TRUNCATED as in
+ *     sc_field_paths_batch; a target on a terminal cell gives len 1.
+ *   Anchors: with one valid seed of cost 0 per field, g and fstatus are bit-identical to sc_cost_field_batch (with pen: to
+ *     sc_cost_field_weighted_batch), the read-out to sc_field_paths_batch / sc_field_paths_weighted_batch, and owner is that
+ *     seed wherever g is finite.  In general g is the elementwise minimum of the single-root fields plus their seed costs,
+ *     and, unweighted, path, len and cost - seed_cost[which] equal sc_astar_batch(seed[which], target).
+ * sc_cost_field_multi_batch: g int32 [F][H][W]; owner int32 [F][H][W] or NULL (no owner pass); fstatus [F] or NULL;
+ *   seed_off int32 [F + 1]; seed may be NULL only when n_seed == 0 (every field SC_Q_BAD_ENDPOINT).  On the device
+ *   seed_off is clamped into 0..n_seed.  The owner pass takes ceil(log2(W*H)) + 3 launches, fixed on the host; a launch
+ *   that finds nothing left returns at once.
+ * sc_field_paths_multi_batch: g, owner and seed as sc_cost_field_multi_batch took and wrote them; which int32 [Q] or
+ *   NULL.  An owner outside 0..n_seed-1 gives SC_Q_NO_PATH, so nothing is read out of bounds whatever the arrays hold.
+ * The device forms only enqueue (no host synchronisation, no device-to-host copy).  Errors otherwise as
+ *   sc_cost_field_batch / sc_field_paths_batch, and n_seed < 0 or seed_off NULL.  The _host forms check the data before
+ *   any launch (seed_off non-decreasing within 0..n_seed, seed costs inside the contract, every g value >= 0:
+ *   SC_ERR_INVALID).  Scratch: that of sc_cost_field_batch, which now takes about 16 B per (field, 64 x 64 tile) (4 B more:
+ *   the flag of the tiles that hold a seed), plus 4 * (ceil(log2(W*H)) + 1) B of owner-pass counts; grows only.  Timed as
+ *   SC_K_ASTAR. */
+#define SC_FIELD_SEED_COST_MAX (1 << 24)
+int sc_cost_field_multi_batch(sc_ctx* ctx, const int32_t* d2, const uint8_t* pen, int pen_cap, int G, const int32_t* fgrid, int W, int H,
+                              int32_t r2_clear, const int32_t* seed, const int32_t* seed_cost, const int32_t* seed_off, int n_seed, int F,
+                              int rounds, int32_t* g, int32_t* owner, int32_t* fstatus);
+int sc_cost_field_multi_batch_host(sc_ctx* ctx, const int32_t* d2, const uint8_t* pen, int pen_cap, int G, const int32_t* fgrid, int W,
+                                   int H, int32_t r2_clear, const int32_t* seed, const int32_t* seed_cost, const int32_t* seed_off,
+                                   int n_seed, int F, int rounds, int32_t* g, int32_t* owner, int32_t* fstatus);
+int sc_field_paths_multi_batch(sc_ctx* ctx, const int32_t* d2, const uint8_t* pen, int pen_cap, int G, const int32_t* fgrid, int W, int H,
+                               int32_t r2_clear, const int32_t* g, const int32_t* owner, const int32_t* seed, int n_seed, int F,
+                               const int32_t* qfield, const int32_t* target, int Q, int Lmax, int to_seed, int32_t* path, int32_t* len,
+                               int32_t* cost, int32_t* status, int32_t* which);
+int sc_field_paths_multi_batch_host(sc_ctx* ctx, const int32_t* d2, const uint8_t* pen, int pen_cap, int G, const int32_t* fgrid, int W,
+                                    int H, int32_t r2_clear, const int32_t* g, const int32_t* owner, const int32_t* seed, int n_seed,
+                                    int F, const int32_t* qfield, const int32_t* target, int Q, int Lmax, int to_seed, int32_t* path,
+                                    int32_t* len, int32_t* cost, int32_t* status, int32_t* which);
 
 /* ---- free-space components ---------------------------------------------------------------------------
  * Labels the connected components of the traversable cells once, so that "is there a path from a to b" is answered

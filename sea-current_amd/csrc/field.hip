@@ -24,6 +24,21 @@
 // its column's 64 capped penalties, four to a register; every move it relaxes enters one of its own cells, so it needs
 // no penalty of a halo cell.  The row closing becomes a min-scan over prefix sums of the entry costs (close_row).  The
 // unweighted builds take the `if constexpr` branches they always had.
+//
+// Multi-source fields (sc_cost_field_multi_batch, sc_field_paths_multi_batch): field f starts from a
+// list of seeds, each with a start cost; g[c] = min over its valid seeds s of seed_cost[s] + dist(seed[s], c).  The
+// relaxation is the one above: only the init differs (field_fill_kernel + field_seed_kernel: INF, then atomicMin of the
+// seed costs; it queues every seed's tile and the neighbour tiles whose halo holds the seed) and a visit's `force`, which
+// reads a per-(field, tile) flag the init sets where a tile holds a seed.  The single-root entries are the case of one
+// seed of cost 0 per field and run through the same init.
+//   Owner pass: a cell is terminal iff a valid seed s sits on it with seed_cost[s] == g; its owner is the smallest such
+//   s.  Every other finite cell's owner is that of its parent (the read-out's rule).  owner_claim_kernel: atomicMin of s
+//   over the terminal seeds.  owner_parent_kernel: every unclaimed finite cell stores its parent p as -2 - p.
+//   owner_jump_kernel, ceil(log2(W H)) launches: a cell that holds -2 - p reads owner[p] (up to OWN_HOPS times): a value
+//   >= 0 is its owner, a value <= -2 a farther ancestor.  The stores are in place and unordered: whatever a cell reads is
+//   an ancestor of it or its final owner, so the result does not depend on the order.  A launch counts the cells it left
+//   unresolved for the next one, which returns at once when that count is 0.
+//   Read-out: field_paths_kernel with the end cell seed[owner[target]] in place of the root.
 #include <type_traits>
 
 #include "sc_internal.h"
@@ -42,10 +57,10 @@ struct field_args {
     const uint64_t* mask;    // [G][TY][W] bit y: T(x, ty*64 + y)
     const int32_t* d2;       // [G][H][W]
     const int32_t* fgrid;    // [F] or NULL (G == 1)
-    const int32_t* root;     // [F]
     int32_t* g;              // [F][H][W]
-    int32_t* ok;             // [F] 1: the field is computed
+    int32_t* ok;             // [F] 1: the field has a valid seed
     int32_t* stamp;          // [F][nt] round + 1 a tile is queued for (grows only)
+    int32_t* seeded;         // [F][nt] != 0: the tile holds a valid seed of the field
     int32_t* list[2];        // [F * nt] each: f * nt + tile
     int32_t* ctr;            // [rounds + 1] list length of each round
     int G, W, H, F, TX, TY, nt;
@@ -199,9 +214,10 @@ __device__ __forceinline__ bool sweep(tile_state<WT>& s, bool down, int lane, bo
     return c;
 }
 
-// Visit tile (tx, ty) of field f with one wavefront; mark(tx', ty') queues a neighbour (called by every lane, uniform).
+// Visit tile (tx, ty) of field f with one wavefront; e = f * nt + ty * TX + tx, its index in stamp and seeded; mark(tx', ty')
+// queues a neighbour (called by every lane, uniform).
 template <bool WEIGHTED, class Args, class Mark>
-__device__ __forceinline__ void visit_tile(const Args& a, int f, int tx, int ty, Mark mark) {
+__device__ __forceinline__ void visit_tile(const Args& a, int f, int tx, int ty, size_t e, Mark mark) {
     const int lane = threadIdx.x & 63;
     const int W = a.W, H = a.H;
     const int gi = a.fgrid ? a.fgrid[f] : 0;
@@ -254,9 +270,9 @@ __device__ __forceinline__ void visit_tile(const Args& a, int f, int tx, int ty,
         }
     }
     s.chg = 0;
-    // the root's tile starts with rows that are not closed (0 at the root, INF beside it): its first sweep closes every row
-    const int rt = a.root[f];
-    const bool force = (rt % W) / FT == tx && (rt / W) / FT == ty;
+    // a tile that holds a seed starts with rows that are not closed (its cost at the seed, INF beside it): its first sweep
+    // closes every row
+    const bool force = a.seeded[e] != 0;
     bool down = true;
     for (int n = 0;; ++n) {
         const bool c = sweep(s, down, lane, force && n == 0);
@@ -298,30 +314,69 @@ __global__ void field_mask_kernel(const int32_t* __restrict__ d2, int G, int W, 
     mask[i] = m;
 }
 
-__device__ __forceinline__ bool field_root_ok(const field_args& a, int f) {
-    const int gi = a.fgrid ? a.fgrid[f] : 0;
-    const int r = a.root[f];
-    return gi >= 0 && gi < a.G && r >= 0 && (long long)r < (long long)a.W * a.H && a.d2[(size_t)gi * a.W * a.H + r] >= a.thr;
+// the seed lists of a call: field f owns seeds off[f] .. off[f + 1] - 1 (off NULL: seed f alone), cost NULL: all 0
+struct seed_args {
+    const int32_t* seed;
+    const int32_t* cost;
+    const int32_t* off;
+    int n_seed;
+};
+
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+__device__ __forceinline__ void seed_range(const seed_args& sa, int f, int& lo, int& hi) {
+    lo = sa.off ? clampi(sa.off[f], 0, sa.n_seed) : clampi(f, 0, sa.n_seed);
+    hi = sa.off ? clampi(sa.off[f + 1], 0, sa.n_seed) : clampi(f + 1, 0, sa.n_seed);
 }
 
-// g = INF everywhere, 0 at a valid root; grid (blocks, fields), fields strided.  Block 0 of a field writes its status and queues the root's tile
-// for round 0 (stamp 1).
-__global__ void field_init_kernel(field_args a, int32_t* fstatus) {
+// seed s of a field on grid gi (in range) is valid; c = its cell, sc = its cost
+__device__ __forceinline__ bool seed_ok(const seed_args& sa, const int32_t* d2, int gi, long long n, int32_t thr, int s, int& c, int32_t& sc) {
+    c = sa.seed[s];
+    sc = sa.cost ? sa.cost[s] : 0;
+    return c >= 0 && c < n && sc >= 0 && sc <= SC_FIELD_SEED_COST_MAX && d2[(size_t)gi * n + c] >= thr;
+}
+
+// g = INF everywhere; grid (blocks, fields), fields strided.  Block 0 of a field writes "no valid seed" into its ok flag and status.
+__global__ void field_fill_kernel(field_args a, int32_t* fstatus) {
     const size_t n = (size_t)a.W * a.H;
     for (int f = blockIdx.y; f < a.F; f += gridDim.y) {
-        const bool ok = field_root_ok(a, f);
-        const int r = ok ? a.root[f] : -1;
         int32_t* G = a.g + (size_t)f * n;
-        for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-            G[i] = (int64_t)i == r ? 0 : (int32_t)FINF;
+        for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) G[i] = (int32_t)FINF;
         if (blockIdx.x == 0 && threadIdx.x == 0) {
-            a.ok[f] = ok;
-            if (fstatus) fstatus[f] = ok ? SC_Q_OK : SC_Q_BAD_ENDPOINT;
-            if (ok) {
-                const int t = (r / a.W / FT) * a.TX + (r % a.W) / FT;
-                a.stamp[(size_t)f * a.nt + t] = 1;
-                a.list[0][atomicAdd(a.ctr, 1)] = f * a.nt + t;
-            }
+            a.ok[f] = 0;
+            if (fstatus) fstatus[f] = SC_Q_BAD_ENDPOINT;
+        }
+    }
+}
+
+// One block per field (strided), one thread per seed (strided): a valid seed lowers g at its cell to its cost, marks the
+// field ok and its tile seeded, and queues for round 0 (stamp 1, at most once per tile) its tile and every neighbour tile
+// whose one-cell halo holds the seed.  The neighbours are needed: the seed's value does not change in its tile's first
+// visit, so when nothing else in the tile changes, that visit marks no neighbour.
+__global__ void field_seed_kernel(field_args a, seed_args sa, int32_t* fstatus) {
+    const long long n = (long long)a.W * a.H;
+    for (int f = blockIdx.x; f < a.F; f += gridDim.x) {
+        const int gi = a.fgrid ? a.fgrid[f] : 0;
+        if (gi < 0 || gi >= a.G) continue;
+        int lo, hi;
+        seed_range(sa, f, lo, hi);
+        for (int s = lo + (int)threadIdx.x; s < hi; s += blockDim.x) {
+            int c;
+            int32_t sc;
+            if (!seed_ok(sa, a.d2, gi, n, a.thr, s, c, sc)) continue;
+            atomicMin(a.g + (size_t)f * n + c, sc);
+            a.ok[f] = 1;
+            if (fstatus) fstatus[f] = SC_Q_OK;
+            const int x = c % a.W, y = c / a.W, tx = x / FT, ty = y / FT, lx = x % FT, ly = y % FT;
+            a.seeded[(size_t)f * a.nt + ty * a.TX + tx] = 1;
+            for (int dy = -1; dy <= 1; ++dy)
+                for (int dx = -1; dx <= 1; ++dx) {
+                    const int ux = tx + dx, uy = ty + dy;
+                    if (ux < 0 || uy < 0 || ux >= a.TX || uy >= a.TY) continue;
+                    if ((dx < 0 && lx != 0) || (dx > 0 && lx != FT - 1) || (dy < 0 && ly != 0) || (dy > 0 && ly != FT - 1)) continue;
+                    const int u = f * a.nt + uy * a.TX + ux;
+                    if (atomicMax(a.stamp + u, 1) < 1) a.list[0][atomicAdd(a.ctr, 1)] = u;
+                }
         }
     }
 }
@@ -337,7 +392,7 @@ __global__ __launch_bounds__(64) void field_round_kernel(std::conditional_t<WEIG
     for (int i = blockIdx.x; i < n; i += gridDim.x) {
         const int e = cur[i];
         const int f = e / a.nt, t = e % a.nt;
-        visit_tile<WEIGHTED>(a, f, t % a.TX, t / a.TX, [&](int ux, int uy) {
+        visit_tile<WEIGHTED>(a, f, t % a.TX, t / a.TX, (size_t)e, [&](int ux, int uy) {
             if (lane == 0) {
                 const int u = f * a.nt + uy * a.TX + ux;
                 if (atomicMax(a.stamp + u, r + 2) < r + 2) nxt[atomicAdd(nctr, 1)] = u;
@@ -380,9 +435,10 @@ __global__ __launch_bounds__(64 * WAVES) void field_finish_kernel(std::condition
         __syncthreads();
         const int n = count;
         if (n == 0) break;
-        for (int i = wave; i < n; i += WAVES) {
-            const int t = work[i];
-            visit_tile<WEIGHTED>(a, f, t % a.TX, t / a.TX, [&](int ux, int uy) {
+        // the wave index and the tile are the same in every lane: said outright, the tile's addresses are scalar
+        for (int i = __builtin_amdgcn_readfirstlane(wave); i < n; i += WAVES) {
+            const int t = __builtin_amdgcn_readfirstlane((int)work[i]);
+            visit_tile<WEIGHTED>(a, f, t % a.TX, t / a.TX, (size_t)f * nt + t, [&](int ux, int uy) {
                 if (lane == 0) {
                     const int u = uy * a.TX + ux;
                     atomicOr(&dirty[u >> 5], 1u << (u & 31));
@@ -393,26 +449,114 @@ __global__ __launch_bounds__(64 * WAVES) void field_finish_kernel(std::condition
     }
 }
 
+// ---- owner pass ----------------------------------------------------------------------------------------------------
+constexpr int OWN_HOPS = 4;                // ancestors a cell follows per jump launch
+constexpr int32_t OWN_FREE = 0x7F7F7F7F;   // what the memset before owner_claim_kernel leaves: no seed has claimed the cell
+
+__constant__ int RP_DX[8] = {1, -1, 0, 0, 1, -1, 1, -1};
+__constant__ int RP_DY[8] = {0, 0, 1, -1, 1, 1, -1, -1};
+
+struct owner_args {
+    const int32_t* d2;
+    const uint8_t* pen;      // NULL: unweighted
+    const int32_t* fgrid;
+    const int32_t* g;
+    int32_t* owner;          // [F][H][W]
+    int32_t* left;           // [jumps + 1] cells without an owner before jump launch k
+    int G, W, H, F;
+    int32_t thr;
+    uint32_t cap;
+};
+
+// terminal seeds claim their cell: the smallest valid s with seed_cost[s] == g[seed[s]]
+__global__ void owner_claim_kernel(owner_args a, seed_args sa) {
+    const long long n = (long long)a.W * a.H;
+    for (int f = blockIdx.x; f < a.F; f += gridDim.x) {
+        const int gi = a.fgrid ? a.fgrid[f] : 0;
+        if (gi < 0 || gi >= a.G) continue;
+        int lo, hi;
+        seed_range(sa, f, lo, hi);
+        for (int s = lo + (int)threadIdx.x; s < hi; s += blockDim.x) {
+            int c;
+            int32_t sc;
+            if (seed_ok(sa, a.d2, gi, n, a.thr, s, c, sc) && a.g[(size_t)f * n + c] == sc) atomicMin(a.owner + (size_t)f * n + c, s);
+        }
+    }
+}
+
+// every cell no seed claimed: -1 where g is INF, else -2 - p with p its parent by the read-out's rule, decided from g alone
+// (the side cells of a diagonal: reachable <=> traversable next to a reachable cell)
+__global__ void owner_parent_kernel(owner_args a) {
+    const int W = a.W, H = a.H;
+    const size_t n = (size_t)W * H, total = n * a.F;
+    int open = 0;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        if (a.owner[i] != OWN_FREE) continue;
+        const int f = (int)(i / n), c = (int)(i % n);
+        const int32_t* G = a.g + (size_t)f * n;
+        const uint32_t gc = (uint32_t)G[c];
+        int32_t o = -1;
+        const int gi = a.fgrid ? a.fgrid[f] : 0;
+        if (gc < FINF && gi >= 0 && gi < a.G) {
+            const uint32_t pc = a.pen ? min((uint32_t)a.pen[(size_t)gi * n + c], a.cap) : 0u;
+            const int cx = c % W, cy = c / W;
+            for (int d = 0; d < 8; ++d) {
+                const int px = cx - RP_DX[d], py = cy - RP_DY[d];
+                if (px < 0 || py < 0 || px >= W || py >= H) continue;
+                const uint32_t gp = (uint32_t)G[(size_t)py * W + px];
+                if (gp >= FINF || gp + (d < 4 ? 10u : 14u) + pc != gc) continue;
+                if (d >= 4 && ((uint32_t)G[(size_t)cy * W + px] >= FINF || (uint32_t)G[(size_t)py * W + cx] >= FINF)) continue;
+                o = -2 - (py * W + px);
+                break;
+            }
+        }
+        a.owner[i] = o;
+        open |= o <= -2;
+    }
+    if (__syncthreads_or(open) && threadIdx.x == 0) atomicAdd(a.left, 1);
+}
+
+// jump launch k: a cell that holds -2 - p takes what its ancestor p holds, up to OWN_HOPS times
+__global__ void owner_jump_kernel(owner_args a, int k) {
+    if (a.left[k] == 0) return;
+    const size_t n = (size_t)a.W * a.H, total = n * a.F;
+    int open = 0;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        int32_t v = a.owner[i];
+        if (v > -2) continue;
+        int32_t* O = a.owner + (i / n) * n;
+        for (int h = 0; h < OWN_HOPS && v <= -2; ++h) {
+            const long long p = -2ll - v;
+            v = p < (long long)n ? __hip_atomic_load(O + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : -1;
+        }
+        if (v >= OWN_FREE) v = -1;
+        __hip_atomic_store(a.owner + i, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        open |= v <= -2;
+    }
+    if (__syncthreads_or(open) && threadIdx.x == 0) atomicAdd(a.left + k + 1, 1);
+}
+
 // ---- read-out ------------------------------------------------------------------------------------------------------
 struct paths_args {
     const int32_t* d2;
     const int32_t* fgrid;
     const int32_t* g;
-    const int32_t* root;
+    const int32_t* root;     // [F] the end cell of field f; NULL: multi-source, the end cell of a query is seed[owner[target]]
     const int32_t* qfield;
     const int32_t* target;
     int G, W, H, F, Q, Lmax, to_root;
     int32_t thr;
     int32_t *path, *len, *cost, *status;
+    const int32_t* owner = nullptr;   // multi-source: [F][H][W]
+    const int32_t* seed = nullptr;    // [n_seed]
+    int32_t* which = nullptr;         // [Q] or NULL
+    int n_seed = 0;
 };
 
 struct paths_args_w : paths_args {
     const uint8_t* pen;
     uint32_t cap;
 };
-
-__constant__ int RP_DX[8] = {1, -1, 0, 0, 1, -1, 1, -1};
-__constant__ int RP_DY[8] = {0, 0, 1, -1, 1, 1, -1, -1};
 
 // WEIGHTED: a second window holds the capped penalties.  The step into the current cell c cost w_d + penalty(c), so the
 // parent test and the cost walked back both add the penalty of c.
@@ -429,17 +573,24 @@ __global__ __launch_bounds__(64 * RP_WAVES) void field_paths_kernel(std::conditi
     const long long n = (long long)W * H;
     const int fq = a.qfield[q];
     const int gi = (fq >= 0 && fq < a.F) ? (a.fgrid ? a.fgrid[fq] : 0) : -1;
-    const int r = fq >= 0 && fq < a.F ? a.root[fq] : -1;
+    const bool multi = a.root == nullptr;
+    int r = !multi && fq >= 0 && fq < a.F ? a.root[fq] : -1;
     const int t = a.target[q];
-    const bool ok = gi >= 0 && gi < a.G && r >= 0 && r < n && t >= 0 && t < n && a.d2[(size_t)gi * n + r] >= a.thr &&
-                    a.d2[(size_t)gi * n + t] >= a.thr;
+    if (lane == 0 && a.which) a.which[q] = -1;
+    const bool ok = gi >= 0 && gi < a.G && t >= 0 && t < n && a.d2[(size_t)gi * n + t] >= a.thr &&
+                    (multi || (r >= 0 && r < n && a.d2[(size_t)gi * n + r] >= a.thr));
     if (!ok) {
         if (lane == 0) { a.len[q] = 0; a.cost[q] = -1; a.status[q] = SC_Q_BAD_ENDPOINT; }
         return;
     }
     const int32_t* G = a.g + (size_t)fq * n;
     const uint32_t gt = (uint32_t)G[t];
-    if (gt >= FINF) {
+    int own = -1;
+    if (multi && gt < FINF) {
+        own = a.owner[(size_t)fq * n + t];
+        r = own >= 0 && own < a.n_seed ? a.seed[own] : -1;
+    }
+    if (gt >= FINF || r < 0 || r >= n) {
         if (lane == 0) { a.len[q] = 0; a.cost[q] = -1; a.status[q] = SC_Q_NO_PATH; }
         return;
     }
@@ -505,7 +656,10 @@ __global__ __launch_bounds__(64 * RP_WAVES) void field_paths_kernel(std::conditi
             P[Li - 1 - i] = u;
         }
     }
-    if (lane == 0) { a.len[q] = Li; a.cost[q] = (int32_t)gt; a.status[q] = Li <= a.Lmax ? SC_Q_OK : SC_Q_TRUNCATED; }
+    if (lane == 0) {
+        a.len[q] = Li; a.cost[q] = (int32_t)gt; a.status[q] = Li <= a.Lmax ? SC_Q_OK : SC_Q_TRUNCATED;
+        if (a.which) a.which[q] = own;
+    }
 }
 
 int field_default_rounds(int TX, int TY) { return 2 * (TX + TY) + 16; }
@@ -532,29 +686,41 @@ static bool weighted_args_ok(const uint8_t* pen, int pen_cap, int W, int H) {
 }
 
 // both field entries; pen NULL: the unweighted kernels
+// the jump launches of the owner pass: ceil(log2(W H))
+static int owner_jumps(int W, int H) {
+    int k = 0;
+    while ((1ll << k) < (long long)W * H) ++k;
+    return k;
+}
+
+// every field entry; pen NULL: the unweighted kernels.  sa: the seed lists (the single-root entries: seed = root, one per
+// field, cost 0).  owner != NULL: the owner pass follows.
 static int cost_field_launch(sc_ctx* ctx, const int32_t* d2, const uint8_t* pen, int pen_cap, int G, const int32_t* fgrid, int W, int H,
-                             int32_t r2_clear, const int32_t* root, int F, int rounds, int32_t* g, int32_t* fstatus) {
+                             int32_t r2_clear, const seed_args& sa, int F, int rounds, int32_t* g, int32_t* owner, int32_t* fstatus) {
     SC_HIP(ctx, hipSetDevice(ctx->device));
     const int TX = (W + FT - 1) / FT, TY = (H + FT - 1) / FT, nt = TX * TY;
     if ((long long)F * nt > 0x7FFFFFFF / 2) return SC_ERR_INVALID;
     if (rounds < 0) rounds = field_default_rounds(TX, TY);
+    const int jumps = owner_jumps(W, H);
     const size_t mask_b = (size_t)G * TY * W * 8;
-    const size_t o_ok = 0, o_stamp = al256((size_t)F * 4), o_l0 = o_stamp + al256((size_t)F * nt * 4), o_l1 = o_l0 + al256((size_t)F * nt * 4),
-                 o_ctr = o_l1 + al256((size_t)F * nt * 4), total = o_ctr + al256((size_t)(rounds + 1) * 4);
+    // stamp and seeded lie next to each other: one memset clears both
+    const size_t o_ok = 0, o_stamp = al256((size_t)F * 4), o_seeded = o_stamp + al256((size_t)F * nt * 4),
+                 o_l0 = o_seeded + al256((size_t)F * nt * 4), o_l1 = o_l0 + al256((size_t)F * nt * 4), o_ctr = o_l1 + al256((size_t)F * nt * 4),
+                 o_left = o_ctr + al256((size_t)(rounds + 1) * 4), total = o_left + al256((size_t)(jumps + 1) * 4);
     int r = sc_scratch_reserve(ctx, &ctx->fld_mask, mask_b);
     if (r == SC_OK) r = sc_scratch_reserve(ctx, &ctx->fld_state, total);
     if (r != SC_OK) return r;
     char* b = (char*)ctx->fld_state.p;
     field_args_w a;
     a.pen = pen; a.cap = (uint32_t)pen_cap;
-    a.mask = (const uint64_t*)ctx->fld_mask.p; a.d2 = d2; a.fgrid = fgrid; a.root = root; a.g = g;
-    a.ok = (int32_t*)(b + o_ok); a.stamp = (int32_t*)(b + o_stamp);
+    a.mask = (const uint64_t*)ctx->fld_mask.p; a.d2 = d2; a.fgrid = fgrid; a.g = g;
+    a.ok = (int32_t*)(b + o_ok); a.stamp = (int32_t*)(b + o_stamp); a.seeded = (int32_t*)(b + o_seeded);
     a.list[0] = (int32_t*)(b + o_l0); a.list[1] = (int32_t*)(b + o_l1); a.ctr = (int32_t*)(b + o_ctr);
     a.G = G; a.W = W; a.H = H; a.F = F; a.TX = TX; a.TY = TY; a.nt = nt;
     a.thr = r2_clear > 1 ? r2_clear : 1;
     int tk = sc_time_begin(ctx, SC_K_ASTAR);
-    SC_HIP(ctx, hipMemsetAsync(b + o_stamp, 0, (size_t)F * nt * 4, ctx->stream));
-    SC_HIP(ctx, hipMemsetAsync(b + o_ctr, 0, (size_t)(rounds + 1) * 4, ctx->stream));
+    SC_HIP(ctx, hipMemsetAsync(b + o_stamp, 0, o_l0 - o_stamp, ctx->stream));
+    SC_HIP(ctx, hipMemsetAsync(b + o_ctr, 0, total - o_ctr, ctx->stream));
     {
         const size_t nm = (size_t)G * TY * W;
         hipLaunchKernelGGL(field_mask_kernel, dim3((unsigned)((nm + 255) / 256)), dim3(256), 0, ctx->stream, d2, G, W, H, TY, a.thr,
@@ -564,7 +730,8 @@ static int cost_field_launch(sc_ctx* ctx, const int32_t* d2, const uint8_t* pen,
         const size_t n = (size_t)W * H;
         unsigned bx = (unsigned)((n + 1023) / 1024);
         if (bx > 1024) bx = 1024;
-        hipLaunchKernelGGL(field_init_kernel, dim3(bx, F < 65535 ? F : 65535), dim3(1024), 0, ctx->stream, (field_args)a, fstatus);
+        hipLaunchKernelGGL(field_fill_kernel, dim3(bx, F < 65535 ? F : 65535), dim3(1024), 0, ctx->stream, (field_args)a, fstatus);
+        hipLaunchKernelGGL(field_seed_kernel, dim3(F < 65535 ? F : 65535), dim3(64), 0, ctx->stream, (field_args)a, sa, fstatus);
     }
     if (rounds > 0) {
         if (!ctx->cu_count) {
@@ -581,6 +748,21 @@ static int cost_field_launch(sc_ctx* ctx, const int32_t* d2, const uint8_t* pen,
     }
     if (pen) hipLaunchKernelGGL((field_finish_kernel<true, FIN_WAVES_W>), dim3(F), dim3(64 * FIN_WAVES_W), 0, ctx->stream, a, rounds);
     else hipLaunchKernelGGL((field_finish_kernel<false, FIN_WAVES>), dim3(F), dim3(64 * FIN_WAVES), 0, ctx->stream, (field_args)a, rounds);
+    if (owner) {
+        const size_t cells = (size_t)F * W * H;
+        owner_args oa{d2, pen, fgrid, g, owner, (int32_t*)(b + o_left), G, W, H, F, a.thr, (uint32_t)pen_cap};
+        if (!ctx->cu_count) {
+            int cu = 0;
+            SC_HIP(ctx, hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, ctx->device));
+            ctx->cu_count = cu > 0 ? cu : 1;
+        }
+        const size_t cap = (size_t)ctx->cu_count * 8, need = (cells + 255) / 256;
+        const unsigned blocks = (unsigned)(need < cap ? need : cap);
+        SC_HIP(ctx, hipMemsetAsync(owner, 0x7F, cells * 4, ctx->stream));
+        hipLaunchKernelGGL(owner_claim_kernel, dim3(F < 65535 ? F : 65535), dim3(64), 0, ctx->stream, oa, sa);
+        hipLaunchKernelGGL(owner_parent_kernel, dim3(blocks), dim3(256), 0, ctx->stream, oa);
+        for (int k = 0; k < jumps; ++k) hipLaunchKernelGGL(owner_jump_kernel, dim3(blocks), dim3(256), 0, ctx->stream, oa, k);
+    }
     sc_time_end(ctx, tk);
     SC_HIP(ctx, hipGetLastError());
     return SC_OK;
@@ -589,14 +771,14 @@ static int cost_field_launch(sc_ctx* ctx, const int32_t* d2, const uint8_t* pen,
 extern "C" int sc_cost_field_batch(sc_ctx* ctx, const int32_t* d2, int G, const int32_t* fgrid, int W, int H, int32_t r2_clear,
                                    const int32_t* root, int F, int rounds, int32_t* g, int32_t* fstatus) {
     if (!cost_field_args_ok(ctx, d2, G, fgrid, W, H, root, F, g)) return SC_ERR_INVALID;
-    return cost_field_launch(ctx, d2, nullptr, 0, G, fgrid, W, H, r2_clear, root, F, rounds, g, fstatus);
+    return cost_field_launch(ctx, d2, nullptr, 0, G, fgrid, W, H, r2_clear, seed_args{root, nullptr, nullptr, F}, F, rounds, g, nullptr, fstatus);
 }
 
 extern "C" int sc_cost_field_weighted_batch(sc_ctx* ctx, const int32_t* d2, const uint8_t* pen, int pen_cap, int G, const int32_t* fgrid,
                                             int W, int H, int32_t r2_clear, const int32_t* root, int F, int rounds, int32_t* g,
                                             int32_t* fstatus) {
     if (!cost_field_args_ok(ctx, d2, G, fgrid, W, H, root, F, g) || !weighted_args_ok(pen, pen_cap, W, H)) return SC_ERR_INVALID;
-    return cost_field_launch(ctx, d2, pen, pen_cap, G, fgrid, W, H, r2_clear, root, F, rounds, g, fstatus);
+    return cost_field_launch(ctx, d2, pen, pen_cap, G, fgrid, W, H, r2_clear, seed_args{root, nullptr, nullptr, F}, F, rounds, g, nullptr, fstatus);
 }
 
 extern "C" int sc_field_paths_batch(sc_ctx* ctx, const int32_t* d2, int G, const int32_t* fgrid, int W, int H, int32_t r2_clear,
@@ -631,6 +813,111 @@ extern "C" int sc_field_paths_weighted_batch(sc_ctx* ctx, const int32_t* d2, con
     sc_time_end(ctx, tk);
     SC_HIP(ctx, hipGetLastError());
     return SC_OK;
+}
+
+// the overflow contract of the multi-source entries: a simple path enters each of the other W*H - 1 cells at most once, on
+// top of a seed cost
+static bool multi_args_ok(const uint8_t* pen, int pen_cap, int W, int H) {
+    if (pen && (pen_cap < 0 || pen_cap > 255)) return false;
+    return (long long)(14 + (pen ? pen_cap : 0)) * ((long long)W * H - 1) + SC_FIELD_SEED_COST_MAX <= (long long)INT32_MAX - 1;
+}
+
+static bool cost_field_multi_args_ok(const sc_ctx* ctx, const int32_t* d2, const uint8_t* pen, int pen_cap, int G, const int32_t* fgrid, int W,
+                                     int H, const int32_t* seed, const int32_t* seed_off, int n_seed, int F, const int32_t* g) {
+    return ctx && d2 && g && seed_off && n_seed >= 0 && (seed || n_seed == 0) && G > 0 && F > 0 && W > 0 && H > 0 && W <= SC_MAX_DIM &&
+           H <= SC_MAX_DIM && (fgrid || G == 1) && multi_args_ok(pen, pen_cap, W, H);
+}
+
+static bool field_paths_multi_args_ok(const sc_ctx* ctx, const int32_t* d2, const uint8_t* pen, int pen_cap, int G, const int32_t* fgrid, int W,
+                                      int H, const int32_t* g, const int32_t* owner, const int32_t* seed, int n_seed, int F,
+                                      const int32_t* qfield, const int32_t* target, int Q, int Lmax, const int32_t* path, const int32_t* len,
+                                      const int32_t* cost, const int32_t* status) {
+    return ctx && d2 && g && owner && qfield && target && path && len && cost && status && n_seed >= 0 && (seed || n_seed == 0) && G > 0 &&
+           F > 0 && W > 0 && H > 0 && W <= SC_MAX_DIM && H <= SC_MAX_DIM && Q >= 0 && Lmax > 0 && (fgrid || G == 1) &&
+           multi_args_ok(pen, pen_cap, W, H);
+}
+
+extern "C" int sc_cost_field_multi_batch(sc_ctx* ctx, const int32_t* d2, const uint8_t* pen, int pen_cap, int G, const int32_t* fgrid, int W,
+                                         int H, int32_t r2_clear, const int32_t* seed, const int32_t* seed_cost, const int32_t* seed_off,
+                                         int n_seed, int F, int rounds, int32_t* g, int32_t* owner, int32_t* fstatus) {
+    if (!cost_field_multi_args_ok(ctx, d2, pen, pen_cap, G, fgrid, W, H, seed, seed_off, n_seed, F, g)) return SC_ERR_INVALID;
+    return cost_field_launch(ctx, d2, pen, pen_cap, G, fgrid, W, H, r2_clear, seed_args{seed, seed_cost, seed_off, n_seed}, F, rounds, g, owner,
+                             fstatus);
+}
+
+extern "C" int sc_field_paths_multi_batch(sc_ctx* ctx, const int32_t* d2, const uint8_t* pen, int pen_cap, int G, const int32_t* fgrid, int W,
+                                          int H, int32_t r2_clear, const int32_t* g, const int32_t* owner, const int32_t* seed, int n_seed,
+                                          int F, const int32_t* qfield, const int32_t* target, int Q, int Lmax, int to_seed, int32_t* path,
+                                          int32_t* len, int32_t* cost, int32_t* status, int32_t* which) {
+    if (!field_paths_multi_args_ok(ctx, d2, pen, pen_cap, G, fgrid, W, H, g, owner, seed, n_seed, F, qfield, target, Q, Lmax, path, len, cost,
+                                   status))
+        return SC_ERR_INVALID;
+    if (Q == 0) return SC_OK;
+    SC_HIP(ctx, hipSetDevice(ctx->device));
+    paths_args_w a;
+    (paths_args&)a = paths_args{d2, fgrid, g, nullptr, qfield, target, G, W, H, F, Q, Lmax, to_seed ? 1 : 0, r2_clear > 1 ? r2_clear : 1,
+                                path, len, cost, status, owner, seed, which, n_seed};
+    a.pen = pen; a.cap = (uint32_t)pen_cap;
+    int tk = sc_time_begin(ctx, SC_K_ASTAR);
+    const dim3 grid((unsigned)((Q + RP_WAVES - 1) / RP_WAVES)), block(64 * RP_WAVES);
+    if (pen) hipLaunchKernelGGL(field_paths_kernel<true>, grid, block, 0, ctx->stream, a);
+    else hipLaunchKernelGGL(field_paths_kernel<false>, grid, block, 0, ctx->stream, (paths_args)a);
+    sc_time_end(ctx, tk);
+    SC_HIP(ctx, hipGetLastError());
+    return SC_OK;
+}
+
+extern "C" int sc_cost_field_multi_batch_host(sc_ctx* ctx, const int32_t* d2, const uint8_t* pen, int pen_cap, int G, const int32_t* fgrid,
+                                              int W, int H, int32_t r2_clear, const int32_t* seed, const int32_t* seed_cost,
+                                              const int32_t* seed_off, int n_seed, int F, int rounds, int32_t* g, int32_t* owner,
+                                              int32_t* fstatus) {
+    if (!cost_field_multi_args_ok(ctx, d2, pen, pen_cap, G, fgrid, W, H, seed, seed_off, n_seed, F, g)) return SC_ERR_INVALID;
+    // data contract: seed_off non-decreasing within 0 .. n_seed, every seed cost within 0 .. SC_FIELD_SEED_COST_MAX
+    for (int f = 0; f <= F; ++f)
+        if (seed_off[f] < 0 || seed_off[f] > n_seed || (f > 0 && seed_off[f] < seed_off[f - 1])) return SC_ERR_INVALID;
+    for (int s = 0; seed_cost && s < n_seed; ++s)
+        if (seed_cost[s] < 0 || seed_cost[s] > SC_FIELD_SEED_COST_MAX) return SC_ERR_INVALID;
+    SC_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t n = (size_t)W * H, fb = (size_t)F * 4, sb = (size_t)n_seed * 4;
+    sc_stage st(ctx);
+    const int i_d2 = st.in(d2, (size_t)G * n * 4), i_pen = st.in(pen, pen ? (size_t)G * n : 0), i_fg = st.in(fgrid, fb), i_sd = st.in(seed, sb),
+              i_sc = st.in(seed_cost, sb), i_so = st.in(seed_off, fb + 4);
+    const int o_g = st.out(g, fb * n), o_ow = st.out(owner, owner ? fb * n : 0), o_st = st.out(fstatus, fb);
+    int r = st.upload();
+    if (r == SC_OK)
+        r = sc_cost_field_multi_batch(ctx, st.dev<const int32_t>(i_d2), pen ? st.dev<const uint8_t>(i_pen) : nullptr, pen_cap, G,
+                                      fgrid ? st.dev<const int32_t>(i_fg) : nullptr, W, H, r2_clear, st.dev<const int32_t>(i_sd),
+                                      seed_cost ? st.dev<const int32_t>(i_sc) : nullptr, st.dev<const int32_t>(i_so), n_seed, F, rounds,
+                                      st.dev<int32_t>(o_g), owner ? st.dev<int32_t>(o_ow) : nullptr, fstatus ? st.dev<int32_t>(o_st) : nullptr);
+    return st.finish(r);
+}
+
+extern "C" int sc_field_paths_multi_batch_host(sc_ctx* ctx, const int32_t* d2, const uint8_t* pen, int pen_cap, int G, const int32_t* fgrid,
+                                               int W, int H, int32_t r2_clear, const int32_t* g, const int32_t* owner, const int32_t* seed,
+                                               int n_seed, int F, const int32_t* qfield, const int32_t* target, int Q, int Lmax, int to_seed,
+                                               int32_t* path, int32_t* len, int32_t* cost, int32_t* status, int32_t* which) {
+    if (!field_paths_multi_args_ok(ctx, d2, pen, pen_cap, G, fgrid, W, H, g, owner, seed, n_seed, F, qfield, target, Q, Lmax, path, len, cost,
+                                   status))
+        return SC_ERR_INVALID;
+    if (Q == 0) return SC_OK;
+    // data contract: every g value is a cost or SC_FIELD_INF
+    const size_t n = (size_t)W * H;
+    for (size_t i = 0; i < (size_t)F * n; ++i)
+        if (g[i] < 0) return SC_ERR_INVALID;
+    SC_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t fb = (size_t)F * 4, qb = (size_t)Q * 4;
+    sc_stage st(ctx);
+    const int i_d2 = st.in(d2, (size_t)G * n * 4), i_pen = st.in(pen, pen ? (size_t)G * n : 0), i_fg = st.in(fgrid, fb), i_g = st.in(g, fb * n),
+              i_ow = st.in(owner, fb * n), i_sd = st.in(seed, (size_t)n_seed * 4), i_qf = st.in(qfield, qb), i_t = st.in(target, qb);
+    const int o_p = st.out(path, qb * Lmax), o_len = st.out(len, qb), o_c = st.out(cost, qb), o_s = st.out(status, qb), o_w = st.out(which, qb);
+    int r = st.upload();
+    if (r == SC_OK)
+        r = sc_field_paths_multi_batch(ctx, st.dev<const int32_t>(i_d2), pen ? st.dev<const uint8_t>(i_pen) : nullptr, pen_cap, G,
+                                       fgrid ? st.dev<const int32_t>(i_fg) : nullptr, W, H, r2_clear, st.dev<const int32_t>(i_g),
+                                       st.dev<const int32_t>(i_ow), st.dev<const int32_t>(i_sd), n_seed, F, st.dev<const int32_t>(i_qf),
+                                       st.dev<const int32_t>(i_t), Q, Lmax, to_seed, st.dev<int32_t>(o_p), st.dev<int32_t>(o_len),
+                                       st.dev<int32_t>(o_c), st.dev<int32_t>(o_s), which ? st.dev<int32_t>(o_w) : nullptr);
+    return st.finish(r);
 }
 
 extern "C" int sc_cost_field_batch_host(sc_ctx* ctx, const int32_t* d2, int G, const int32_t* fgrid, int W, int H, int32_t r2_clear,

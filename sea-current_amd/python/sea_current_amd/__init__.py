@@ -19,6 +19,7 @@ HEADER_PATH = os.path.join(REPO_ROOT, "include", "sea_current_hip.h")
 
 EDT_INF = 2**31 - 1
 FIELD_INF = 2**31 - 1
+FIELD_SEED_COST_MAX = 1 << 24
 Q_OK, Q_NO_PATH, Q_BAD_ENDPOINT, Q_TRUNCATED, Q_RING_OVERFLOW, Q_BAD_PATH = 0, 1, 2, 3, 4, 5
 K_EDT_COLBITS, K_EDT_BAND, K_MOVES, K_ASTAR, K_TOPPRA, K_TOPPRA_SAMPLE, K_BEZIER, K_ARCLENGTH, K_RESAMPLE, K_OCC, K_NEAREST, K_FMT, K_GATHER = range(13)
 K_WAYPOINTS = 13
@@ -78,6 +79,12 @@ _SIGNATURES = {
                                            _vp]),
     "sc_field_paths_weighted_batch_host": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, C.c_int32, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp,
                                                 _vp, _vp]),
+    "sc_cost_field_multi_batch": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, C.c_int32, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "sc_cost_field_multi_batch_host": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, C.c_int32, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "sc_field_paths_multi_batch": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, C.c_int32, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp,
+                                        _vp, _vp, _vp]),
+    "sc_field_paths_multi_batch_host": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, C.c_int32, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _vp,
+                                             _vp, _vp, _vp, _vp]),
     "sc_components_batch": (_i, [_vp, _vp, _i, _i, _i, C.c_int32, _vp, _vp, _vp, _vp]),
     "sc_components_batch_host": (_i, [_vp, _vp, _i, _i, _i, C.c_int32, _vp, _vp, _vp, _vp]),
     "sc_reachable_batch": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _vp, _i, _vp]),
@@ -359,6 +366,47 @@ class Context:
         self._ck(self._l.sc_field_paths_batch(self._h, _ptr(d2), G, _ptr(fgrid), W, H, r2, _ptr(g), _ptr(roots), F, _ptr(qfield),
                                               _ptr(targets), Q, Lmax, int(bool(to_root)), _ptr(out["path"]), _ptr(out["len"]),
                                               _ptr(out["cost"]), _ptr(out["status"])), "sc_field_paths_batch")
+        return out
+
+    def cost_fields_multi(self, d2, seeds, seed_off, seed_cost=None, r2=0, fgrid=None, rounds=-1, want_owner=True, pen=None, pen_cap=255,
+                          out=None):
+        """Multi-source cost fields (sc_cost_field_multi_batch): field f starts from seeds[seed_off[f]:seed_off[f+1]] (cell
+        indices on grid fgrid[f]), each with the start cost seed_cost[s] (None: 0).  d2 int32 [H,W] or [G,H,W], seeds /
+        seed_cost int32 [n_seed], seed_off int32 [F+1], fgrid int32 [F] (None only with one grid), pen uint8 shaped like d2
+        (None: unweighted), all on the GPU.  Returns dict(g int32 [F,H,W], owner int32 [F,H,W]: the index into seeds of the
+        seed every cell's path ends at, -1 where g is FIELD_INF, None without want_owner; status int32 [F])."""
+        import torch
+        G, H, W = (1,) + tuple(d2.shape) if d2.dim() == 2 else tuple(d2.shape)
+        F = seed_off.shape[0] - 1
+        dev = d2.device
+        if out is None:
+            out = dict(g=torch.empty((F, H, W), dtype=torch.int32, device=dev),
+                       owner=torch.empty((F, H, W), dtype=torch.int32, device=dev) if want_owner else None,
+                       status=torch.empty(F, dtype=torch.int32, device=dev))
+        self._ck(self._l.sc_cost_field_multi_batch(self._h, _ptr(d2), _ptr(pen), pen_cap, G, _ptr(fgrid), W, H, r2, _ptr(seeds),
+                                                   _ptr(seed_cost), _ptr(seed_off), seeds.shape[0], F, rounds, _ptr(out["g"]),
+                                                   _ptr(out.get("owner")), _ptr(out["status"])), "sc_cost_field_multi_batch")
+        return out
+
+    def field_paths_multi(self, d2, fields, seeds, qfield, targets, r2=0, Lmax=4096, to_seed=False, fgrid=None, pen=None, pen_cap=255,
+                          out=None):
+        """Paths read from multi-source fields (sc_field_paths_multi_batch): query q follows field qfield[q] of `fields` (the
+        dict cost_fields_multi returned, with its owner) from targets[q] to the seed that owns it.  Returns astar_batch's dict
+        of GPU tensors plus which int32 [Q] (the index into seeds of that seed, -1 without a path); to_seed=True writes every
+        path target..seed.  pen, pen_cap: those cost_fields_multi computed the fields with."""
+        import torch
+        G, H, W = (1,) + tuple(d2.shape) if d2.dim() == 2 else tuple(d2.shape)
+        F = fields["g"].shape[0]
+        Q = targets.shape[0]
+        dev = d2.device
+        if out is None:
+            out = dict(path=torch.empty((Q, Lmax), dtype=torch.int32, device=dev), len=torch.empty(Q, dtype=torch.int32, device=dev),
+                       cost=torch.empty(Q, dtype=torch.int32, device=dev), status=torch.empty(Q, dtype=torch.int32, device=dev),
+                       which=torch.empty(Q, dtype=torch.int32, device=dev))
+        self._ck(self._l.sc_field_paths_multi_batch(self._h, _ptr(d2), _ptr(pen), pen_cap, G, _ptr(fgrid), W, H, r2, _ptr(fields["g"]),
+                                                    _ptr(fields["owner"]), _ptr(seeds), seeds.shape[0], F, _ptr(qfield), _ptr(targets), Q,
+                                                    Lmax, int(bool(to_seed)), _ptr(out["path"]), _ptr(out["len"]), _ptr(out["cost"]),
+                                                    _ptr(out["status"]), _ptr(out["which"])), "sc_field_paths_multi_batch")
         return out
 
     def path_waypoints(self, d2, res, r2=0, Wmax=None, out=None):
@@ -898,6 +946,39 @@ class Context:
         self._ck(self._l.sc_field_paths_batch_host(self._h, _ptr(d2), G, _ptr(fgrid), W, H, r2, _ptr(g), _ptr(roots), F, _ptr(qfield),
                                                    _ptr(targets), Q, Lmax, int(bool(to_root)), _ptr(out["path"]), _ptr(out["len"]),
                                                    _ptr(out["cost"]), _ptr(out["status"])), "sc_field_paths_batch_host")
+        return out
+
+    def cost_fields_multi_host(self, d2, seeds, seed_off, seed_cost=None, r2=0, fgrid=None, rounds=-1, want_owner=True, pen=None,
+                               pen_cap=255):
+        """Host form of cost_fields_multi (numpy in, numpy out)."""
+        d2 = np.ascontiguousarray(d2, dtype=np.int32)
+        seeds, seed_off = (np.ascontiguousarray(a, dtype=np.int32) for a in (seeds, seed_off))
+        seed_cost = None if seed_cost is None else np.ascontiguousarray(seed_cost, dtype=np.int32)
+        fgrid = None if fgrid is None else np.ascontiguousarray(fgrid, dtype=np.int32)
+        pen = None if pen is None else np.ascontiguousarray(pen, dtype=np.uint8)
+        G, H, W = (1,) + d2.shape if d2.ndim == 2 else d2.shape
+        F = seed_off.shape[0] - 1
+        out = dict(g=np.zeros((F, H, W), np.int32), owner=np.zeros((F, H, W), np.int32) if want_owner else None, status=np.zeros(F, np.int32))
+        self._ck(self._l.sc_cost_field_multi_batch_host(self._h, _ptr(d2), _ptr(pen), pen_cap, G, _ptr(fgrid), W, H, r2, _ptr(seeds),
+                                                        _ptr(seed_cost), _ptr(seed_off), seeds.shape[0], F, rounds, _ptr(out["g"]),
+                                                        _ptr(out["owner"]), _ptr(out["status"])), "sc_cost_field_multi_batch_host")
+        return out
+
+    def field_paths_multi_host(self, d2, fields, seeds, qfield, targets, r2=0, Lmax=4096, to_seed=False, fgrid=None, pen=None, pen_cap=255):
+        """Host form of field_paths_multi (numpy in, numpy out)."""
+        d2 = np.ascontiguousarray(d2, dtype=np.int32)
+        g, owner = (np.ascontiguousarray(fields[k], dtype=np.int32) for k in ("g", "owner"))
+        seeds, qfield, targets = (np.ascontiguousarray(a, dtype=np.int32) for a in (seeds, qfield, targets))
+        fgrid = None if fgrid is None else np.ascontiguousarray(fgrid, dtype=np.int32)
+        pen = None if pen is None else np.ascontiguousarray(pen, dtype=np.uint8)
+        G, H, W = (1,) + d2.shape if d2.ndim == 2 else d2.shape
+        F, Q = g.shape[0], targets.shape[0]
+        out = dict(path=np.full((Q, Lmax), -1, dtype=np.int32), len=np.zeros(Q, np.int32), cost=np.zeros(Q, np.int32),
+                   status=np.zeros(Q, np.int32), which=np.zeros(Q, np.int32))
+        self._ck(self._l.sc_field_paths_multi_batch_host(self._h, _ptr(d2), _ptr(pen), pen_cap, G, _ptr(fgrid), W, H, r2, _ptr(g), _ptr(owner),
+                                                         _ptr(seeds), seeds.shape[0], F, _ptr(qfield), _ptr(targets), Q, Lmax,
+                                                         int(bool(to_seed)), _ptr(out["path"]), _ptr(out["len"]), _ptr(out["cost"]),
+                                                         _ptr(out["status"]), _ptr(out["which"])), "sc_field_paths_multi_batch_host")
         return out
 
     def path_waypoints_host(self, d2, path, lens, status=None, r2=0, Wmax=None):

@@ -26,6 +26,8 @@
 //   (new) occupancy_grid::cost_fields / field_paths, planning_space::plan_from / plan_to: one search per shared endpoint
 //   (new) occupancy_grid::clearance_penalty, cost_fields / field_paths with a costmap, planning_space::soft_clearance /
 //         soft_penalty: clearance-weighted cost fields (an inflation layer) behind plan_from / plan_to
+//   (new) occupancy_grid::cost_fields_multi / field_paths_multi, planning_space::plan_to_nearest: one field from many
+//         goals, every start to the cheapest of them
 //
 // Differences that are deliberate: obstacle::closed is initialised (the reference leaves it
 // uninitialised, :197); library code never prints or calls std::exit (SC_ASSERT throws in DEBUG);
@@ -531,6 +533,61 @@ public:
                   "sc_field_paths_batch_host");
         return r;
     }
+    // Multi-source cost fields (sc_cost_field_multi_batch): field f starts from seeds[seed_off[f] .. seed_off[f+1]-1], each
+    // with the start cost seed_cost[s] (empty: all 0); g[f] = the cost to the cheapest of them, owner[f] = for every cell the
+    // index into seeds of the seed its path ends at (-1 where g is SC_FIELD_INF).  pen ([H][W], empty: unweighted) and
+    // pen_cap: the costmap of the weighted fields.  The result remembers what field_paths_multi needs.
+    struct multi_field_result {
+        std::vector<int32_t> g, owner, status, seeds, seed_off, seed_cost;  // g and owner are [F][H][W]
+        int32_t r2 = 0;
+        std::vector<uint8_t> pen;
+        int pen_cap = 0;
+    };
+    multi_field_result cost_fields_multi(const std::vector<int32_t>& seeds, const std::vector<int32_t>& seed_off,
+                                         const std::vector<int32_t>& seed_cost = {}, int32_t r2_clear = 0, int rounds = -1,
+                                         const std::vector<uint8_t>& pen = {}, int pen_cap = 255, gpu_context& ctx = default_context()) {
+        if (d2.size() != occ.size()) edt(ctx);
+        if (seed_off.empty()) throw std::invalid_argument("occupancy_grid::cost_fields_multi: seed_off needs one entry per field and one more");
+        if (!seed_cost.empty() && seed_cost.size() != seeds.size())
+            throw std::invalid_argument("occupancy_grid::cost_fields_multi: seeds and seed_cost differ in size");
+        if (!pen.empty() && pen.size() != occ.size()) throw std::invalid_argument("occupancy_grid::cost_fields_multi: pen is not [H][W]");
+        multi_field_result r;
+        const int F = (int)seed_off.size() - 1;
+        r.seeds = seeds; r.seed_off = seed_off; r.seed_cost = seed_cost;
+        r.r2 = r2_clear;
+        r.pen = pen;
+        r.pen_cap = pen.empty() ? 0 : pen_cap;
+        r.g.assign((size_t)F * W * H, SC_FIELD_INF); r.owner.assign((size_t)F * W * H, -1); r.status.assign(F, SC_Q_BAD_ENDPOINT);
+        if (F == 0) return r;
+        ctx.check(sc_cost_field_multi_batch_host(ctx.get(), d2.data(), pen.empty() ? nullptr : pen.data(), r.pen_cap, 1, nullptr, W, H, r2_clear,
+                                                 seeds.data(), seed_cost.empty() ? nullptr : seed_cost.data(), seed_off.data(),
+                                                 (int)seeds.size(), F, rounds, r.g.data(), r.owner.data(), r.status.data()),
+                  "sc_cost_field_multi_batch_host");
+        return r;
+    }
+    // Paths read from multi-source fields (sc_field_paths_multi_batch): query q walks field qfield[q] from targets[q] to the
+    // seed that owns it; which[q] = that seed's index into seeds, -1 without a path.  to_seed = false writes seed..target,
+    // true target..seed.  Unweighted, path, len and cost - seed_cost[which] equal astar_batch(seeds[which], target).
+    struct multi_batch_result : batch_result {
+        std::vector<int32_t> which;
+    };
+    multi_batch_result field_paths_multi(const multi_field_result& fr, const std::vector<int32_t>& qfield, const std::vector<int32_t>& targets,
+                                         int Lmax = 0, bool to_seed = false, gpu_context& ctx = default_context()) {
+        if (d2.size() != occ.size()) edt(ctx);
+        multi_batch_result r;
+        const int Q = (int)targets.size(), F = (int)fr.status.size();
+        if (qfield.size() != targets.size()) throw std::invalid_argument("occupancy_grid::field_paths_multi: qfield and targets differ in size");
+        r.Lmax = Lmax > 0 ? Lmax : 4 * (W + H);
+        r.path.assign((size_t)Q * r.Lmax, -1); r.len.assign(Q, 0); r.cost.assign(Q, -1); r.status.assign(Q, SC_Q_NO_PATH); r.which.assign(Q, -1);
+        if (Q == 0) return r;
+        if (F == 0) { r.status.assign(Q, SC_Q_BAD_ENDPOINT); return r; }
+        ctx.check(sc_field_paths_multi_batch_host(ctx.get(), d2.data(), fr.pen.empty() ? nullptr : fr.pen.data(), fr.pen_cap, 1, nullptr, W, H,
+                                                  fr.r2, fr.g.data(), fr.owner.data(), fr.seeds.data(), (int)fr.seeds.size(), F, qfield.data(),
+                                                  targets.data(), Q, r.Lmax, to_seed ? 1 : 0, r.path.data(), r.len.data(), r.cost.data(),
+                                                  r.status.data(), r.which.data()),
+                  "sc_field_paths_multi_batch_host");
+        return r;
+    }
     struct waypoint_result {
         std::vector<int32_t> wp, n, status;  // wp is [Q][Wmax] cell indices, start..goal; n / status [Q]
         int Wmax = 0;
@@ -793,6 +850,47 @@ public:
         auto br = g.field_paths(fr, qf, s, 0, true, ctx);
         return to_points(g, br, r2, starts, std::vector<Vector2f>(starts.size(), goal), "plan_to", ctx);
     }
+    // Many starts, many goals (a fleet where every robot goes to the cheapest of K docks): one multi-source field seeded at
+    // all goal cells, goal k with the start cost goal_costs[k] (empty: all 0; in the units of the move costs, 10 per cell
+    // step) -- weighted when the soft knobs are on, as for plan_to.  Per start: the path start..goal, the index of the chosen
+    // goal (-1 without a path) and the cost, goal cost included (-1 without a path).  paths[q] equals
+    // plan_to(starts, goals[goal[q]])[q].
+    struct nearest_result {
+        std::vector<std::optional<std::vector<Vector2f>>> paths;
+        std::vector<int32_t> goal, cost;
+    };
+    nearest_result plan_to_nearest(const std::vector<Vector2f>& starts, const std::vector<Vector2f>& goals,
+                                   const std::vector<int32_t>& goal_costs = {}, gpu_context& ctx = default_context()) {
+        if (!goal_costs.empty() && goal_costs.size() != goals.size())
+            throw std::invalid_argument("planning_space::plan_to_nearest: goals and goal_costs differ in size");
+        occupancy_grid g = make_grid(ctx);
+        g.edt(ctx);
+        std::vector<int32_t> s(starts.size()), qf(starts.size(), 0), seeds(goals.size());
+        for (size_t i = 0; i < starts.size(); ++i) s[i] = g.cell_of(starts[i]);
+        for (size_t k = 0; k < goals.size(); ++k) seeds[k] = g.cell_of(goals[k]);
+        const int32_t r2 = clearance_r2(g);
+        occupancy_grid::multi_field_result fr;
+        if (soft_clearance > 0.0f && soft_penalty > 0) {
+            int32_t r2_soft;
+            int pen_max;
+            soft_knobs(g, r2_soft, pen_max);
+            fr = g.cost_fields_multi(seeds, {0, (int32_t)seeds.size()}, goal_costs, r2, -1, g.clearance_penalty(r2, r2_soft, pen_max, ctx),
+                                     pen_max, ctx);
+        } else {
+            fr = g.cost_fields_multi(seeds, {0, (int32_t)seeds.size()}, goal_costs, r2, -1, {}, 255, ctx);
+        }
+        auto br = g.field_paths_multi(fr, qf, s, 0, true, ctx);
+        std::vector<Vector2f> ends(starts.size(), Vector2f(0, 0));
+        for (size_t q = 0; q < starts.size(); ++q)
+            if (br.which[q] >= 0) ends[q] = goals[(size_t)br.which[q]];
+        nearest_result out;
+        out.paths = to_points(g, br, r2, starts, ends, "plan_to_nearest", ctx);
+        out.goal = br.which;
+        out.cost = br.cost;
+        for (size_t q = 0; q < starts.size(); ++q)
+            if (!out.paths[q]) { out.goal[q] = -1; out.cost[q] = -1; }
+        return out;
+    }
 
 private:
     int32_t clearance_r2(const occupancy_grid& g) const {
@@ -802,10 +900,16 @@ private:
     // the field of plan_from / plan_to: weighted when both soft knobs are positive, else today's
     occupancy_grid::field_result fields_of(occupancy_grid& g, int32_t root, int32_t r2, gpu_context& ctx) const {
         if (!(soft_clearance > 0.0f && soft_penalty > 0)) return g.cost_fields({root}, r2, -1, ctx);
-        const float sc = soft_clearance / g.resolution;
-        const int32_t r2_soft = std::max((int32_t)std::ceil(sc * sc), (int32_t)1);
-        const int pen_max = std::min(soft_penalty, 255);
+        int32_t r2_soft;
+        int pen_max;
+        soft_knobs(g, r2_soft, pen_max);
         return g.cost_fields({root}, g.clearance_penalty(r2, r2_soft, pen_max, ctx), pen_max, r2, -1, ctx);
+    }
+    // the costmap parameters the soft knobs stand for
+    void soft_knobs(const occupancy_grid& g, int32_t& r2_soft, int& pen_max) const {
+        const float sc = soft_clearance / g.resolution;
+        r2_soft = std::max((int32_t)std::ceil(sc * sc), (int32_t)1);
+        pen_max = std::min(soft_penalty, 255);
     }
     // cell paths (astar_batch's layout) -> the exact endpoints around the centres of the interior cells or waypoints
     std::vector<std::optional<std::vector<Vector2f>>> to_points(occupancy_grid& g, const occupancy_grid::batch_result& br, int32_t r2,
