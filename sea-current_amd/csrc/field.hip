@@ -666,26 +666,56 @@ int field_default_rounds(int TX, int TY) { return 2 * (TX + TY) + 16; }
 
 }  // namespace
 
-// the argument checks of the device and _host forms
-static bool cost_field_args_ok(const sc_ctx* ctx, const int32_t* d2, int G, const int32_t* fgrid, int W, int H, const int32_t* root, int F,
-                               const int32_t* g) {
-    return ctx && d2 && root && g && G > 0 && F > 0 && W > 0 && H > 0 && W <= SC_MAX_DIM && H <= SC_MAX_DIM && (fgrid || G == 1);
+// ---- host side -----------------------------------------------------------------------------------------------------
+// The twelve entries (three contracts x build / read-out x device / _host form) pack their arguments and call one of four
+// functions: field_build, field_read and their _host stagers.  field_args_ok is the argument contract of all of them.
+enum field_contract { FC_ROOTS, FC_ROOTS_WEIGHTED, FC_MULTI };
+
+// the map side of a call; pen NULL: unweighted (the FC_ROOTS entries pass none)
+struct field_map {
+    const int32_t* d2;
+    const uint8_t* pen;
+    int pen_cap, G;
+    const int32_t* fgrid;
+    int W, H;
+    int32_t r2_clear;
+    int F;
+};
+
+// the query side of a read-out; to_end: write target..end cell; which [Q] or NULL (FC_MULTI)
+struct field_query {
+    const int32_t* qfield;
+    const int32_t* target;
+    int Q, Lmax, to_end;
+    int32_t *path, *len, *cost, *status, *which;
+};
+
+// Where the paths of a field end is a seed_args in every contract: the seed lists (FC_MULTI), or {root, NULL, NULL, F} --
+// one seed of cost 0 per field.  q NULL: the call is a build (FC_MULTI: seed_off required), else a read-out (FC_MULTI: owner
+// required).  Overflow contract: a simple path enters each of the other W*H - 1 cells at most once, on top of a seed cost
+// (FC_MULTI); unweighted it holds at every size up to SC_MAX_DIM^2, so FC_ROOTS has no bound of its own.
+static bool field_args_ok(const sc_ctx* ctx, field_contract c, const field_map& m, const seed_args& sa, const int32_t* g,
+                          const int32_t* owner, const field_query* q) {
+    if (!ctx || !m.d2 || !g || m.G <= 0 || m.F <= 0 || m.W <= 0 || m.H <= 0) return false;
+    if (!(m.W <= SC_MAX_DIM && m.H <= SC_MAX_DIM && (m.fgrid || m.G == 1))) return false;
+    if (sa.n_seed < 0 || (!sa.seed && sa.n_seed > 0)) return false;
+    if (c == FC_ROOTS_WEIGHTED && !m.pen) return false;
+    if (m.pen && (m.pen_cap < 0 || m.pen_cap > 255)) return false;
+    const long long cap = m.pen ? m.pen_cap : 0, top = c == FC_MULTI ? SC_FIELD_SEED_COST_MAX : 0;
+    if ((14 + cap) * ((long long)m.W * m.H - 1) + top > (long long)INT32_MAX - 1) return false;
+    if (!q) return c != FC_MULTI || sa.off;
+    return (c != FC_MULTI || owner) && q->qfield && q->target && q->path && q->len && q->cost && q->status && q->Q >= 0 && q->Lmax > 0;
 }
 
-static bool field_paths_args_ok(const sc_ctx* ctx, const int32_t* d2, int G, const int32_t* fgrid, int W, int H, const int32_t* g,
-                                const int32_t* root, int F, const int32_t* qfield, const int32_t* target, int Q, int Lmax, const int32_t* path,
-                                const int32_t* len, const int32_t* cost, const int32_t* status) {
-    return ctx && d2 && g && root && qfield && target && path && len && cost && status && G > 0 && F > 0 && W > 0 && H > 0 &&
-           W <= SC_MAX_DIM && H <= SC_MAX_DIM && Q >= 0 && Lmax > 0 && (fgrid || G == 1);
+// the compute units of the context's device, asked once
+static int field_cu_count(sc_ctx* ctx) {
+    if (ctx->cu_count) return SC_OK;
+    int cu = 0;
+    SC_HIP(ctx, hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, ctx->device));
+    ctx->cu_count = cu > 0 ? cu : 1;
+    return SC_OK;
 }
 
-// the overflow contract of the weighted entries: a simple path enters each of the other W*H - 1 cells at most once
-static bool weighted_args_ok(const uint8_t* pen, int pen_cap, int W, int H) {
-    if (!pen || pen_cap < 0 || pen_cap > 255) return false;
-    return (long long)(14 + pen_cap) * ((long long)W * H - 1) <= (long long)INT32_MAX - 1;
-}
-
-// both field entries; pen NULL: the unweighted kernels
 // the jump launches of the owner pass: ceil(log2(W H))
 static int owner_jumps(int W, int H) {
     int k = 0;
@@ -693,11 +723,12 @@ static int owner_jumps(int W, int H) {
     return k;
 }
 
-// every field entry; pen NULL: the unweighted kernels.  sa: the seed lists (the single-root entries: seed = root, one per
-// field, cost 0).  owner != NULL: the owner pass follows.
-static int cost_field_launch(sc_ctx* ctx, const int32_t* d2, const uint8_t* pen, int pen_cap, int G, const int32_t* fgrid, int W, int H,
-                             int32_t r2_clear, const seed_args& sa, int F, int rounds, int32_t* g, int32_t* owner, int32_t* fstatus) {
+// every build; m.pen NULL: the unweighted kernels.  owner != NULL: the owner pass follows.
+static int field_build(sc_ctx* ctx, field_contract c, const field_map& m, const seed_args& sa, int rounds, int32_t* g, int32_t* owner,
+                       int32_t* fstatus) {
+    if (!field_args_ok(ctx, c, m, sa, g, owner, nullptr)) return SC_ERR_INVALID;
     SC_HIP(ctx, hipSetDevice(ctx->device));
+    const int G = m.G, W = m.W, H = m.H, F = m.F;
     const int TX = (W + FT - 1) / FT, TY = (H + FT - 1) / FT, nt = TX * TY;
     if ((long long)F * nt > 0x7FFFFFFF / 2) return SC_ERR_INVALID;
     if (rounds < 0) rounds = field_default_rounds(TX, TY);
@@ -709,21 +740,22 @@ static int cost_field_launch(sc_ctx* ctx, const int32_t* d2, const uint8_t* pen,
                  o_left = o_ctr + al256((size_t)(rounds + 1) * 4), total = o_left + al256((size_t)(jumps + 1) * 4);
     int r = sc_scratch_reserve(ctx, &ctx->fld_mask, mask_b);
     if (r == SC_OK) r = sc_scratch_reserve(ctx, &ctx->fld_state, total);
+    if (r == SC_OK) r = field_cu_count(ctx);
     if (r != SC_OK) return r;
     char* b = (char*)ctx->fld_state.p;
     field_args_w a;
-    a.pen = pen; a.cap = (uint32_t)pen_cap;
-    a.mask = (const uint64_t*)ctx->fld_mask.p; a.d2 = d2; a.fgrid = fgrid; a.g = g;
+    a.pen = m.pen; a.cap = (uint32_t)m.pen_cap;
+    a.mask = (const uint64_t*)ctx->fld_mask.p; a.d2 = m.d2; a.fgrid = m.fgrid; a.g = g;
     a.ok = (int32_t*)(b + o_ok); a.stamp = (int32_t*)(b + o_stamp); a.seeded = (int32_t*)(b + o_seeded);
     a.list[0] = (int32_t*)(b + o_l0); a.list[1] = (int32_t*)(b + o_l1); a.ctr = (int32_t*)(b + o_ctr);
     a.G = G; a.W = W; a.H = H; a.F = F; a.TX = TX; a.TY = TY; a.nt = nt;
-    a.thr = r2_clear > 1 ? r2_clear : 1;
+    a.thr = m.r2_clear > 1 ? m.r2_clear : 1;
     int tk = sc_time_begin(ctx, SC_K_ASTAR);
     SC_HIP(ctx, hipMemsetAsync(b + o_stamp, 0, o_l0 - o_stamp, ctx->stream));
     SC_HIP(ctx, hipMemsetAsync(b + o_ctr, 0, total - o_ctr, ctx->stream));
     {
         const size_t nm = (size_t)G * TY * W;
-        hipLaunchKernelGGL(field_mask_kernel, dim3((unsigned)((nm + 255) / 256)), dim3(256), 0, ctx->stream, d2, G, W, H, TY, a.thr,
+        hipLaunchKernelGGL(field_mask_kernel, dim3((unsigned)((nm + 255) / 256)), dim3(256), 0, ctx->stream, m.d2, G, W, H, TY, a.thr,
                            (uint64_t*)ctx->fld_mask.p);
     }
     {
@@ -734,28 +766,18 @@ static int cost_field_launch(sc_ctx* ctx, const int32_t* d2, const uint8_t* pen,
         hipLaunchKernelGGL(field_seed_kernel, dim3(F < 65535 ? F : 65535), dim3(64), 0, ctx->stream, (field_args)a, sa, fstatus);
     }
     if (rounds > 0) {
-        if (!ctx->cu_count) {
-            int cu = 0;
-            SC_HIP(ctx, hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, ctx->device));
-            ctx->cu_count = cu > 0 ? cu : 1;
-        }
         const long long cap = (long long)ctx->cu_count * 8;
         const unsigned blocks = (unsigned)((long long)F * nt < cap ? (long long)F * nt : cap);
         for (int k = 0; k < rounds; ++k) {
-            if (pen) hipLaunchKernelGGL(field_round_kernel<true>, dim3(blocks), dim3(64), 0, ctx->stream, a, k);
+            if (m.pen) hipLaunchKernelGGL(field_round_kernel<true>, dim3(blocks), dim3(64), 0, ctx->stream, a, k);
             else hipLaunchKernelGGL(field_round_kernel<false>, dim3(blocks), dim3(64), 0, ctx->stream, (field_args)a, k);
         }
     }
-    if (pen) hipLaunchKernelGGL((field_finish_kernel<true, FIN_WAVES_W>), dim3(F), dim3(64 * FIN_WAVES_W), 0, ctx->stream, a, rounds);
+    if (m.pen) hipLaunchKernelGGL((field_finish_kernel<true, FIN_WAVES_W>), dim3(F), dim3(64 * FIN_WAVES_W), 0, ctx->stream, a, rounds);
     else hipLaunchKernelGGL((field_finish_kernel<false, FIN_WAVES>), dim3(F), dim3(64 * FIN_WAVES), 0, ctx->stream, (field_args)a, rounds);
     if (owner) {
         const size_t cells = (size_t)F * W * H;
-        owner_args oa{d2, pen, fgrid, g, owner, (int32_t*)(b + o_left), G, W, H, F, a.thr, (uint32_t)pen_cap};
-        if (!ctx->cu_count) {
-            int cu = 0;
-            SC_HIP(ctx, hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, ctx->device));
-            ctx->cu_count = cu > 0 ? cu : 1;
-        }
+        owner_args oa{m.d2, m.pen, m.fgrid, g, owner, (int32_t*)(b + o_left), G, W, H, F, a.thr, (uint32_t)m.pen_cap};
         const size_t cap = (size_t)ctx->cu_count * 8, need = (cells + 255) / 256;
         const unsigned blocks = (unsigned)(need < cap ? need : cap);
         SC_HIP(ctx, hipMemsetAsync(owner, 0x7F, cells * 4, ctx->stream));
@@ -768,236 +790,162 @@ static int cost_field_launch(sc_ctx* ctx, const int32_t* d2, const uint8_t* pen,
     return SC_OK;
 }
 
+// every read-out: the end cell of a query is sa.seed[qfield] (the roots), FC_MULTI: sa.seed[owner[target]]
+static int field_read(sc_ctx* ctx, field_contract c, const field_map& m, const seed_args& sa, const int32_t* g, const int32_t* owner,
+                      const field_query& q) {
+    if (!field_args_ok(ctx, c, m, sa, g, owner, &q)) return SC_ERR_INVALID;
+    if (q.Q == 0) return SC_OK;
+    SC_HIP(ctx, hipSetDevice(ctx->device));
+    const bool multi = c == FC_MULTI;
+    paths_args_w a;
+    (paths_args&)a = paths_args{m.d2, m.fgrid, g, multi ? nullptr : sa.seed, q.qfield, q.target, m.G, m.W, m.H, m.F, q.Q, q.Lmax,
+                                q.to_end ? 1 : 0, m.r2_clear > 1 ? m.r2_clear : 1, q.path, q.len, q.cost, q.status, owner,
+                                multi ? sa.seed : nullptr, q.which, multi ? sa.n_seed : 0};
+    a.pen = m.pen; a.cap = (uint32_t)m.pen_cap;
+    int tk = sc_time_begin(ctx, SC_K_ASTAR);
+    const dim3 grid((unsigned)((q.Q + RP_WAVES - 1) / RP_WAVES)), block(64 * RP_WAVES);
+    if (!m.pen) hipLaunchKernelGGL(field_paths_kernel<false>, grid, block, 0, ctx->stream, (paths_args)a);
+    else hipLaunchKernelGGL(field_paths_kernel<true>, grid, block, 0, ctx->stream, a);
+    sc_time_end(ctx, tk);
+    SC_HIP(ctx, hipGetLastError());
+    return SC_OK;
+}
+
+// the device copy of a staged array, NULL where the caller passed none
+template <class T> static T* staged(const sc_stage& st, int i, T* host) { return host ? st.dev<T>(i) : nullptr; }
+
+// the _host form of every build: the data contract, then field_build on device copies (an absent array: an empty slot)
+static int field_build_host(sc_ctx* ctx, field_contract c, const field_map& m, const seed_args& sa, int rounds, int32_t* g,
+                            int32_t* owner, int32_t* fstatus) {
+    if (!field_args_ok(ctx, c, m, sa, g, owner, nullptr)) return SC_ERR_INVALID;
+    // data contract: seed_off non-decreasing within 0 .. n_seed, every seed cost within 0 .. SC_FIELD_SEED_COST_MAX
+    for (int f = 0; sa.off && f <= m.F; ++f)
+        if (sa.off[f] < 0 || sa.off[f] > sa.n_seed || (f > 0 && sa.off[f] < sa.off[f - 1])) return SC_ERR_INVALID;
+    for (int s = 0; sa.cost && s < sa.n_seed; ++s)
+        if (sa.cost[s] < 0 || sa.cost[s] > SC_FIELD_SEED_COST_MAX) return SC_ERR_INVALID;
+    SC_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t n = (size_t)m.W * m.H, fb = (size_t)m.F * 4, sb = (size_t)sa.n_seed * 4;
+    sc_stage st(ctx);
+    const int i_d2 = st.in(m.d2, (size_t)m.G * n * 4), i_pen = st.in(m.pen, m.pen ? (size_t)m.G * n : 0), i_fg = st.in(m.fgrid, fb),
+              i_sd = st.in(sa.seed, sb), i_sc = st.in(sa.cost, sa.cost ? sb : 0), i_so = st.in(sa.off, sa.off ? fb + 4 : 0);
+    const int o_g = st.out(g, fb * n), o_ow = st.out(owner, owner ? fb * n : 0), o_st = st.out(fstatus, fb);
+    int r = st.upload();
+    if (r == SC_OK)
+        r = field_build(ctx, c, {staged(st, i_d2, m.d2), staged(st, i_pen, m.pen), m.pen_cap, m.G, staged(st, i_fg, m.fgrid), m.W, m.H, m.r2_clear, m.F},
+                        {staged(st, i_sd, sa.seed), staged(st, i_sc, sa.cost), staged(st, i_so, sa.off), sa.n_seed}, rounds, staged(st, o_g, g),
+                        staged(st, o_ow, owner), staged(st, o_st, fstatus));
+    return st.finish(r);
+}
+
+// the _host form of every read-out
+static int field_read_host(sc_ctx* ctx, field_contract c, const field_map& m, const seed_args& sa, const int32_t* g, const int32_t* owner,
+                           const field_query& q) {
+    if (!field_args_ok(ctx, c, m, sa, g, owner, &q)) return SC_ERR_INVALID;
+    if (q.Q == 0) return SC_OK;
+    // data contract: every g value is a cost or SC_FIELD_INF
+    const size_t n = (size_t)m.W * m.H;
+    for (size_t i = 0; i < (size_t)m.F * n; ++i)
+        if (g[i] < 0) return SC_ERR_INVALID;
+    SC_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t fb = (size_t)m.F * 4, qb = (size_t)q.Q * 4;
+    sc_stage st(ctx);
+    const int i_d2 = st.in(m.d2, (size_t)m.G * n * 4), i_pen = st.in(m.pen, m.pen ? (size_t)m.G * n : 0), i_fg = st.in(m.fgrid, fb),
+              i_g = st.in(g, fb * n), i_ow = st.in(owner, owner ? fb * n : 0), i_sd = st.in(sa.seed, (size_t)sa.n_seed * 4),
+              i_qf = st.in(q.qfield, qb), i_t = st.in(q.target, qb);
+    const int o_p = st.out(q.path, qb * q.Lmax), o_len = st.out(q.len, qb), o_c = st.out(q.cost, qb), o_s = st.out(q.status, qb),
+              o_w = st.out(q.which, qb);
+    int r = st.upload();
+    if (r == SC_OK)
+        r = field_read(ctx, c, {staged(st, i_d2, m.d2), staged(st, i_pen, m.pen), m.pen_cap, m.G, staged(st, i_fg, m.fgrid), m.W, m.H, m.r2_clear, m.F},
+                       {staged(st, i_sd, sa.seed), nullptr, nullptr, sa.n_seed}, staged(st, i_g, g), staged(st, i_ow, owner),
+                       {staged(st, i_qf, q.qfield), staged(st, i_t, q.target), q.Q, q.Lmax, q.to_end, staged(st, o_p, q.path),
+                        staged(st, o_len, q.len), staged(st, o_c, q.cost), staged(st, o_s, q.status), staged(st, o_w, q.which)});
+    return st.finish(r);
+}
+
+// ---- the C ABI: each entry packs {map}, {ends}, [{query}] for its contract
 extern "C" int sc_cost_field_batch(sc_ctx* ctx, const int32_t* d2, int G, const int32_t* fgrid, int W, int H, int32_t r2_clear,
                                    const int32_t* root, int F, int rounds, int32_t* g, int32_t* fstatus) {
-    if (!cost_field_args_ok(ctx, d2, G, fgrid, W, H, root, F, g)) return SC_ERR_INVALID;
-    return cost_field_launch(ctx, d2, nullptr, 0, G, fgrid, W, H, r2_clear, seed_args{root, nullptr, nullptr, F}, F, rounds, g, nullptr, fstatus);
+    return field_build(ctx, FC_ROOTS, {d2, nullptr, 0, G, fgrid, W, H, r2_clear, F}, {root, nullptr, nullptr, F}, rounds, g, nullptr, fstatus);
+}
+
+extern "C" int sc_cost_field_batch_host(sc_ctx* ctx, const int32_t* d2, int G, const int32_t* fgrid, int W, int H, int32_t r2_clear,
+                                        const int32_t* root, int F, int rounds, int32_t* g, int32_t* fstatus) {
+    return field_build_host(ctx, FC_ROOTS, {d2, nullptr, 0, G, fgrid, W, H, r2_clear, F}, {root, nullptr, nullptr, F}, rounds, g, nullptr,
+                            fstatus);
 }
 
 extern "C" int sc_cost_field_weighted_batch(sc_ctx* ctx, const int32_t* d2, const uint8_t* pen, int pen_cap, int G, const int32_t* fgrid,
                                             int W, int H, int32_t r2_clear, const int32_t* root, int F, int rounds, int32_t* g,
                                             int32_t* fstatus) {
-    if (!cost_field_args_ok(ctx, d2, G, fgrid, W, H, root, F, g) || !weighted_args_ok(pen, pen_cap, W, H)) return SC_ERR_INVALID;
-    return cost_field_launch(ctx, d2, pen, pen_cap, G, fgrid, W, H, r2_clear, seed_args{root, nullptr, nullptr, F}, F, rounds, g, nullptr, fstatus);
+    return field_build(ctx, FC_ROOTS_WEIGHTED, {d2, pen, pen_cap, G, fgrid, W, H, r2_clear, F}, {root, nullptr, nullptr, F}, rounds, g, nullptr,
+                       fstatus);
 }
 
-extern "C" int sc_field_paths_batch(sc_ctx* ctx, const int32_t* d2, int G, const int32_t* fgrid, int W, int H, int32_t r2_clear,
-                                    const int32_t* g, const int32_t* root, int F, const int32_t* qfield, const int32_t* target, int Q,
-                                    int Lmax, int to_root, int32_t* path, int32_t* len, int32_t* cost, int32_t* status) {
-    if (!field_paths_args_ok(ctx, d2, G, fgrid, W, H, g, root, F, qfield, target, Q, Lmax, path, len, cost, status)) return SC_ERR_INVALID;
-    if (Q == 0) return SC_OK;
-    SC_HIP(ctx, hipSetDevice(ctx->device));
-    paths_args a{d2, fgrid, g, root, qfield, target, G, W, H, F, Q, Lmax, to_root ? 1 : 0, r2_clear > 1 ? r2_clear : 1, path, len, cost, status};
-    int tk = sc_time_begin(ctx, SC_K_ASTAR);
-    hipLaunchKernelGGL(field_paths_kernel<false>, dim3((unsigned)((Q + RP_WAVES - 1) / RP_WAVES)), dim3(64 * RP_WAVES), 0, ctx->stream, a);
-    sc_time_end(ctx, tk);
-    SC_HIP(ctx, hipGetLastError());
-    return SC_OK;
-}
-
-extern "C" int sc_field_paths_weighted_batch(sc_ctx* ctx, const int32_t* d2, const uint8_t* pen, int pen_cap, int G, const int32_t* fgrid,
-                                             int W, int H, int32_t r2_clear, const int32_t* g, const int32_t* root, int F,
-                                             const int32_t* qfield, const int32_t* target, int Q, int Lmax, int to_root, int32_t* path,
-                                             int32_t* len, int32_t* cost, int32_t* status) {
-    if (!field_paths_args_ok(ctx, d2, G, fgrid, W, H, g, root, F, qfield, target, Q, Lmax, path, len, cost, status) ||
-        !weighted_args_ok(pen, pen_cap, W, H))
-        return SC_ERR_INVALID;
-    if (Q == 0) return SC_OK;
-    SC_HIP(ctx, hipSetDevice(ctx->device));
-    paths_args_w a;
-    (paths_args&)a = paths_args{d2, fgrid, g, root, qfield, target, G, W, H, F, Q, Lmax, to_root ? 1 : 0, r2_clear > 1 ? r2_clear : 1,
-                                path, len, cost, status};
-    a.pen = pen; a.cap = (uint32_t)pen_cap;
-    int tk = sc_time_begin(ctx, SC_K_ASTAR);
-    hipLaunchKernelGGL(field_paths_kernel<true>, dim3((unsigned)((Q + RP_WAVES - 1) / RP_WAVES)), dim3(64 * RP_WAVES), 0, ctx->stream, a);
-    sc_time_end(ctx, tk);
-    SC_HIP(ctx, hipGetLastError());
-    return SC_OK;
-}
-
-// the overflow contract of the multi-source entries: a simple path enters each of the other W*H - 1 cells at most once, on
-// top of a seed cost
-static bool multi_args_ok(const uint8_t* pen, int pen_cap, int W, int H) {
-    if (pen && (pen_cap < 0 || pen_cap > 255)) return false;
-    return (long long)(14 + (pen ? pen_cap : 0)) * ((long long)W * H - 1) + SC_FIELD_SEED_COST_MAX <= (long long)INT32_MAX - 1;
-}
-
-static bool cost_field_multi_args_ok(const sc_ctx* ctx, const int32_t* d2, const uint8_t* pen, int pen_cap, int G, const int32_t* fgrid, int W,
-                                     int H, const int32_t* seed, const int32_t* seed_off, int n_seed, int F, const int32_t* g) {
-    return ctx && d2 && g && seed_off && n_seed >= 0 && (seed || n_seed == 0) && G > 0 && F > 0 && W > 0 && H > 0 && W <= SC_MAX_DIM &&
-           H <= SC_MAX_DIM && (fgrid || G == 1) && multi_args_ok(pen, pen_cap, W, H);
-}
-
-static bool field_paths_multi_args_ok(const sc_ctx* ctx, const int32_t* d2, const uint8_t* pen, int pen_cap, int G, const int32_t* fgrid, int W,
-                                      int H, const int32_t* g, const int32_t* owner, const int32_t* seed, int n_seed, int F,
-                                      const int32_t* qfield, const int32_t* target, int Q, int Lmax, const int32_t* path, const int32_t* len,
-                                      const int32_t* cost, const int32_t* status) {
-    return ctx && d2 && g && owner && qfield && target && path && len && cost && status && n_seed >= 0 && (seed || n_seed == 0) && G > 0 &&
-           F > 0 && W > 0 && H > 0 && W <= SC_MAX_DIM && H <= SC_MAX_DIM && Q >= 0 && Lmax > 0 && (fgrid || G == 1) &&
-           multi_args_ok(pen, pen_cap, W, H);
+extern "C" int sc_cost_field_weighted_batch_host(sc_ctx* ctx, const int32_t* d2, const uint8_t* pen, int pen_cap, int G, const int32_t* fgrid,
+                                                 int W, int H, int32_t r2_clear, const int32_t* root, int F, int rounds, int32_t* g,
+                                                 int32_t* fstatus) {
+    return field_build_host(ctx, FC_ROOTS_WEIGHTED, {d2, pen, pen_cap, G, fgrid, W, H, r2_clear, F}, {root, nullptr, nullptr, F}, rounds, g,
+                            nullptr, fstatus);
 }
 
 extern "C" int sc_cost_field_multi_batch(sc_ctx* ctx, const int32_t* d2, const uint8_t* pen, int pen_cap, int G, const int32_t* fgrid, int W,
                                          int H, int32_t r2_clear, const int32_t* seed, const int32_t* seed_cost, const int32_t* seed_off,
                                          int n_seed, int F, int rounds, int32_t* g, int32_t* owner, int32_t* fstatus) {
-    if (!cost_field_multi_args_ok(ctx, d2, pen, pen_cap, G, fgrid, W, H, seed, seed_off, n_seed, F, g)) return SC_ERR_INVALID;
-    return cost_field_launch(ctx, d2, pen, pen_cap, G, fgrid, W, H, r2_clear, seed_args{seed, seed_cost, seed_off, n_seed}, F, rounds, g, owner,
-                             fstatus);
-}
-
-extern "C" int sc_field_paths_multi_batch(sc_ctx* ctx, const int32_t* d2, const uint8_t* pen, int pen_cap, int G, const int32_t* fgrid, int W,
-                                          int H, int32_t r2_clear, const int32_t* g, const int32_t* owner, const int32_t* seed, int n_seed,
-                                          int F, const int32_t* qfield, const int32_t* target, int Q, int Lmax, int to_seed, int32_t* path,
-                                          int32_t* len, int32_t* cost, int32_t* status, int32_t* which) {
-    if (!field_paths_multi_args_ok(ctx, d2, pen, pen_cap, G, fgrid, W, H, g, owner, seed, n_seed, F, qfield, target, Q, Lmax, path, len, cost,
-                                   status))
-        return SC_ERR_INVALID;
-    if (Q == 0) return SC_OK;
-    SC_HIP(ctx, hipSetDevice(ctx->device));
-    paths_args_w a;
-    (paths_args&)a = paths_args{d2, fgrid, g, nullptr, qfield, target, G, W, H, F, Q, Lmax, to_seed ? 1 : 0, r2_clear > 1 ? r2_clear : 1,
-                                path, len, cost, status, owner, seed, which, n_seed};
-    a.pen = pen; a.cap = (uint32_t)pen_cap;
-    int tk = sc_time_begin(ctx, SC_K_ASTAR);
-    const dim3 grid((unsigned)((Q + RP_WAVES - 1) / RP_WAVES)), block(64 * RP_WAVES);
-    if (pen) hipLaunchKernelGGL(field_paths_kernel<true>, grid, block, 0, ctx->stream, a);
-    else hipLaunchKernelGGL(field_paths_kernel<false>, grid, block, 0, ctx->stream, (paths_args)a);
-    sc_time_end(ctx, tk);
-    SC_HIP(ctx, hipGetLastError());
-    return SC_OK;
+    return field_build(ctx, FC_MULTI, {d2, pen, pen_cap, G, fgrid, W, H, r2_clear, F}, {seed, seed_cost, seed_off, n_seed}, rounds, g, owner,
+                       fstatus);
 }
 
 extern "C" int sc_cost_field_multi_batch_host(sc_ctx* ctx, const int32_t* d2, const uint8_t* pen, int pen_cap, int G, const int32_t* fgrid,
                                               int W, int H, int32_t r2_clear, const int32_t* seed, const int32_t* seed_cost,
                                               const int32_t* seed_off, int n_seed, int F, int rounds, int32_t* g, int32_t* owner,
                                               int32_t* fstatus) {
-    if (!cost_field_multi_args_ok(ctx, d2, pen, pen_cap, G, fgrid, W, H, seed, seed_off, n_seed, F, g)) return SC_ERR_INVALID;
-    // data contract: seed_off non-decreasing within 0 .. n_seed, every seed cost within 0 .. SC_FIELD_SEED_COST_MAX
-    for (int f = 0; f <= F; ++f)
-        if (seed_off[f] < 0 || seed_off[f] > n_seed || (f > 0 && seed_off[f] < seed_off[f - 1])) return SC_ERR_INVALID;
-    for (int s = 0; seed_cost && s < n_seed; ++s)
-        if (seed_cost[s] < 0 || seed_cost[s] > SC_FIELD_SEED_COST_MAX) return SC_ERR_INVALID;
-    SC_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t n = (size_t)W * H, fb = (size_t)F * 4, sb = (size_t)n_seed * 4;
-    sc_stage st(ctx);
-    const int i_d2 = st.in(d2, (size_t)G * n * 4), i_pen = st.in(pen, pen ? (size_t)G * n : 0), i_fg = st.in(fgrid, fb), i_sd = st.in(seed, sb),
-              i_sc = st.in(seed_cost, sb), i_so = st.in(seed_off, fb + 4);
-    const int o_g = st.out(g, fb * n), o_ow = st.out(owner, owner ? fb * n : 0), o_st = st.out(fstatus, fb);
-    int r = st.upload();
-    if (r == SC_OK)
-        r = sc_cost_field_multi_batch(ctx, st.dev<const int32_t>(i_d2), pen ? st.dev<const uint8_t>(i_pen) : nullptr, pen_cap, G,
-                                      fgrid ? st.dev<const int32_t>(i_fg) : nullptr, W, H, r2_clear, st.dev<const int32_t>(i_sd),
-                                      seed_cost ? st.dev<const int32_t>(i_sc) : nullptr, st.dev<const int32_t>(i_so), n_seed, F, rounds,
-                                      st.dev<int32_t>(o_g), owner ? st.dev<int32_t>(o_ow) : nullptr, fstatus ? st.dev<int32_t>(o_st) : nullptr);
-    return st.finish(r);
+    return field_build_host(ctx, FC_MULTI, {d2, pen, pen_cap, G, fgrid, W, H, r2_clear, F}, {seed, seed_cost, seed_off, n_seed}, rounds, g,
+                            owner, fstatus);
 }
 
-extern "C" int sc_field_paths_multi_batch_host(sc_ctx* ctx, const int32_t* d2, const uint8_t* pen, int pen_cap, int G, const int32_t* fgrid,
-                                               int W, int H, int32_t r2_clear, const int32_t* g, const int32_t* owner, const int32_t* seed,
-                                               int n_seed, int F, const int32_t* qfield, const int32_t* target, int Q, int Lmax, int to_seed,
-                                               int32_t* path, int32_t* len, int32_t* cost, int32_t* status, int32_t* which) {
-    if (!field_paths_multi_args_ok(ctx, d2, pen, pen_cap, G, fgrid, W, H, g, owner, seed, n_seed, F, qfield, target, Q, Lmax, path, len, cost,
-                                   status))
-        return SC_ERR_INVALID;
-    if (Q == 0) return SC_OK;
-    // data contract: every g value is a cost or SC_FIELD_INF
-    const size_t n = (size_t)W * H;
-    for (size_t i = 0; i < (size_t)F * n; ++i)
-        if (g[i] < 0) return SC_ERR_INVALID;
-    SC_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t fb = (size_t)F * 4, qb = (size_t)Q * 4;
-    sc_stage st(ctx);
-    const int i_d2 = st.in(d2, (size_t)G * n * 4), i_pen = st.in(pen, pen ? (size_t)G * n : 0), i_fg = st.in(fgrid, fb), i_g = st.in(g, fb * n),
-              i_ow = st.in(owner, fb * n), i_sd = st.in(seed, (size_t)n_seed * 4), i_qf = st.in(qfield, qb), i_t = st.in(target, qb);
-    const int o_p = st.out(path, qb * Lmax), o_len = st.out(len, qb), o_c = st.out(cost, qb), o_s = st.out(status, qb), o_w = st.out(which, qb);
-    int r = st.upload();
-    if (r == SC_OK)
-        r = sc_field_paths_multi_batch(ctx, st.dev<const int32_t>(i_d2), pen ? st.dev<const uint8_t>(i_pen) : nullptr, pen_cap, G,
-                                       fgrid ? st.dev<const int32_t>(i_fg) : nullptr, W, H, r2_clear, st.dev<const int32_t>(i_g),
-                                       st.dev<const int32_t>(i_ow), st.dev<const int32_t>(i_sd), n_seed, F, st.dev<const int32_t>(i_qf),
-                                       st.dev<const int32_t>(i_t), Q, Lmax, to_seed, st.dev<int32_t>(o_p), st.dev<int32_t>(o_len),
-                                       st.dev<int32_t>(o_c), st.dev<int32_t>(o_s), which ? st.dev<int32_t>(o_w) : nullptr);
-    return st.finish(r);
-}
-
-extern "C" int sc_cost_field_batch_host(sc_ctx* ctx, const int32_t* d2, int G, const int32_t* fgrid, int W, int H, int32_t r2_clear,
-                                        const int32_t* root, int F, int rounds, int32_t* g, int32_t* fstatus) {
-    if (!cost_field_args_ok(ctx, d2, G, fgrid, W, H, root, F, g)) return SC_ERR_INVALID;
-    SC_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t n = (size_t)W * H, fb = (size_t)F * 4;
-    sc_stage st(ctx);
-    const int i_d2 = st.in(d2, (size_t)G * n * 4), i_fg = st.in(fgrid, fb), i_rt = st.in(root, fb);
-    const int o_g = st.out(g, fb * n), o_st = st.out(fstatus, fb);
-    int r = st.upload();
-    if (r == SC_OK)
-        r = sc_cost_field_batch(ctx, st.dev<const int32_t>(i_d2), G, fgrid ? st.dev<const int32_t>(i_fg) : nullptr, W, H, r2_clear,
-                                st.dev<const int32_t>(i_rt), F, rounds, st.dev<int32_t>(o_g), st.dev<int32_t>(o_st));
-    return st.finish(r);
+extern "C" int sc_field_paths_batch(sc_ctx* ctx, const int32_t* d2, int G, const int32_t* fgrid, int W, int H, int32_t r2_clear,
+                                    const int32_t* g, const int32_t* root, int F, const int32_t* qfield, const int32_t* target, int Q,
+                                    int Lmax, int to_root, int32_t* path, int32_t* len, int32_t* cost, int32_t* status) {
+    return field_read(ctx, FC_ROOTS, {d2, nullptr, 0, G, fgrid, W, H, r2_clear, F}, {root, nullptr, nullptr, F}, g, nullptr,
+                      {qfield, target, Q, Lmax, to_root, path, len, cost, status, nullptr});
 }
 
 extern "C" int sc_field_paths_batch_host(sc_ctx* ctx, const int32_t* d2, int G, const int32_t* fgrid, int W, int H, int32_t r2_clear,
                                          const int32_t* g, const int32_t* root, int F, const int32_t* qfield, const int32_t* target, int Q,
                                          int Lmax, int to_root, int32_t* path, int32_t* len, int32_t* cost, int32_t* status) {
-    if (!field_paths_args_ok(ctx, d2, G, fgrid, W, H, g, root, F, qfield, target, Q, Lmax, path, len, cost, status)) return SC_ERR_INVALID;
-    if (Q == 0) return SC_OK;
-    // data contract: every g value is a cost or SC_FIELD_INF
-    const size_t n = (size_t)W * H;
-    for (size_t i = 0; i < (size_t)F * n; ++i)
-        if (g[i] < 0) return SC_ERR_INVALID;
-    SC_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t fb = (size_t)F * 4, qb = (size_t)Q * 4;
-    sc_stage st(ctx);
-    const int i_d2 = st.in(d2, (size_t)G * n * 4), i_fg = st.in(fgrid, fb), i_g = st.in(g, fb * n), i_rt = st.in(root, fb),
-              i_qf = st.in(qfield, qb), i_t = st.in(target, qb);
-    const int o_p = st.out(path, qb * Lmax), o_len = st.out(len, qb), o_c = st.out(cost, qb), o_s = st.out(status, qb);
-    int r = st.upload();
-    if (r == SC_OK)
-        r = sc_field_paths_batch(ctx, st.dev<const int32_t>(i_d2), G, fgrid ? st.dev<const int32_t>(i_fg) : nullptr, W, H, r2_clear,
-                                 st.dev<const int32_t>(i_g), st.dev<const int32_t>(i_rt), F, st.dev<const int32_t>(i_qf), st.dev<const int32_t>(i_t),
-                                 Q, Lmax, to_root, st.dev<int32_t>(o_p), st.dev<int32_t>(o_len), st.dev<int32_t>(o_c), st.dev<int32_t>(o_s));
-    return st.finish(r);
+    return field_read_host(ctx, FC_ROOTS, {d2, nullptr, 0, G, fgrid, W, H, r2_clear, F}, {root, nullptr, nullptr, F}, g, nullptr,
+                           {qfield, target, Q, Lmax, to_root, path, len, cost, status, nullptr});
 }
 
-extern "C" int sc_cost_field_weighted_batch_host(sc_ctx* ctx, const int32_t* d2, const uint8_t* pen, int pen_cap, int G, const int32_t* fgrid,
-                                                 int W, int H, int32_t r2_clear, const int32_t* root, int F, int rounds, int32_t* g,
-                                                 int32_t* fstatus) {
-    if (!cost_field_args_ok(ctx, d2, G, fgrid, W, H, root, F, g) || !weighted_args_ok(pen, pen_cap, W, H)) return SC_ERR_INVALID;
-    SC_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t n = (size_t)W * H, fb = (size_t)F * 4;
-    sc_stage st(ctx);
-    const int i_d2 = st.in(d2, (size_t)G * n * 4), i_pen = st.in(pen, (size_t)G * n), i_fg = st.in(fgrid, fb), i_rt = st.in(root, fb);
-    const int o_g = st.out(g, fb * n), o_st = st.out(fstatus, fb);
-    int r = st.upload();
-    if (r == SC_OK)
-        r = sc_cost_field_weighted_batch(ctx, st.dev<const int32_t>(i_d2), st.dev<const uint8_t>(i_pen), pen_cap, G,
-                                         fgrid ? st.dev<const int32_t>(i_fg) : nullptr, W, H, r2_clear, st.dev<const int32_t>(i_rt), F,
-                                         rounds, st.dev<int32_t>(o_g), st.dev<int32_t>(o_st));
-    return st.finish(r);
+extern "C" int sc_field_paths_weighted_batch(sc_ctx* ctx, const int32_t* d2, const uint8_t* pen, int pen_cap, int G, const int32_t* fgrid,
+                                             int W, int H, int32_t r2_clear, const int32_t* g, const int32_t* root, int F,
+                                             const int32_t* qfield, const int32_t* target, int Q, int Lmax, int to_root, int32_t* path,
+                                             int32_t* len, int32_t* cost, int32_t* status) {
+    return field_read(ctx, FC_ROOTS_WEIGHTED, {d2, pen, pen_cap, G, fgrid, W, H, r2_clear, F}, {root, nullptr, nullptr, F}, g, nullptr,
+                      {qfield, target, Q, Lmax, to_root, path, len, cost, status, nullptr});
 }
 
 extern "C" int sc_field_paths_weighted_batch_host(sc_ctx* ctx, const int32_t* d2, const uint8_t* pen, int pen_cap, int G,
                                                   const int32_t* fgrid, int W, int H, int32_t r2_clear, const int32_t* g, const int32_t* root,
                                                   int F, const int32_t* qfield, const int32_t* target, int Q, int Lmax, int to_root,
                                                   int32_t* path, int32_t* len, int32_t* cost, int32_t* status) {
-    if (!field_paths_args_ok(ctx, d2, G, fgrid, W, H, g, root, F, qfield, target, Q, Lmax, path, len, cost, status) ||
-        !weighted_args_ok(pen, pen_cap, W, H))
-        return SC_ERR_INVALID;
-    if (Q == 0) return SC_OK;
-    // data contract: every g value is a cost or SC_FIELD_INF
-    const size_t n = (size_t)W * H;
-    for (size_t i = 0; i < (size_t)F * n; ++i)
-        if (g[i] < 0) return SC_ERR_INVALID;
-    SC_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t fb = (size_t)F * 4, qb = (size_t)Q * 4;
-    sc_stage st(ctx);
-    const int i_d2 = st.in(d2, (size_t)G * n * 4), i_pen = st.in(pen, (size_t)G * n), i_fg = st.in(fgrid, fb), i_g = st.in(g, fb * n),
-              i_rt = st.in(root, fb), i_qf = st.in(qfield, qb), i_t = st.in(target, qb);
-    const int o_p = st.out(path, qb * Lmax), o_len = st.out(len, qb), o_c = st.out(cost, qb), o_s = st.out(status, qb);
-    int r = st.upload();
-    if (r == SC_OK)
-        r = sc_field_paths_weighted_batch(ctx, st.dev<const int32_t>(i_d2), st.dev<const uint8_t>(i_pen), pen_cap, G,
-                                          fgrid ? st.dev<const int32_t>(i_fg) : nullptr, W, H, r2_clear, st.dev<const int32_t>(i_g),
-                                          st.dev<const int32_t>(i_rt), F, st.dev<const int32_t>(i_qf), st.dev<const int32_t>(i_t), Q, Lmax,
-                                          to_root, st.dev<int32_t>(o_p), st.dev<int32_t>(o_len), st.dev<int32_t>(o_c), st.dev<int32_t>(o_s));
-    return st.finish(r);
+    return field_read_host(ctx, FC_ROOTS_WEIGHTED, {d2, pen, pen_cap, G, fgrid, W, H, r2_clear, F}, {root, nullptr, nullptr, F}, g, nullptr,
+                           {qfield, target, Q, Lmax, to_root, path, len, cost, status, nullptr});
+}
+
+extern "C" int sc_field_paths_multi_batch(sc_ctx* ctx, const int32_t* d2, const uint8_t* pen, int pen_cap, int G, const int32_t* fgrid, int W,
+                                          int H, int32_t r2_clear, const int32_t* g, const int32_t* owner, const int32_t* seed, int n_seed,
+                                          int F, const int32_t* qfield, const int32_t* target, int Q, int Lmax, int to_seed, int32_t* path,
+                                          int32_t* len, int32_t* cost, int32_t* status, int32_t* which) {
+    return field_read(ctx, FC_MULTI, {d2, pen, pen_cap, G, fgrid, W, H, r2_clear, F}, {seed, nullptr, nullptr, n_seed}, g, owner,
+                      {qfield, target, Q, Lmax, to_seed, path, len, cost, status, which});
+}
+
+extern "C" int sc_field_paths_multi_batch_host(sc_ctx* ctx, const int32_t* d2, const uint8_t* pen, int pen_cap, int G, const int32_t* fgrid,
+                                               int W, int H, int32_t r2_clear, const int32_t* g, const int32_t* owner, const int32_t* seed,
+                                               int n_seed, int F, const int32_t* qfield, const int32_t* target, int Q, int Lmax, int to_seed,
+                                               int32_t* path, int32_t* len, int32_t* cost, int32_t* status, int32_t* which) {
+    return field_read_host(ctx, FC_MULTI, {d2, pen, pen_cap, G, fgrid, W, H, r2_clear, F}, {seed, nullptr, nullptr, n_seed}, g, owner,
+                           {qfield, target, Q, Lmax, to_seed, path, len, cost, status, which});
 }

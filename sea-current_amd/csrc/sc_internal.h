@@ -65,7 +65,7 @@ struct __attribute__((visibility("hidden"))) sc_ctx {
     sc_scratch sm_vlim;     // smoothing with per-stage limits: fp64 vlo [P][N+1] | vhi [P][N+1]
     sc_scratch occ_prep;    // polygon occupancy: float4 box [n_obs] | int2 cell-row range [n_obs] of every obstacle
     sc_scratch fld_mask;    // cost fields: uint64 [G][tile rows][W] traversability of 64 rows per column
-    sc_scratch fld_state;   // cost fields: per-field ok [F] | tile stamps [F][tiles] | two tile lists [F * tiles] | round counts
+    sc_scratch fld_state;   // cost fields: int32 ok [F] | stamp [F][tiles] | seeded [F][tiles] | list0, list1 [F * tiles] | ctr [rounds + 1] | left [jumps + 1]
     sc_scratch cmp_state;   // components: int32 [G][H][W] sizes when the caller passes none | uint64 [G] largest keys
     sc_scratch cmp_start;   // screened A*: int32 [Q] the starts, -1 where the endpoints lie in different components
     int astar_cap = 1 << 16;         // ring entries per bucket (power of two)

@@ -165,6 +165,35 @@ def _ptr(t):
     return t.data_ptr()
 
 
+def _ghw(d2):
+    """(G, H, W) of a map-shaped tensor or array: [H,W] is one grid, [G,H,W] a stack."""
+    return (1,) + tuple(d2.shape) if len(d2.shape) == 2 else tuple(d2.shape)
+
+
+def _field_entry(stem, pen, pen_cap, host=False):
+    """The single-root field entry `stem` (sc_cost_field / sc_field_paths) for a costmap or none: its name and the
+    arguments the weighted form takes after d2."""
+    name = stem + ("_batch" if pen is None else "_weighted_batch") + ("_host" if host else "")
+    return name, (() if pen is None else (_ptr(pen), pen_cap))
+
+
+def _paths_out_torch(Q, Lmax, dev, which=False):
+    """The uninitialised result dict of a read-out on the GPU (astar_batch's layout; which: the multi-source read-out's)."""
+    import torch
+    out = dict(path=torch.empty((Q, Lmax), dtype=torch.int32, device=dev))
+    for k in ("len", "cost", "status") + (("which",) if which else ()):
+        out[k] = torch.empty(Q, dtype=torch.int32, device=dev)
+    return out
+
+
+def _paths_out_numpy(Q, Lmax, which=False):
+    """The result dict of a _host read-out: path -1, the rest 0."""
+    out = dict(path=np.full((Q, Lmax), -1, dtype=np.int32))
+    for k in ("len", "cost", "status") + (("which",) if which else ()):
+        out[k] = np.zeros(Q, np.int32)
+    return out
+
+
 class Context:
     """One sc_ctx: one GPU, one stream.  `device` is the HIP device ordinal."""
 
@@ -332,40 +361,29 @@ class Context:
         pen (uint8, shaped like d2): the weighted fields (sc_cost_field_weighted_batch), entering cell c costs
         min(pen[c], pen_cap) more."""
         import torch
-        G, H, W = (1,) + tuple(d2.shape) if d2.dim() == 2 else tuple(d2.shape)
+        G, H, W = _ghw(d2)
         F = roots.shape[0]
         dev = d2.device
         if out is None:
             out = dict(g=torch.empty((F, H, W), dtype=torch.int32, device=dev), status=torch.empty(F, dtype=torch.int32, device=dev))
-        if pen is not None:
-            self._ck(self._l.sc_cost_field_weighted_batch(self._h, _ptr(d2), _ptr(pen), pen_cap, G, _ptr(fgrid), W, H, r2, _ptr(roots), F,
-                                                          rounds, _ptr(out["g"]), _ptr(out["status"])), "sc_cost_field_weighted_batch")
-            return out
-        self._ck(self._l.sc_cost_field_batch(self._h, _ptr(d2), G, _ptr(fgrid), W, H, r2, _ptr(roots), F, rounds, _ptr(out["g"]),
-                                             _ptr(out["status"])), "sc_cost_field_batch")
+        name, costmap = _field_entry("sc_cost_field", pen, pen_cap)
+        self._ck(getattr(self._l, name)(self._h, _ptr(d2), *costmap, G, _ptr(fgrid), W, H, r2, _ptr(roots), F, rounds, _ptr(out["g"]),
+                                        _ptr(out["status"])), name)
         return out
 
     def field_paths(self, d2, g, roots, qfield, targets, r2=0, Lmax=4096, to_root=False, fgrid=None, out=None, pen=None, pen_cap=255):
         """Paths read from cost fields (sc_field_paths_batch): query q follows field qfield[q] (g int32 [F,H,W] and roots [F]
         as cost_fields took and returned them) to targets[q].  Returns astar_batch's dict of GPU tensors; to_root=True
         writes every path target..root.  pen, pen_cap: those cost_fields computed g with (sc_field_paths_weighted_batch)."""
-        import torch
-        G, H, W = (1,) + tuple(d2.shape) if d2.dim() == 2 else tuple(d2.shape)
+        G, H, W = _ghw(d2)
         F = roots.shape[0]
         Q = targets.shape[0]
-        dev = d2.device
         if out is None:
-            out = dict(path=torch.empty((Q, Lmax), dtype=torch.int32, device=dev), len=torch.empty(Q, dtype=torch.int32, device=dev),
-                       cost=torch.empty(Q, dtype=torch.int32, device=dev), status=torch.empty(Q, dtype=torch.int32, device=dev))
-        if pen is not None:
-            self._ck(self._l.sc_field_paths_weighted_batch(self._h, _ptr(d2), _ptr(pen), pen_cap, G, _ptr(fgrid), W, H, r2, _ptr(g),
-                                                           _ptr(roots), F, _ptr(qfield), _ptr(targets), Q, Lmax, int(bool(to_root)),
-                                                           _ptr(out["path"]), _ptr(out["len"]), _ptr(out["cost"]), _ptr(out["status"])),
-                     "sc_field_paths_weighted_batch")
-            return out
-        self._ck(self._l.sc_field_paths_batch(self._h, _ptr(d2), G, _ptr(fgrid), W, H, r2, _ptr(g), _ptr(roots), F, _ptr(qfield),
-                                              _ptr(targets), Q, Lmax, int(bool(to_root)), _ptr(out["path"]), _ptr(out["len"]),
-                                              _ptr(out["cost"]), _ptr(out["status"])), "sc_field_paths_batch")
+            out = _paths_out_torch(Q, Lmax, d2.device)
+        name, costmap = _field_entry("sc_field_paths", pen, pen_cap)
+        self._ck(getattr(self._l, name)(self._h, _ptr(d2), *costmap, G, _ptr(fgrid), W, H, r2, _ptr(g), _ptr(roots), F, _ptr(qfield),
+                                        _ptr(targets), Q, Lmax, int(bool(to_root)), _ptr(out["path"]), _ptr(out["len"]),
+                                        _ptr(out["cost"]), _ptr(out["status"])), name)
         return out
 
     def cost_fields_multi(self, d2, seeds, seed_off, seed_cost=None, r2=0, fgrid=None, rounds=-1, want_owner=True, pen=None, pen_cap=255,
@@ -376,7 +394,7 @@ class Context:
         (None: unweighted), all on the GPU.  Returns dict(g int32 [F,H,W], owner int32 [F,H,W]: the index into seeds of the
         seed every cell's path ends at, -1 where g is FIELD_INF, None without want_owner; status int32 [F])."""
         import torch
-        G, H, W = (1,) + tuple(d2.shape) if d2.dim() == 2 else tuple(d2.shape)
+        G, H, W = _ghw(d2)
         F = seed_off.shape[0] - 1
         dev = d2.device
         if out is None:
@@ -394,15 +412,11 @@ class Context:
         dict cost_fields_multi returned, with its owner) from targets[q] to the seed that owns it.  Returns astar_batch's dict
         of GPU tensors plus which int32 [Q] (the index into seeds of that seed, -1 without a path); to_seed=True writes every
         path target..seed.  pen, pen_cap: those cost_fields_multi computed the fields with."""
-        import torch
-        G, H, W = (1,) + tuple(d2.shape) if d2.dim() == 2 else tuple(d2.shape)
+        G, H, W = _ghw(d2)
         F = fields["g"].shape[0]
         Q = targets.shape[0]
-        dev = d2.device
         if out is None:
-            out = dict(path=torch.empty((Q, Lmax), dtype=torch.int32, device=dev), len=torch.empty(Q, dtype=torch.int32, device=dev),
-                       cost=torch.empty(Q, dtype=torch.int32, device=dev), status=torch.empty(Q, dtype=torch.int32, device=dev),
-                       which=torch.empty(Q, dtype=torch.int32, device=dev))
+            out = _paths_out_torch(Q, Lmax, d2.device, which=True)
         self._ck(self._l.sc_field_paths_multi_batch(self._h, _ptr(d2), _ptr(pen), pen_cap, G, _ptr(fgrid), W, H, r2, _ptr(fields["g"]),
                                                     _ptr(fields["owner"]), _ptr(seeds), seeds.shape[0], F, _ptr(qfield), _ptr(targets), Q,
                                                     Lmax, int(bool(to_seed)), _ptr(out["path"]), _ptr(out["len"]), _ptr(out["cost"]),
@@ -913,17 +927,13 @@ class Context:
         d2 = np.ascontiguousarray(d2, dtype=np.int32)
         roots = np.ascontiguousarray(roots, dtype=np.int32)
         fgrid = None if fgrid is None else np.ascontiguousarray(fgrid, dtype=np.int32)
-        G, H, W = (1,) + d2.shape if d2.ndim == 2 else d2.shape
+        pen = None if pen is None else np.ascontiguousarray(pen, dtype=np.uint8)
+        G, H, W = _ghw(d2)
         F = roots.shape[0]
         out = dict(g=np.zeros((F, H, W), np.int32), status=np.zeros(F, np.int32))
-        if pen is not None:
-            pen = np.ascontiguousarray(pen, dtype=np.uint8)
-            self._ck(self._l.sc_cost_field_weighted_batch_host(self._h, _ptr(d2), _ptr(pen), pen_cap, G, _ptr(fgrid), W, H, r2, _ptr(roots),
-                                                               F, rounds, _ptr(out["g"]), _ptr(out["status"])),
-                     "sc_cost_field_weighted_batch_host")
-            return out
-        self._ck(self._l.sc_cost_field_batch_host(self._h, _ptr(d2), G, _ptr(fgrid), W, H, r2, _ptr(roots), F, rounds, _ptr(out["g"]),
-                                                  _ptr(out["status"])), "sc_cost_field_batch_host")
+        name, costmap = _field_entry("sc_cost_field", pen, pen_cap, host=True)
+        self._ck(getattr(self._l, name)(self._h, _ptr(d2), *costmap, G, _ptr(fgrid), W, H, r2, _ptr(roots), F, rounds, _ptr(out["g"]),
+                                        _ptr(out["status"])), name)
         return out
 
     def field_paths_host(self, d2, g, roots, qfield, targets, r2=0, Lmax=4096, to_root=False, fgrid=None, pen=None, pen_cap=255):
@@ -932,20 +942,14 @@ class Context:
         g = np.ascontiguousarray(g, dtype=np.int32)
         roots, qfield, targets = (np.ascontiguousarray(a, dtype=np.int32) for a in (roots, qfield, targets))
         fgrid = None if fgrid is None else np.ascontiguousarray(fgrid, dtype=np.int32)
-        G, H, W = (1,) + d2.shape if d2.ndim == 2 else d2.shape
+        pen = None if pen is None else np.ascontiguousarray(pen, dtype=np.uint8)
+        G, H, W = _ghw(d2)
         F, Q = roots.shape[0], targets.shape[0]
-        out = dict(path=np.full((Q, Lmax), -1, dtype=np.int32), len=np.zeros(Q, np.int32), cost=np.zeros(Q, np.int32),
-                   status=np.zeros(Q, np.int32))
-        if pen is not None:
-            pen = np.ascontiguousarray(pen, dtype=np.uint8)
-            self._ck(self._l.sc_field_paths_weighted_batch_host(self._h, _ptr(d2), _ptr(pen), pen_cap, G, _ptr(fgrid), W, H, r2, _ptr(g),
-                                                                _ptr(roots), F, _ptr(qfield), _ptr(targets), Q, Lmax, int(bool(to_root)),
-                                                                _ptr(out["path"]), _ptr(out["len"]), _ptr(out["cost"]),
-                                                                _ptr(out["status"])), "sc_field_paths_weighted_batch_host")
-            return out
-        self._ck(self._l.sc_field_paths_batch_host(self._h, _ptr(d2), G, _ptr(fgrid), W, H, r2, _ptr(g), _ptr(roots), F, _ptr(qfield),
-                                                   _ptr(targets), Q, Lmax, int(bool(to_root)), _ptr(out["path"]), _ptr(out["len"]),
-                                                   _ptr(out["cost"]), _ptr(out["status"])), "sc_field_paths_batch_host")
+        out = _paths_out_numpy(Q, Lmax)
+        name, costmap = _field_entry("sc_field_paths", pen, pen_cap, host=True)
+        self._ck(getattr(self._l, name)(self._h, _ptr(d2), *costmap, G, _ptr(fgrid), W, H, r2, _ptr(g), _ptr(roots), F, _ptr(qfield),
+                                        _ptr(targets), Q, Lmax, int(bool(to_root)), _ptr(out["path"]), _ptr(out["len"]),
+                                        _ptr(out["cost"]), _ptr(out["status"])), name)
         return out
 
     def cost_fields_multi_host(self, d2, seeds, seed_off, seed_cost=None, r2=0, fgrid=None, rounds=-1, want_owner=True, pen=None,
@@ -956,7 +960,7 @@ class Context:
         seed_cost = None if seed_cost is None else np.ascontiguousarray(seed_cost, dtype=np.int32)
         fgrid = None if fgrid is None else np.ascontiguousarray(fgrid, dtype=np.int32)
         pen = None if pen is None else np.ascontiguousarray(pen, dtype=np.uint8)
-        G, H, W = (1,) + d2.shape if d2.ndim == 2 else d2.shape
+        G, H, W = _ghw(d2)
         F = seed_off.shape[0] - 1
         out = dict(g=np.zeros((F, H, W), np.int32), owner=np.zeros((F, H, W), np.int32) if want_owner else None, status=np.zeros(F, np.int32))
         self._ck(self._l.sc_cost_field_multi_batch_host(self._h, _ptr(d2), _ptr(pen), pen_cap, G, _ptr(fgrid), W, H, r2, _ptr(seeds),
@@ -971,10 +975,9 @@ class Context:
         seeds, qfield, targets = (np.ascontiguousarray(a, dtype=np.int32) for a in (seeds, qfield, targets))
         fgrid = None if fgrid is None else np.ascontiguousarray(fgrid, dtype=np.int32)
         pen = None if pen is None else np.ascontiguousarray(pen, dtype=np.uint8)
-        G, H, W = (1,) + d2.shape if d2.ndim == 2 else d2.shape
+        G, H, W = _ghw(d2)
         F, Q = g.shape[0], targets.shape[0]
-        out = dict(path=np.full((Q, Lmax), -1, dtype=np.int32), len=np.zeros(Q, np.int32), cost=np.zeros(Q, np.int32),
-                   status=np.zeros(Q, np.int32), which=np.zeros(Q, np.int32))
+        out = _paths_out_numpy(Q, Lmax, which=True)
         self._ck(self._l.sc_field_paths_multi_batch_host(self._h, _ptr(d2), _ptr(pen), pen_cap, G, _ptr(fgrid), W, H, r2, _ptr(g), _ptr(owner),
                                                          _ptr(seeds), seeds.shape[0], F, _ptr(qfield), _ptr(targets), Q, Lmax,
                                                          int(bool(to_seed)), _ptr(out["path"]), _ptr(out["len"]), _ptr(out["cost"]),

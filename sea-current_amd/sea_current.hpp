@@ -467,17 +467,7 @@ public:
     };
     field_result cost_fields(const std::vector<int32_t>& roots, int32_t r2_clear = 0, int rounds = -1,
                              gpu_context& ctx = default_context()) {
-        if (d2.size() != occ.size()) edt(ctx);
-        field_result r;
-        const int F = (int)roots.size();
-        r.roots = roots;
-        r.r2 = r2_clear;
-        r.g.assign((size_t)F * W * H, SC_FIELD_INF); r.status.assign(F, SC_Q_BAD_ENDPOINT);
-        if (F == 0) return r;
-        ctx.check(sc_cost_field_batch_host(ctx.get(), d2.data(), 1, nullptr, W, H, r2_clear, roots.data(), F, rounds, r.g.data(),
-                                           r.status.data()),
-                  "sc_cost_field_batch_host");
-        return r;
+        return cost_fields_with(roots, nullptr, 0, r2_clear, rounds, ctx);
     }
     // The costmap of the weighted fields from d2 (sc_clearance_penalty_u8): pen_max next to the hard clearance r2_clear,
     // falling linearly with the distance to 0 at sqrt(r2_soft) cells.
@@ -492,20 +482,7 @@ public:
     // of the move; pen is [H][W].  The result remembers pen and pen_cap for field_paths.
     field_result cost_fields(const std::vector<int32_t>& roots, const std::vector<uint8_t>& pen, int pen_cap, int32_t r2_clear = 0,
                              int rounds = -1, gpu_context& ctx = default_context()) {
-        if (d2.size() != occ.size()) edt(ctx);
-        if (pen.size() != occ.size()) throw std::invalid_argument("occupancy_grid::cost_fields: pen is not [H][W]");
-        field_result r;
-        const int F = (int)roots.size();
-        r.roots = roots;
-        r.r2 = r2_clear;
-        r.pen = pen;
-        r.pen_cap = pen_cap;
-        r.g.assign((size_t)F * W * H, SC_FIELD_INF); r.status.assign(F, SC_Q_BAD_ENDPOINT);
-        if (F == 0) return r;
-        ctx.check(sc_cost_field_weighted_batch_host(ctx.get(), d2.data(), pen.data(), pen_cap, 1, nullptr, W, H, r2_clear, roots.data(), F,
-                                                    rounds, r.g.data(), r.status.data()),
-                  "sc_cost_field_weighted_batch_host");
-        return r;
+        return cost_fields_with(roots, &pen, pen_cap, r2_clear, rounds, ctx);
     }
     // Paths read from fields (sc_field_paths_batch): query q follows field qfield[q] to targets[q].  Equal to astar_batch
     // with start roots[qfield[q]] and goal targets[q] (to_root = false), or to its paths reversed (to_root = true).  A
@@ -520,17 +497,13 @@ public:
         r.path.assign((size_t)Q * r.Lmax, -1); r.len.assign(Q, 0); r.cost.assign(Q, -1); r.status.assign(Q, SC_Q_NO_PATH);
         if (Q == 0) return r;
         if (F == 0) { r.status.assign(Q, SC_Q_BAD_ENDPOINT); return r; }
-        if (!fr.pen.empty()) {
-            ctx.check(sc_field_paths_weighted_batch_host(ctx.get(), d2.data(), fr.pen.data(), fr.pen_cap, 1, nullptr, W, H, fr.r2, fr.g.data(),
-                                                         fr.roots.data(), F, qfield.data(), targets.data(), Q, r.Lmax, to_root ? 1 : 0,
-                                                         r.path.data(), r.len.data(), r.cost.data(), r.status.data()),
-                      "sc_field_paths_weighted_batch_host");
-            return r;
-        }
-        ctx.check(sc_field_paths_batch_host(ctx.get(), d2.data(), 1, nullptr, W, H, fr.r2, fr.g.data(), fr.roots.data(), F, qfield.data(),
-                                            targets.data(), Q, r.Lmax, to_root ? 1 : 0, r.path.data(), r.len.data(), r.cost.data(),
-                                            r.status.data()),
-                  "sc_field_paths_batch_host");
+        // the weighted entry takes the costmap after d2, the rest is one argument list
+        auto call = [&](auto entry, auto... costmap) {
+            return entry(ctx.get(), d2.data(), costmap..., 1, nullptr, W, H, fr.r2, fr.g.data(), fr.roots.data(), F, qfield.data(),
+                         targets.data(), Q, r.Lmax, to_root ? 1 : 0, r.path.data(), r.len.data(), r.cost.data(), r.status.data());
+        };
+        if (fr.pen.empty()) ctx.check(call(sc_field_paths_batch_host), "sc_field_paths_batch_host");
+        else ctx.check(call(sc_field_paths_weighted_batch_host, fr.pen.data(), fr.pen_cap), "sc_field_paths_weighted_batch_host");
         return r;
     }
     // Multi-source cost fields (sc_cost_field_multi_batch): field f starts from seeds[seed_off[f] .. seed_off[f+1]-1], each
@@ -605,6 +578,26 @@ public:
         ctx.check(sc_path_waypoints_batch_host(ctx.get(), d2.data(), W, H, r2_clear, br.path.data(), br.len.data(), br.status.data(), Q,
                                                br.Lmax, r.Wmax, r.wp.data(), r.n.data(), r.status.data()),
                   "sc_path_waypoints_batch_host");
+        return r;
+    }
+private:
+    // both cost_fields overloads; pen NULL: the unweighted fields
+    field_result cost_fields_with(const std::vector<int32_t>& roots, const std::vector<uint8_t>* pen, int pen_cap, int32_t r2_clear, int rounds,
+                                  gpu_context& ctx) {
+        if (d2.size() != occ.size()) edt(ctx);
+        if (pen && pen->size() != occ.size()) throw std::invalid_argument("occupancy_grid::cost_fields: pen is not [H][W]");
+        field_result r;
+        const int F = (int)roots.size();
+        r.roots = roots;
+        r.r2 = r2_clear;
+        if (pen) { r.pen = *pen; r.pen_cap = pen_cap; }
+        r.g.assign((size_t)F * W * H, SC_FIELD_INF); r.status.assign(F, SC_Q_BAD_ENDPOINT);
+        if (F == 0) return r;
+        auto call = [&](auto entry, auto... costmap) {
+            return entry(ctx.get(), d2.data(), costmap..., 1, nullptr, W, H, r2_clear, roots.data(), F, rounds, r.g.data(), r.status.data());
+        };
+        if (!pen) ctx.check(call(sc_cost_field_batch_host), "sc_cost_field_batch_host");
+        else ctx.check(call(sc_cost_field_weighted_batch_host, pen->data(), pen_cap), "sc_cost_field_weighted_batch_host");
         return r;
     }
 };

@@ -43,7 +43,7 @@ def alternate(fw, f0, ctx, repeats):
         w.append(once(fw, ctx))
         u.append(once(f0, ctx))
     mw, mu = float(np.median(w)), float(np.median(u))
-    return dict(weighted_ms=mw, unweighted_ms=mu, ratio=mw / mu)
+    return dict(weighted_ms=mw, unweighted_ms=mu, ratio=mw / mu, weighted_all=w, unweighted_all=u)
 
 
 def main():
