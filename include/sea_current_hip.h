@@ -92,10 +92,11 @@ int sc_ctx_destroy(sc_ctx* ctx);
 int sc_ctx_set_stream(sc_ctx* ctx, void* hip_stream);
 /* Go back to the context's own non-blocking stream (the default after create). */
 int sc_ctx_use_own_stream(sc_ctx* ctx);
-/* Wait for everything enqueued on the context's stream.  Also where a context adapts to what its launches met: A* rings
- * that overflowed (later calls start with larger ones), maps of open space at widths of 513 .. 1024 (later EDTs run the
- * band kernel's build with the site search, until a launch meets none), and where a wide-row EDT whose bounded waits ran
- * out is reported (SC_ERR_HIP).  Results never depend on the adapted state. */
+/* Wait for everything enqueued on the context's stream.  Also where a context adapts to what its OWN launches met (the
+ * state is per context: contexts that share a device do not see each other's): A* rings that overflowed (later calls
+ * start with larger ones), maps of open space at widths of 513 .. 1024 (later EDTs run the band kernel's build with the
+ * site search, until a launch meets none), and where a wide-row EDT whose bounded waits ran out is reported (SC_ERR_HIP).
+ * Results never depend on the adapted state. */
 int sc_ctx_synchronize(sc_ctx* ctx);
 /* Kernel timing: when enabled every kernel launch is bracketed by HIP events on
  * the context's stream; sc_ctx_get_timing synchronises and returns the summed
@@ -203,7 +204,8 @@ int sc_astar_batch_multi(sc_ctx* ctx, const int32_t* d2, int G, const int32_t* q
 /* Node expansions of the last sc_astar_batch call on this context (synchronises). */
 int sc_astar_last_expansions(sc_ctx* ctx, int64_t* expansions);
 /* Debug: per-query expansions, popped queue entries, kilo-cycles and steps (int32 [4][Q]) of the last sc_astar_batch
- * (synchronises).  sc_astar_debug_peek: the launch counters, read without waiting for the stream (bring-up aid). */
+ * (synchronises).  sc_astar_debug_peek: the launch counters (words 0 .. 3: queue positions and overflow counts of the main
+ * and the retry pass), read without waiting for the stream (bring-up aid). */
 int sc_astar_debug_stats(sc_ctx* ctx, int32_t* stats4, int Q);
 int sc_astar_debug_peek(sc_ctx* ctx, int32_t* out16);
 /* Debug/parity: g field of ONE query (uint32 [H][W]): the optimal cost-to-come g* of every node the search

@@ -97,7 +97,7 @@ struct astar_args {
     int32_t* counter;    // queue position handed out next
     int32_t* ovf_list;   // queries whose rings overflowed ...
     int32_t* ovf_count;  // ... and how many
-    int32_t* ovf_sticky; // set on any overflow, cleared by the host when it next synchronises
+    int32_t* ovf_sticky; // set on any overflow (the context's status word), cleared by the host when it next synchronises
     int nstat;           // Q of the batch (stride of the statistics arrays)
     int lazy;            // two-wavefront kernel: more queries than slots -- wavefront 1 waits for fuller batches
     int tw, bw;          // tiles per row of the g array / of the closed bitmap
@@ -1158,14 +1158,15 @@ static int astar_run(sc_ctx* ctx, const int32_t* d2, int G, const int32_t* qgrid
         if (r != SC_OK) return r;
         SC_HIP(ctx, hipMemsetAsync(ctx->actr.p, 0, 16 * sizeof(int32_t), ctx->stream));
     }
-    int32_t* ctr = (int32_t*)ctx->actr.p;   // [0] main queue, [1] main overflow count, [2] retry queue, [3] retry overflow count, [4] sticky
+    int32_t* ctr = (int32_t*)ctx->actr.p;   // [0] main queue, [1] main overflow count, [2] retry queue, [3] retry overflow count
+    ctx->status_armed = true;               // an overflow sets SC_ST_ASTAR_OVERFLOW of the context's status block
 
     const bool sorted = (size_t)Q > slots;   // every query starts at once otherwise
     int tk = sc_time_begin(ctx, SC_K_ASTAR);
     hipLaunchKernelGGL(astar_prep_kernel, dim3(1), dim3(1024), 0, ctx->stream, start, goal, Q, W, H, sorted ? order : (int32_t*)nullptr, ctr);
     astar_args a{(const uint8_t*)ctx->moves.p, d2, W, H, rmin, start, goal, qgrid, sorted ? order : nullptr, nullptr, Q, Lmax, path, len,
                  cost, status, ctx->gslots.p, (uint32_t*)ctx->closed.p, (uint32_t*)ctx->buckets.p, cap, expanded, ctr,
-                 ovf_list, ctr + 1, ctr + 4, Q, (dual && (size_t)Q > slots) ? 1 : 0, tw, bw, gcells, bwords};
+                 ovf_list, ctr + 1, ctx->status + SC_ST_ASTAR_OVERFLOW, Q, (dual && (size_t)Q > slots) ? 1 : 0, tw, bw, gcells, bwords};
     if (full_g) hipLaunchKernelGGL(astar_kernel<uint32_t>, dim3((unsigned)slots), dim3(64), 0, ctx->stream, a);
     else if (dual && latency && (size_t)Q <= slots)
         hipLaunchKernelGGL((astar_kernel_dual<uint8_t, ASTAR_CQ_LATENCY, ASTAR_RU_LATENCY>), dim3((unsigned)slots), dim3(128), 0, ctx->stream, a);

@@ -24,7 +24,14 @@ extern "C" int sc_ctx_create(int device, sc_ctx** out) {
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0 || device < 0 || device >= n) return SC_ERR_NO_DEVICE;
     sc_ctx* c = new sc_ctx();
     c->device = device;
-    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) != hipSuccess) {
+    // with the stream the status block (sc_status_word) and its pinned mirror: zeroed, and waited for, before anything can be enqueued
+    const size_t sb = SC_ST_COUNT * sizeof(int32_t);
+    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) != hipSuccess ||
+        hipMalloc((void**)&c->status, sb) != hipSuccess || hipMemsetAsync(c->status, 0, sb, c->own_stream) != hipSuccess ||
+        hipStreamSynchronize(c->own_stream) != hipSuccess ||
+        hipHostMalloc((void**)&c->status_host, sb, hipHostMallocDefault) != hipSuccess) {
+        (void)hipFree(c->status);
+        if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
         delete c;
         return SC_ERR_HIP;
     }
@@ -44,6 +51,7 @@ extern "C" int sc_ctx_destroy(sc_ctx* ctx) {
     for (auto e : ctx->ev_pool) (void)hipEventDestroy(e);
     if (ctx->wait_ev) (void)hipEventDestroy(ctx->wait_ev);
     (void)hipStreamDestroy(ctx->own_stream);
+    (void)hipFree(ctx->status); (void)hipHostFree(ctx->status_host);
     delete ctx;   // the scratch buffers free themselves
     return SC_OK;
 }
@@ -77,30 +85,27 @@ int sc_stream_wait(sc_ctx* ctx) {
 extern "C" int sc_ctx_synchronize(sc_ctx* ctx) {
     if (!ctx) return SC_ERR_INVALID;
     SC_HIP(ctx, hipSetDevice(ctx->device));
-    int r = sc_stream_wait(ctx);
-    if (r != SC_OK) return r;
-    // A* bucket rings overflowed in some launch since the last synchronisation (the overflowed queries were rerun
-    // with 16x the space on the device): start later launches with larger rings
-    if (ctx->actr.p) {
-        int32_t sticky = 0;
-        SC_HIP(ctx, hipMemcpy(&sticky, (const int32_t*)ctx->actr.p + 4, sizeof(sticky), hipMemcpyDeviceToHost));
-        if (sticky) {
-            SC_HIP(ctx, hipMemset((int32_t*)ctx->actr.p + 4, 0, sizeof(int32_t)));
-            if (ctx->astar_cap < (1 << 22)) ctx->astar_cap *= 4;
-        }
-    }
-    r = sc_edt_open_mode_update(ctx);
-    if (r != SC_OK) return r;
+    const size_t sb = SC_ST_COUNT * sizeof(int32_t);
+    // what the launches since the last synchronisation met (sc_status_word): ONE copy, in front of the event the wait sleeps on
+    const hipError_t status_copy = ctx->status_armed ? hipMemcpyAsync(ctx->status_host, ctx->status, sb, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess;
+    const int r = sc_stream_wait(ctx);   // whatever the copy did: the caller's work is waited for
+    if (r != SC_OK || !ctx->status_armed) return r;
+    SC_HIP(ctx, status_copy);
+    ctx->status_armed = false;
+    const int32_t* st = ctx->status_host;
+    int32_t any = 0;
+    for (int i = 0; i < SC_ST_COUNT; ++i) any |= st[i];
+    // cleared in stream order, ahead of any later launch; the outcome is looked at last, so that nothing hides a fault
+    const hipError_t status_clear = any ? hipMemsetAsync(ctx->status, 0, sb, ctx->stream) : hipSuccess;
+    // A* bucket rings overflowed (the overflowed queries were rerun with 16x the space on the device): larger rings from now on
+    if (st[SC_ST_ASTAR_OVERFLOW] && ctx->astar_cap < (1 << 22)) ctx->astar_cap *= 4;
+    sc_edt_open_mode_update(ctx, st[SC_ST_EDT_OPEN_SEEN], st[SC_ST_EDT_OPEN_STILL]);
     // the wide-row EDT kernel's wavefronts wait for one another with bounded spins: one that ran out left rows unwritten
-    if (ctx->edt_fault.p) {
-        int32_t fault = 0;
-        SC_HIP(ctx, hipMemcpy(&fault, ctx->edt_fault.p, sizeof(fault), hipMemcpyDeviceToHost));
-        if (fault) {
-            SC_HIP(ctx, hipMemset(ctx->edt_fault.p, 0, sizeof(int32_t)));
-            snprintf(ctx->err, sizeof(ctx->err), "edt_band_wide_kernel: a wait between the wavefronts of a workgroup ran out; the distances of that call are incomplete");
-            return SC_ERR_HIP;
-        }
+    if (st[SC_ST_EDT_FAULT]) {
+        snprintf(ctx->err, sizeof(ctx->err), "edt_band_wide_kernel: a wait between the wavefronts of a workgroup ran out; the distances of that call are incomplete");
+        return SC_ERR_HIP;
     }
+    SC_HIP(ctx, status_clear);
     return SC_OK;
 }
 

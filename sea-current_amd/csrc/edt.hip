@@ -31,19 +31,19 @@
 //                recurrence into LDS bytes first
 //   W <= 1024    edt_band_k16_kernel: the headline width.  g8's structure with the add + min3 step
 //                (pk_min3_f16bits); its OPEN twin adds a site search for open space and runs, with
-//                edt_updown_kernel in front, while the context is in open-space mode (g_edt_open,
-//                sc_edt_open_mode_update)
+//                edt_updown_kernel in front, while the context is in open-space mode (the two open-space words
+//                of its status block, sc_edt_open_mode_update)
 //   W <= 4096    edt_updown_kernel, then edt_band_wide_kernel: whole rows of up to four
 //                1024-pixel stretches in registers, one persistent workgroup per CU
 //   W <= 8192    launch_band_windows: 1024-column windows through edt_band_g8_kernel<16, true, TILED>,
 //                twice, then edt_band_kernel<128> for the bands the windows gave up on
 // The legal-move kernels that read d2 are in moves.hip.
 //
-// One translation unit on purpose.  The band kernels share edt_gdist_global (__noinline__) and g_edt_open (the library
-// is built without relocatable device code).  And what else is in the unit changes the code of a kernel: compiled in a
-// unit without edt_updown_kernel, every band kernel, edt_band_wide_kernel included, comes out different (the clz of the
-// device library loses its guard for a zero input, and the schedule around it moves).  So compare the assembly kernel by
-// kernel before and after moving one out of this file; the benchmark's kernels are touchy that way.
+// One translation unit on purpose.  The band kernels share edt_gdist_global (__noinline__; the library is built without
+// relocatable device code).  And what else is in the unit changes the code of a kernel: compiled in a unit without
+// edt_updown_kernel, every band kernel, edt_band_wide_kernel included, comes out different (the clz of the device library
+// loses its guard for a zero input, and the schedule around it moves).  So compare the assembly kernel by kernel before
+// and after moving one out of this file; the benchmark's kernels are touchy that way.
 #include "sc_internal.h"
 
 #define EDT_G_INF 0x7FFF                       // "no obstacle in this column"
@@ -1208,11 +1208,6 @@ edt_band_wide_kernel(const uint32_t* __restrict__ colbits, const uint32_t* __res
     }
 }
 
-// Open space at widths up to 1024 (a hint between launches, per device): [0] a row of edt_band_k16_kernel<.., false> took the
-// 32-bit fallback; [1] a row of its OPEN build took the site search.  sc_ctx_synchronize reads and clears them: a context
-// that has seen [0] runs the OPEN build (with edt_updown_kernel in front) until a launch of it leaves [1] clear.
-__device__ int32_t g_edt_open[2];
-
 // One row of open space by the site search, for edt_band_k16_kernel's OPEN build: the row's sites -- obstacle columns with
 // their exact vertical distance, from the band's column word and its up / down word -- compacted in column order into 512
 // words of LDS (SA: the wave's transposition buffer, SB: the first KiB of its first row's bytes), then the monotone
@@ -1324,9 +1319,18 @@ __device__ __forceinline__ int edt_k16_site_row(const uint32_t* __restrict__ cbr
 //    that every lane stores ONE dword per two rows instead of two 2-byte pieces each;
 //  * the transposition re-pairs the registers so that a dword holds two ADJACENT pixels: a 16-byte global store is then ONE
 //    8-byte LDS read (half the read traffic of reading packed registers back and keeping one half of every dword).
+// The launching context's status block is the kernel's seventh argument; its two SC_ST_EDT_OPEN words are the hint to later
+// launches.  The two cold sites that set one fetch the pointer from the kernel-argument segment (edt_k16_args mirrors the
+// argument list): as a named parameter it is live across the row loop, costs every build 2 more SGPR spills and block maps
+// 2.8 % of the band time (profiles/ctx_status_time.json).
+struct edt_k16_args { const uint32_t* colbits; int W, H, nb; int32_t* d2; const uint32_t* udg; int32_t* status; };
+__device__ __forceinline__ int32_t* edt_k16_status() {
+    return ((const edt_k16_args*)__builtin_amdgcn_kernarg_segment_ptr())->status;   // (a C cast: out of the constant address space)
+}
 template <bool FULL, bool OPEN>
 __global__ void __launch_bounds__(512, 8)
-edt_band_k16_kernel(const uint32_t* __restrict__ colbits, int W, int H, int nb, int32_t* __restrict__ d2, const uint32_t* __restrict__ udg) {
+edt_band_k16_kernel(const uint32_t* __restrict__ colbits, int W, int H, int nb, int32_t* __restrict__ d2, const uint32_t* __restrict__ udg,
+                    int32_t* /* status: edt_k16_status() */) {
     constexpr int WAVES = 8, WP = 1024;
     constexpr uint32_t GC2 = EDT_W_GCAP | (EDT_W_GCAP << 16);
     constexpr uint32_t EDGE = 0x7BFF7BFFu;          // beyond the row ends: above every value, below the f16 NaN patterns
@@ -1522,7 +1526,7 @@ edt_band_k16_kernel(const uint32_t* __restrict__ colbits, int W, int H, int nb, 
         // OPEN, not settled (or not tried): the site search
         ++open_rows;
         open_sites = edt_k16_site_row<FULL>(cb + (size_t)b * W, udg + ((size_t)g * nb + b) * W, W, i, lane, tr, smem + (size_t)wave * (WP / 4), out);
-        if (lane == 0) g_edt_open[1] = 1;
+        if (lane == 0) edt_k16_status()[SC_ST_EDT_OPEN_STILL] = 1;
         if (open_sites <= 508) { row_done = true; break; }
         // more sites than the search's LDS holds: the rest of the 175 steps after all; when the first try already ran
         // all of them, the row stays saturated and takes the exact 32-bit cascade below
@@ -1566,7 +1570,7 @@ edt_band_k16_kernel(const uint32_t* __restrict__ colbits, int W, int H, int nb, 
             wave_lds_sync();
         } else {
             // ---- the packed cascade cannot settle this row (open space: some distance beyond 175 columns) ----
-            if (!OPEN && lane == 0) g_edt_open[0] = 1;             // the site search is in this kernel's OPEN twin: tell the host
+            if (!OPEN && lane == 0) edt_k16_status()[SC_ST_EDT_OPEN_SEEN] = 1;   // the site search is in this kernel's OPEN twin: tell the host
             // 32-bit cascade with exact distances (OPEN: rows with more sites than the search's LDS holds)
             uint32_t V[16];
 #pragma unroll
@@ -1619,7 +1623,7 @@ static int edt_band_time_begin(sc_ctx* ctx, int cb_tk) {
 template <bool FULL>
 static int launch_band_k16(sc_ctx* ctx, const uint32_t* colbits, int W, int H, int nb, int batch, int32_t* d2, int cb_tk) {
     const size_t lds = (size_t)32 * 1024 + 8 * 1024;
-    ctx->edt_k16_launched = true;
+    ctx->status_armed = true;
     if (ctx->edt_open_mode) {
         // open space seen on this context (sc_ctx_synchronize): the up / down words first, then the build with the site search
         int r_ = sc_scratch_reserve(ctx, &ctx->updown, (size_t)batch * nb * W * sizeof(uint32_t));
@@ -1627,7 +1631,7 @@ static int launch_band_k16(sc_ctx* ctx, const uint32_t* colbits, int W, int H, i
         const int tk = edt_band_time_begin(ctx, cb_tk);
         launch_updown(ctx, colbits, W, nb, batch, (uint32_t*)ctx->updown.p);
         hipLaunchKernelGGL((edt_band_k16_kernel<FULL, true>), dim3((unsigned)(nb * batch)), dim3(512), lds, ctx->stream, colbits, W, H, nb, d2,
-                           (const uint32_t*)ctx->updown.p);
+                           (const uint32_t*)ctx->updown.p, ctx->status);
         ctx->edt_open_launched = true;
         sc_time_end(ctx, tk);
         SC_HIP(ctx, hipGetLastError());
@@ -1635,26 +1639,17 @@ static int launch_band_k16(sc_ctx* ctx, const uint32_t* colbits, int W, int H, i
     }
     const int tk = edt_band_time_begin(ctx, cb_tk);
     hipLaunchKernelGGL((edt_band_k16_kernel<FULL, false>), dim3((unsigned)(nb * batch)), dim3(512), lds, ctx->stream, colbits, W, H, nb, d2,
-                       (const uint32_t*)nullptr);
+                       (const uint32_t*)nullptr, ctx->status);
     sc_time_end(ctx, tk);
     SC_HIP(ctx, hipGetLastError());
     return SC_OK;
 }
 
-// sc_ctx_synchronize: open space seen / still there?  (Only after a launch of edt_band_k16_kernel on this context.)
-int sc_edt_open_mode_update(sc_ctx* ctx) {
-    if (!ctx->edt_k16_launched) return SC_OK;
-    int32_t h[2] = {0, 0};
-    SC_HIP(ctx, hipMemcpyFromSymbol(h, HIP_SYMBOL(g_edt_open), sizeof(h)));
-    if (h[0] || h[1]) {
-        const int32_t z[2] = {0, 0};
-        SC_HIP(ctx, hipMemcpyToSymbol(HIP_SYMBOL(g_edt_open), z, sizeof(z)));
-    }
-    if (h[0]) ctx->edt_open_mode = true;
-    else if (ctx->edt_open_mode && ctx->edt_open_launched && !h[1]) ctx->edt_open_mode = false;
-    ctx->edt_k16_launched = false;
+// sc_ctx_synchronize: open space seen (SC_ST_EDT_OPEN_SEEN) -> the OPEN build, until a launch of it leaves SC_ST_EDT_OPEN_STILL clear
+void sc_edt_open_mode_update(sc_ctx* ctx, int32_t seen, int32_t still) {
+    if (seen) ctx->edt_open_mode = true;
+    else if (ctx->edt_open_mode && ctx->edt_open_launched && !still) ctx->edt_open_mode = false;
     ctx->edt_open_launched = false;
-    return SC_OK;
 }
 
 // 257 .. 512 columns: edt_band_g8_kernel with 8 pixels per lane
@@ -1716,13 +1711,9 @@ static int launch_band_wide(sc_ctx* ctx, const uint32_t* colbits, int W, int H, 
     }
     // one workgroup (16 wavefronts) per CU, each with a strided set of row groups
     const int nwg = min(ngroups, ctx->cu_count);
-    if (!ctx->edt_fault.p) {
-        int r_ = sc_scratch_reserve(ctx, &ctx->edt_fault, sizeof(int32_t));
-        if (r_ != SC_OK) return r_;
-        SC_HIP(ctx, hipMemsetAsync(ctx->edt_fault.p, 0, sizeof(int32_t), ctx->stream));
-    }
+    ctx->status_armed = true;
     hipLaunchKernelGGL((edt_band_wide_kernel<TILES, FULL>), dim3((unsigned)nwg), dim3(1024), lds, ctx->stream, colbits,
-                       (const uint32_t*)ctx->updown.p, W, H, nb, nsb, ngroups, d2, (int32_t*)ctx->edt_fault.p);
+                       (const uint32_t*)ctx->updown.p, W, H, nb, nsb, ngroups, d2, ctx->status + SC_ST_EDT_FAULT);
     SC_HIP(ctx, hipGetLastError());
     return SC_OK;
 }

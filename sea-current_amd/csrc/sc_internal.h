@@ -22,12 +22,24 @@ struct sc_scratch {
 
 static inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
 
+// What a context's launches tell its host: int32 words of ctx->status (device, one block per context) that kernels only ever
+// set to 1 and that sc_ctx_synchronize copies into ctx->status_host, acts on and clears.
+enum sc_status_word {
+    SC_ST_ASTAR_OVERFLOW,   // A*: a bucket ring overflowed (the query was rerun with 16x the space): later calls start with 4x the rings
+    SC_ST_EDT_OPEN_SEEN,    // EDT, rows of 513 .. 1024 pixels: a row of edt_band_k16_kernel<.., false> took the 32-bit fallback (open space)
+    SC_ST_EDT_OPEN_STILL,   // the same widths: a row of the OPEN build took the site search
+    SC_ST_EDT_FAULT,        // EDT, rows wider than 1024: a wavefront's bounded wait ran out, the distances of that call are incomplete
+    SC_ST_COUNT
+};
+
 // hidden: the library's own types; their (inline) members are not part of the exported symbols
 struct __attribute__((visibility("hidden"))) sc_ctx {
     int device = 0;
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;
     hipEvent_t wait_ev = nullptr;   // blocking-sync event: host waits sleep instead of spinning (one host thread per context in flight)
+    int32_t *status = nullptr, *status_host = nullptr;   // [SC_ST_COUNT] on the device (zeroed) and its pinned mirror: created and freed with the context
+    bool status_armed = false;       // a launch that can set a status word has been enqueued since the last sc_ctx_synchronize
     char err[256] = {0};
     // timing
     int timing = 0;
@@ -41,15 +53,14 @@ struct __attribute__((visibility("hidden"))) sc_ctx {
     sc_scratch host_stage;  // the _host wrappers' device copies (sc_stage), one call at a time
     sc_scratch astar_ends;  // sc_astar_gfield: int32 start, goal, len, path[1] of its one query
     sc_scratch colbits;     // EDT: uint32 [batch][nb][W]
-    sc_scratch updown;      // EDT, rows wider than 1024: uint32 [batch][nb][W], rows to the nearest obstacle in the bands above / below
-    sc_scratch edt_fault;   // EDT, rows wider than 1024: int32 [1], set by a wavefront whose bounded wait ran out (read by sc_ctx_synchronize)
+    sc_scratch updown;      // EDT, rows wider than 1024 and rows of 513 .. 1024 in open-space mode: uint32 [batch][nb][W], rows to the nearest obstacle in the bands above / below
     sc_scratch edt_flags;   // EDT, rows wider than 1024: int32 [2][batch][bands], != 0 where a windowed pass gave a band up
     sc_scratch moves;       // A*: uint8 [H][W]
     sc_scratch gslots;      // A*: uint32 [S][g cells] (4 x 4-cell tiles)
     sc_scratch closed;      // A*: uint32 [S][bitmap words] closed set, one bit per cell (32 x 16-cell tiles)
     sc_scratch buckets;     // A*: uint32 [S][32][cap]
     sc_scratch qstats;      // A*: int32 expanded[Q] | queue order[Q] | overflow list[Q]
-    sc_scratch actr;        // A*: int32 [8] queue / overflow counters of a launch, [4] = sticky overflow flag
+    sc_scratch actr;        // A*: int32 [16], [0 .. 3] queue / overflow counters of a launch (the rest: markers of debug builds)
     sc_scratch bez_tang;    // Bezier: double [P][n_max][2] tangents
     sc_scratch bez_gl;      // Bezier: 32 Gauss-Legendre nodes + 32 weights
     sc_scratch bez_seginfo; // resample: int4 [S] (first sample, last sample, spline, segment in spline)
@@ -77,8 +88,8 @@ struct __attribute__((visibility("hidden"))) sc_ctx {
     int64_t gather_bytes = 0;       // bytes every rank received in the last gather
     std::set<const void*> big_lds_done;   // kernels whose dynamic-LDS limit this context has raised on its device
     int cu_count = 0;               // compute units of the device (0: not asked yet)
-    bool edt_open_mode = false;     // EDT, rows of 513 .. 1024 pixels: open space seen -> the band kernel's build with the site search
-    bool edt_k16_launched = false, edt_open_launched = false;   // since the last sc_ctx_synchronize
+    bool edt_open_mode = false;     // EDT, rows of 513 .. 1024 pixels: this context has seen open space -> the band kernel's build with the site search
+    bool edt_open_launched = false; // that build has been launched since the last sc_ctx_synchronize
     int astar_waves = 0;            // wavefronts an A* launch keeps resident (0: not yet determined)
     int astar_dual = -1;   // queries the two-wavefront A* kernel keeps resident (-1: not asked yet, 0: off)
     int astar_dual_lat = -1;   // the same for its latency build (larger LDS ring: fewer per CU)
@@ -179,7 +190,7 @@ int sc_allow_big_lds(sc_ctx* ctx, const void* kernel, int bytes);
 
 // wait for everything enqueued on the context's stream without burning a host core
 int sc_stream_wait(sc_ctx* ctx);
-int sc_edt_open_mode_update(sc_ctx* ctx);
+void sc_edt_open_mode_update(sc_ctx* ctx, int32_t seen, int32_t still);   // the two open-space status words -> ctx->edt_open_mode (edt.hip; host only)
 
 #ifdef __HIPCC__
 __device__ __forceinline__ void wave_lds_sync() {

@@ -192,6 +192,35 @@ def test_astar_ring_overflow_retry(ctx, oracle, monkeypatch):
     _compare(_run(ctx, d2, s, g, Lmax=4096), ref, 96)
 
 
+def test_astar_ring_overflow_grows_later_rings(ctx, monkeypatch):
+    """A context whose rings overflowed learns of it when it synchronises and starts later calls with 4x the rings: the
+    batch that overflowed with small rings is then found whole, in more ring scratch than a context that never overflowed.
+    X and Y run nothing but these A* calls (the distance map comes from `ctx`), so their scratch differs in the rings alone."""
+    import torch
+    import sea_current_amd as sc
+    from sea_current_amd import synth
+    occ = synth.salt_grid(768, 768, 0.05, seed=5)
+    s, g = synth.queries(occ == 0, 96, seed=6)     # the inputs of test_astar_ring_overflow_retry, which asserts they overflow
+    sd, gd = torch.from_numpy(s).cuda(), torch.from_numpy(g).cuda()
+    d2 = ctx.edt(torch.from_numpy(occ).cuda())
+    ctx.synchronize()
+    X, Y = sc.Context(0), sc.Context(0)
+    try:
+        monkeypatch.setenv("SC_ASTAR_CAP", "1024")
+        X.astar_batch(d2, sd, gd, Lmax=4096)
+        X.synchronize()
+        monkeypatch.delenv("SC_ASTAR_CAP")
+        status = X.astar_batch(d2, sd, gd, Lmax=4096)["status"]
+        X.synchronize()
+        Y.astar_batch(d2, sd, gd, Lmax=4096)
+        Y.synchronize()
+        status, x, y = status.cpu().numpy(), X.scratch_bytes(), Y.scratch_bytes()
+    finally:
+        X.close(); Y.close()
+    assert np.all(status == 0)
+    assert x > y, "the flag read at the synchronisation enlarges the rings of later calls"
+
+
 def test_astar_full_headline_batch(ctx, oracle):
     """The whole headline batch (BASELINE configs[1]: 1024 queries on the 1024^2 salt20 grid, the bench's own inputs), every
     query against the oracle: status, cost, length, path, and the number of expanded nodes."""

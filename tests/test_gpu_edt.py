@@ -298,3 +298,34 @@ def test_edt_open_space_mode_up_to_1024_columns(oracle):
             for k in range(a.shape[0]):
                 assert np.array_equal(got[k], refs[id(a)][k]), (W, H, k)
     c.close()
+
+
+@pytest.mark.parametrize("W", [1024, 600])
+def test_edt_open_space_mode_is_per_context(oracle, W):
+    """Two contexts on one device: the open-space hint of edt_band_k16_kernel belongs to the context that launched it.  A (a
+    map of open space) enters open mode at its synchronisation, whichever context synchronises first, and reserves the
+    up / down words at its next call; B (a dense map) reserves nothing."""
+    import torch
+    import sea_current_amd as sc
+    H, batch = 64, 1
+    rng = np.random.default_rng(W)
+    occ_a = np.zeros((H, W), np.uint8); occ_a[32, 10] = 1      # every row has distances beyond 175 columns: the fallback
+    occ_b = (rng.random((H, W)) < 0.2).astype(np.uint8)
+    ref_a, ref_b = oracle.edt(occ_a), oracle.edt(occ_b)
+    ta, tb = torch.from_numpy(occ_a).cuda(), torch.from_numpy(occ_b).cuda()
+    A, B = sc.Context(0), sc.Context(0)
+    try:
+        got = [(A.edt(ta), ref_a), (B.edt(tb), ref_b)]
+        torch.cuda.synchronize()
+        B.synchronize(); A.synchronize()
+        a1, b1 = A.scratch_bytes(), B.scratch_bytes()
+        got += [(A.edt(ta), ref_a), (B.edt(tb), ref_b)]
+        torch.cuda.synchronize()
+        B.synchronize(); A.synchronize()
+        a2, b2 = A.scratch_bytes(), B.scratch_bytes()
+    finally:
+        A.close(); B.close()
+    for d, ref in got:
+        assert np.array_equal(d.cpu().numpy(), ref)
+    assert b2 == b1, "B never met open space: no up / down words"
+    assert a2 == a1 + batch * ((H + 31) // 32) * W * 4, "A met open space: its next call runs the OPEN build"
