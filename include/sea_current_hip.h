@@ -205,7 +205,7 @@ int sc_astar_batch_multi(sc_ctx* ctx, const int32_t* d2, int G, const int32_t* q
 int sc_astar_last_expansions(sc_ctx* ctx, int64_t* expansions);
 /* Debug: per-query expansions, popped queue entries, kilo-cycles and steps (int32 [4][Q]) of the last sc_astar_batch
  * (synchronises).  sc_astar_debug_peek: the launch counters (words 0 .. 3: queue positions and overflow counts of the main
- * and the retry pass), read without waiting for the stream (bring-up aid). */
+ * and the retry pass; words 4 .. 15 are reserved and read 0), read without waiting for the stream. */
 int sc_astar_debug_stats(sc_ctx* ctx, int32_t* stats4, int Q);
 int sc_astar_debug_peek(sc_ctx* ctx, int32_t* out16);
 /* Debug/parity: g field of ONE query (uint32 [H][W]): the optimal cost-to-come g* of every node the search

@@ -25,7 +25,8 @@
 // (consecutive slots by mbcnt rank of the ballot); successors of other levels take their slot in
 // the HBM ring of their level with one LDS atomic add.  When the LDS ring runs empty it is refilled
 // from the level's HBM ring with coalesced loads, so every pop is an LDS read.
-// Lane layout: frontiers of <= 8 nodes use 8 lanes per node (one per move); wider ones one lane per
+// Lane layout of the one-wavefront kernel (astar_kernel; the two-wavefront kernel's steps are described
+// in astar_query): frontiers of <= 8 nodes use 8 lanes per node (one per move); wider ones one lane per
 // node for the pop, then the legal successors of all nodes are compacted into a list and pushed 64 at
 // a time (1-3 successors per node survive the pruning below, so that is 2-3 passes instead of 8).
 //
@@ -58,20 +59,13 @@
 //   throughput  CQ 1024, RU 4: 13.1 KiB of LDS and <= 80 VGPRs, 12 searches per CU -- batches larger than the chip holds;
 //   latency     CQ 2048, RU 8: 17.2 KiB and 81 VGPRs, 9 per CU -- every search of the batch resident at once, where
 //               the call lasts as long as its longest search and a refill of a wide level is half as many round trips.
-#ifndef ASTAR_CQ_THROUGHPUT
 #define ASTAR_CQ_THROUGHPUT 1024
 #define ASTAR_RU_THROUGHPUT 4
-#endif
-#ifndef ASTAR_CQ_LATENCY
 #define ASTAR_CQ_LATENCY 2048
 #define ASTAR_RU_LATENCY 8
-#endif
 #define E_RUN (1u << 18)       // entry flag: the node's continuation in its arrival direction is already queued
 #define E_START (4u << 13 | 3u << 16)   // the start node: no parent (a diagonal arrival never has side flags)
 #define RUNK 8                 // cells of a same-f straight or diagonal run queued at once
-#ifndef WIDE_RUNS
-#define WIDE_RUNS 0            // runs in wide steps too (measured: fewer steps, but 1.6x the entries popped; slower on all maps but blocks)
-#endif
 
 struct astar_args {
     const uint8_t* moves;
@@ -230,35 +224,17 @@ __device__ __forceinline__ void pop_run_issue(const uint8_t* const (&ra)[RUNK - 
 __device__ __forceinline__ void pop_run_wait_loads(uint32_t (&rm)[RUNK - 1], uint32_t& pmv, uint32_t& old) {
     asm volatile("s_waitcnt vmcnt(1)" : "+v"(pmv), "+v"(old), "+v"(rm[0]), "+v"(rm[1]), "+v"(rm[2]), "+v"(rm[3]), "+v"(rm[4]), "+v"(rm[5]), "+v"(rm[6]) : : "memory");
 }
-// The legal-move bytes of the next RUNK - 1 cells of a wide step's successor lanes (issued behind the step's pair).
-__device__ __forceinline__ void run_loads_issue(const uint8_t* const (&ra)[RUNK - 1], uint32_t (&rm)[RUNK - 1]) {
-    asm volatile("global_load_ubyte %[r0], %[p0], off\n\t"
-                 "global_load_ubyte %[r1], %[p1], off\n\t"
-                 "global_load_ubyte %[r2], %[p2], off\n\t"
-                 "global_load_ubyte %[r3], %[p3], off\n\t"
-                 "global_load_ubyte %[r4], %[p4], off\n\t"
-                 "global_load_ubyte %[r5], %[p5], off\n\t"
-                 "global_load_ubyte %[r6], %[p6], off"
-                 : [r0] "=&v"(rm[0]), [r1] "=&v"(rm[1]), [r2] "=&v"(rm[2]), [r3] "=&v"(rm[3]), [r4] "=&v"(rm[4]), [r5] "=&v"(rm[5]), [r6] "=&v"(rm[6])
-                 : [p0] "v"(ra[0]), [p1] "v"(ra[1]), [p2] "v"(ra[2]), [p3] "v"(ra[3]), [p4] "v"(ra[4]), [p5] "v"(ra[5]), [p6] "v"(ra[6])
-                 : "memory");
-}
-__device__ __forceinline__ void run_loads_wait(uint32_t (&rm)[RUNK - 1]) {
-    asm volatile("s_waitcnt vmcnt(0)" : "+v"(rm[0]), "+v"(rm[1]), "+v"(rm[2]), "+v"(rm[3]), "+v"(rm[4]), "+v"(rm[5]), "+v"(rm[6]) : : "memory");
-}
-// wait for the atomic issued in front of RUNK - 1 run loads (memory operations return in order)
-__device__ __forceinline__ void atomic_wait_but(uint32_t& old, uint32_t (&rm)[RUNK - 1]) {
-    asm volatile("s_waitcnt vmcnt(7)" : "+v"(old), "+v"(rm[0]), "+v"(rm[1]), "+v"(rm[2]), "+v"(rm[3]), "+v"(rm[4]), "+v"(rm[5]), "+v"(rm[6]) : : "memory");
-}
 __device__ __forceinline__ void pop_pair_wait_load(uint32_t& pmv, uint32_t& old) { asm volatile("s_waitcnt vmcnt(1)" : "+v"(pmv), "+v"(old) : : "memory"); }
 
 // Two-wavefront kernel: a query's closed bitmap has ONE writer (its wavefront 0), so the test-and-set of a popped node need
 // not be a returning atomic (about twice a load's latency): the word is LOADED (agent scope: from L2) beside the legal-move
 // byte, duplicates inside the step are settled in LDS while the loads are under way (dup_settle), and the bits of the
-// nodes that were won are set by an atomic OR nobody waits for: the OR of one step and the load of a later one travel the
-// same path to the same L2 channel in issue order, so the load sees the bit without waiting for the OR's acknowledgement
-// (waiting for it put the atomic's latency back on the path; a stale word would show as a node expanded twice, which
-// the expansion counts in tests/test_gpu_astar.py, equal to the oracle's query by query, would catch).
+// nodes that were won are set by an atomic OR nobody waits for (waiting for it put the atomic's latency back on the path).
+// The load of a later step still sees the bit: from step t + 2 on it is issued behind step t + 1's s_waitcnt vmcnt(0)
+// (pop_loads_wait), which the OR of step t has completed by then -- vmcnt counts atomics; a duplicate popped in step t + 1
+// is caught by dup_tbl, which keeps the exact node per slot across steps (see dup_settle).  Nothing rests on how the memory
+// system orders a wave's operations.  A stale word would show as a node expanded twice, which the expansion counts in
+// tests/test_gpu_astar.py, equal to the oracle's query by query, would catch.
 __device__ __forceinline__ void pop_loads_issue(const uint8_t* mv_addr, const uint32_t* w_addr, uint32_t& byte, uint32_t& word) {
     asm volatile("global_load_ubyte %0, %2, off\n\t"
                  "global_load_dword %1, %3, off sc1"
@@ -282,17 +258,6 @@ __device__ __forceinline__ uint32_t bcast_group8(uint32_t v) {
     return q | r;
 }
 
-#ifdef ASTAR_MARKERS   // bring-up aid: progress words the host can read while a launch is still running
-#define MARK(i, v) do { if (threadIdx.x == 0 && blockIdx.x == 0) __hip_atomic_store(&a.counter[8 + (i)], (int)(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); } while (0)
-#else
-#define MARK(i, v) do { } while (0)
-#endif
-#ifdef ASTAR_STAMPS    // measurement aid: cycles per phase of the wide steps, left in the first words of the query's path
-#define STAMP(i) do { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); stamp[i] += (long long)(t_ - t_last); t_last = t_; } while (0)
-#else
-#define STAMP(i) do { } while (0)
-#endif
-
 // One query in scratch slot `slot`: by one wavefront (DUAL = false), or by two (DUAL = true, astar_kernel_dual).
 // A search is bound by what ONE wavefront can issue per
 // frontier step, so the second wavefront takes the part of a wide step that the next step does not wait for:
@@ -304,9 +269,7 @@ __device__ __forceinline__ uint32_t bcast_group8(uint32_t v) {
 // They meet only when a level is exhausted: wavefront 0 waits until wavefront 1 has nothing left (everything for the
 // later levels is then in their rings) before it picks the next level.  No barrier per step -- the two earlier
 // multi-wavefront forms (four wavefronts per query, a master with workers; round 2, in the history) lost exactly there.
-#ifndef HQ
 #define HQ 256   // records of the hand-over ring
-#endif
 #define ASTAR_SPIN_LIMIT (1 << 20)   // polls (about 100 cycles each) wavefront 0 waits for wavefront 1 before it gives the query up
 template <typename GT, bool DUAL, int CQ, int REFILL_UNROLL>
 __device__ __forceinline__ void astar_query(const astar_args& a, const int q, const int slot) {
@@ -340,7 +303,6 @@ __device__ __forceinline__ void astar_query(const astar_args& a, const int q, co
         if (lane == 0 && wv == 0) path[0] = s;
         out_len = 1; out_cost = 0; nexp = 1;   // the oracle counts the start node of a trivial query as expanded
     } else {
-    MARK(0, 1);
     const int tw = a.tw, bw = a.bw;
     GT* g = static_cast<GT*>(a.g) + (size_t)slot * a.gcells;
     uint32_t* cl = a.closed + (size_t)slot * a.bwords;
@@ -370,15 +332,9 @@ __device__ __forceinline__ void astar_query(const astar_args& a, const int q, co
     wave_lds_sync();
     if (DUAL) __syncthreads();
     int lh = 0, lt = 1;  // LDS ring of the current f (wave-uniform)
-    MARK(0, 2);
 
     bool found = false, ovf = false;
     const unsigned long long t_begin = __builtin_amdgcn_s_memtime();
-#ifdef ASTAR_STAMPS
-    long long stamp[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned long long t_last = t_begin;
-    int nwide = 0, nrounds = 0, n_qfull = 0, n_lvl = 0, b_batches = 0, b_records = 0, b_idle = 0, n_refill = 0;
-#endif
     // Every step pops at least one entry and a search pushes at most 8 entries per cell: a bound that a correct search
     // cannot reach.  It bounds wavefront 0's pop loop; its two waits on wavefront 1 (a full hand-over ring, the end of a
     // level) give up after ASTAR_SPIN_LIMIT polls -- wavefront 1 needs microseconds for a full ring -- and end the query as
@@ -428,9 +384,6 @@ __device__ __forceinline__ void astar_query(const astar_args& a, const int q, co
                 hq_hd = __builtin_amdgcn_readfirstlane(__hip_atomic_load(&hq_head, __ATOMIC_RELAXED, SCOPE));
                 if (hq_tl + cnt - hq_hd > HQ) {
                     __builtin_amdgcn_s_sleep(1);
-#ifdef ASTAR_STAMPS
-                    ++n_qfull;
-#endif
                     if (++waited > ASTAR_SPIN_LIMIT) {   // a lost hand-over must not hang the queue: the query ends as a ring overflow
                         ovf = true; steps_left = -1;
                         return wm;
@@ -504,9 +457,6 @@ __device__ __forceinline__ void astar_query(const astar_args& a, const int q, co
                 }
                 if (stop) break;
                 __builtin_amdgcn_s_sleep(4);
-#ifdef ASTAR_STAMPS
-                ++b_idle;
-#endif
                 continue;
             }
             if (a.lazy && tl - hd < 48 && !stop &&
@@ -515,9 +465,6 @@ __device__ __forceinline__ void astar_query(const astar_args& a, const int q, co
                 __builtin_amdgcn_s_sleep(4);
                 continue;
             }
-#ifdef ASTAR_STAMPS
-            ++b_batches; b_records += min(tl - hd, 64);
-#endif
             const int n = min(tl - hd, 64);
             const bool valid = lane < n;
             const int r = (hd + lane) & (HQ - 1);
@@ -566,9 +513,6 @@ __device__ __forceinline__ void astar_query(const astar_args& a, const int q, co
             }
             wave_lds_sync();
         }
-#ifdef ASTAR_STAMPS
-        if (lane == 0 && a.Lmax >= 32) { path[16] = b_batches; path[17] = b_records; path[18] = b_idle; }
-#endif
     } else {
     for (;;) {
         const int b = fcur & 31;
@@ -576,7 +520,6 @@ __device__ __forceinline__ void astar_query(const astar_args& a, const int q, co
         // drain everything with f == fcur: the LDS ring, refilled from what earlier levels left in HBM
         for (;;) {
             if (__builtin_expect(lt == lh, 0)) {
-                STAMP(0);   // loop overhead
                 wave_lds_sync();
                 const int hd = __builtin_amdgcn_readfirstlane(__hip_atomic_load(&s_head[b], __ATOMIC_RELAXED, SCOPE));
                 const int tl = __builtin_amdgcn_readfirstlane(__hip_atomic_load(&s_tail[b], __ATOMIC_RELAXED, SCOPE));
@@ -596,14 +539,9 @@ __device__ __forceinline__ void astar_query(const astar_args& a, const int q, co
                 lt += n;
                 if (lane == 0) __hip_atomic_store(&s_head[b], hd + n, __ATOMIC_RELAXED, SCOPE);
                 wave_lds_sync();
-                STAMP(10);  // refills
-#ifdef ASTAR_STAMPS
-                ++n_refill;
-#endif
             }
             const int n = min(64, lt - lh);
             npop += n; ++nstep;
-            STAMP(0);   // loop overhead, refills
             if (DUAL && n <= 16) {
                 // ---- narrow step, two wavefronts: lane (node, direction, k) for the two same-f directions of a node and
                 // k = 0 .. KL-1 cells along them (KL = 8 for up to 4 nodes, 4 / 2 / 1 for up to 8 / 16 / 32): ONE load per lane (the
@@ -656,7 +594,6 @@ __device__ __forceinline__ void astar_query(const astar_args& a, const int q, co
                 }
                 hand_over(won1, x, y, (byte & ~prune) & ~(bD | bS), byte);
                 nexp += __popcll(wm1);
-                STAMP(8);   // narrow steps
             } else if (!DUAL && n <= 8) {
                 // ---- narrow step: 8 lanes per node, lane (sub, d) handles move d of node sub ----
                 const int sub = lane >> 3, d = lane & 7;
@@ -706,12 +643,8 @@ __device__ __forceinline__ void astar_query(const astar_args& a, const int q, co
                 nexp += __popcll(__ballot(won && d == 0));
                 if (__ballot(won && x == gx && y == gy)) found = true;
                 if (won && d == 0) g[gidx<GT>(x, y, tw)] = (GT)(fcur - hc);
-                STAMP(8);   // narrow steps
             } else if (DUAL) {
                 // ---- wide step, two wavefronts: close the nodes, queue their same-f successors, hand the rest over ----
-#ifdef ASTAR_STAMPS
-                ++nwide;
-#endif
                 const bool valid = lane < n;
                 const uint32_t e_raw = qe[(lh + lane) & (CQ - 1)];   // read under the full EXEC mask
                 const uint32_t e = valid ? e_raw : 0u;
@@ -755,14 +688,12 @@ __device__ __forceinline__ void astar_query(const astar_args& a, const int q, co
                     }
                 }
                 nexp += __popcll(hand_over(won, x, y, cand & ~(bD | bS), pmv));
-                STAMP(6);
             } else {
                 // ---- wide step: one lane per node, then the legal successors of all nodes 64 at a time ----
                 // The successor list is built while the atomic is still under way, as if every node were won (most are);
                 // the successors of a node that turns out to be somebody else's are dropped when they would be pushed.
-                // Same-f successors look RUNK cells ahead exactly as in the narrow step (their loads go out before the
-                // atomic is waited for), so the equal-f chains of a wide frontier advance RUNK cells per step too.
-                STAMP(0);   // everything outside the wide steps
+                // Same-f successors are queued one cell at a time here: runs (RUNK cells ahead, as in the narrow step) were
+                // measured in this step too -- fewer steps, but 1.6x the entries popped, slower on all maps but blocks.
                 const bool valid = lane < n;
                 const uint32_t e = valid ? qe[(lh + lane) & (CQ - 1)] : 0u;
                 lh += n;
@@ -772,9 +703,7 @@ __device__ __forceinline__ void astar_query(const astar_args& a, const int q, co
                 pop_pair_issue(mvs + (y * W + x), &cl[cix(x, y, bw)], valid ? bit : 0u, pmv, old);   // invalid lanes read cell 0: harmless
                 const uint32_t prune = prune_tbl[(e >> 13) & 63u];
                 const int hc = octile(x, y, gx, gy);
-                STAMP(1);   // pop and issue
                 pop_pair_wait_load(pmv, old);
-                STAMP(2);   // the load
                 uint32_t mv = valid ? (pmv & ~prune) : 0u;
                 nd_xy[lane] = (uint32_t)y << 16 | (uint32_t)x;
                 nd_mv[lane] = pmv;
@@ -793,15 +722,8 @@ __device__ __forceinline__ void astar_query(const astar_args& a, const int q, co
                     succ[base++] = (uint16_t)(lane << 3 | dd);
                 }
                 wave_lds_sync();
-                STAMP(3);   // successor list
                 bool won = false;
-#ifdef ASTAR_STAMPS
-                ++nwide;
-#endif
                 for (int j0 = 0; j0 < total; j0 += 64) {
-#ifdef ASTAR_STAMPS
-                    ++nrounds;
-#endif
                     const bool act = j0 + lane < total;
                     const uint32_t sd = act ? succ[j0 + lane] : 0u;
                     const int par = (int)(sd >> 3), d = (int)(sd & 7u);
@@ -810,21 +732,15 @@ __device__ __forceinline__ void astar_query(const astar_args& a, const int q, co
                     const int ddx_ = (int)((0x2252u >> (2 * d)) & 3u) - 1, ddy_ = (int)((0x0A25u >> (2 * d)) & 3u) - 1;
                     const int nx = px + ddx_, ny = py + ddy_;
                     const int df = (d < 4 ? 10 : 14) + octile(nx, ny, gx, gy) - octile(px, py, gx, gy);
-                    const int adx = abs(gx - px), ady = abs(gy - py);
-                    const int lgeom = d >= 4 ? min(adx, ady) : abs(adx - ady);
-                    const int lmax = WIDE_RUNS && act && df == 0 ? min(RUNK, lgeom) : 1;
-                    const int so = ddy_ * W + ddx_;
-                    const uint8_t* const cell = mvs + (py * W + px);
+                    // Dead on purpose: what is left of the set-up of the removed wide-step runs.  The compiler drops it, but with it
+                    // gone it numbers the registers and orders the instructions of astar_kernel differently (same instructions,
+                    // same register counts); with it the device code is byte for byte what has been tested and timed.
                     const uint8_t* ra[RUNK - 1];
-                    uint32_t rm[RUNK - 1];
 #pragma unroll
-                    for (int k = 1; k < RUNK; ++k) ra[k - 1] = cell + min(k, lmax - 1) * so;
-                    if (WIDE_RUNS) run_loads_issue(ra, rm);
+                    for (int k = 1; k < RUNK; ++k) ra[k - 1] = mvs + (py * W + px);
+                    (void)ra;
                     if (j0 == 0) {
-                        // the pop's atomic is older than the run loads: in-order return, RUNK - 1 operations may remain
-                        STAMP(4);   // first round's preparation
-                        if (WIDE_RUNS) atomic_wait_but(old, rm); else atomic_wait(old);
-                        STAMP(5);   // the atomic
+                        atomic_wait(old);
                         won = valid && !(old & bit);   // duplicates inside one pop: the atomics serialise, one lane wins
                         nexp += __popcll(__ballot(won));
                         if (__ballot(won && x == gx && y == gy)) found = true;
@@ -832,21 +748,7 @@ __device__ __forceinline__ void astar_query(const astar_args& a, const int q, co
                         wave_lds_sync();
                     }
                     const bool go = act && ((nd_mv[par] >> 8) & 1u);
-                    int run = 1;
-                    if (WIDE_RUNS) {
-                        run_loads_wait(rm);
-#pragma unroll
-                        for (int k = 1; k < RUNK; ++k)
-                            if (run == k && k < lmax && ((rm[k - 1] >> d) & 1u)) run = k + 1;
-                    }
-                    push_entry(go, entry_pack(nx, ny, d, pmvp) | (run > 1 ? E_RUN : 0u), df);
-                    if (WIDE_RUNS) {
-#pragma unroll
-                        for (int k = 2; k <= RUNK; ++k) {
-                            if (__ballot(go && run >= k) == 0) break;
-                            push_entry(go && run >= k, entry_pack(px + k * ddx_, py + k * ddy_, d, rm[k - 2]) | (run > k ? E_RUN : 0u), 0);
-                        }
-                    }
+                    push_entry(go, entry_pack(nx, ny, d, pmvp), df);
                 }
                 if (total == 0) {
                     atomic_wait(old);
@@ -855,7 +757,6 @@ __device__ __forceinline__ void astar_query(const astar_args& a, const int q, co
                     if (__ballot(won && x == gx && y == gy)) found = true;
                 }
                 if (won) g[gidx<GT>(x, y, tw)] = (GT)(fcur - hc);
-                STAMP(6);   // pushes
             }
             // wave-uniform by construction (ballots, popcounts); the joins above hide that from the compiler, which would
             // otherwise run these loops under EXEC masks with the counters in VGPRs
@@ -864,25 +765,19 @@ __device__ __forceinline__ void astar_query(const astar_args& a, const int q, co
             nexp = __builtin_amdgcn_readfirstlane(nexp);
             found = __builtin_amdgcn_readfirstlane((int)found) != 0;
             wave_lds_sync();
-            MARK(1, steps_left); MARK(2, fcur); MARK(3, nexp); MARK(4, lt - lh);
             if (--steps_left < 0) ovf = true;
             if (__builtin_expect(DUAL ? steps_left < 0 : __ballot(ovf) != 0, 0)) break;
         }
         if (DUAL) {
             // every node of this level has been handed over: wait until wavefront 1 has pushed what follows from them
-            STAMP(0);
             if (a.lazy && lane == 0) __hip_atomic_store(&hq_flush, hq_tl, __ATOMIC_RELAXED, SCOPE);
             for (int waited = 0; __builtin_amdgcn_readfirstlane(__hip_atomic_load(&hq_clean, __ATOMIC_RELAXED, SCOPE)) != hq_tl;) {
                 __builtin_amdgcn_s_sleep(1);
-#ifdef ASTAR_STAMPS
-                ++n_lvl;
-#endif
                 if (++waited > ASTAR_SPIN_LIMIT) { ovf = true; break; }   // as above: never expected, never a hang
             }
             wave_lds_sync();
             if (__hip_atomic_load(&hq_ovf, __ATOMIC_RELAXED, SCOPE)) ovf = true;
             if (__builtin_amdgcn_readfirstlane(__hip_atomic_load(&hq_found, __ATOMIC_RELAXED, SCOPE))) found = true;
-            STAMP(7);
         }
         if (__ballot(ovf) || found) break;
         // level fcur is exhausted: advance to the next non-empty bucket
@@ -894,7 +789,6 @@ __device__ __forceinline__ void astar_query(const astar_args& a, const int q, co
         const uint32_t rot = r0 ? (nonempty >> r0) | (nonempty << (32 - r0)) : nonempty;
         fcur += 1 + (__ffs((int)rot) - 1);
         if (DUAL && lane == 0) __hip_atomic_store(&hq_fcur, fcur, __ATOMIC_RELAXED, SCOPE);   // the ring is empty: wavefront 1 reads it with the next records
-        STAMP(9);   // next level
     }
     if (DUAL && lane == 0) __hip_atomic_store(&hq_stop, 1, __ATOMIC_RELAXED, SCOPE);   // wavefront 1 has nothing left (level-end wait): it leaves
     }   // wavefront 0
@@ -912,7 +806,6 @@ __device__ __forceinline__ void astar_query(const astar_args& a, const int q, co
         out_st = SC_Q_NO_PATH;
     } else {
         // ---- canonical parent chain, goal -> start, written right-aligned then shifted left ----
-        STAMP(9);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // every g store of this wave has reached L2
         const int Lmax = a.Lmax;
         int cx = gx, cy = gy, L = 1;
@@ -971,15 +864,8 @@ __device__ __forceinline__ void astar_query(const astar_args& a, const int q, co
             }
             out_len = L; out_cost = fcur;
         }
-        STAMP(11);  // path extraction
     }
     kcyc = (int)((__builtin_amdgcn_s_memtime() - t_begin) >> 10);
-#ifdef ASTAR_STAMPS
-    if (lane == 0 && wv == 0 && a.Lmax >= 16) {
-        for (int i = 0; i < 12; ++i) path[i] = (int)(stamp[i] >> 10);
-        path[12] = nwide; path[13] = nrounds; path[14] = n_qfull; path[15] = n_lvl; path[19] = n_refill;
-    }
-#endif
     }   // search
     if (lane == 0 && wv == 0) {
         a.status[q] = out_st; a.len[q] = out_len; a.cost[q] = out_cost;
@@ -1246,7 +1132,7 @@ extern "C" int sc_astar_gfield(sc_ctx* ctx, const int32_t* d2, int W, int H, int
     return SC_OK;
 }
 
-// debug: the 16 counter / marker words of the A* launches, read WITHOUT waiting for the context's stream
+// debug: the 16 counter words of the A* launches (4 .. 15 reserved, 0), read WITHOUT waiting for the context's stream
 extern "C" int sc_astar_debug_peek(sc_ctx* ctx, int32_t* out16) {
     if (!ctx || !out16 || !ctx->actr.p) return SC_ERR_INVALID;
     hipStream_t s;

@@ -60,7 +60,7 @@ struct __attribute__((visibility("hidden"))) sc_ctx {
     sc_scratch closed;      // A*: uint32 [S][bitmap words] closed set, one bit per cell (32 x 16-cell tiles)
     sc_scratch buckets;     // A*: uint32 [S][32][cap]
     sc_scratch qstats;      // A*: int32 expanded[Q] | queue order[Q] | overflow list[Q]
-    sc_scratch actr;        // A*: int32 [16], [0 .. 3] queue / overflow counters of a launch (the rest: markers of debug builds)
+    sc_scratch actr;        // A*: int32 [16], [0 .. 3] queue / overflow counters of a launch ([4 .. 15] reserved, read 0)
     sc_scratch bez_tang;    // Bezier: double [P][n_max][2] tangents
     sc_scratch bez_gl;      // Bezier: 32 Gauss-Legendre nodes + 32 weights
     sc_scratch bez_seginfo; // resample: int4 [S] (first sample, last sample, spline, segment in spline)

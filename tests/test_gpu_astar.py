@@ -254,6 +254,60 @@ def test_astar_full_headline_batch(ctx, oracle):
         del os.environ["SC_ASTAR_LATENCY"]
 
 
+def _chain_queries(trav, seed):
+    """64 queries on a 96 x 96 map: straight lines, diagonals and near-diagonals across the whole grid (same-f runs far longer
+    than the RUNK cells a narrow step queues at once), trivial ones, one wide parallelogram per octant, random ones."""
+    H, W = trav.shape
+    m = W - 1
+    xy = []
+    for y in (0, 30, m):
+        xy += [(0, y, m, y), (m, y, 0, y)]                                  # horizontals
+    for x in (0, 50, m):
+        xy += [(x, 0, x, m), (x, m, x, 0)]                                  # verticals
+    xy += [(0, 0, m, m), (m, m, 0, 0), (m, 0, 0, m), (0, m, m, 0)]          # diagonals
+    xy += [(0, 0, m, m - 1), (0, 0, m - 1, m), (m, m, 0, 1), (m, m, 1, 0),  # | |dx| - |dy| | = 1
+           (m, 0, 0, m - 1), (m, 0, 1, m), (0, m, m, 1), (0, m, m - 1, 0)]
+    xy += [(0, 0, 0, 0), (50, 50, 50, 50)]                                  # s == t
+    for dx, dy in ((88, 37), (37, 88)):                                     # every cell of the parallelogram has f = C*
+        xy += [(3, 2, 3 + dx, 2 + dy), (m - 3, 2, m - 3 - dx, 2 + dy), (3, m - 2, 3 + dx, m - 2 - dy), (m - 3, m - 2, m - 3 - dx, m - 2 - dy)]
+    s = np.array([y0 * W + x0 for x0, y0, _, _ in xy], np.int32)
+    g = np.array([y1 * W + x1 for _, _, x1, y1 in xy], np.int32)
+    assert trav.ravel()[s].all() and trav.ravel()[g].all()
+    rng = np.random.default_rng(seed)
+    free = np.flatnonzero(trav.ravel()).astype(np.int32)
+    n = 64 - s.shape[0]
+    return np.concatenate([s, rng.choice(free, n)]).astype(np.int32), np.concatenate([g, rng.choice(free, n)]).astype(np.int32)
+
+
+def test_astar_single_wavefront_long_equal_f_chains(oracle, monkeypatch):
+    """The one-wavefront kernel (SC_ASTAR_DUAL=0) on long equal-f chains: an obstacle-free 96 x 96 grid, where the octile
+    heuristic is exact and a whole search is ONE f level, and the same grid cut by a wall one cell thick with one gap.
+    Every query against the oracle: status, cost, length, path and the number of expanded nodes."""
+    import sea_current_amd as sc
+    W = H = 96
+    open_map = np.zeros((H, W), np.uint8)
+    wall_map = open_map.copy()
+    wall_map[:, 48] = 1
+    wall_map[30, 48] = 0
+    monkeypatch.setenv("SC_ASTAR_DUAL", "0")            # read when the context runs its first A*
+    c = sc.Context(0)
+    try:
+        for name, occ in (("open", open_map), ("wall", wall_map)):
+            d2 = oracle.edt(occ)
+            s, g = _chain_queries(d2 >= 1, seed=96)
+            ref = oracle.astar_batch(d2, s, g, Lmax=512, nthreads=4)
+            assert (ref["status"] == 0).all(), name
+            got = _run(c, d2, s, g, Lmax=512)
+            _compare(got, ref, 64)
+            if name == "open":
+                # a narrow step of this kernel pops at most 8 nodes: more expansions per step than that on average
+                # means the search ran lane-per-node (wide) steps
+                steps = c.astar_debug_stats(64)[3]
+                assert (got["expanded"] > 8 * steps).any()
+    finally:
+        c.close()
+
+
 def test_astar_scratch_fits_what_the_device_has_free(oracle):
     """The per-search scratch is budgeted per context but allocated on a shared device: with most of the HBM taken by
     somebody else a large batch must still run -- on fewer resident searches -- and give the same results."""
@@ -286,3 +340,4 @@ def test_astar_scratch_fits_what_the_device_has_free(oracle):
     sub = {k: v[sel] for k, v in got.items()}
     sub["expanded"] = got_ex[sel]
     _compare(sub, ref, sel.shape[0])
+
