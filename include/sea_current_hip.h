@@ -71,8 +71,9 @@ typedef enum {
     SC_K_FMT = 11,        /* FMT* over Halton samples (the reference's own planner), one wavefront per query */
     SC_K_GATHER = 12,     /* gather of result paths: pack, ncclAllGather, unpack */
     SC_K_WAYPOINTS = 13,  /* A* cell paths -> line-of-sight waypoints, one wavefront per path */
-    SC_K_SMOOTH = 14,     /* sc_smooth_paths_batch's own kernels (checks, scans, compaction, TOPP-RA inputs, ang_vel) and
-                           * sc_cells_to_points_batch; the library kernels it runs keep their own ids */
+    SC_K_SMOOTH = 14,     /* sc_smooth_paths_batch's own kernels (checks, scans, compaction, TOPP-RA inputs, ang_vel),
+                           * sc_cells_to_points_batch, the speed limits and the path conflicts (sc_traj_*, sc_fleet_conflicts_batch);
+                           * the library kernels it runs keep their own ids */
     SC_K_COUNT = 15
 } sc_kernel_id;
 
@@ -676,6 +677,86 @@ int sc_smooth_paths_limited_batch_host(sc_ctx* ctx, const float* path, const int
                                        float* acc, float* pts, float* curvature, float* ang_vel, float* tpar, int32_t* seg,
                                        const double* dyn, int J, const int32_t* d2, int W, int H, float x_min, float y_min, float res_x,
                                        float res_y, double* vmax_stage, float* min_clear);
+
+/* ---- conflicts between timed paths: who meets whom, when, how close --------------------------------------------
+ * sc_smooth_paths_batch leaves P timed paths on the device; these calls compare them with each other.  Detection only:
+ * nothing is re-planned, delayed or moved (the caller can change a start delay and call again).  A moving obstacle is
+ * one more timed path (two samples and a radius).  The reference has nothing of this kind.
+ *
+ * Definition.  All arithmetic is fp64 on the float32 inputs, in exactly this order of operations, without fused
+ * multiply-adds (tests/traj_twin.py states it in NumPy, tests/cpp/traj_ref.c in C).
+ *   Input: P timed paths in the packed layout sc_smooth_paths_batch writes: offsets int32 [P+1], length int32 [P], status
+ *     int32 [P] (may be NULL = all SC_SMOOTH_OK), time fp64 [M], pts float [M][2]; path p's samples are offsets[p] ..
+ *     offsets[p] + length[p] - 1.  Per path: t0 fp64 [P] start delay (NULL = 0); flags int32 [P], bit 0 = stands at its
+ *     first point before it starts, bit 1 = stands at its last point after it ends (NULL = 3); radius fp64 [P]; group int32
+ *     [P] (NULL = all different): two paths with the same group >= 0 are never compared, a negative group equals nobody.
+ *   Path status (tstatus int32 [P], sc_traj_status): SC_TRAJ_SKIPPED when status[p] != SC_SMOOTH_OK or length[p] < 1;
+ *     SC_TRAJ_BAD when a sample, t0 or radius is not finite, radius < 0, or time decreases; else SC_TRAJ_OK.  Paths that
+ *     are not OK take part in nothing: their knots are NaN and their outputs read "none".  Decided on the device.
+ *   Common clock: tau_k = T0 + k * dt_c for k = 0 .. K.
+ *   Knot of path p at tau_k: u = tau_k - t0[p].  u < time[first]: the first point if flag bit 0 is set, else absent
+ *     (NaN, NaN).  u > time[last]: the last point if flag bit 1 is set, else absent.  A path of one sample is its point.
+ *     Otherwise j = the last index with time[j] <= u, at most len - 2; f = (u - time[j]) / (time[j+1] - time[j]), or 0 when
+ *     that denominator is <= 0; knot = a + f * (b - a) per coordinate with a, b = (double)pts[j], (double)pts[j+1].  The
+ *     motion compared is the piecewise-linear interpolant of the knots.
+ *   Pair (lo < hi) on interval k, compared only when all four knots are present: d0 = knot[hi][k] - knot[lo][k],
+ *     d1 = knot[hi][k+1] - knot[lo][k+1], e = d1 - d0; a = ex*ex + ey*ey, b = d0x*ex + d0y*ey, c = d0x*d0x + d0y*d0y;
+ *     lam = a > 0 ? clamp(-b / a, 0, 1) : 0; m2 = (d0x + lam*ex)^2 + (d0y + lam*ey)^2; R = radius[lo] + radius[hi].  The
+ *     interval conflicts iff m2 < R*R; then lc = 0 if c < R*R, else lc = clamp((-b - sqrt(max(b*b - a*(c - R*R), 0))) / a,
+ *     0, lam), and the time of the conflict is tau_k + lc * dt_c.  clamp(x, l, h) = x < l ? l : (x > h ? h : x), max(x, 0) =
+ *     x > 0 ? x : 0.  Everything is in terms of lo and hi, so (p, q) and (q, p) agree bit for bit.
+ *   Pair result: first(p,q) = the minimum over k of those times (+inf if none); sep2(p,q) = the minimum over k of m2 (+inf
+ *     if the two are never both present on an interval).
+ *   Outputs per path, each may be NULL: first_t fp64 = the minimum over partners of first; first_with int32 = the smallest
+ *     partner attaining it (-1 if none); min_sep fp64 = sqrt(min over partners of sep2) if that is < sep_cap, else +inf;
+ *     min_with int32 = the smallest partner attaining it, else -1; n_conf int32 = the number of partners with a conflict.
+ *   Optional bit matrix: conflict uint32 [P][ceil(P/32)], symmetric, bit q of row p set iff the pair conflicts.
+ *   sep_cap: fp64 > 0, +inf = report every separation.  It exists so that far-apart pairs may be skipped by a
+ *     conservative bound without changing any output; this version evaluates every pair.
+ *   Every output is independent of the order of execution: minima, counts and bit-ORs only.
+ *
+ * sc_traj_knots_batch: the knots fp64 [P][K+1][2] and tstatus (samples, t0, time) of P paths.
+ * sc_traj_conflicts_batch: the outputs above from knots; tstatus is read and written: a path that is OK on entry and whose
+ *   radius is outside the contract becomes SC_TRAJ_BAD.  Knots of any origin may be passed (tstatus all 0 then).
+ * sc_fleet_conflicts_batch: the two in sequence with the arguments of both; knots and tstatus may be NULL (context scratch).
+ * Device pointers; the calls only enqueue on the context's stream (kernels timed under SC_K_SMOOTH): no host
+ * synchronisation, no device-to-host copy, so they chain behind sc_smooth_paths_batch reading its offsets / length / status
+ * / time / pts directly.  Scratch of the context: 24 bytes * P * slots with slots <= ceil(4096 / ceil(P/64)) (at most
+ * 6 MiB, reached at P = 1024; 4096 is the number of workgroups a launch aims for), P * ceil(P/32) * 4 bytes when n_conf is asked without the matrix, and in sc_fleet_conflicts_batch
+ * 16 * P * (K+1) bytes when knots is NULL.
+ * The _host forms take host pointers and return SC_ERR_INVALID before any launch for offsets that decrease or are
+ * negative, a readable path (status OK, length >= 1) that ends past offsets[P] (= M), flags outside 0..3 and for t0 or
+ * radius outside the contract (what the kernel would mark SC_TRAJ_BAD from the per-path arguments; samples are judged on
+ * the device).
+ * Errors: SC_ERR_INVALID for NULL required pointers, P outside 1..16384, K outside 1..65535, P * (K+1) > 2^26, dt_c not
+ * finite or <= 0, T0 not finite, sep_cap NaN or <= 0. */
+typedef enum {
+    SC_TRAJ_OK = 0,
+    SC_TRAJ_SKIPPED = 1,
+    SC_TRAJ_BAD = 2
+} sc_traj_status;
+int sc_traj_knots_batch(sc_ctx* ctx, const double* time, const float* pts, const int32_t* offsets, const int32_t* length,
+                        const int32_t* status, int P, const double* t0, const int32_t* flags, double T0, double dt_c, int K,
+                        double* knots, int32_t* tstatus);
+int sc_traj_knots_batch_host(sc_ctx* ctx, const double* time, const float* pts, const int32_t* offsets, const int32_t* length,
+                             const int32_t* status, int P, const double* t0, const int32_t* flags, double T0, double dt_c, int K,
+                             double* knots, int32_t* tstatus);
+int sc_traj_conflicts_batch(sc_ctx* ctx, const double* knots, int32_t* tstatus, int P, int K, double T0, double dt_c,
+                            const double* radius, const int32_t* group, double sep_cap, double* first_t, int32_t* first_with,
+                            double* min_sep, int32_t* min_with, int32_t* n_conf, uint32_t* conflict);
+int sc_traj_conflicts_batch_host(sc_ctx* ctx, const double* knots, int32_t* tstatus, int P, int K, double T0, double dt_c,
+                                 const double* radius, const int32_t* group, double sep_cap, double* first_t, int32_t* first_with,
+                                 double* min_sep, int32_t* min_with, int32_t* n_conf, uint32_t* conflict);
+int sc_fleet_conflicts_batch(sc_ctx* ctx, const double* time, const float* pts, const int32_t* offsets, const int32_t* length,
+                             const int32_t* status, int P, const double* t0, const int32_t* flags, double T0, double dt_c, int K,
+                             double* knots, int32_t* tstatus, const double* radius, const int32_t* group, double sep_cap,
+                             double* first_t, int32_t* first_with, double* min_sep, int32_t* min_with, int32_t* n_conf,
+                             uint32_t* conflict);
+int sc_fleet_conflicts_batch_host(sc_ctx* ctx, const double* time, const float* pts, const int32_t* offsets, const int32_t* length,
+                                  const int32_t* status, int P, const double* t0, const int32_t* flags, double T0, double dt_c, int K,
+                                  double* knots, int32_t* tstatus, const double* radius, const int32_t* group, double sep_cap,
+                                  double* first_t, int32_t* first_with, double* min_sep, int32_t* min_with, int32_t* n_conf,
+                                  uint32_t* conflict);
 
 /* ---- the reference's own planner, batched -----------------------------------------------
  * planning_space::fast_marching_trees (sea_current.hpp:1339-1407) with near (:1328-1337), cost (:1315-1326) and

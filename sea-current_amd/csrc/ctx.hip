@@ -38,6 +38,9 @@ extern "C" int sc_ctx_create(int device, sc_ctx** out) {
     c->stream = c->own_stream;
     // scratch the A* slots of this context may take, in GiB (a slot = one resident wavefront's g array, closed bitmap and rings)
     if (const char* e = getenv("SC_ASTAR_SLOT_GB")) { const long v = atol(e); if (v >= 1 && v <= 256) c->astar_slot_budget = (size_t)v << 30; }
+    // workgroups the pair kernel of the path conflicts aims for (the tests lower it so that small fleets walk several tick
+    // chunks and column tiles per workgroup)
+    if (const char* e = getenv("SC_TRAJ_WORKGROUPS")) { const long v = atol(e); if (v >= 1 && v <= 65536) c->traj_wg_target = (int)v; }
     *out = c;
     return SC_OK;
 }

@@ -25,6 +25,8 @@ K_EDT_COLBITS, K_EDT_BAND, K_MOVES, K_ASTAR, K_TOPPRA, K_TOPPRA_SAMPLE, K_BEZIER
 K_WAYPOINTS = 13
 K_SMOOTH = 14
 SMOOTH_OK, SMOOTH_BAD_INPUT, SMOOTH_NONFINITE, SMOOTH_TOPPRA_FAILED, SMOOTH_TRUNCATED, SMOOTH_EMPTY_SEGMENT = range(6)
+TRAJ_OK, TRAJ_SKIPPED, TRAJ_BAD = range(3)
+TRAJ_MAX_TICKS = 65535
 
 _lib = None
 
@@ -125,6 +127,12 @@ _SIGNATURES = {
                                       [_vp, _i, _vp, _i, _i] + [C.c_float] * 4 + [_vp, _vp]),
     "sc_smooth_paths_limited_batch_host": (_i, [_vp, _vp, _vp, _i, _i, _vp, C.c_float, _vp, _i, C.c_float, _i, _i, C.c_int64] + [_vp] * 16 +
                                            [_vp, _i, _vp, _i, _i] + [C.c_float] * 4 + [_vp, _vp]),
+    "sc_traj_knots_batch": (_i, [_vp] * 6 + [_i, _vp, _vp, _d, _d, _i, _vp, _vp]),
+    "sc_traj_knots_batch_host": (_i, [_vp] * 6 + [_i, _vp, _vp, _d, _d, _i, _vp, _vp]),
+    "sc_traj_conflicts_batch": (_i, [_vp] * 3 + [_i, _i, _d, _d, _vp, _vp, _d] + [_vp] * 6),
+    "sc_traj_conflicts_batch_host": (_i, [_vp] * 3 + [_i, _i, _d, _d, _vp, _vp, _d] + [_vp] * 6),
+    "sc_fleet_conflicts_batch": (_i, [_vp] * 6 + [_i, _vp, _vp, _d, _d, _i, _vp, _vp, _vp, _vp, _d] + [_vp] * 6),
+    "sc_fleet_conflicts_batch_host": (_i, [_vp] * 6 + [_i, _vp, _vp, _d, _d, _i, _vp, _vp, _vp, _vp, _d] + [_vp] * 6),
     "sc_rank_range": (None, [_i, _i, _i, C.POINTER(_i), C.POINTER(_i)]),
     "sc_comm_unique_id": (_i, [_vp]),
     "sc_comm_init": (_i, [_vp, _vp, _i, _i]),
@@ -605,6 +613,172 @@ class Context:
         self._ck(self._l.sc_smooth_paths_limited_batch_host(*args, _ptr(dyn), J, _ptr(d2), *self._frame(d2, frame), _ptr(o["vmax_stage"]),
                                                             _ptr(o["min_clear"])), "sc_smooth_paths_limited_batch_host")
         return o
+
+    # ---- conflicts between timed paths (sc_traj_knots_batch, sc_traj_conflicts_batch, sc_fleet_conflicts_batch) ----
+    @staticmethod
+    def _traj_ticks(sm, t0, T0, dt_c):
+        """K that covers the longest path plus its delay: the last tick at or after max(time[last] + t0) over the paths that
+        have samples.  Reads the paths' end times (torch: synchronises)."""
+        off, ln = sm["offsets"], sm["length"]
+        st = sm.get("status")
+        if isinstance(ln, np.ndarray):
+            use = (ln >= 1) & ((st == SMOOTH_OK) if st is not None else True)
+            if not use.any():
+                return 1
+            end = sm["time"][(off[:-1] + ln - 1)[use]] + (0.0 if t0 is None else np.asarray(t0, np.float64)[use])
+            end = float(end[np.isfinite(end)].max()) if np.isfinite(end).any() else T0
+        else:
+            import torch
+            use = ln >= 1
+            if st is not None:
+                use = use & (st == SMOOTH_OK)
+            idx = (off[:-1].long() + ln.long() - 1)[use]
+            if idx.numel() == 0:
+                return 1
+            end = sm["time"][idx] + (0.0 if t0 is None else t0[use])
+            end = end[torch.isfinite(end)]
+            end = float(end.max()) if end.numel() else T0
+        return int(min(max(np.ceil((end - T0) / dt_c), 1), TRAJ_MAX_TICKS))
+
+    @staticmethod
+    def _traj_out(P, dev, want_matrix):
+        import torch
+        f = lambda: torch.empty(P, dtype=torch.float64, device=dev)
+        i = lambda: torch.empty(P, dtype=torch.int32, device=dev)
+        # the bits of a row as int32 words (torch has no uint32 arithmetic): bit q % 32 of word q // 32
+        return dict(first_t=f(), first_with=i(), min_sep=f(), min_with=i(), n_conf=i(),
+                    conflict=torch.empty((P, (P + 31) // 32), dtype=torch.int32, device=dev) if want_matrix else None)
+
+    @staticmethod
+    def _traj_out_host(P, want_matrix):
+        return dict(first_t=np.zeros(P), first_with=np.zeros(P, np.int32), min_sep=np.zeros(P), min_with=np.zeros(P, np.int32),
+                    n_conf=np.zeros(P, np.int32), conflict=np.zeros((P, (P + 31) // 32), np.uint32) if want_matrix else None)
+
+    @staticmethod
+    def _per_path(v, P, dtype, dev=None):
+        """A per-path argument as a contiguous [P] array / tensor of dtype (a number stands for every path; None stays None)."""
+        if v is None:
+            return None
+        if dev is None:
+            return np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=dtype), (P,)))
+        import torch
+        v = v if torch.is_tensor(v) else torch.tensor(v, dtype=dtype, device=dev)
+        return v.to(dtype).expand(P).contiguous()
+
+    def traj_knots(self, sm, t0=None, flags=None, T0=0.0, dt_c=0.1, K=None):
+        """The positions of P timed paths on the common clock T0 + k * dt_c, k = 0 .. K (sc_traj_knots_batch; the definition
+        is in include/sea_current_hip.h).  sm: the dict smooth_paths returned, or any dict of GPU tensors time float64 [M],
+        pts float32 [M,2], offsets int32 [P+1], length int32 [P] and optionally status int32 [P].  t0 float64 [P] start
+        delays, flags int32 [P] (bit 0 / 1: stands at its first / last point before / after its run; None = 3).  K=None
+        covers the longest path plus its delay (reads the end times: synchronises); with a K the call only enqueues.
+        Returns dict(knots float64 [P,K+1,2], NaN where a path is absent; tstatus int32 [P]; K)."""
+        import torch
+        P = sm["length"].shape[0]
+        dev = sm["length"].device
+        t0, flags = self._per_path(t0, P, torch.float64, dev), self._per_path(flags, P, torch.int32, dev)
+        if K is None:
+            K = self._traj_ticks(sm, t0, T0, dt_c)
+        out = dict(knots=torch.empty((P, K + 1, 2), dtype=torch.float64, device=dev), tstatus=torch.empty(P, dtype=torch.int32, device=dev), K=K)
+        self._ck(self._l.sc_traj_knots_batch(self._h, _ptr(sm["time"]), _ptr(sm["pts"]), _ptr(sm["offsets"]), _ptr(sm["length"]),
+                                             _ptr(sm.get("status")), P, _ptr(t0), _ptr(flags), T0, dt_c, K, _ptr(out["knots"]),
+                                             _ptr(out["tstatus"])), "sc_traj_knots_batch")
+        return out
+
+    def traj_conflicts(self, knots, tstatus, radius, group=None, T0=0.0, dt_c=0.1, sep_cap=float("inf"), want_matrix=False):
+        """Who meets whom, when and how close, from knots (sc_traj_conflicts_batch): knots float64 [P,K+1,2] and tstatus int32
+        [P] as traj_knots returned them (tstatus is updated: TRAJ_BAD for a radius outside the contract), radius float64 [P]
+        or a number, group int32 [P] or None, T0 and dt_c those of the knots.  Returns dict(first_t, first_with, min_sep,
+        min_with, n_conf, conflict int32 [P, ceil(P/32)] bit words or None without want_matrix, tstatus).  Only enqueues."""
+        import torch
+        P, K = knots.shape[0], knots.shape[1] - 1
+        dev = knots.device
+        radius, group = self._per_path(radius, P, torch.float64, dev), self._per_path(group, P, torch.int32, dev)
+        out = self._traj_out(P, dev, want_matrix)
+        self._ck(self._l.sc_traj_conflicts_batch(self._h, _ptr(knots), _ptr(tstatus), P, K, T0, dt_c, _ptr(radius), _ptr(group), sep_cap,
+                                                 _ptr(out["first_t"]), _ptr(out["first_with"]), _ptr(out["min_sep"]), _ptr(out["min_with"]),
+                                                 _ptr(out["n_conf"]), _ptr(out["conflict"])), "sc_traj_conflicts_batch")
+        out["tstatus"] = tstatus
+        return out
+
+    def fleet_conflicts(self, sm, radius, t0=None, flags=None, group=None, T0=0.0, dt_c=0.1, K=None, sep_cap=float("inf"),
+                        want_matrix=False, want_knots=False):
+        """traj_knots and traj_conflicts in one call behind smooth_paths (sc_fleet_conflicts_batch): sm is the dict
+        smooth_paths returned (see traj_knots), the other arguments are those of the two calls.  K=None covers the longest
+        path plus its delay (synchronises once to read it); with a K the call only enqueues.  Returns traj_conflicts' dict
+        plus K, and knots with want_knots (otherwise they stay in the context's scratch)."""
+        import torch
+        P = sm["length"].shape[0]
+        dev = sm["length"].device
+        t0, flags = self._per_path(t0, P, torch.float64, dev), self._per_path(flags, P, torch.int32, dev)
+        radius, group = self._per_path(radius, P, torch.float64, dev), self._per_path(group, P, torch.int32, dev)
+        if K is None:
+            K = self._traj_ticks(sm, t0, T0, dt_c)
+        out = self._traj_out(P, dev, want_matrix)
+        out["tstatus"] = torch.empty(P, dtype=torch.int32, device=dev)
+        out["K"] = K
+        if want_knots:
+            out["knots"] = torch.empty((P, K + 1, 2), dtype=torch.float64, device=dev)
+        self._ck(self._l.sc_fleet_conflicts_batch(self._h, _ptr(sm["time"]), _ptr(sm["pts"]), _ptr(sm["offsets"]), _ptr(sm["length"]),
+                                                  _ptr(sm.get("status")), P, _ptr(t0), _ptr(flags), T0, dt_c, K, _ptr(out.get("knots")),
+                                                  _ptr(out["tstatus"]), _ptr(radius), _ptr(group), sep_cap, _ptr(out["first_t"]),
+                                                  _ptr(out["first_with"]), _ptr(out["min_sep"]), _ptr(out["min_with"]), _ptr(out["n_conf"]),
+                                                  _ptr(out["conflict"])), "sc_fleet_conflicts_batch")
+        return out
+
+    @staticmethod
+    def _traj_host_paths(sm):
+        st = sm.get("status")
+        return (np.ascontiguousarray(sm["time"], dtype=np.float64), np.ascontiguousarray(sm["pts"], dtype=np.float32),
+                np.ascontiguousarray(sm["offsets"], dtype=np.int32), np.ascontiguousarray(sm["length"], dtype=np.int32),
+                None if st is None else np.ascontiguousarray(st, dtype=np.int32))
+
+    def traj_knots_host(self, sm, t0=None, flags=None, T0=0.0, dt_c=0.1, K=None):
+        """Host form of traj_knots (numpy in, numpy out; sc_traj_knots_batch_host)."""
+        time, pts, offsets, length, status = self._traj_host_paths(sm)
+        P = length.shape[0]
+        t0, flags = self._per_path(t0, P, np.float64), self._per_path(flags, P, np.int32)
+        if K is None:
+            K = self._traj_ticks(dict(time=time, offsets=offsets, length=length, status=status), t0, T0, dt_c)
+        out = dict(knots=np.zeros((P, K + 1, 2)), tstatus=np.zeros(P, np.int32), K=K)
+        self._ck(self._l.sc_traj_knots_batch_host(self._h, _ptr(time), _ptr(pts), _ptr(offsets), _ptr(length), _ptr(status), P, _ptr(t0),
+                                                  _ptr(flags), T0, dt_c, K, _ptr(out["knots"]), _ptr(out["tstatus"])),
+                 "sc_traj_knots_batch_host")
+        return out
+
+    def traj_conflicts_host(self, knots, tstatus, radius, group=None, T0=0.0, dt_c=0.1, sep_cap=float("inf"), want_matrix=False):
+        """Host form of traj_conflicts (numpy in, numpy out; sc_traj_conflicts_batch_host).  tstatus is copied, not updated in
+        place; conflict is uint32 [P, ceil(P/32)]."""
+        knots = np.ascontiguousarray(knots, dtype=np.float64)
+        P, K = knots.shape[0], knots.shape[1] - 1
+        radius, group = self._per_path(radius, P, np.float64), self._per_path(group, P, np.int32)
+        out = self._traj_out_host(P, want_matrix)
+        out["tstatus"] = np.array(tstatus, dtype=np.int32)
+        self._ck(self._l.sc_traj_conflicts_batch_host(self._h, _ptr(knots), _ptr(out["tstatus"]), P, K, T0, dt_c, _ptr(radius), _ptr(group),
+                                                      sep_cap, _ptr(out["first_t"]), _ptr(out["first_with"]), _ptr(out["min_sep"]),
+                                                      _ptr(out["min_with"]), _ptr(out["n_conf"]), _ptr(out["conflict"])),
+                 "sc_traj_conflicts_batch_host")
+        return out
+
+    def fleet_conflicts_host(self, sm, radius, t0=None, flags=None, group=None, T0=0.0, dt_c=0.1, K=None, sep_cap=float("inf"),
+                             want_matrix=False, want_knots=False):
+        """Host form of fleet_conflicts (numpy in, numpy out; sc_fleet_conflicts_batch_host)."""
+        time, pts, offsets, length, status = self._traj_host_paths(sm)
+        P = length.shape[0]
+        t0, flags = self._per_path(t0, P, np.float64), self._per_path(flags, P, np.int32)
+        radius, group = self._per_path(radius, P, np.float64), self._per_path(group, P, np.int32)
+        if K is None:
+            K = self._traj_ticks(dict(time=time, offsets=offsets, length=length, status=status), t0, T0, dt_c)
+        out = self._traj_out_host(P, want_matrix)
+        out["tstatus"] = np.zeros(P, np.int32)
+        out["K"] = K
+        if want_knots:
+            out["knots"] = np.zeros((P, K + 1, 2))
+        self._ck(self._l.sc_fleet_conflicts_batch_host(self._h, _ptr(time), _ptr(pts), _ptr(offsets), _ptr(length), _ptr(status), P, _ptr(t0),
+                                                       _ptr(flags), T0, dt_c, K, _ptr(out.get("knots")), _ptr(out["tstatus"]), _ptr(radius),
+                                                       _ptr(group), sep_cap, _ptr(out["first_t"]), _ptr(out["first_with"]),
+                                                       _ptr(out["min_sep"]), _ptr(out["min_with"]), _ptr(out["n_conf"]), _ptr(out["conflict"])),
+                 "sc_fleet_conflicts_batch_host")
+        return out
 
     # ---- multi-GPU gather (RCCL through the C ABI) ----
     @staticmethod

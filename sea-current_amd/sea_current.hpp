@@ -28,6 +28,7 @@
 //         soft_penalty: clearance-weighted cost fields (an inflation layer) behind plan_from / plan_to
 //   (new) occupancy_grid::cost_fields_multi / field_paths_multi, planning_space::plan_to_nearest: one field from many
 //         goals, every start to the cheapest of them
+//   (new) fleet_conflicts: who meets whom among the results of smooth_paths_batch, when first, and how close
 //
 // Differences that are deliberate: obstacle::closed is initialised (the reference leaves it
 // uninitialised, :197); library code never prints or calls std::exit (SC_ASSERT throws in DEBUG);
@@ -1481,6 +1482,64 @@ inline std::vector<smooth_result> smooth_paths_batch(const std::vector<smooth_re
                                                      const occupancy_grid& grid, float dt = 0.02f, float precision = 0.01f,
                                                      gpu_context& ctx = default_context()) {
     return smooth_paths_batch_impl(requests, space, &grid, dt, precision, ctx);
+}
+
+// ---- (new) conflicts between timed paths (sc_fleet_conflicts_batch_host; the definition is in sea_current_hip.h) -------
+// Who comes within radius[p] + radius[q] of whom among the results of smooth_paths_batch, when first, and how close
+// everybody gets, on the common clock k * dt_c from 0 to past the end of the longest path plus its delay.  Detection only.
+// delays (start delay of every path, default 0), flags (bit 0 / 1: stands at its first / last point before / after its run,
+// default 3) and groups (paths with the same group >= 0 are never compared, default all different) are empty or one entry
+// per path.  A moving obstacle is one more smooth_result: status SC_SMOOTH_OK, spline.pts and profile.time filled.
+// status holds an sc_traj_status per path; a path that is not SC_TRAJ_OK (its smooth status was not OK, or it has no
+// sample) reads first_t = min_sep = +inf, first_with = min_with = -1, n_conf = 0 and is invisible to the others.
+struct conflict_result {
+    std::vector<double> first_t, min_sep;
+    std::vector<int> first_with, min_with, n_conf, status;
+};
+inline conflict_result fleet_conflicts(const std::vector<smooth_result>& paths, const std::vector<double>& radius,
+                                       const std::vector<double>& delays = {}, const std::vector<int>& flags = {},
+                                       const std::vector<int>& groups = {}, double dt_c = 0.1,
+                                       double sep_cap = std::numeric_limits<double>::infinity(), gpu_context& ctx = default_context()) {
+    const int P = (int)paths.size();
+    conflict_result out;
+    if (P == 0) return out;
+    if ((int)radius.size() != P) throw std::invalid_argument("fleet_conflicts: one radius per path expected");
+    if (!(std::isfinite(dt_c) && dt_c > 0.0)) throw std::invalid_argument("fleet_conflicts: dt_c must be finite and > 0");
+    if ((!delays.empty() && (int)delays.size() != P) || (!flags.empty() && (int)flags.size() != P) || (!groups.empty() && (int)groups.size() != P))
+        throw std::invalid_argument("fleet_conflicts: delays, flags and groups are empty or hold one entry per path");
+    std::vector<int32_t> offsets(P + 1, 0), length(P), status(P), fl(flags.begin(), flags.end()), gr(groups.begin(), groups.end());
+    for (int p = 0; p < P; ++p) {
+        const int L = paths[p].status == SC_SMOOTH_OK ? std::min((int)paths[p].spline.pts.rows(), (int)paths[p].profile.time.size()) : 0;
+        status[p] = paths[p].status;
+        length[p] = L;
+        offsets[p + 1] = offsets[p] + L;
+    }
+    const size_t M = (size_t)offsets[P];
+    std::vector<double> time(std::max<size_t>(M, 1));
+    std::vector<float> pts(2 * std::max<size_t>(M, 1));
+    double end = 0.0;
+    for (int p = 0; p < P; ++p) {
+        for (int j = 0; j < length[p]; ++j) {
+            time[(size_t)offsets[p] + j] = paths[p].profile.time(j);
+            pts[2 * ((size_t)offsets[p] + j)] = paths[p].spline.pts(j, 0);
+            pts[2 * ((size_t)offsets[p] + j) + 1] = paths[p].spline.pts(j, 1);
+        }
+        if (length[p] > 0) {
+            const double e = paths[p].profile.time(length[p] - 1) + (delays.empty() ? 0.0 : delays[p]);
+            if (std::isfinite(e)) end = std::max(end, e);
+        }
+    }
+    const int K = (int)std::min(std::max(std::ceil(end / dt_c), 1.0), 65535.0);
+    out.first_t.resize(P); out.min_sep.resize(P);
+    std::vector<int32_t> fw(P), mw(P), nc(P), ts(P);
+    ctx.check(sc_fleet_conflicts_batch_host(ctx.get(), time.data(), pts.data(), offsets.data(), length.data(), status.data(), P,
+                                            delays.empty() ? nullptr : delays.data(), fl.empty() ? nullptr : fl.data(), 0.0, dt_c, K, nullptr,
+                                            ts.data(), radius.data(), gr.empty() ? nullptr : gr.data(), sep_cap, out.first_t.data(), fw.data(),
+                                            out.min_sep.data(), mw.data(), nc.data(), nullptr),
+              "sc_fleet_conflicts_batch_host");
+    out.first_with.assign(fw.begin(), fw.end()); out.min_with.assign(mw.begin(), mw.end());
+    out.n_conf.assign(nc.begin(), nc.end()); out.status.assign(ts.begin(), ts.end());
+    return out;
 }
 
 // The same limits through the reference's own hook: a vel_lim_func for gen_vel_prof<1>(ad.arclength, 0, 0, 0, f, ..) along
