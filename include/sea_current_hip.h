@@ -758,6 +758,88 @@ int sc_fleet_conflicts_batch_host(sc_ctx* ctx, const double* time, const float* 
                                   double* first_t, int32_t* first_with, double* min_sep, int32_t* min_with, int32_t* n_conf,
                                   uint32_t* conflict);
 
+/* ---- delay schedules for timed paths: shift table and priority greedy ------------------------------------------
+ * The cheapest resolution of a conflict is to let the lower-priority path wait.  These calls answer "does p, started s ticks
+ * later than q, still meet q?" for every pair and every relative delay, and read a start slot per path off the answers.
+ * They only delay: nothing is re-planned.  The reference has nothing of this kind.
+ *
+ * Definition.  Everything is defined on the knots fp64 [P][K+1][2] that sc_traj_knots_batch writes, with tstatus, radius and
+ * group as sc_traj_conflicts_batch reads them.  No new floating-point formula: the only predicate is "interval conflicts iff
+ * m2 < R*R" of the block above, the same operations in the same order, fp64, no fused multiply-adds; every output is
+ * integers and bits and equals the CPU statements (tests/traj_sched_twin.py in NumPy, tests/cpp/traj_sched_ref.c in C) exactly.
+ *   Delays are whole ticks.  D = the number of candidate slots, 1 .. 32; stride = ticks per slot, >= 1, (D-1) * stride <= K.
+ *     Path p in slot j is its knot row shifted by s = j * stride ticks, holding the tick-0 knot while it waits:
+ *       knot_s[p][k] = knots[p][max(k - s, 0)],  k = 0 .. K.
+ *     A path whose tick-0 knot is absent (flag bit 0 clear, not yet started) stays absent while it waits.  The horizon stays
+ *     tau_K: what a shift pushes beyond it is not compared.
+ *   Pair at relative shift r = j_p - j_q, r in -(D-1) .. D-1: p is shifted by max(r, 0) * stride ticks, q by max(-r, 0) *
+ *     stride, and the intervals k = 0 .. K-1 are compared exactly as above (differences hi - lo with lo = min(p, q); NaN knots
+ *     fail the comparison).  conf(p, q, r) is true iff some interval conflicts; conf(p, q, r) == conf(q, p, -r).
+ *     A pair is not compared, and all its bits are 0, when either path is not SC_TRAJ_OK, either radius is outside the
+ *     contract (such a path becomes SC_TRAJ_BAD, as in the conflicts call), both have the same group >= 0, or p == q.
+ *   Table: uint64 table[P][P]; bit r + D - 1 of table[p][q] = conf(p, q, r); bits from 2D-1 up are 0; every entry is written.
+ *     8 MiB at P = 1024; calls that take a table accept P in 1 .. 8192 (512 MiB).
+ *   Schedule.  order int32 [P] or NULL = 0, 1, 2, ..: earlier entries have higher priority; an entry outside 0 .. P-1 or
+ *     one that repeats an earlier entry is skipped.  jmax int32 [P] or NULL = D-1 everywhere; a value >= 0 is clamped to
+ *     D-1, a value < 0 means pinned.  Walk order; for each path p:
+ *       1. p is not OK: slot[p] = SC_SLOT_NOT_OK.
+ *       2. p is pinned: slot[p] = 0 unconditionally; it still blocks the paths after it (moving obstacles, paths under way).
+ *       3. otherwise busy = OR over every earlier path q with slot[q] >= 0 of (table[p][q] >> (D-1-slot[q])) & (2^D - 1),
+ *          and slot[p] = the smallest j <= jmax[p] whose bit in busy is 0;
+ *       4. no such j: slot[p] = SC_SLOT_UNRESOLVED; the path takes no further part and blocks nobody (the caller re-plans it).
+ *     A path never named in order gets SC_SLOT_UNNAMED and blocks nobody.  counts int32 [4]: the paths with slot 0, with
+ *     slot > 0, unresolved, and not scheduled (SC_SLOT_NOT_OK or SC_SLOT_UNNAMED).
+ *   Shifted knots: knots_out[p][k] = knots[p][max(k - max(slot[p], 0) * stride, 0)]; a path with slot < 0 becomes all NaN
+ *     (absent), so that sc_traj_conflicts_batch on knots_out gives the residual report in the existing format.
+ *   Note (the tests rely on it): equivalence with absolute delays.  Suppose every path is at rest or absent from tick
+ *     K - (D-1) * stride onward.  Then two paths at slots j_p, j_q conflict in the absolute picture (both rows shifted, the
+ *     predicate on intervals 0 .. K-1) iff conf(p, q, j_p - j_q): the intervals the relative picture sees beyond the absolute
+ *     horizon repeat the last, stationary interval, and the intervals on which both paths wait are implied by interval 0 of
+ *     any relative shift (lam = 0 gives the tick-0 distance).  Under that condition on K a schedule leaves no conflict among
+ *     the paths with slot >= 0.  The Python Context.fleet_schedule(K=None) chooses K to cover the longest path, its delay and
+ *     (D-1) * stride more ticks.
+ *   Shifting knots is not bit-equal to recomputing them with t0 + j * stride * dt_c (tau - t0 rounds differently): the
+ *     definition is the shift.
+ *   A pair whose boxes of present knots are at least R apart is written 0 without its ticks being read.  The gap is taken
+ *     conservatively (2^-48 of the boxes' span below the exact one), so the skip changes no bit; SC_TRAJ_SCHED_NOSKIP=1 in
+ *     the environment when the context is created turns it off.
+ *
+ * sc_traj_shift_table_batch: table from knots; tstatus is read and written like in sc_traj_conflicts_batch.
+ * sc_traj_schedule_batch: slot int32 [P] and counts from a table and the tstatus the table call left.
+ * sc_traj_shift_knots_batch: knots_out fp64 [P][K+1][2] (not the knots array itself) from knots and slot.
+ * sc_fleet_schedule_batch: sc_traj_knots_batch, then the three; knots, tstatus and table may be NULL (context scratch: 16 * P *
+ *   (K+1), 4 * P and 8 * P * P bytes), knots_out may be NULL (not wanted).
+ * Device pointers; the calls only enqueue on the context's stream (kernels timed under SC_K_SMOOTH): no host synchronisation,
+ * no device-to-host copy.  Scratch of the context: 32 * P bytes of boxes.  The _host forms take host pointers and return
+ * SC_ERR_INVALID before any launch for a radius outside the contract (and sc_fleet_schedule_batch_host for what
+ * sc_traj_knots_batch_host refuses).
+ * Errors: SC_ERR_INVALID for NULL required pointers (everything but group, order, jmax and the pointers named above), P outside
+ * 1 .. 8192, K outside 1 .. 65535, D outside 1 .. 32, stride < 1, (D-1) * stride > K, P * (K+1) > 2^26, and in
+ * sc_fleet_schedule_batch the clock errors of sc_traj_knots_batch. */
+#define SC_SLOT_UNRESOLVED (-1)
+#define SC_SLOT_NOT_OK (-2)
+#define SC_SLOT_UNNAMED (-3)
+int sc_traj_shift_table_batch(sc_ctx* ctx, const double* knots, int32_t* tstatus, int P, int K, const double* radius,
+                              const int32_t* group, int D, int stride, uint64_t* table);
+int sc_traj_shift_table_batch_host(sc_ctx* ctx, const double* knots, int32_t* tstatus, int P, int K, const double* radius,
+                                   const int32_t* group, int D, int stride, uint64_t* table);
+int sc_traj_schedule_batch(sc_ctx* ctx, const uint64_t* table, const int32_t* tstatus, int P, int D, const int32_t* order,
+                           const int32_t* jmax, int32_t* slot, int32_t* counts);
+int sc_traj_schedule_batch_host(sc_ctx* ctx, const uint64_t* table, const int32_t* tstatus, int P, int D, const int32_t* order,
+                                const int32_t* jmax, int32_t* slot, int32_t* counts);
+int sc_traj_shift_knots_batch(sc_ctx* ctx, const double* knots, int P, int K, const int32_t* slot, int stride, double* knots_out);
+int sc_traj_shift_knots_batch_host(sc_ctx* ctx, const double* knots, int P, int K, const int32_t* slot, int stride, double* knots_out);
+int sc_fleet_schedule_batch(sc_ctx* ctx, const double* time, const float* pts, const int32_t* offsets, const int32_t* length,
+                            const int32_t* status, int P, const double* t0, const int32_t* flags, double T0, double dt_c, int K,
+                            double* knots, int32_t* tstatus, const double* radius, const int32_t* group, int D, int stride,
+                            uint64_t* table, const int32_t* order, const int32_t* jmax, int32_t* slot, int32_t* counts,
+                            double* knots_out);
+int sc_fleet_schedule_batch_host(sc_ctx* ctx, const double* time, const float* pts, const int32_t* offsets, const int32_t* length,
+                                 const int32_t* status, int P, const double* t0, const int32_t* flags, double T0, double dt_c, int K,
+                                 double* knots, int32_t* tstatus, const double* radius, const int32_t* group, int D, int stride,
+                                 uint64_t* table, const int32_t* order, const int32_t* jmax, int32_t* slot, int32_t* counts,
+                                 double* knots_out);
+
 /* ---- the reference's own planner, batched -----------------------------------------------
  * planning_space::fast_marching_trees (sea_current.hpp:1339-1407) with near (:1328-1337), cost (:1315-1326) and
  * intersects (:142-178): FMT* from starts[q] to goals[q] (float [Q][2]) over n shared free samples (float [n][2], e.g.

@@ -41,6 +41,8 @@ extern "C" int sc_ctx_create(int device, sc_ctx** out) {
     // workgroups the pair kernel of the path conflicts aims for (the tests lower it so that small fleets walk several tick
     // chunks and column tiles per workgroup)
     if (const char* e = getenv("SC_TRAJ_WORKGROUPS")) { const long v = atol(e); if (v >= 1 && v <= 65536) c->traj_wg_target = (int)v; }
+    // the shift table evaluates every pair, also those whose boxes are too far apart to meet (the tests compare the two)
+    if (const char* e = getenv("SC_TRAJ_SCHED_NOSKIP")) c->traj_sched_noskip = atol(e) == 1;
     *out = c;
     return SC_OK;
 }

@@ -27,6 +27,7 @@ K_SMOOTH = 14
 SMOOTH_OK, SMOOTH_BAD_INPUT, SMOOTH_NONFINITE, SMOOTH_TOPPRA_FAILED, SMOOTH_TRUNCATED, SMOOTH_EMPTY_SEGMENT = range(6)
 TRAJ_OK, TRAJ_SKIPPED, TRAJ_BAD = range(3)
 TRAJ_MAX_TICKS = 65535
+SLOT_UNRESOLVED, SLOT_NOT_OK, SLOT_UNNAMED = -1, -2, -3
 
 _lib = None
 
@@ -133,6 +134,14 @@ _SIGNATURES = {
     "sc_traj_conflicts_batch_host": (_i, [_vp] * 3 + [_i, _i, _d, _d, _vp, _vp, _d] + [_vp] * 6),
     "sc_fleet_conflicts_batch": (_i, [_vp] * 6 + [_i, _vp, _vp, _d, _d, _i, _vp, _vp, _vp, _vp, _d] + [_vp] * 6),
     "sc_fleet_conflicts_batch_host": (_i, [_vp] * 6 + [_i, _vp, _vp, _d, _d, _i, _vp, _vp, _vp, _vp, _d] + [_vp] * 6),
+    "sc_traj_shift_table_batch": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp]),
+    "sc_traj_shift_table_batch_host": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp]),
+    "sc_traj_schedule_batch": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "sc_traj_schedule_batch_host": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "sc_traj_shift_knots_batch": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp]),
+    "sc_traj_shift_knots_batch_host": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp]),
+    "sc_fleet_schedule_batch": (_i, [_vp] * 6 + [_i, _vp, _vp, _d, _d, _i, _vp, _vp, _vp, _vp, _i, _i] + [_vp] * 6),
+    "sc_fleet_schedule_batch_host": (_i, [_vp] * 6 + [_i, _vp, _vp, _d, _d, _i, _vp, _vp, _vp, _vp, _i, _i] + [_vp] * 6),
     "sc_rank_range": (None, [_i, _i, _i, C.POINTER(_i), C.POINTER(_i)]),
     "sc_comm_unique_id": (_i, [_vp]),
     "sc_comm_init": (_i, [_vp, _vp, _i, _i]),
@@ -778,6 +787,144 @@ class Context:
                                                        _ptr(group), sep_cap, _ptr(out["first_t"]), _ptr(out["first_with"]),
                                                        _ptr(out["min_sep"]), _ptr(out["min_with"]), _ptr(out["n_conf"]), _ptr(out["conflict"])),
                  "sc_fleet_conflicts_batch_host")
+        return out
+
+    # ---- delay schedules for timed paths (sc_traj_shift_table_batch, sc_traj_schedule_batch, sc_traj_shift_knots_batch,
+    # sc_fleet_schedule_batch) ----
+    def traj_shift_table(self, knots, tstatus, radius, group=None, D=8, stride=1):
+        """For every pair of paths and every relative delay of -(D-1) .. D-1 slots of `stride` ticks: do they still meet
+        (sc_traj_shift_table_batch; the definition is in include/sea_current_hip.h)?  knots, tstatus, radius and group as in
+        traj_conflicts (tstatus is updated).  Returns dict(table int64 [P,P]: bit r + D - 1 of table[p][q] is set iff p,
+        started r slots later than q, meets q; tstatus).  Only enqueues."""
+        import torch
+        P, K = knots.shape[0], knots.shape[1] - 1
+        dev = knots.device
+        radius, group = self._per_path(radius, P, torch.float64, dev), self._per_path(group, P, torch.int32, dev)
+        table = torch.empty((P, P), dtype=torch.int64, device=dev)   # torch has no uint64 arithmetic: the words as int64
+        self._ck(self._l.sc_traj_shift_table_batch(self._h, _ptr(knots), _ptr(tstatus), P, K, _ptr(radius), _ptr(group), D, stride, _ptr(table)),
+                 "sc_traj_shift_table_batch")
+        return dict(table=table, tstatus=tstatus)
+
+    def traj_schedule(self, table, tstatus, D=8, order=None, jmax=None):
+        """Start slots by priority from a shift table (sc_traj_schedule_batch): walks order (int32 [P], None = 0, 1, ..) and
+        gives every path the first slot <= jmax[p] (int32 [P] or a number, None = D-1, negative = pinned to slot 0) in which
+        it meets none of the paths placed before it.  Returns dict(slot int32 [P]: >= 0, SLOT_UNRESOLVED, SLOT_NOT_OK or
+        SLOT_UNNAMED; counts int32 [4]: slot 0, slot > 0, unresolved, not scheduled).  Only enqueues."""
+        import torch
+        P = table.shape[0]
+        dev = table.device
+        order = None if order is None else (order if torch.is_tensor(order) else torch.tensor(order, device=dev)).to(torch.int32).contiguous()
+        if order is not None and order.shape[0] != P:
+            raise ValueError("order has P entries")
+        jmax = self._per_path(jmax, P, torch.int32, dev)
+        out = dict(slot=torch.empty(P, dtype=torch.int32, device=dev), counts=torch.empty(4, dtype=torch.int32, device=dev))
+        self._ck(self._l.sc_traj_schedule_batch(self._h, _ptr(table), _ptr(tstatus), P, D, _ptr(order), _ptr(jmax), _ptr(out["slot"]),
+                                                _ptr(out["counts"])), "sc_traj_schedule_batch")
+        return out
+
+    def traj_shift_knots(self, knots, slot, stride=1):
+        """knots with every path held at its first knot for slot[p] * stride ticks; a path with slot < 0 becomes absent
+        (sc_traj_shift_knots_batch).  Returns float64 [P,K+1,2].  Only enqueues."""
+        import torch
+        P, K = knots.shape[0], knots.shape[1] - 1
+        out = torch.empty_like(knots)
+        self._ck(self._l.sc_traj_shift_knots_batch(self._h, _ptr(knots), P, K, _ptr(slot), stride, _ptr(out)), "sc_traj_shift_knots_batch")
+        return out
+
+    def fleet_schedule(self, sm, radius, t0=None, flags=None, group=None, T0=0.0, dt_c=0.1, K=None, D=8, stride=1, order=None, jmax=None,
+                       want_table=False, want_knots=False):
+        """traj_knots, traj_shift_table, traj_schedule and traj_shift_knots in one call behind smooth_paths
+        (sc_fleet_schedule_batch).  K=None covers the longest path, its delay and (D-1) * stride more ticks, so that every
+        path is at rest where the shifts end and the schedule leaves no conflict among the paths with slot >= 0
+        (synchronises once to read the end times); with a K the call only enqueues.  Returns dict(slot, counts, delay float64
+        [P] = slot * stride * dt_c seconds, NaN for slot < 0; tstatus, K; table with want_table; knots and knots_out with
+        want_knots)."""
+        import torch
+        P = sm["length"].shape[0]
+        dev = sm["length"].device
+        t0, flags = self._per_path(t0, P, torch.float64, dev), self._per_path(flags, P, torch.int32, dev)
+        radius, group = self._per_path(radius, P, torch.float64, dev), self._per_path(group, P, torch.int32, dev)
+        order = None if order is None else (order if torch.is_tensor(order) else torch.tensor(order, device=dev)).to(torch.int32).contiguous()
+        if order is not None and order.shape[0] != P:
+            raise ValueError("order has P entries")
+        jmax = self._per_path(jmax, P, torch.int32, dev)
+        if K is None:
+            K = min(self._traj_ticks(sm, t0, T0, dt_c) + (D - 1) * stride, TRAJ_MAX_TICKS)
+        out = dict(slot=torch.empty(P, dtype=torch.int32, device=dev), counts=torch.empty(4, dtype=torch.int32, device=dev),
+                   tstatus=torch.empty(P, dtype=torch.int32, device=dev), K=K)
+        if want_table:
+            out["table"] = torch.empty((P, P), dtype=torch.int64, device=dev)
+        if want_knots:
+            out["knots"] = torch.empty((P, K + 1, 2), dtype=torch.float64, device=dev)
+            out["knots_out"] = torch.empty((P, K + 1, 2), dtype=torch.float64, device=dev)
+        self._ck(self._l.sc_fleet_schedule_batch(self._h, _ptr(sm["time"]), _ptr(sm["pts"]), _ptr(sm["offsets"]), _ptr(sm["length"]),
+                                                 _ptr(sm.get("status")), P, _ptr(t0), _ptr(flags), T0, dt_c, K, _ptr(out.get("knots")),
+                                                 _ptr(out["tstatus"]), _ptr(radius), _ptr(group), D, stride, _ptr(out.get("table")),
+                                                 _ptr(order), _ptr(jmax), _ptr(out["slot"]), _ptr(out["counts"]), _ptr(out.get("knots_out"))),
+                 "sc_fleet_schedule_batch")
+        out["delay"] = torch.where(out["slot"] >= 0, (out["slot"] * stride).to(torch.float64) * dt_c, float("nan"))
+        return out
+
+    def traj_shift_table_host(self, knots, tstatus, radius, group=None, D=8, stride=1):
+        """Host form of traj_shift_table (numpy in, numpy out; sc_traj_shift_table_batch_host).  tstatus is copied, not
+        updated in place; table is uint64 [P,P]."""
+        knots = np.ascontiguousarray(knots, dtype=np.float64)
+        P, K = knots.shape[0], knots.shape[1] - 1
+        radius, group = self._per_path(radius, P, np.float64), self._per_path(group, P, np.int32)
+        out = dict(table=np.zeros((P, P), np.uint64), tstatus=np.array(tstatus, dtype=np.int32))
+        self._ck(self._l.sc_traj_shift_table_batch_host(self._h, _ptr(knots), _ptr(out["tstatus"]), P, K, _ptr(radius), _ptr(group), D, stride,
+                                                        _ptr(out["table"])), "sc_traj_shift_table_batch_host")
+        return out
+
+    def traj_schedule_host(self, table, tstatus, D=8, order=None, jmax=None):
+        """Host form of traj_schedule (numpy in, numpy out; sc_traj_schedule_batch_host)."""
+        table = np.ascontiguousarray(table).view(np.uint64)
+        P = table.shape[0]
+        tstatus = np.ascontiguousarray(tstatus, dtype=np.int32)
+        order = None if order is None else np.ascontiguousarray(order, dtype=np.int32)
+        if order is not None and order.shape[0] != P:
+            raise ValueError("order has P entries")
+        jmax = self._per_path(jmax, P, np.int32)
+        out = dict(slot=np.zeros(P, np.int32), counts=np.zeros(4, np.int32))
+        self._ck(self._l.sc_traj_schedule_batch_host(self._h, _ptr(table), _ptr(tstatus), P, D, _ptr(order), _ptr(jmax), _ptr(out["slot"]),
+                                                     _ptr(out["counts"])), "sc_traj_schedule_batch_host")
+        return out
+
+    def traj_shift_knots_host(self, knots, slot, stride=1):
+        """Host form of traj_shift_knots (numpy in, numpy out; sc_traj_shift_knots_batch_host)."""
+        knots = np.ascontiguousarray(knots, dtype=np.float64)
+        slot = np.ascontiguousarray(slot, dtype=np.int32)
+        out = np.zeros_like(knots)
+        self._ck(self._l.sc_traj_shift_knots_batch_host(self._h, _ptr(knots), knots.shape[0], knots.shape[1] - 1, _ptr(slot), stride, _ptr(out)),
+                 "sc_traj_shift_knots_batch_host")
+        return out
+
+    def fleet_schedule_host(self, sm, radius, t0=None, flags=None, group=None, T0=0.0, dt_c=0.1, K=None, D=8, stride=1, order=None, jmax=None,
+                            want_table=False, want_knots=False):
+        """Host form of fleet_schedule (numpy in, numpy out; sc_fleet_schedule_batch_host)."""
+        time, pts, offsets, length, status = self._traj_host_paths(sm)
+        P = length.shape[0]
+        t0, flags = self._per_path(t0, P, np.float64), self._per_path(flags, P, np.int32)
+        radius, group = self._per_path(radius, P, np.float64), self._per_path(group, P, np.int32)
+        order = None if order is None else np.ascontiguousarray(order, dtype=np.int32)
+        if order is not None and order.shape[0] != P:
+            raise ValueError("order has P entries")
+        jmax = self._per_path(jmax, P, np.int32)
+        if K is None:
+            K = min(self._traj_ticks(dict(time=time, offsets=offsets, length=length, status=status), t0, T0, dt_c) + (D - 1) * stride,
+                    TRAJ_MAX_TICKS)
+        out = dict(slot=np.zeros(P, np.int32), counts=np.zeros(4, np.int32), tstatus=np.zeros(P, np.int32), K=K)
+        if want_table:
+            out["table"] = np.zeros((P, P), np.uint64)
+        if want_knots:
+            out["knots"] = np.zeros((P, K + 1, 2))
+            out["knots_out"] = np.zeros((P, K + 1, 2))
+        self._ck(self._l.sc_fleet_schedule_batch_host(self._h, _ptr(time), _ptr(pts), _ptr(offsets), _ptr(length), _ptr(status), P, _ptr(t0),
+                                                      _ptr(flags), T0, dt_c, K, _ptr(out.get("knots")), _ptr(out["tstatus"]), _ptr(radius),
+                                                      _ptr(group), D, stride, _ptr(out.get("table")), _ptr(order), _ptr(jmax), _ptr(out["slot"]),
+                                                      _ptr(out["counts"]), _ptr(out.get("knots_out"))), "sc_fleet_schedule_batch_host")
+        with np.errstate(invalid="ignore"):
+            out["delay"] = np.where(out["slot"] >= 0, (out["slot"] * stride).astype(np.float64) * dt_c, np.nan)
         return out
 
     # ---- multi-GPU gather (RCCL through the C ABI) ----

@@ -29,6 +29,7 @@
 //   (new) occupancy_grid::cost_fields_multi / field_paths_multi, planning_space::plan_to_nearest: one field from many
 //         goals, every start to the cheapest of them
 //   (new) fleet_conflicts: who meets whom among the results of smooth_paths_batch, when first, and how close
+//   (new) fleet_schedule: start slots by priority that let the lower-priority path wait until it meets nobody
 //
 // Differences that are deliberate: obstacle::closed is initialised (the reference leaves it
 // uninitialised, :197); library code never prints or calls std::exit (SC_ASSERT throws in DEBUG);
@@ -1496,6 +1497,46 @@ struct conflict_result {
     std::vector<double> first_t, min_sep;
     std::vector<int> first_with, min_with, n_conf, status;
 };
+// smooth_results in the packed layout the sc_traj_* / sc_fleet_* host forms read, and the end of the last path plus its delay
+struct packed_timed_paths {
+    std::vector<int32_t> offsets, length, status, flags, groups;
+    std::vector<double> time;
+    std::vector<float> pts;
+    double end = 0.0;
+};
+inline packed_timed_paths pack_timed_paths(const char* who, const std::vector<smooth_result>& paths, const std::vector<double>& radius,
+                                           const std::vector<double>& delays, const std::vector<int>& flags, const std::vector<int>& groups,
+                                           double dt_c) {
+    const int P = (int)paths.size();
+    if ((int)radius.size() != P) throw std::invalid_argument(std::string(who) + ": one radius per path expected");
+    if (!(std::isfinite(dt_c) && dt_c > 0.0)) throw std::invalid_argument(std::string(who) + ": dt_c must be finite and > 0");
+    if ((!delays.empty() && (int)delays.size() != P) || (!flags.empty() && (int)flags.size() != P) || (!groups.empty() && (int)groups.size() != P))
+        throw std::invalid_argument(std::string(who) + ": delays, flags and groups are empty or hold one entry per path");
+    packed_timed_paths k;
+    k.offsets.assign(P + 1, 0); k.length.resize(P); k.status.resize(P);
+    k.flags.assign(flags.begin(), flags.end()); k.groups.assign(groups.begin(), groups.end());
+    for (int p = 0; p < P; ++p) {
+        const int L = paths[p].status == SC_SMOOTH_OK ? std::min((int)paths[p].spline.pts.rows(), (int)paths[p].profile.time.size()) : 0;
+        k.status[p] = paths[p].status;
+        k.length[p] = L;
+        k.offsets[p + 1] = k.offsets[p] + L;
+    }
+    const size_t M = (size_t)k.offsets[P];
+    k.time.resize(std::max<size_t>(M, 1));
+    k.pts.resize(2 * std::max<size_t>(M, 1));
+    for (int p = 0; p < P; ++p) {
+        for (int j = 0; j < k.length[p]; ++j) {
+            k.time[(size_t)k.offsets[p] + j] = paths[p].profile.time(j);
+            k.pts[2 * ((size_t)k.offsets[p] + j)] = paths[p].spline.pts(j, 0);
+            k.pts[2 * ((size_t)k.offsets[p] + j) + 1] = paths[p].spline.pts(j, 1);
+        }
+        if (k.length[p] > 0) {
+            const double e = paths[p].profile.time(k.length[p] - 1) + (delays.empty() ? 0.0 : delays[p]);
+            if (std::isfinite(e)) k.end = std::max(k.end, e);
+        }
+    }
+    return k;
+}
 inline conflict_result fleet_conflicts(const std::vector<smooth_result>& paths, const std::vector<double>& radius,
                                        const std::vector<double>& delays = {}, const std::vector<int>& flags = {},
                                        const std::vector<int>& groups = {}, double dt_c = 0.1,
@@ -1503,42 +1544,59 @@ inline conflict_result fleet_conflicts(const std::vector<smooth_result>& paths, 
     const int P = (int)paths.size();
     conflict_result out;
     if (P == 0) return out;
-    if ((int)radius.size() != P) throw std::invalid_argument("fleet_conflicts: one radius per path expected");
-    if (!(std::isfinite(dt_c) && dt_c > 0.0)) throw std::invalid_argument("fleet_conflicts: dt_c must be finite and > 0");
-    if ((!delays.empty() && (int)delays.size() != P) || (!flags.empty() && (int)flags.size() != P) || (!groups.empty() && (int)groups.size() != P))
-        throw std::invalid_argument("fleet_conflicts: delays, flags and groups are empty or hold one entry per path");
-    std::vector<int32_t> offsets(P + 1, 0), length(P), status(P), fl(flags.begin(), flags.end()), gr(groups.begin(), groups.end());
-    for (int p = 0; p < P; ++p) {
-        const int L = paths[p].status == SC_SMOOTH_OK ? std::min((int)paths[p].spline.pts.rows(), (int)paths[p].profile.time.size()) : 0;
-        status[p] = paths[p].status;
-        length[p] = L;
-        offsets[p + 1] = offsets[p] + L;
-    }
-    const size_t M = (size_t)offsets[P];
-    std::vector<double> time(std::max<size_t>(M, 1));
-    std::vector<float> pts(2 * std::max<size_t>(M, 1));
-    double end = 0.0;
-    for (int p = 0; p < P; ++p) {
-        for (int j = 0; j < length[p]; ++j) {
-            time[(size_t)offsets[p] + j] = paths[p].profile.time(j);
-            pts[2 * ((size_t)offsets[p] + j)] = paths[p].spline.pts(j, 0);
-            pts[2 * ((size_t)offsets[p] + j) + 1] = paths[p].spline.pts(j, 1);
-        }
-        if (length[p] > 0) {
-            const double e = paths[p].profile.time(length[p] - 1) + (delays.empty() ? 0.0 : delays[p]);
-            if (std::isfinite(e)) end = std::max(end, e);
-        }
-    }
-    const int K = (int)std::min(std::max(std::ceil(end / dt_c), 1.0), 65535.0);
+    const packed_timed_paths k = pack_timed_paths("fleet_conflicts", paths, radius, delays, flags, groups, dt_c);
+    const int K = (int)std::min(std::max(std::ceil(k.end / dt_c), 1.0), 65535.0);
     out.first_t.resize(P); out.min_sep.resize(P);
     std::vector<int32_t> fw(P), mw(P), nc(P), ts(P);
-    ctx.check(sc_fleet_conflicts_batch_host(ctx.get(), time.data(), pts.data(), offsets.data(), length.data(), status.data(), P,
-                                            delays.empty() ? nullptr : delays.data(), fl.empty() ? nullptr : fl.data(), 0.0, dt_c, K, nullptr,
-                                            ts.data(), radius.data(), gr.empty() ? nullptr : gr.data(), sep_cap, out.first_t.data(), fw.data(),
-                                            out.min_sep.data(), mw.data(), nc.data(), nullptr),
+    ctx.check(sc_fleet_conflicts_batch_host(ctx.get(), k.time.data(), k.pts.data(), k.offsets.data(), k.length.data(), k.status.data(), P,
+                                            delays.empty() ? nullptr : delays.data(), k.flags.empty() ? nullptr : k.flags.data(), 0.0, dt_c, K,
+                                            nullptr, ts.data(), radius.data(), k.groups.empty() ? nullptr : k.groups.data(), sep_cap,
+                                            out.first_t.data(), fw.data(), out.min_sep.data(), mw.data(), nc.data(), nullptr),
               "sc_fleet_conflicts_batch_host");
     out.first_with.assign(fw.begin(), fw.end()); out.min_with.assign(mw.begin(), mw.end());
     out.n_conf.assign(nc.begin(), nc.end()); out.status.assign(ts.begin(), ts.end());
+    return out;
+}
+
+// ---- (new) delay schedules for timed paths (sc_fleet_schedule_batch_host; the definition is in sea_current_hip.h) -------
+// The cheapest resolution of what fleet_conflicts reports: the lower-priority path waits.  paths, radius, delays, flags and
+// groups as in fleet_conflicts.  Every path gets one of D start slots (1 .. 32) of `stride` ticks of dt_c: walking `order`
+// (empty = 0, 1, 2, ..; earlier = higher priority), a path takes the first slot <= jmax[p] (empty = D-1 everywhere; negative
+// = pinned to slot 0, a moving obstacle) in which it meets none of the paths placed before it.  slot[p] >= 0, or
+// SC_SLOT_UNRESOLVED (no slot is free: re-plan it; it blocks nobody), SC_SLOT_NOT_OK, SC_SLOT_UNNAMED (not in order).
+// delay[p] = slot * stride * dt_c seconds to add to the path's start delay, NaN for slot < 0.  The clock runs (D-1) * stride
+// ticks past the end of the longest path, so every path rests where the shifts end and the paths with slot >= 0 are
+// conflict-free among themselves.  counts: slot 0, slot > 0, unresolved, not scheduled.
+struct schedule_result {
+    std::vector<int> slot, status;
+    std::vector<double> delay;
+    int counts[4] = {0, 0, 0, 0};
+};
+inline schedule_result fleet_schedule(const std::vector<smooth_result>& paths, const std::vector<double>& radius,
+                                      const std::vector<double>& delays = {}, const std::vector<int>& flags = {},
+                                      const std::vector<int>& groups = {}, double dt_c = 0.1, int D = 8, int stride = 1,
+                                      const std::vector<int>& order = {}, const std::vector<int>& jmax = {},
+                                      gpu_context& ctx = default_context()) {
+    const int P = (int)paths.size();
+    schedule_result out;
+    if (P == 0) return out;
+    const packed_timed_paths k = pack_timed_paths("fleet_schedule", paths, radius, delays, flags, groups, dt_c);
+    if (D < 1 || D > 32 || stride < 1) throw std::invalid_argument("fleet_schedule: D in 1 .. 32 and stride >= 1 expected");
+    if ((!order.empty() && (int)order.size() != P) || (!jmax.empty() && (int)jmax.size() != P))
+        throw std::invalid_argument("fleet_schedule: order and jmax are empty or hold one entry per path");
+    const int K = (int)std::min(std::max(std::ceil(k.end / dt_c), 1.0) + (double)(D - 1) * stride, 65535.0);
+    const std::vector<int32_t> ord(order.begin(), order.end()), jm(jmax.begin(), jmax.end());
+    std::vector<int32_t> sl(P), ts(P), cnt(4);
+    ctx.check(sc_fleet_schedule_batch_host(ctx.get(), k.time.data(), k.pts.data(), k.offsets.data(), k.length.data(), k.status.data(), P,
+                                           delays.empty() ? nullptr : delays.data(), k.flags.empty() ? nullptr : k.flags.data(), 0.0, dt_c, K,
+                                           nullptr, ts.data(), radius.data(), k.groups.empty() ? nullptr : k.groups.data(), D, stride, nullptr,
+                                           ord.empty() ? nullptr : ord.data(), jm.empty() ? nullptr : jm.data(), sl.data(), cnt.data(),
+                                           nullptr),
+              "sc_fleet_schedule_batch_host");
+    out.slot.assign(sl.begin(), sl.end()); out.status.assign(ts.begin(), ts.end());
+    out.delay.resize(P);
+    for (int p = 0; p < P; ++p) out.delay[p] = sl[p] >= 0 ? (double)(sl[p] * stride) * dt_c : std::numeric_limits<double>::quiet_NaN();
+    for (int v = 0; v < 4; ++v) out.counts[v] = cnt[v];
     return out;
 }
 
