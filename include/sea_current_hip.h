@@ -60,7 +60,8 @@ typedef enum {
     SC_K_MOVES = 2,       /* d2 + clearance -> legal-move byte per cell; also sc_clearance_penalty_u8, sc_components_batch,
                            * sc_reachable_batch */
     SC_K_ASTAR = 3,       /* batched A*: two wavefronts per query (prep + search + retry launches); also the cost fields and
-                           * their read-out (sc_cost_field_batch, sc_field_paths_batch, the weighted and the multi-source forms) */
+                           * their read-out (sc_cost_field_batch, sc_field_paths_batch, the weighted and the multi-source forms),
+                           * and the assignment on them (sc_field_cost_matrix, sc_assign_batch, sc_fleet_assign_batch) */
     SC_K_TOPPRA = 4,      /* batched TOPP-RA: computeParams + backward + forward sweep */
     SC_K_TOPPRA_SAMPLE = 5,
     SC_K_BEZIER = 6,      /* tangents + control points, curve evaluation */
@@ -839,6 +840,75 @@ int sc_fleet_schedule_batch_host(sc_ctx* ctx, const double* time, const float* p
                                  double* knots, int32_t* tstatus, const double* radius, const int32_t* group, int D, int stride,
                                  uint64_t* table, const int32_t* order, const int32_t* jmax, int32_t* slot, int32_t* counts,
                                  double* knots_out);
+
+/* ---- robots to goals: the cost matrix of the fields and an optimal one-to-one matching -------------------------
+ * sc_cost_field_batch rooted at the goals gives every robot's exact cost to every goal.  These calls take the R x F matrix out
+ * of the fields and match robots to goals one to one, on the device, in the form sc_field_paths_batch accepts:
+ * qfield[q] = col_of[q], to_root = 1, and an unassigned robot's -1 becomes SC_Q_BAD_ENDPOINT by the rule for an out-of-range
+ * qfield.  The reference has nothing of this kind.
+ *
+ * Problem.  cost int32 [B][R][C], rows contiguous, 1 <= R, C <= SC_ASSIGN_MAX_DIM (1024).  An entry is valid when
+ *   0 <= c < INT32_MAX; c == SC_FIELD_INF means forbidden (the goal is unreachable for that robot).  A negative entry makes
+ *   that one problem SC_ASSIGN_BAD: its outputs are col_of / row_of -1 and u, v, matched, total, steps 0; the other problems
+ *   of the batch are unaffected.
+ * Matching.  A set of (row, column) pairs over valid, not forbidden entries, every row and every column used at most once.
+ *   The result has the most pairs possible and, among those, the smallest sum of costs.
+ * Padded form.  a[r][c] = cost, or SC_ASSIGN_BIG = 2^42 where forbidden.  2^42 exceeds 1024 * 2^31, so one forbidden edge
+ *   outweighs any set of real ones; n * BIG <= 2^52, so everything fits int64.
+ * The optimum is not unique under ties, so the library returns the result of one stated procedure: the textbook O(n^2 m)
+ * shortest-augmenting-path Hungarian method on int64.
+ *   If R <= C the lines are the rows and the posts the columns, otherwise the roles swap (the same procedure on the
+ *   transpose).  n lines, m posts, n <= m.  Start with u[n] = 0, v[m] = 0, p[m] = none.  For line i = 0 .. n-1 in index order:
+ *     minv[j] = +inf, way[j] = none, used[j] = false, i0 = i, j0 = none.
+ *     Loop (each pass counts one step):
+ *       for every unused j: cur = a[i0][j] - u[i0] - v[j]; if cur < minv[j] then minv[j] = cur and way[j] = j0;
+ *       j1 = the unused post of smallest minv, lowest j among equals; delta = minv[j1];
+ *       u[i] += delta; for every used j: u[p[j]] += delta and v[j] -= delta; for every unused j: minv[j] -= delta;
+ *       used[j1] = true, j0 = j1; leave the loop if p[j0] is none, else i0 = p[j0].
+ *     Augment: walk way back from j0, moving each p along (p[j0] = p[way[j0]], j0 = way[j0]); the last post gets i.
+ * Outputs, in the caller's orientation whichever side was the lines:
+ *   col_of int32 [B][R]  the column row r is paired with over a real edge, -1 otherwise;
+ *   row_of int32 [B][C]  the inverse;
+ *   u int64 [B][R], v int64 [B][C]  the duals of the rows and of the columns;
+ *   info int64 [B][4] = {matched, total, steps, status}: total is the sum over real pairs, status SC_ASSIGN_OK or SC_ASSIGN_BAD.
+ * Certificate (it holds for the procedure's output and proves optimality without any reference):
+ *   u[r] + v[c] <= a[r][c] for all r, c;  the duals of the longer side are <= 0, and 0 on unpaired posts (a post paired over a
+ *   forbidden edge reads -1 but may carry a dual: at most min(R, C) - matched of them);
+ *   sum u + sum v == total + SC_ASSIGN_BIG * (min(R, C) - matched).
+ * Bound on work: line i takes at most i + 1 passes, so steps <= n (n + 1) / 2 = 524 800 at 1024; the kernel's loops are
+ *   bounded by it.  The kernels apply the deltas lazily (one running offset, u and v settled once per line); in integers that
+ *   equals the eager form above exactly, and every output equals the CPU statements (tests/assign_twin.py in NumPy,
+ *   tests/cpp/assign_ref.c in C) bit for bit, steps included.
+ *
+ * sc_field_cost_matrix: cost[r][f] = g[f][cell[r]], plus col_cost[f] when given (int32 [F] or NULL, 0 ..
+ *   SC_FIELD_SEED_COST_MAX: a price per goal); the sum is done in int64 and clamped to INT32_MAX - 1; SC_FIELD_INF stays
+ *   SC_FIELD_INF; a cell[r] out of range makes that whole row SC_FIELD_INF.  g int32 [F][H][W] is any field array: plain,
+ *   weighted or multi-source.  One thread per (r, f).
+ * sc_assign_batch: B problems, one workgroup each (64, 256 or 1024 threads by max(R, C); R > C: a transpose into context
+ *   scratch, 4 * B * R * C bytes, comes first).  row_of, u and v may be NULL.  B == 0 is a no-op.
+ * sc_fleet_assign_batch: the two calls above with B = 1 and C = F; its parameter list is the matrix call's followed by what
+ *   sc_assign_batch takes after cost, B, R, C.  cost may be NULL: the matrix then lives in context scratch (4 * R * F bytes).
+ * Device pointers; the calls only enqueue on the context's stream (kernels timed under SC_K_ASTAR): no host synchronisation,
+ * no device-to-host copy.  The _host forms take host pointers, check the data before any launch (a g value below 0 or a
+ * col_cost outside its range: SC_ERR_INVALID), copy, run, copy back and synchronise.
+ * Errors: SC_ERR_INVALID for NULL cost / col_of / info (g, cell in the matrix calls), R or C (F in the combined call) outside
+ *   1 .. SC_ASSIGN_MAX_DIM, B < 0, and in the matrix call F < 1, R < 1, R * F > 2^30, W or H outside 1 .. SC_MAX_DIM. */
+#define SC_ASSIGN_MAX_DIM 1024
+#define SC_ASSIGN_BIG (1ll << 42)
+#define SC_ASSIGN_OK 0
+#define SC_ASSIGN_BAD 1
+int sc_field_cost_matrix(sc_ctx* ctx, const int32_t* g, int F, int W, int H, const int32_t* cell, int R, const int32_t* col_cost,
+                         int32_t* cost);
+int sc_field_cost_matrix_host(sc_ctx* ctx, const int32_t* g, int F, int W, int H, const int32_t* cell, int R, const int32_t* col_cost,
+                              int32_t* cost);
+int sc_assign_batch(sc_ctx* ctx, const int32_t* cost, int B, int R, int C, int32_t* col_of, int32_t* row_of, int64_t* u, int64_t* v,
+                    int64_t* info);
+int sc_assign_batch_host(sc_ctx* ctx, const int32_t* cost, int B, int R, int C, int32_t* col_of, int32_t* row_of, int64_t* u, int64_t* v,
+                         int64_t* info);
+int sc_fleet_assign_batch(sc_ctx* ctx, const int32_t* g, int F, int W, int H, const int32_t* cell, int R, const int32_t* col_cost,
+                          int32_t* cost, int32_t* col_of, int32_t* row_of, int64_t* u, int64_t* v, int64_t* info);
+int sc_fleet_assign_batch_host(sc_ctx* ctx, const int32_t* g, int F, int W, int H, const int32_t* cell, int R, const int32_t* col_cost,
+                               int32_t* cost, int32_t* col_of, int32_t* row_of, int64_t* u, int64_t* v, int64_t* info);
 
 /* ---- the reference's own planner, batched -----------------------------------------------
  * planning_space::fast_marching_trees (sea_current.hpp:1339-1407) with near (:1328-1337), cost (:1315-1326) and

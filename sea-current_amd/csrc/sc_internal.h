@@ -83,6 +83,8 @@ struct __attribute__((visibility("hidden"))) sc_ctx {
     sc_scratch traj_knots;  // sc_fleet_conflicts_batch without the caller's buffers: fp64 knots [P][K+1][2] | int32 tstatus [P]
     sc_scratch traj_box;    // delay schedules: fp64 [P][4] box of every path's present knots
     sc_scratch traj_table;  // sc_fleet_schedule_batch without the caller's table: uint64 [P][P]
+    sc_scratch assign_t;    // assignment with more rows than columns: int32 [B][C][R], the transposed cost matrices
+    sc_scratch assign_cost; // sc_fleet_assign_batch without the caller's matrix: int32 [R][F]
     int astar_cap = 1 << 16;         // ring entries per bucket (power of two)
     size_t astar_slot_budget = (size_t)96 << 30;  // bytes of g + bitmap + ring scratch this context may take (SC_ASTAR_SLOT_GB), further bounded by what the device has free; 4096^2: 96 GiB = 1966 slots measured best (48: -34 %, 160: -17 %)
     int traj_wg_target = 4096;      // path conflicts: workgroups a launch of the pair kernel aims for (16 per CU; SC_TRAJ_WORKGROUPS)

@@ -28,6 +28,9 @@ SMOOTH_OK, SMOOTH_BAD_INPUT, SMOOTH_NONFINITE, SMOOTH_TOPPRA_FAILED, SMOOTH_TRUN
 TRAJ_OK, TRAJ_SKIPPED, TRAJ_BAD = range(3)
 TRAJ_MAX_TICKS = 65535
 SLOT_UNRESOLVED, SLOT_NOT_OK, SLOT_UNNAMED = -1, -2, -3
+ASSIGN_MAX_DIM = 1024
+ASSIGN_BIG = 1 << 42
+ASSIGN_OK, ASSIGN_BAD = 0, 1
 
 _lib = None
 
@@ -142,6 +145,12 @@ _SIGNATURES = {
     "sc_traj_shift_knots_batch_host": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp]),
     "sc_fleet_schedule_batch": (_i, [_vp] * 6 + [_i, _vp, _vp, _d, _d, _i, _vp, _vp, _vp, _vp, _i, _i] + [_vp] * 6),
     "sc_fleet_schedule_batch_host": (_i, [_vp] * 6 + [_i, _vp, _vp, _d, _d, _i, _vp, _vp, _vp, _vp, _i, _i] + [_vp] * 6),
+    "sc_field_cost_matrix": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp]),
+    "sc_field_cost_matrix_host": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp]),
+    "sc_assign_batch": (_i, [_vp, _vp, _i, _i, _i] + [_vp] * 5),
+    "sc_assign_batch_host": (_i, [_vp, _vp, _i, _i, _i] + [_vp] * 5),
+    "sc_fleet_assign_batch": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp] + [_vp] * 6),
+    "sc_fleet_assign_batch_host": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp] + [_vp] * 6),
     "sc_rank_range": (None, [_i, _i, _i, C.POINTER(_i), C.POINTER(_i)]),
     "sc_comm_unique_id": (_i, [_vp]),
     "sc_comm_init": (_i, [_vp, _vp, _i, _i]),
@@ -925,6 +934,92 @@ class Context:
                                                       _ptr(out["counts"]), _ptr(out.get("knots_out"))), "sc_fleet_schedule_batch_host")
         with np.errstate(invalid="ignore"):
             out["delay"] = np.where(out["slot"] >= 0, (out["slot"] * stride).astype(np.float64) * dt_c, np.nan)
+        return out
+
+    # ---- robots to goals (sc_field_cost_matrix, sc_assign_batch, sc_fleet_assign_batch) ----
+    def field_cost_matrix(self, g, cells, col_cost=None, out=None):
+        """The R x F cost matrix of robots at `cells` (int32 [R]) against the fields g (int32 [F,H,W], any of cost_fields' or
+        cost_fields_multi's arrays): out[r][f] = g[f][cells[r]] (+ col_cost[f], int32 [F], 0 .. FIELD_SEED_COST_MAX), FIELD_INF
+        kept; a cell out of range gives a row of FIELD_INF (sc_field_cost_matrix).  Returns int32 [R,F].  Only enqueues."""
+        import torch
+        F, H, W = g.shape
+        R = cells.shape[0]
+        if out is None:
+            out = torch.empty((R, F), dtype=torch.int32, device=g.device)
+        self._ck(self._l.sc_field_cost_matrix(self._h, _ptr(g), F, W, H, _ptr(cells), R, _ptr(col_cost), _ptr(out)), "sc_field_cost_matrix")
+        return out
+
+    def assign(self, cost):
+        """Optimal one-to-one matchings (sc_assign_batch; the definition is in include/sea_current_hip.h): cost int32 [B,R,C]
+        or [R,C] (B = 1), FIELD_INF = forbidden.  Returns dict(col_of int32 [B,R], row_of int32 [B,C], u int64 [B,R], v int64
+        [B,C], info int64 [B,4] = matched, total, steps, status), without the leading B for 2-D input.  Only enqueues."""
+        import torch
+        flat = cost.dim() == 2
+        B, R, Cc = (1,) + tuple(cost.shape) if flat else tuple(cost.shape)
+        dev = cost.device
+        lead = () if flat else (B,)
+        out = dict(col_of=torch.empty(lead + (R,), dtype=torch.int32, device=dev), row_of=torch.empty(lead + (Cc,), dtype=torch.int32, device=dev),
+                   u=torch.empty(lead + (R,), dtype=torch.int64, device=dev), v=torch.empty(lead + (Cc,), dtype=torch.int64, device=dev),
+                   info=torch.empty(lead + (4,), dtype=torch.int64, device=dev))
+        self._ck(self._l.sc_assign_batch(self._h, _ptr(cost), B, R, Cc, _ptr(out["col_of"]), _ptr(out["row_of"]), _ptr(out["u"]), _ptr(out["v"]),
+                                         _ptr(out["info"])), "sc_assign_batch")
+        return out
+
+    def fleet_assign(self, g, cells, col_cost=None, want_cost=False):
+        """field_cost_matrix and assign in one call (sc_fleet_assign_batch): robots at `cells` to the goals the fields g are
+        rooted at, one goal per robot.  Returns assign's dict for one problem (col_of[r] = the field of robot r or -1: what
+        field_paths takes as qfield with to_root=True), plus cost int32 [R,F] with want_cost.  Only enqueues."""
+        import torch
+        F, H, W = g.shape
+        R = cells.shape[0]
+        dev = g.device
+        out = dict(col_of=torch.empty(R, dtype=torch.int32, device=dev), row_of=torch.empty(F, dtype=torch.int32, device=dev),
+                   u=torch.empty(R, dtype=torch.int64, device=dev), v=torch.empty(F, dtype=torch.int64, device=dev),
+                   info=torch.empty(4, dtype=torch.int64, device=dev))
+        if want_cost:
+            out["cost"] = torch.empty((R, F), dtype=torch.int32, device=dev)
+        self._ck(self._l.sc_fleet_assign_batch(self._h, _ptr(g), F, W, H, _ptr(cells), R, _ptr(col_cost), _ptr(out.get("cost")),
+                                               _ptr(out["col_of"]), _ptr(out["row_of"]), _ptr(out["u"]), _ptr(out["v"]), _ptr(out["info"])),
+                 "sc_fleet_assign_batch")
+        return out
+
+    def field_cost_matrix_host(self, g, cells, col_cost=None, out=None):
+        """Host form of field_cost_matrix (numpy in, numpy out; sc_field_cost_matrix_host)."""
+        g, cells = np.ascontiguousarray(g, dtype=np.int32), np.ascontiguousarray(cells, dtype=np.int32)
+        col_cost = None if col_cost is None else np.ascontiguousarray(col_cost, dtype=np.int32)
+        F, H, W = g.shape
+        R = cells.shape[0]
+        if out is None:
+            out = np.zeros((R, F), np.int32)
+        self._ck(self._l.sc_field_cost_matrix_host(self._h, _ptr(g), F, W, H, _ptr(cells), R, _ptr(col_cost), _ptr(out)),
+                 "sc_field_cost_matrix_host")
+        return out
+
+    def assign_host(self, cost):
+        """Host form of assign (numpy in, numpy out; sc_assign_batch_host)."""
+        cost = np.ascontiguousarray(cost, dtype=np.int32)
+        flat = cost.ndim == 2
+        B, R, Cc = (1,) + cost.shape if flat else cost.shape
+        lead = () if flat else (B,)
+        out = dict(col_of=np.zeros(lead + (R,), np.int32), row_of=np.zeros(lead + (Cc,), np.int32), u=np.zeros(lead + (R,), np.int64),
+                   v=np.zeros(lead + (Cc,), np.int64), info=np.zeros(lead + (4,), np.int64))
+        self._ck(self._l.sc_assign_batch_host(self._h, _ptr(cost), B, R, Cc, _ptr(out["col_of"]), _ptr(out["row_of"]), _ptr(out["u"]),
+                                              _ptr(out["v"]), _ptr(out["info"])), "sc_assign_batch_host")
+        return out
+
+    def fleet_assign_host(self, g, cells, col_cost=None, want_cost=False):
+        """Host form of fleet_assign (numpy in, numpy out; sc_fleet_assign_batch_host)."""
+        g, cells = np.ascontiguousarray(g, dtype=np.int32), np.ascontiguousarray(cells, dtype=np.int32)
+        col_cost = None if col_cost is None else np.ascontiguousarray(col_cost, dtype=np.int32)
+        F, H, W = g.shape
+        R = cells.shape[0]
+        out = dict(col_of=np.zeros(R, np.int32), row_of=np.zeros(F, np.int32), u=np.zeros(R, np.int64), v=np.zeros(F, np.int64),
+                   info=np.zeros(4, np.int64))
+        if want_cost:
+            out["cost"] = np.zeros((R, F), np.int32)
+        self._ck(self._l.sc_fleet_assign_batch_host(self._h, _ptr(g), F, W, H, _ptr(cells), R, _ptr(col_cost), _ptr(out.get("cost")),
+                                                    _ptr(out["col_of"]), _ptr(out["row_of"]), _ptr(out["u"]), _ptr(out["v"]),
+                                                    _ptr(out["info"])), "sc_fleet_assign_batch_host")
         return out
 
     # ---- multi-GPU gather (RCCL through the C ABI) ----

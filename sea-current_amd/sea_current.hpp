@@ -30,6 +30,7 @@
 //         goals, every start to the cheapest of them
 //   (new) fleet_conflicts: who meets whom among the results of smooth_paths_batch, when first, and how close
 //   (new) fleet_schedule: start slots by priority that let the lower-priority path wait until it meets nobody
+//   (new) planning_space::plan_assigned: one goal per robot, the cheapest such assignment, from fields rooted at the goals
 //
 // Differences that are deliberate: obstacle::closed is initialised (the reference leaves it
 // uninitialised, :197); library code never prints or calls std::exit (SC_ASSERT throws in DEBUG);
@@ -887,6 +888,56 @@ public:
         return out;
     }
 
+    // Many starts, many goals, one goal per start (a fleet and its docks): one cost field per goal -- weighted when the soft
+    // knobs are on, exactly as for plan_to -- then the matching that pairs as many starts as possible and, among those, at the
+    // smallest sum of costs (sc_fleet_assign_batch_host; goal k priced at goal_costs[k], empty: all 0, in the units of the move
+    // costs), then the paths read from the fields.  At most SC_ASSIGN_MAX_DIM starts and goals.  Per start: the path
+    // start..goal, the index of its goal and the cost, goal cost included; nullopt, -1 and -1 for a start left without a goal.
+    // paths[q] equals plan_to(starts, goals[goal[q]])[q]; matched starts have a goal, and their costs add up to total.
+    struct assigned_result {
+        std::vector<std::optional<std::vector<Vector2f>>> paths;
+        std::vector<int32_t> goal, cost;
+        int64_t matched = 0, total = 0;
+    };
+    assigned_result plan_assigned(const std::vector<Vector2f>& starts, const std::vector<Vector2f>& goals,
+                                  const std::vector<int32_t>& goal_costs = {}, gpu_context& ctx = default_context()) {
+        if (!goal_costs.empty() && goal_costs.size() != goals.size())
+            throw std::invalid_argument("planning_space::plan_assigned: goals and goal_costs differ in size");
+        if (starts.size() > SC_ASSIGN_MAX_DIM || goals.size() > SC_ASSIGN_MAX_DIM)
+            throw std::invalid_argument("planning_space::plan_assigned: at most SC_ASSIGN_MAX_DIM starts and goals");
+        assigned_result out;
+        const int R = (int)starts.size(), F = (int)goals.size();
+        out.paths.resize(R);
+        out.goal.assign(R, -1);
+        out.cost.assign(R, -1);
+        if (R == 0 || F == 0) return out;
+        occupancy_grid g = make_grid(ctx);
+        g.edt(ctx);
+        std::vector<int32_t> s(R), roots(F);
+        for (int i = 0; i < R; ++i) s[i] = g.cell_of(starts[i]);
+        for (int k = 0; k < F; ++k) roots[k] = g.cell_of(goals[k]);
+        const int32_t r2 = clearance_r2(g);
+        auto fr = fields_of(g, roots, r2, ctx);
+        std::vector<int32_t> col_of(R, -1);
+        int64_t info[4] = {0, 0, 0, 0};
+        ctx.check(sc_fleet_assign_batch_host(ctx.get(), fr.g.data(), F, g.W, g.H, s.data(), R, goal_costs.empty() ? nullptr : goal_costs.data(),
+                                             nullptr, col_of.data(), nullptr, nullptr, nullptr, info),
+                  "sc_fleet_assign_batch_host");
+        auto br = g.field_paths(fr, col_of, s, 0, true, ctx);
+        std::vector<Vector2f> ends(R, Vector2f(0, 0));
+        for (int q = 0; q < R; ++q)
+            if (col_of[q] >= 0) ends[q] = goals[(size_t)col_of[q]];
+        out.paths = to_points(g, br, r2, starts, ends, "plan_assigned", ctx);
+        out.matched = info[0];
+        out.total = info[1];
+        for (int q = 0; q < R; ++q)
+            if (out.paths[q]) {
+                out.goal[q] = col_of[q];
+                out.cost[q] = br.cost[q] + (goal_costs.empty() ? 0 : goal_costs[(size_t)col_of[q]]);
+            }
+        return out;
+    }
+
 private:
     int32_t clearance_r2(const occupancy_grid& g) const {
         const float cc = clearance / g.resolution;
@@ -894,11 +945,15 @@ private:
     }
     // the field of plan_from / plan_to: weighted when both soft knobs are positive, else today's
     occupancy_grid::field_result fields_of(occupancy_grid& g, int32_t root, int32_t r2, gpu_context& ctx) const {
-        if (!(soft_clearance > 0.0f && soft_penalty > 0)) return g.cost_fields({root}, r2, -1, ctx);
+        return fields_of(g, std::vector<int32_t>{root}, r2, ctx);
+    }
+    // the same for several roots (plan_assigned: one field per goal)
+    occupancy_grid::field_result fields_of(occupancy_grid& g, const std::vector<int32_t>& roots, int32_t r2, gpu_context& ctx) const {
+        if (!(soft_clearance > 0.0f && soft_penalty > 0)) return g.cost_fields(roots, r2, -1, ctx);
         int32_t r2_soft;
         int pen_max;
         soft_knobs(g, r2_soft, pen_max);
-        return g.cost_fields({root}, g.clearance_penalty(r2, r2_soft, pen_max, ctx), pen_max, r2, -1, ctx);
+        return g.cost_fields(roots, g.clearance_penalty(r2, r2_soft, pen_max, ctx), pen_max, r2, -1, ctx);
     }
     // the costmap parameters the soft knobs stand for
     void soft_knobs(const occupancy_grid& g, int32_t& r2_soft, int& pen_max) const {
