@@ -61,7 +61,8 @@ typedef enum {
                            * sc_reachable_batch */
     SC_K_ASTAR = 3,       /* batched A*: two wavefronts per query (prep + search + retry launches); also the cost fields and
                            * their read-out (sc_cost_field_batch, sc_field_paths_batch, the weighted and the multi-source forms),
-                           * and the assignment on them (sc_field_cost_matrix, sc_assign_batch, sc_fleet_assign_batch) */
+                           * the assignment on them (sc_field_cost_matrix, sc_assign_batch, sc_fleet_assign_batch), and the
+                           * space-time plans (sc_traj_reserve_batch, sc_tplan_batch, sc_fleet_replan_batch) */
     SC_K_TOPPRA = 4,      /* batched TOPP-RA: computeParams + backward + forward sweep */
     SC_K_TOPPRA_SAMPLE = 5,
     SC_K_BEZIER = 6,      /* tangents + control points, curve evaluation */
@@ -909,6 +910,102 @@ int sc_fleet_assign_batch(sc_ctx* ctx, const int32_t* g, int F, int W, int H, co
                           int32_t* cost, int32_t* col_of, int32_t* row_of, int64_t* u, int64_t* v, int64_t* info);
 int sc_fleet_assign_batch_host(sc_ctx* ctx, const int32_t* g, int F, int W, int H, const int32_t* cell, int R, const int32_t* col_cost,
                                int32_t* cost, int32_t* col_of, int32_t* row_of, int64_t* u, int64_t* v, int64_t* info);
+
+/* ---- re-planning in space-time around the scheduled fleet -------------------------------------------------------
+ * sc_fleet_schedule_batch only delays: a path that finds no free slot comes back SC_SLOT_UNRESOLVED.  These calls plan such a
+ * robot again in (cell, time): the paths that did get a slot are rasterised into reservations, and an exact earliest-arrival
+ * search on the time-expanded grid goes around them.  The result is knot rows that sc_traj_conflicts_batch takes directly.  The
+ * reference has nothing of this kind.
+ *
+ * Definition (tests/tplan_twin.py states it in NumPy, tests/cpp/tplan_ref.c in C; every output equals them exactly).
+ *   Clock and grid.  Layer t is tick t of the knots' clock, tau_t = T0 + t * dt_c; there are L = K + 1 layers.  The caller
+ *     chooses dt_c as the time one grid move takes.  A cell's centre is the point sc_cells_to_points_batch writes: (x_min +
+ *     (c % W + 0.5) * res_x, y_min + (c / W + 0.5) * res_y) in float32 without contraction, widened to fp64 where needed.
+ *     Bitmaps are uint32 [H][Wq], Wq = ceil(W / 32): cell (x, y) is bit x & 31 of word [y][x >> 5]; bits at x >= W are 0.
+ *   Reservation.  res uint32 [L][H][Wq].  For path q and interval k with both knots present, cell c is hit iff m2 < R*R of the
+ *     path conflicts above with d0 = knot[q][k] - c, d1 = knot[q][k+1] - c, R = radius[q] + pad: the same operations in the same
+ *     order, fp64, no fused multiply-adds.  It says "a robot standing at c through interval k would conflict with q".  A hit
+ *     sets c's bit in layers k and k+1.  An interval with an absent knot reserves nothing (the conflicts call does not compare
+ *     it).  Paths whose tstatus is not SC_TRAJ_OK reserve nothing (tstatus NULL = all OK), nor do paths with select[q] == 0
+ *     (select int32 [P], NULL = all).  A path that is OK and whose radius is outside the contract becomes SC_TRAJ_BAD, as in
+ *     the conflicts call, and reserves nothing.  The call ORs into res: several calls accumulate, the caller zeroes it first.
+ *   Why pad.  pad is the caller's fp64 argument; the library does not derive it.  Let pad >= r_new + hyp / 2 with hyp =
+ *     sqrt(res_x^2 + res_y^2), the longest move, and let a robot of radius r_new step between cells that are unreserved at
+ *     their layers.  Then it never comes within radius[q] + r_new of q on a compared interval:
+ *       on interval t the robot is at a + lam * (b - a), lam in [0, 1], a its cell at layer t and b at layer t+1;
+ *       a (unreserved at layer t) and b (at layer t+1) are both at least R from q's motion relative to a standing robot on
+ *       interval t; the robot's offset from the nearer of a and b is at most |b - a| / 2 <= hyp / 2,
+ *       so it stays at least R - hyp / 2 >= radius[q] + r_new away.
+ *   Search, for each of B queries.  start, goal: cells; t_start: the layer at which the robot appears (int32 [B], NULL = 0; it
+ *     is absent before); hold: 0 or 1, one value for the call.  free(c) and the move byte of a cell are sc_moves_i32_u8's for
+ *     r2_clear (no corner cutting, directions d in its order, delta_d = (dx, dy) = {1,-1,0,0,1,-1,1,-1}, {0,0,1,-1,1,1,-1,-1}).
+ *       reach[t_start] = {start};
+ *       reach[t+1] = the cells c unreserved at layer t+1 with c in reach[t] (a wait) or c = s + delta_d for some s in reach[t]
+ *         with bit d of moves[s] set.
+ *     t_hold = with hold, 1 + the last layer at which goal is reserved (0 if never); without hold, 0.
+ *     arrive = the smallest t >= max(t_start, t_hold) with goal in reach[t].
+ *     status (sc_tplan_status), decided in this order: SC_TP_BAD_ENDPOINT when start or goal is out of range or not free, or
+ *     t_start is outside 0 .. L-1; SC_TP_START_BLOCKED when start is reserved at t_start; SC_TP_NO_PATH when there is no
+ *     arrival by layer L-1; else SC_TP_OK.  res NULL = nothing is reserved.
+ *   Path.  Walk back from (goal, arrive).  The predecessor of cell c at layer t is c itself if c is in reach[t-1] (waits come
+ *     first: otherwise they pile up as back-and-forth moves); failing that, c - delta_d for the first d in 0 .. 7 with
+ *     c - delta_d in reach[t-1] and bit d of moves[c - delta_d] set.  This is one stated earliest-arrival path; it is NOT the
+ *     shortest in metres among them, and nothing is smoothed.
+ *   Outputs, each may be NULL except status.  path int32 [B][L]: path[b][i] = the cell at layer t_start + i for i < len[b],
+ *     entries past len are not written.  len, arrive, status int32 [B]; len = arrive - t_start + 1; len 0 and arrive -1 when the
+ *     status is not OK.  knots_out fp64 [B][L][2]: NaN before t_start, the cell's centre at layers t_start .. arrive, after
+ *     arrive the goal's centre with hold and NaN without, all NaN when the status is not OK.  A caller puts knots_out behind the
+ *     fleet's rows in one [P+B][K+1][2] buffer and calls sc_traj_conflicts_batch: a failed plan is NaN rows, which reserve
+ *     nothing and conflict with nobody.  reach uint32 [B][L][H][Wq] (NULL = context scratch): defined for layers t_start ..
+ *     arrive, or .. L-1 when there is no arrival; other layers, and all layers of a query that is BAD_ENDPOINT or
+ *     START_BLOCKED, are unspecified.
+ *
+ * sc_traj_reserve_batch: ORs the reservations of P knot rows into res.
+ * sc_tplan_batch: the search.  The frame (x_min .. res_y) is read for knots_out only.
+ * sc_fleet_replan_batch: the arguments of both, then r_new fp64 [B] and sequential.  It reserves the selected fleet paths; with
+ *   sequential = 0 it plans all B robots against them in one batch (r_new may be NULL); with sequential = 1 it plans robot i
+ *   and then reserves knots_out[i] with radius r_new[i] and the same pad, for i = 0, 1, .., so that robot i+1 goes around it:
+ *   prioritised planning in the caller's order (needs r_new and knots_out).  L must be K + 1.
+ * Device pointers; the calls only enqueue on the context's stream (kernels timed under SC_K_ASTAR): no host synchronisation, no
+ * device-to-host copy.  Scratch of the context: W * H bytes of move bytes and eight direction planes uint32 [8][H][Wq]; 24 bytes
+ * per query of a group; 4 * L bytes per query when knots_out is asked without path; and, when reach is NULL, B_g * L * H * Wq * 4
+ * bytes of layers: the B queries are served in groups of B_g that fit a budget, SC_TPLAN_GB GiB (a decimal number, at most 64, default 8) in the
+ * environment when the context is created.  One query whose layers exceed the budget is SC_ERR_INVALID, with the needed size in
+ * sc_last_error.  A launch of the search advances SC_TPLAN_LAYERS layers (1 .. 16, default 16, which measured best; read at context creation); no
+ * output depends on it.
+ * The _host forms take host pointers (res and tstatus are copied back) and return SC_ERR_INVALID before any launch for a radius
+ * or r_new outside the contract.
+ * Errors: SC_ERR_INVALID for NULL required pointers (knots, radius, res in the reserving calls; d2, start, goal, status), W or H
+ * outside 1 .. SC_MAX_DIM, P outside 1 .. 16384, K outside 1 .. 65535, P * (K+1) > 2^26, L outside 1 .. 65536, L != K + 1 in
+ * the combined call, pad not finite or negative, B outside 1 .. 65536, and, where the frame is read (the reserving calls, and
+ * knots_out), x_min or y_min not finite or res_x, res_y not finite and positive. */
+typedef enum {
+    SC_TP_OK = 0,
+    SC_TP_NO_PATH = 1,
+    SC_TP_BAD_ENDPOINT = 2,
+    SC_TP_START_BLOCKED = 3
+} sc_tplan_status;
+int sc_traj_reserve_batch(sc_ctx* ctx, const double* knots, int32_t* tstatus, int P, int K, const double* radius, const int32_t* select,
+                          double pad, int W, int H, float x_min, float y_min, float res_x, float res_y, uint32_t* res);
+int sc_traj_reserve_batch_host(sc_ctx* ctx, const double* knots, int32_t* tstatus, int P, int K, const double* radius,
+                               const int32_t* select, double pad, int W, int H, float x_min, float y_min, float res_x, float res_y,
+                               uint32_t* res);
+int sc_tplan_batch(sc_ctx* ctx, const int32_t* d2, int W, int H, int32_t r2_clear, const uint32_t* res, int L, const int32_t* start,
+                   const int32_t* goal, const int32_t* t_start, int B, int hold, int32_t* path, int32_t* len, int32_t* arrive,
+                   int32_t* status, double* knots_out, float x_min, float y_min, float res_x, float res_y, uint32_t* reach);
+int sc_tplan_batch_host(sc_ctx* ctx, const int32_t* d2, int W, int H, int32_t r2_clear, const uint32_t* res, int L, const int32_t* start,
+                        const int32_t* goal, const int32_t* t_start, int B, int hold, int32_t* path, int32_t* len, int32_t* arrive,
+                        int32_t* status, double* knots_out, float x_min, float y_min, float res_x, float res_y, uint32_t* reach);
+int sc_fleet_replan_batch(sc_ctx* ctx, const double* knots, int32_t* tstatus, int P, int K, const double* radius, const int32_t* select,
+                          double pad, int W, int H, float x_min, float y_min, float res_x, float res_y, uint32_t* res, const int32_t* d2,
+                          int32_t r2_clear, int L, const int32_t* start, const int32_t* goal, const int32_t* t_start, int B, int hold,
+                          int32_t* path, int32_t* len, int32_t* arrive, int32_t* status, double* knots_out, uint32_t* reach,
+                          const double* r_new, int sequential);
+int sc_fleet_replan_batch_host(sc_ctx* ctx, const double* knots, int32_t* tstatus, int P, int K, const double* radius,
+                               const int32_t* select, double pad, int W, int H, float x_min, float y_min, float res_x, float res_y,
+                               uint32_t* res, const int32_t* d2, int32_t r2_clear, int L, const int32_t* start, const int32_t* goal,
+                               const int32_t* t_start, int B, int hold, int32_t* path, int32_t* len, int32_t* arrive, int32_t* status,
+                               double* knots_out, uint32_t* reach, const double* r_new, int sequential);
 
 /* ---- the reference's own planner, batched -----------------------------------------------
  * planning_space::fast_marching_trees (sea_current.hpp:1339-1407) with near (:1328-1337), cost (:1315-1326) and

@@ -43,6 +43,10 @@ extern "C" int sc_ctx_create(int device, sc_ctx** out) {
     if (const char* e = getenv("SC_TRAJ_WORKGROUPS")) { const long v = atol(e); if (v >= 1 && v <= 65536) c->traj_wg_target = (int)v; }
     // the shift table evaluates every pair, also those whose boxes are too far apart to meet (the tests compare the two)
     if (const char* e = getenv("SC_TRAJ_SCHED_NOSKIP")) c->traj_sched_noskip = atol(e) == 1;
+    // space-time plans: GiB of layer scratch a group of queries may take, and the layers one launch of the step kernel advances
+    // (the tests set both: several groups, and every blocking from 1 to 16)
+    if (const char* e = getenv("SC_TPLAN_GB")) { const double v = atof(e); if (v > 0.0 && v <= 64.0) c->tplan_budget = (size_t)(v * 1073741824.0); }
+    if (const char* e = getenv("SC_TPLAN_LAYERS")) { const long v = atol(e); if (v >= 1 && v <= 16) c->tplan_layers = (int)v; }
     *out = c;
     return SC_OK;
 }

@@ -85,10 +85,15 @@ struct __attribute__((visibility("hidden"))) sc_ctx {
     sc_scratch traj_table;  // sc_fleet_schedule_batch without the caller's table: uint64 [P][P]
     sc_scratch assign_t;    // assignment with more rows than columns: int32 [B][C][R], the transposed cost matrices
     sc_scratch assign_cost; // sc_fleet_assign_batch without the caller's matrix: int32 [R][F]
+    sc_scratch tp_planes;   // space-time plans: uint32 [8][H][Wq], plane d = the cells with bit d of the move byte set
+    sc_scratch tp_reach;    // space-time plans without the caller's reach: uint32 [B_g][L][H][Wq], the layers of one group of queries
+    sc_scratch tp_state;    // space-time plans: per-query state [B_g] | int32 path [B_g][L] when only the knots are wanted
     int astar_cap = 1 << 16;         // ring entries per bucket (power of two)
     size_t astar_slot_budget = (size_t)96 << 30;  // bytes of g + bitmap + ring scratch this context may take (SC_ASTAR_SLOT_GB), further bounded by what the device has free; 4096^2: 96 GiB = 1966 slots measured best (48: -34 %, 160: -17 %)
     int traj_wg_target = 4096;      // path conflicts: workgroups a launch of the pair kernel aims for (16 per CU; SC_TRAJ_WORKGROUPS)
     bool traj_sched_noskip = false; // delay schedules: evaluate the pairs the box test would skip (SC_TRAJ_SCHED_NOSKIP=1; the tests prove the skip exact with it)
+    size_t tplan_budget = (size_t)8 << 30;   // space-time plans: bytes of tp_reach a group of queries may take (SC_TPLAN_GB, 1 .. 64)
+    int tplan_layers = 16;          // space-time plans: layers a launch of the step kernel advances, 1 .. 16 (SC_TPLAN_LAYERS); no output depends on it
     int last_Q = 0;
     void* comm = nullptr;           // ncclComm_t of sc_allgather_paths
     bool comm_owned = false;
@@ -205,6 +210,18 @@ __device__ __forceinline__ void wave_lds_sync() {
     // LDS operations of one wave execute in issue order; only the compiler must not reorder them.
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
+}
+
+// m2 of the path conflicts (the definition in include/sea_current_hip.h): the squared closest approach on one interval of two
+// motions whose difference goes from d0 to d1, in the order of operations of traj.hip's pair kernel (compile without contraction)
+__device__ __forceinline__ double sc_traj_m2(double d0x, double d0y, double d1x, double d1y) {
+    const double ex = d1x - d0x, ey = d1y - d0y;
+    const double aa = ex * ex + ey * ey;
+    const double bb = d0x * ex + d0y * ey;
+    const double q = -bb / aa;
+    const double lam = aa > 0.0 ? (q < 0.0 ? 0.0 : (q > 1.0 ? 1.0 : q)) : 0.0;
+    const double px = d0x + lam * ex, py = d0y + lam * ey;
+    return px * px + py * py;
 }
 
 // point (order 0), hodograph (1) or second derivative (2) of the cubic Bezier c [4][2] at parameter s, in fp64

@@ -28,6 +28,7 @@ SMOOTH_OK, SMOOTH_BAD_INPUT, SMOOTH_NONFINITE, SMOOTH_TOPPRA_FAILED, SMOOTH_TRUN
 TRAJ_OK, TRAJ_SKIPPED, TRAJ_BAD = range(3)
 TRAJ_MAX_TICKS = 65535
 SLOT_UNRESOLVED, SLOT_NOT_OK, SLOT_UNNAMED = -1, -2, -3
+TP_OK, TP_NO_PATH, TP_BAD_ENDPOINT, TP_START_BLOCKED = range(4)
 ASSIGN_MAX_DIM = 1024
 ASSIGN_BIG = 1 << 42
 ASSIGN_OK, ASSIGN_BAD = 0, 1
@@ -145,6 +146,14 @@ _SIGNATURES = {
     "sc_traj_shift_knots_batch_host": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp]),
     "sc_fleet_schedule_batch": (_i, [_vp] * 6 + [_i, _vp, _vp, _d, _d, _i, _vp, _vp, _vp, _vp, _i, _i] + [_vp] * 6),
     "sc_fleet_schedule_batch_host": (_i, [_vp] * 6 + [_i, _vp, _vp, _d, _d, _i, _vp, _vp, _vp, _vp, _i, _i] + [_vp] * 6),
+    "sc_traj_reserve_batch": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _d, _i, _i] + [C.c_float] * 4 + [_vp]),
+    "sc_traj_reserve_batch_host": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _d, _i, _i] + [C.c_float] * 4 + [_vp]),
+    "sc_tplan_batch": (_i, [_vp, _vp, _i, _i, C.c_int32, _vp, _i, _vp, _vp, _vp, _i, _i] + [_vp] * 5 + [C.c_float] * 4 + [_vp]),
+    "sc_tplan_batch_host": (_i, [_vp, _vp, _i, _i, C.c_int32, _vp, _i, _vp, _vp, _vp, _i, _i] + [_vp] * 5 + [C.c_float] * 4 + [_vp]),
+    "sc_fleet_replan_batch": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _d, _i, _i] + [C.c_float] * 4 + [_vp] +
+                              [_vp, C.c_int32, _i, _vp, _vp, _vp, _i, _i] + [_vp] * 7 + [_i]),
+    "sc_fleet_replan_batch_host": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _d, _i, _i] + [C.c_float] * 4 + [_vp] +
+                                   [_vp, C.c_int32, _i, _vp, _vp, _vp, _i, _i] + [_vp] * 7 + [_i]),
     "sc_field_cost_matrix": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp]),
     "sc_field_cost_matrix_host": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp]),
     "sc_assign_batch": (_i, [_vp, _vp, _i, _i, _i] + [_vp] * 5),
@@ -934,6 +943,144 @@ class Context:
                                                       _ptr(out["counts"]), _ptr(out.get("knots_out"))), "sc_fleet_schedule_batch_host")
         with np.errstate(invalid="ignore"):
             out["delay"] = np.where(out["slot"] >= 0, (out["slot"] * stride).astype(np.float64) * dt_c, np.nan)
+        return out
+
+    # ---- re-planning in space-time around the scheduled fleet (sc_traj_reserve_batch, sc_tplan_batch, sc_fleet_replan_batch) ----
+    @staticmethod
+    def _tplan_out(B, L, H, W, dev, want_knots, want_reach):
+        """The result buffers of a plan: torch on `dev`, numpy when dev is None.  Bit words are int32 in torch (it has no uint32
+        arithmetic) and uint32 in numpy."""
+        Wq = (W + 31) // 32
+        if dev is None:
+            out = dict(path=np.full((B, L), -1, np.int32), len=np.zeros(B, np.int32), arrive=np.zeros(B, np.int32), status=np.zeros(B, np.int32))
+            if want_knots:
+                out["knots_out"] = np.zeros((B, L, 2))
+            if want_reach:
+                out["reach"] = np.zeros((B, L, H, Wq), np.uint32)
+            return out
+        import torch
+        out = dict(path=torch.full((B, L), -1, dtype=torch.int32, device=dev))
+        for k in ("len", "arrive", "status"):
+            out[k] = torch.empty(B, dtype=torch.int32, device=dev)
+        if want_knots:
+            out["knots_out"] = torch.empty((B, L, 2), dtype=torch.float64, device=dev)
+        if want_reach:
+            out["reach"] = torch.empty((B, L, H, Wq), dtype=torch.int32, device=dev)
+        return out
+
+    def traj_reserve(self, knots, tstatus, radius, W, H, frame, pad, select=None, res=None):
+        """Rasterise knot rows into reservations (sc_traj_reserve_batch; the definition is in include/sea_current_hip.h): cell c
+        is reserved at layers k and k+1 when a robot standing at c through interval k would come within radius[q] + pad of path
+        q.  knots float64 [P,K+1,2], tstatus int32 [P] or None (all OK; updated like in traj_conflicts), radius float64 [P] or a
+        number, frame = (x_min, y_min, res_x, res_y), select int32 [P] or None (0 = leave this path out).  res int32 [K+1, H,
+        ceil(W/32)] bit words is ORed into (None: a zeroed one) and returned.  Only enqueues."""
+        import torch
+        P, K = knots.shape[0], knots.shape[1] - 1
+        dev = knots.device
+        radius, select = self._per_path(radius, P, torch.float64, dev), self._per_path(select, P, torch.int32, dev)
+        if res is None:
+            res = torch.zeros((K + 1, H, (W + 31) // 32), dtype=torch.int32, device=dev)
+        self._ck(self._l.sc_traj_reserve_batch(self._h, _ptr(knots), _ptr(tstatus), P, K, _ptr(radius), _ptr(select), float(pad), W, H,
+                                               *(float(v) for v in frame), _ptr(res)), "sc_traj_reserve_batch")
+        return res
+
+    def tplan(self, d2, start, goal, res=None, L=None, t_start=None, hold=True, r2=0, frame=None, want_reach=False):
+        """Earliest arrival on the time-expanded grid around reservations (sc_tplan_batch).  d2 int32 [H,W]; start, goal int32 [B]
+        cells; res int32 [L,H,ceil(W/32)] as traj_reserve returned it, or None (nothing reserved; L must be given); t_start int32
+        [B] layers or None = 0; hold: the robot stays at its goal, so it arrives only once the goal is never reserved again.
+        Returns dict(path int32 [B,L] (-1 past len), len, arrive, status int32 [B] (TP_OK, TP_NO_PATH, TP_BAD_ENDPOINT,
+        TP_START_BLOCKED); knots_out float64 [B,L,2] with a frame = (x_min, y_min, res_x, res_y): rows that traj_conflicts takes
+        behind the fleet's; reach int32 [B,L,H,ceil(W/32)] with want_reach, otherwise the layers stay in the context's scratch).
+        One stated earliest-arrival path, not the shortest in metres.  Only enqueues."""
+        import torch
+        H, W = d2.shape
+        B = start.shape[0]
+        L = res.shape[0] if L is None else L
+        out = self._tplan_out(B, L, H, W, d2.device, frame is not None, want_reach)
+        fr = (0.0, 0.0, 1.0, 1.0) if frame is None else tuple(float(v) for v in frame)
+        self._ck(self._l.sc_tplan_batch(self._h, _ptr(d2), W, H, r2, _ptr(res), L, _ptr(start), _ptr(goal), _ptr(t_start), B, int(bool(hold)),
+                                        _ptr(out["path"]), _ptr(out["len"]), _ptr(out["arrive"]), _ptr(out["status"]), _ptr(out.get("knots_out")),
+                                        *fr, _ptr(out.get("reach"))), "sc_tplan_batch")
+        return out
+
+    def fleet_replan(self, knots, tstatus, radius, d2, start, goal, frame, pad, r_new=None, select=None, t_start=None, hold=True, r2=0,
+                     sequential=False, res=None, want_reach=False):
+        """traj_reserve of the selected fleet rows, then tplan around them, in one call (sc_fleet_replan_batch): the fleet is knots
+        / tstatus / radius / select as in traj_reserve (e.g. fleet_schedule's knots_out with select = slot >= 0), the robots are
+        start / goal / t_start as in tplan.  pad: r_new + half the grid's diagonal move keeps a robot of radius r_new clear of
+        every reserved path (see the header).  sequential=False plans all robots against the fleet at once; sequential=True
+        plans robot i, reserves its row (radius r_new[i], the same pad) and goes on to robot i+1: prioritised planning in the
+        caller's order (needs r_new, float64 [B] or a number).  Returns tplan's dict (knots_out always) plus res and tstatus.
+        Only enqueues."""
+        import torch
+        P, K = knots.shape[0], knots.shape[1] - 1
+        H, W = d2.shape
+        B = start.shape[0]
+        dev = knots.device
+        radius, select = self._per_path(radius, P, torch.float64, dev), self._per_path(select, P, torch.int32, dev)
+        r_new = self._per_path(r_new, B, torch.float64, dev)
+        if res is None:
+            res = torch.zeros((K + 1, H, (W + 31) // 32), dtype=torch.int32, device=dev)
+        out = self._tplan_out(B, K + 1, H, W, dev, True, want_reach)
+        self._ck(self._l.sc_fleet_replan_batch(self._h, _ptr(knots), _ptr(tstatus), P, K, _ptr(radius), _ptr(select), float(pad), W, H,
+                                               *(float(v) for v in frame), _ptr(res), _ptr(d2), r2, K + 1, _ptr(start), _ptr(goal), _ptr(t_start),
+                                               B, int(bool(hold)), _ptr(out["path"]), _ptr(out["len"]), _ptr(out["arrive"]), _ptr(out["status"]),
+                                               _ptr(out["knots_out"]), _ptr(out.get("reach")), _ptr(r_new), int(bool(sequential))),
+                 "sc_fleet_replan_batch")
+        out["res"] = res
+        out["tstatus"] = tstatus
+        return out
+
+    def traj_reserve_host(self, knots, tstatus, radius, W, H, frame, pad, select=None, res=None):
+        """Host form of traj_reserve (numpy in, numpy out; sc_traj_reserve_batch_host).  Returns (res uint32 [K+1,H,ceil(W/32)],
+        tstatus): copies, the arguments are not updated in place."""
+        knots = np.ascontiguousarray(knots, dtype=np.float64)
+        P, K = knots.shape[0], knots.shape[1] - 1
+        radius, select = self._per_path(radius, P, np.float64), self._per_path(select, P, np.int32)
+        tstatus = None if tstatus is None else np.array(tstatus, dtype=np.int32)
+        res = np.zeros((K + 1, H, (W + 31) // 32), np.uint32) if res is None else np.array(res, dtype=np.uint32)
+        self._ck(self._l.sc_traj_reserve_batch_host(self._h, _ptr(knots), _ptr(tstatus), P, K, _ptr(radius), _ptr(select), float(pad), W, H,
+                                                    *(float(v) for v in frame), _ptr(res)), "sc_traj_reserve_batch_host")
+        return res, tstatus
+
+    def tplan_host(self, d2, start, goal, res=None, L=None, t_start=None, hold=True, r2=0, frame=None, want_reach=False):
+        """Host form of tplan (numpy in, numpy out; sc_tplan_batch_host)."""
+        d2 = np.ascontiguousarray(d2, dtype=np.int32)
+        H, W = d2.shape
+        start, goal = np.ascontiguousarray(start, dtype=np.int32), np.ascontiguousarray(goal, dtype=np.int32)
+        t_start = None if t_start is None else np.ascontiguousarray(t_start, dtype=np.int32)
+        res = None if res is None else np.ascontiguousarray(res).view(np.uint32)
+        B = start.shape[0]
+        L = res.shape[0] if L is None else L
+        out = self._tplan_out(B, L, H, W, None, frame is not None, want_reach)
+        fr = (0.0, 0.0, 1.0, 1.0) if frame is None else tuple(float(v) for v in frame)
+        self._ck(self._l.sc_tplan_batch_host(self._h, _ptr(d2), W, H, r2, _ptr(res), L, _ptr(start), _ptr(goal), _ptr(t_start), B,
+                                             int(bool(hold)), _ptr(out["path"]), _ptr(out["len"]), _ptr(out["arrive"]), _ptr(out["status"]),
+                                             _ptr(out.get("knots_out")), *fr, _ptr(out.get("reach"))), "sc_tplan_batch_host")
+        return out
+
+    def fleet_replan_host(self, knots, tstatus, radius, d2, start, goal, frame, pad, r_new=None, select=None, t_start=None, hold=True, r2=0,
+                          sequential=False, res=None, want_reach=False):
+        """Host form of fleet_replan (numpy in, numpy out; sc_fleet_replan_batch_host); res and tstatus are copies."""
+        knots = np.ascontiguousarray(knots, dtype=np.float64)
+        d2 = np.ascontiguousarray(d2, dtype=np.int32)
+        P, K = knots.shape[0], knots.shape[1] - 1
+        H, W = d2.shape
+        start, goal = np.ascontiguousarray(start, dtype=np.int32), np.ascontiguousarray(goal, dtype=np.int32)
+        t_start = None if t_start is None else np.ascontiguousarray(t_start, dtype=np.int32)
+        B = start.shape[0]
+        radius, select = self._per_path(radius, P, np.float64), self._per_path(select, P, np.int32)
+        r_new = self._per_path(r_new, B, np.float64)
+        tstatus = None if tstatus is None else np.array(tstatus, dtype=np.int32)
+        res = np.zeros((K + 1, H, (W + 31) // 32), np.uint32) if res is None else np.array(res, dtype=np.uint32)
+        out = self._tplan_out(B, K + 1, H, W, None, True, want_reach)
+        self._ck(self._l.sc_fleet_replan_batch_host(self._h, _ptr(knots), _ptr(tstatus), P, K, _ptr(radius), _ptr(select), float(pad), W, H,
+                                                    *(float(v) for v in frame), _ptr(res), _ptr(d2), r2, K + 1, _ptr(start), _ptr(goal),
+                                                    _ptr(t_start), B, int(bool(hold)), _ptr(out["path"]), _ptr(out["len"]), _ptr(out["arrive"]),
+                                                    _ptr(out["status"]), _ptr(out["knots_out"]), _ptr(out.get("reach")), _ptr(r_new),
+                                                    int(bool(sequential))), "sc_fleet_replan_batch_host")
+        out["res"] = res
+        out["tstatus"] = tstatus
         return out
 
     # ---- robots to goals (sc_field_cost_matrix, sc_assign_batch, sc_fleet_assign_batch) ----

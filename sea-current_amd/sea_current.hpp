@@ -30,6 +30,7 @@
 //         goals, every start to the cheapest of them
 //   (new) fleet_conflicts: who meets whom among the results of smooth_paths_batch, when first, and how close
 //   (new) fleet_schedule: start slots by priority that let the lower-priority path wait until it meets nobody
+//   (new) fleet_replan: the paths no slot was free for, planned again in (cell, tick) around the scheduled ones
 //   (new) planning_space::plan_assigned: one goal per robot, the cheapest such assignment, from fields rooted at the goals
 //
 // Differences that are deliberate: obstacle::closed is initialised (the reference leaves it
@@ -1652,6 +1653,82 @@ inline schedule_result fleet_schedule(const std::vector<smooth_result>& paths, c
     out.delay.resize(P);
     for (int p = 0; p < P; ++p) out.delay[p] = sl[p] >= 0 ? (double)(sl[p] * stride) * dt_c : std::numeric_limits<double>::quiet_NaN();
     for (int v = 0; v < 4; ++v) out.counts[v] = cnt[v];
+    return out;
+}
+
+// ---- (new) re-planning in space-time around the scheduled fleet (sc_fleet_replan_batch_host; the definition is in
+// sea_current_hip.h) -------
+// What fleet_schedule leaves SC_SLOT_UNRESOLVED is planned again on the grid, in (cell, tick), around the paths that did get a
+// slot: paths, radius, delays and flags as given to fleet_schedule, `sched` its result, stride its stride.  The fleet is the
+// paths with slot >= 0, each delayed by its slot; the robots are the unresolved ones, robot p from cell start[p] to cell
+// goal[p] (one entry per path; those of scheduled paths are not read), appearing at the first tick at or after its delay and
+// staying at its goal.  One grid move takes one tick of dt_c.  r_new is the robots' radius; the reservations are padded by
+// r_new plus half the grid's diagonal move, which keeps a robot clear of every scheduled path (see the header).  With
+// sequential (the default) the robots are planned in index order and each one's path is reserved before the next: they also
+// stay clear of each other.  The clock runs `extra_ticks` (default 2 * (W + H)) past the end of the last scheduled path.
+// Per path: status = an sc_tplan_status, or -1 for a path that is not a robot; arrive = the arrival tick (-1 without one);
+// t_start = the tick it appears at; path = the timed cell path, path[p][i] the cell at tick t_start[p] + i (waits repeat a
+// cell).  This is one earliest-arrival path, not the shortest in metres, and it is not smoothed.
+struct replan_result {
+    std::vector<int> status, arrive, t_start;
+    std::vector<std::vector<int>> path;
+    int K = 0;   // the last tick of the clock
+};
+inline replan_result fleet_replan(const std::vector<smooth_result>& paths, const std::vector<double>& radius, const schedule_result& sched,
+                                  const occupancy_grid& grid, const std::vector<int>& start, const std::vector<int>& goal, double r_new,
+                                  const std::vector<double>& delays = {}, const std::vector<int>& flags = {}, double dt_c = 0.1,
+                                  int stride = 1, bool sequential = true, int r2_clear = 0, int extra_ticks = -1,
+                                  gpu_context& ctx = default_context()) {
+    const int P = (int)paths.size();
+    replan_result out;
+    if (P == 0) return out;
+    const packed_timed_paths k = pack_timed_paths("fleet_replan", paths, radius, delays, flags, {}, dt_c);
+    if ((int)sched.slot.size() != P || (int)start.size() != P || (int)goal.size() != P)
+        throw std::invalid_argument("fleet_replan: the schedule, start and goal hold one entry per path");
+    if (stride < 1 || !(std::isfinite(r_new) && r_new >= 0.0)) throw std::invalid_argument("fleet_replan: stride >= 1 and r_new >= 0 expected");
+    if (grid.d2.size() != grid.occ.size() || grid.d2.empty()) throw std::invalid_argument("fleet_replan: the grid's d2 is missing: call edt() first");
+    int max_slot = 0;
+    std::vector<int32_t> sl(sched.slot.begin(), sched.slot.end()), select(P), robots;
+    for (int p = 0; p < P; ++p) {
+        max_slot = std::max(max_slot, (int)sl[p]);
+        select[p] = sl[p] >= 0;
+        if (sl[p] == SC_SLOT_UNRESOLVED) robots.push_back(p);
+    }
+    out.status.assign(P, -1); out.arrive.assign(P, -1); out.t_start.assign(P, 0); out.path.resize(P);
+    const int B = (int)robots.size();
+    const int extra = extra_ticks >= 0 ? extra_ticks : 2 * (grid.W + grid.H);
+    const int K = (int)std::min(std::max(std::ceil(k.end / dt_c), 1.0) + (double)max_slot * stride + (double)extra, 65535.0);
+    out.K = K;
+    if (B == 0) return out;
+    const int L = K + 1, Wq = (grid.W + 31) / 32;
+    std::vector<double> knots((size_t)P * L * 2), shifted((size_t)P * L * 2);
+    std::vector<int32_t> ts(P);
+    ctx.check(sc_traj_knots_batch_host(ctx.get(), k.time.data(), k.pts.data(), k.offsets.data(), k.length.data(), k.status.data(), P,
+                                       delays.empty() ? nullptr : delays.data(), k.flags.empty() ? nullptr : k.flags.data(), 0.0, dt_c, K,
+                                       knots.data(), ts.data()),
+              "sc_traj_knots_batch_host");
+    ctx.check(sc_traj_shift_knots_batch_host(ctx.get(), knots.data(), P, K, sl.data(), stride, shifted.data()), "sc_traj_shift_knots_batch_host");
+    const float ry = (grid.bound_rect.y_max - grid.bound_rect.y_min) / (float)grid.H;
+    const double hyp = std::sqrt((double)grid.resolution * (double)grid.resolution + (double)ry * (double)ry);
+    const double pad = r_new + 0.5 * hyp * (1.0 + std::ldexp(1.0, -20));
+    std::vector<int32_t> s(B), g(B), t0(B), path((size_t)B * L), len(B), arr(B), st(B);
+    for (int i = 0; i < B; ++i) {
+        const int p = robots[i];
+        s[i] = start[p]; g[i] = goal[p];
+        t0[i] = (int)std::min(std::max(std::ceil((delays.empty() ? 0.0 : delays[p]) / dt_c), 0.0), (double)K);
+    }
+    std::vector<double> rn(B, r_new), knots_out((size_t)B * L * 2);
+    std::vector<uint32_t> res((size_t)L * grid.H * Wq, 0u);
+    ctx.check(sc_fleet_replan_batch_host(ctx.get(), shifted.data(), ts.data(), P, K, radius.data(), select.data(), pad, grid.W, grid.H,
+                                         grid.bound_rect.x_min, grid.bound_rect.y_min, grid.resolution, ry, res.data(), grid.d2.data(), r2_clear, L,
+                                         s.data(), g.data(), t0.data(), B, 1, path.data(), len.data(), arr.data(), st.data(), knots_out.data(),
+                                         nullptr, rn.data(), sequential ? 1 : 0),
+              "sc_fleet_replan_batch_host");
+    for (int i = 0; i < B; ++i) {
+        const int p = robots[i];
+        out.status[p] = st[i]; out.arrive[p] = arr[i]; out.t_start[p] = t0[i];
+        out.path[p].assign(path.begin() + (size_t)i * L, path.begin() + (size_t)i * L + len[i]);
+    }
     return out;
 }
 
