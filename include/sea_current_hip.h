@@ -74,7 +74,7 @@ typedef enum {
     SC_K_GATHER = 12,     /* gather of result paths: pack, ncclAllGather, unpack */
     SC_K_WAYPOINTS = 13,  /* A* cell paths -> line-of-sight waypoints, one wavefront per path */
     SC_K_SMOOTH = 14,     /* sc_smooth_paths_batch's own kernels (checks, scans, compaction, TOPP-RA inputs, ang_vel),
-                           * sc_cells_to_points_batch, the speed limits and the path conflicts (sc_traj_*, sc_fleet_conflicts_batch);
+                           * sc_cells_to_points_batch, the speed limits, the curve check and repair (sc_curve_*) and the path conflicts (sc_traj_*, sc_fleet_conflicts_batch);
                            * the library kernels it runs keep their own ids */
     SC_K_COUNT = 15
 } sc_kernel_id;
@@ -581,7 +581,9 @@ typedef enum {
     SC_SMOOTH_NONFINITE = 2,
     SC_SMOOTH_TOPPRA_FAILED = 3,
     SC_SMOOTH_TRUNCATED = 4,
-    SC_SMOOTH_EMPTY_SEGMENT = 5
+    SC_SMOOTH_EMPTY_SEGMENT = 5,
+    SC_SMOOTH_COLLIDES = 6 /* sc_curve_clear_batch, sc_smooth_paths_clear_batch: a leg still hits the grid with the tangents at
+                            * its ends shrunk to 2^-max_level; shrinking cannot fix it (the straight leg is not clear either) */
 } sc_smooth_status;
 int sc_smooth_paths_batch(sc_ctx* ctx, const float* path, const int32_t* npts, int P, int n_max, const double* limits, float start_angle,
                           const float* lines, int nlines, float dt, int N, int nsub, int64_t sample_capacity, float* ctrl,
@@ -609,7 +611,7 @@ int sc_cells_to_points_batch(sc_ctx* ctx, const int32_t* wp, const int32_t* n_wp
  * The reference's gen_vel_prof takes a vel_lim_func, a limit that varies along the path (examples/test.cpp:194-209);
  * sc_toppra_hermite_batch takes it as vlim_per_stage = 1.  These calls compute such a limit for curves that have legs
  * and arclength tables, and sc_smooth_paths_limited_batch puts it between the arclength and TOPP-RA of
- * sc_smooth_paths_batch.  Curves are not moved or shrunk: only the speed is limited.
+ * sc_smooth_paths_batch.  Curves are not moved or shrunk: only the speed is limited (sc_curve_clear_batch below shrinks tangents).
  *
  * Per path: ctrl float [ns][4][2] (its legs), cum float [ns][nsub+1] (sc_bezier_arclength_batch), seg_len[j] = cum[j][nsub],
  * AL = arclength (float), limits fp64 (vel_min, vel_max, acc_min, acc_max), dyn fp64 [4] = (omega_max, alat_max, clear_floor,
@@ -679,6 +681,102 @@ int sc_smooth_paths_limited_batch_host(sc_ctx* ctx, const float* path, const int
                                        float* acc, float* pts, float* curvature, float* ang_vel, float* tpar, int32_t* seg,
                                        const double* dyn, int J, const int32_t* d2, int W, int H, float x_min, float y_min, float res_x,
                                        float res_y, double* vmax_stage, float* min_clear);
+
+/* ---- smoothed curves against the grid: check the cells a curve visits, shrink tangents where it hits --------------
+ * A* cell paths and their line-of-sight waypoints never touch a cell with d2 < max(r2_clear, 1).  The Bezier legs that
+ * sc_bezier_from_path_batch lays through those waypoints swing wide on the outside of turns and may enter such cells.
+ * The reference's shrink_tangent tests the stretch Wp +- T against polygon edges, never the curve; on a grid these calls
+ * test the curve itself against the distance map and shrink the tangents of legs that hit.
+ *
+ * Definition.  A leg is its float32 control polygon P0..P3 [4][2]; the grid is d2 int32 [H][W] in the frame (W, H, x_min,
+ * y_min, res_x, res_y) of sc_cells_to_points_batch; r2c = max(r2_clear, 1), the traversability rule of A*.  All arithmetic
+ * is fp64 on the float32 inputs, without contraction.
+ *   Samples of a leg: h = min(res_x, res_y); Lp = |P1-P0| + |P2-P1| + |P3-P2|, each term sqrt(dx*dx + dy*dy) (correctly
+ *     rounded), summed in that order; n = clamp(ceil(6 * Lp / h), 1, 2^20), n = 1 when Lp is not finite; t_k = (double)k / n,
+ *     k = 0..n; the point is B(t) = r r r P0 + 3 r r t P1 + 3 r t t P2 + t t t P3, r = 1 - t, products and sums from the left.
+ *     |B'| <= 3 max|P_{j+1} - P_j| <= 3 Lp, so consecutive samples are at most h / 2 apart along the curve and every point of
+ *     the curve lies within h / 4 of a sample.
+ *   Cell of a point: fx = (x - x_min) / res_x, ix = floor(fx), the same in y; the sample's value is d2[iy][ix], and 0 when fx
+ *     or fy is not finite or the cell is outside 0..W-1 x 0..H-1: leaving the map is a hit.
+ *   leg_min = the minimum of the values of the leg's samples.  A leg HITS iff leg_min < r2c, or n had to be clamped at 2^20,
+ *     or Lp is not finite.
+ *   First hit of a path: hit_leg = the lowest hitting leg, hit_t = (float)t_k of the lowest hitting sample k on it (0 when
+ *     the leg hits without a hitting sample); both -1 when no leg hits.
+ * Guarantee: no sample of a leg that does not hit lies in a blocked cell or outside the map, and no point of the curve is
+ * further than a quarter of a cell from a sample.  It is a sampled test of cell membership, NOT a swept-disc proof: between
+ * two samples the curve may clip the corner of a blocked cell by less than that quarter cell, and a robot's extent enters
+ * only through r2_clear.
+ *   Repair: waypoint j of a path with ns legs (j = 0..ns) has a level lv[j] in 0..max_level (1 <= max_level <=
+ *     SC_CURVE_MAX_LEVEL) and the scale s_j = 2^-lv[j].  The control points are a function of the level-0 float32 control
+ *     points only: leg j keeps P0 and P3; with lv[j] = 0 it keeps P1's bits, else P1 = (float)(P0 + s_j * (P1_0 - P0)); with
+ *     lv[j+1] = 0 it keeps P2's bits, else P2 = (float)(P3 - s_{j+1} * (P3 - P2_0)), in fp64 on the widened floats.  Both legs
+ *     at a waypoint share its level, so the tangent direction stays continuous.  Rounds r = 0, 1, ...: evaluate the legs at
+ *     the current levels; if none hits the path is done with rounds = r; otherwise every waypoint at an end of a hitting leg
+ *     gets lv += 1, saturating at max_level; if that changes no level the path is unresolved (rounds = r, the control points
+ *     of this last round are kept).  The rule is Jacobi: all hits of a round are decided before any level changes, so no
+ *     result depends on the order of execution.  At most max_level * (ns + 1) + 1 rounds occur.
+ * Waypoints of sc_path_waypoints_batch under the same d2, r2_clear and frame are EXPECTED to resolve, not guaranteed to:
+ * their straight legs lie in traversable cells of the supercover, and the curve tends to the straight leg as the levels
+ * rise; float32 cell centres and exact start and goal points can break this where a leg grazes a corner, and
+ * SC_SMOOTH_COLLIDES reports those.  A corridor of d2 < r2c (the straight legs are not clear either) cannot be fixed by
+ * shrinking.
+ *
+ * Layout of all three calls: the packed legs of sc_smooth_paths_batch, ctrl float [S][4][2], seg_off int32 [P+1] read on the
+ * device; status int32 [P] may be NULL (all SC_SMOOTH_OK).  Device pointers; each call enqueues one kernel on the context's
+ * stream (one 256-thread workgroup per path, timed under SC_K_SMOOTH): no host synchronisation, no device-to-host copy.
+ * Errors: SC_ERR_INVALID for NULL pointers, P outside 1..SC_SMOOTH_MAX_PATHS, d2 NULL, r2_clear < 0, W or H outside
+ * 1..SC_MAX_DIM, a frame that is not finite with res > 0, max_level outside 1..SC_CURVE_MAX_LEVEL.
+ *
+ * sc_curve_clearance_batch: the check alone.  leg_min_d2 int32 [S], path_min_d2 int32 [P] (the minimum over the path's legs,
+ * INT32_MAX for a path without legs), hit_legs int32 [P] (how many legs hit), hit_leg int32 [P], hit_t float [P]; each may
+ * be NULL, but not all.  A path whose status is not SC_SMOOTH_OK is skipped: path_min_d2 = 0, hit_legs = 0, hit_leg = -1,
+ * hit_t = -1, its legs' entries of leg_min_d2 untouched. */
+#define SC_CURVE_MAX_LEVEL 30
+#define SC_CURVE_MAX_LEGS 1024 /* legs of one path sc_curve_clear_batch takes: 39 B of LDS per leg, under 40 KiB, four workgroups per CU */
+int sc_curve_clearance_batch(sc_ctx* ctx, const float* ctrl, const int32_t* seg_off, const int32_t* status, int P, const int32_t* d2,
+                             int W, int H, float x_min, float y_min, float res_x, float res_y, int32_t r2_clear, int32_t* leg_min_d2,
+                             int32_t* path_min_d2, int32_t* hit_legs, int32_t* hit_leg, float* hit_t);
+/* host pointers; S = seg_off[P] legs (seg_off must start at or above 0 and not decrease) */
+int sc_curve_clearance_batch_host(sc_ctx* ctx, const float* ctrl, const int32_t* seg_off, const int32_t* status, int P,
+                                  const int32_t* d2, int W, int H, float x_min, float y_min, float res_x, float res_y, int32_t r2_clear,
+                                  int32_t* leg_min_d2, int32_t* path_min_d2, int32_t* hit_legs, int32_t* hit_leg, float* hit_t);
+/* sc_curve_clear_batch: the repair, every round inside the one kernel.  ctrl_out float [S][4][2] may be ctrl_in; level uint8
+ * [S + P], waypoint j of path p at seg_off[p] + p + j; rounds int32 [P]; leg_min_d2 int32 [S] of the last round; status_out
+ * int32 [P] (may be status) = status[p] when that is not SC_SMOOTH_OK, else SC_SMOOTH_COLLIDES for an unresolved path, else
+ * SC_SMOOTH_OK.  level, rounds, leg_min_d2 and status_out may each be NULL.  With no hitting leg ctrl_out is ctrl_in bit for
+ * bit and every level is 0.  A skipped path keeps its control points, gets levels 0 and rounds 0, and leaves its legs'
+ * entries of leg_min_d2 untouched.  A path may have SC_CURVE_MAX_LEGS legs at the most (the kernel's LDS): the device form,
+ * which cannot see the counts, treats a longer one as skipped with SC_SMOOTH_BAD_INPUT; the host form returns
+ * SC_ERR_INVALID. */
+int sc_curve_clear_batch(sc_ctx* ctx, const float* ctrl_in, const int32_t* seg_off, const int32_t* status, int P, const int32_t* d2,
+                         int W, int H, float x_min, float y_min, float res_x, float res_y, int32_t r2_clear, int max_level,
+                         float* ctrl_out, uint8_t* level, int32_t* rounds, int32_t* leg_min_d2, int32_t* status_out);
+int sc_curve_clear_batch_host(sc_ctx* ctx, const float* ctrl_in, const int32_t* seg_off, const int32_t* status, int P, const int32_t* d2,
+                              int W, int H, float x_min, float y_min, float res_x, float res_y, int32_t r2_clear, int max_level,
+                              float* ctrl_out, uint8_t* level, int32_t* rounds, int32_t* leg_min_d2, int32_t* status_out);
+/* sc_smooth_paths_limited_batch with the repair between the compaction of the legs and the arclength: the same arguments in
+ * the same order, then r2_clear, max_level and three more outputs, level uint8 [P*(n_max-1) + P], leg_min_d2 int32
+ * [P*(n_max-1)] (both in the layout above) and rounds int32 [P], each may be NULL.  The arclength, the speed limits, TOPP-RA
+ * and the resample all see the repaired curve, and ctrl holds it.  It builds on the limited call on purpose: a tangent
+ * shrunk by 2^-k is a tight corner, and omega_max / alat_max are what slow the robot down there.  It needs a grid: d2 NULL is
+ * SC_ERR_INVALID, as is n_max - 1 > SC_CURVE_MAX_LEGS.  Status, first that applies: SC_SMOOTH_BAD_INPUT, SC_SMOOTH_NONFINITE,
+ * SC_SMOOTH_COLLIDES (the path keeps its legs, those of its last round, and has length 0), then the rest as before.  When no
+ * leg of the batch hits, every output is bit-identical to sc_smooth_paths_limited_batch on the same inputs.  Scratch grows
+ * by P int32. */
+int sc_smooth_paths_clear_batch(sc_ctx* ctx, const float* path, const int32_t* npts, int P, int n_max, const double* limits,
+                                float start_angle, const float* lines, int nlines, float dt, int N, int nsub, int64_t sample_capacity,
+                                float* ctrl, int32_t* seg_off, float* arclength, int32_t* length, int32_t* offsets, int32_t* status,
+                                int64_t* needed, double* time, float* pos, float* vel, float* acc, float* pts, float* curvature,
+                                float* ang_vel, float* tpar, int32_t* seg, const double* dyn, int J, const int32_t* d2, int W, int H,
+                                float x_min, float y_min, float res_x, float res_y, double* vmax_stage, float* min_clear, int32_t r2_clear,
+                                int max_level, uint8_t* level, int32_t* leg_min_d2, int32_t* rounds);
+int sc_smooth_paths_clear_batch_host(sc_ctx* ctx, const float* path, const int32_t* npts, int P, int n_max, const double* limits,
+                                     float start_angle, const float* lines, int nlines, float dt, int N, int nsub, int64_t sample_capacity,
+                                     float* ctrl, int32_t* seg_off, float* arclength, int32_t* length, int32_t* offsets, int32_t* status,
+                                     int64_t* needed, double* time, float* pos, float* vel, float* acc, float* pts, float* curvature,
+                                     float* ang_vel, float* tpar, int32_t* seg, const double* dyn, int J, const int32_t* d2, int W, int H,
+                                     float x_min, float y_min, float res_x, float res_y, double* vmax_stage, float* min_clear,
+                                     int32_t r2_clear, int max_level, uint8_t* level, int32_t* leg_min_d2, int32_t* rounds);
 
 /* ---- conflicts between timed paths: who meets whom, when, how close --------------------------------------------
  * sc_smooth_paths_batch leaves P timed paths on the device; these calls compare them with each other.  Detection only:

@@ -71,7 +71,7 @@ struct __attribute__((visibility("hidden"))) sc_ctx {
     sc_scratch sm_ctrl;     // smoothing: float [P][n_max-1][4][2] control points of from_path before compaction
     sc_scratch sm_cum;      // smoothing: float [P (n_max-1)][nsub+1] arclength tables | float [P (n_max-1)] segment lengths
     sc_scratch sm_tp;       // smoothing: fp64 TOPP-RA inputs p0 p1 v0 v1 vlo vhi alo ahi [P] | K [P][N+1][2] x t [P][N+1] u [P][N]
-    sc_scratch sm_int;      // smoothing: int32 npts [P] | TOPP-RA status [P] | resample status [P] | resample offsets [P+1]
+    sc_scratch sm_int;      // smoothing: int32 npts [P] | TOPP-RA status [P] | resample status [P] | resample offsets [P+1] | repair status [P] (sc_smooth_paths_clear_batch)
     sc_scratch sm_smp;      // smoothing: float vel | curvature [capacity] when the caller wants ang_vel without them
     sc_scratch sm_vlim;     // smoothing with per-stage limits: fp64 vlo [P][N+1] | vhi [P][N+1]
     sc_scratch occ_prep;    // polygon occupancy: float4 box [n_obs] | int2 cell-row range [n_obs] of every obstacle
@@ -192,6 +192,11 @@ int sc_launch_speed_limits(sc_ctx* ctx, const float* ctrl, const float* cum, con
 int sc_speed_args_ok(int J, const double* dyn, const sc_speed_frame& fr);
 // the contract of dyn [P][4] on the host (the _host forms refuse what the kernel would mark SC_SMOOTH_BAD_INPUT)
 int sc_speed_dyn_ok(const double* dyn, int P);
+// curve.hip: the repair of curves that hit the grid (d2 required); status_out may be status, ctrl_out may be ctrl_in
+int sc_curve_grid_ok(const sc_speed_frame& fr, int32_t r2_clear);
+int sc_launch_curve_clear(sc_ctx* ctx, const float* ctrl_in, float* ctrl_out, const int32_t* seg_off, const int32_t* status, int P,
+                          const sc_speed_frame& fr, int32_t r2_clear, int max_level, uint8_t* level, int32_t* rounds, int32_t* leg_min,
+                          int32_t* status_out);
 int sc_launch_toppra_sample_packed(sc_ctx* ctx, int P, int dof, int N, const double* p0, const double* p1, const double* v0,
                                    const double* v1, const double* x, const double* t, double dt, const int32_t* offsets,
                                    const int32_t* plen, const int32_t* skip, float* pos, float* vel, float* acc, double* times);

@@ -193,17 +193,43 @@ struct sm_limited {
     float* min_clear;
 };
 
-// the sequence of both entry points; lt NULL: one constant limit per path
+// what sc_smooth_paths_clear_batch adds to the limited sequence: the repair of legs that hit the grid, between the
+// compaction and the arclength
+struct sm_clear {
+    int32_t r2_clear;
+    int max_level;
+    uint8_t* level;
+    int32_t *leg_min, *rounds;
+};
+
+// the repair's verdict enters after NONFINITE has been decided: a COLLIDES path gets a harmless TOPP-RA problem
+__global__ void __launch_bounds__(256)
+smooth_collides_kernel(const int32_t* __restrict__ cstat, int P, int32_t* __restrict__ status, double* __restrict__ tp) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= P || status[p] != SC_SMOOTH_OK || cstat[p] != SC_SMOOTH_COLLIDES) return;
+    status[p] = SC_SMOOTH_COLLIDES;
+    tp[(size_t)P + p] = 1.0;
+    tp[(size_t)4 * P + p] = -1.0;
+    tp[(size_t)5 * P + p] = 1.0;
+    tp[(size_t)6 * P + p] = -1.0;
+    tp[(size_t)7 * P + p] = 1.0;
+}
+
+// the sequence of the entry points; lt NULL: one constant limit per path; cl (only with lt and its grid): the repair
 static int smooth_run(sc_ctx* ctx, const float* path, const int32_t* npts, int P, int n_max, const double* limits, float start_angle,
                       const float* lines, int nlines, float dt, int N, int nsub, int64_t sample_capacity, float* ctrl, int32_t* seg_off,
                       float* arclength, int32_t* length, int32_t* offsets, int32_t* status, int64_t* needed, double* time, float* pos,
-                      float* vel, float* acc, float* pts, float* curvature, float* ang_vel, float* tpar, int32_t* seg, const sm_limited* lt) {
+                      float* vel, float* acc, float* pts, float* curvature, float* ang_vel, float* tpar, int32_t* seg, const sm_limited* lt,
+                      const sm_clear* cl = nullptr) {
     if (!ctx || !path || !npts || !limits || !ctrl || !seg_off || !arclength || !length || !offsets || !status || !needed || !pos || !pts ||
         P <= 0 || P > SC_SMOOTH_MAX_PATHS || n_max < 2 || (long long)P * (n_max - 1) > INT32_MAX / 8 || nlines < 0 || (nlines > 0 && !lines) ||
         !(dt > 0.f) || !isfinite(dt) || N <= 0 || nsub <= 0 || nsub > SC_RESAMPLE_MAX_NSUB || sample_capacity < 0 ||
         sample_capacity > INT32_MAX)
         return SC_ERR_INVALID;
     if (lt && (!sc_speed_args_ok(lt->J, lt->dyn, lt->fr) || (long long)P * ((long long)N + 1) > INT32_MAX)) return SC_ERR_INVALID;
+    if (cl && (!lt || !sc_curve_grid_ok(lt->fr, cl->r2_clear) || cl->max_level < 1 || cl->max_level > SC_CURVE_MAX_LEVEL ||
+               n_max - 1 > SC_CURVE_MAX_LEGS))
+        return SC_ERR_INVALID;
     SC_HIP(ctx, hipSetDevice(ctx->device));
     const int Smax = P * (n_max - 1);
     const long long cap = sample_capacity;
@@ -212,7 +238,7 @@ static int smooth_run(sc_ctx* ctx, const float* path, const int32_t* npts, int P
     const size_t tp_in = (size_t)8 * P, oK = tp_in, ox = oK + (size_t)P * (N + 1) * 2, ot = ox + (size_t)P * (N + 1),
                  ou = ot + (size_t)P * (N + 1), tp_words = ou + (size_t)P * N;
     if (r == SC_OK) r = sc_scratch_reserve(ctx, &ctx->sm_tp, tp_words * 8);
-    if (r == SC_OK) r = sc_scratch_reserve(ctx, &ctx->sm_int, (size_t)(4 * P + 1) * 4);
+    if (r == SC_OK) r = sc_scratch_reserve(ctx, &ctx->sm_int, (size_t)((cl ? 5 : 4) * P + 1) * 4);
     const bool need_vel = ang_vel && !vel, need_curv = ang_vel && !curvature;
     if (r == SC_OK && (need_vel || need_curv)) r = sc_scratch_reserve(ctx, &ctx->sm_smp, (size_t)2 * (cap > 0 ? cap : 1) * 4);
     if (r == SC_OK && lt) r = sc_scratch_reserve(ctx, &ctx->sm_vlim, (size_t)2 * P * (N + 1) * 8);
@@ -222,7 +248,7 @@ static int smooth_run(sc_ctx* ctx, const float* path, const int32_t* npts, int P
     float* seg_len = (float*)((char*)ctx->sm_cum.p + al256((size_t)Smax * (nsub + 1) * 4));
     double* tp = (double*)ctx->sm_tp.p;
     int32_t* npts_eff = (int32_t*)ctx->sm_int.p;
-    int32_t *tstat = npts_eff + P, *rstat = tstat + P, *roff = rstat + P;
+    int32_t *tstat = npts_eff + P, *rstat = tstat + P, *roff = rstat + P, *cstat = roff + P + 1;
     float* vel_o = need_vel ? (float*)ctx->sm_smp.p : vel;
     float* curv_o = need_curv ? (float*)ctx->sm_smp.p + (cap > 0 ? cap : 1) : curvature;
 
@@ -238,11 +264,17 @@ static int smooth_run(sc_ctx* ctx, const float* path, const int32_t* npts, int P
                        (const int32_t*)seg_off, P, n_max, ctrl);
     sc_time_end(ctx, tk);
     SC_HIP(ctx, hipGetLastError());
+    if (cl) {   // in place; its verdict waits in cstat until NONFINITE has been decided on the repaired legs
+        r = sc_launch_curve_clear(ctx, ctrl, ctrl, seg_off, status, P, lt->fr, cl->r2_clear, cl->max_level, cl->level, cl->rounds, cl->leg_min,
+                                  cstat);
+        if (r != SC_OK) return r;
+    }
     r = sc_launch_arclength(ctx, ctrl, Smax, nsub, cum, seg_len, seg_off + P);
     if (r != SC_OK) return r;
     tk = sc_time_begin(ctx, SC_K_SMOOTH);
     hipLaunchKernelGGL(smooth_toppra_inputs_kernel, dim3((P + 3) / 4), dim3(256), 0, ctx->stream, (const float*)ctrl, (const float*)seg_len,
                        (const int32_t*)seg_off, limits, P, status, arclength, tp);
+    if (cl) hipLaunchKernelGGL(smooth_collides_kernel, dim3((P + 255) / 256), dim3(256), 0, ctx->stream, (const int32_t*)cstat, P, status, tp);
     sc_time_end(ctx, tk);
     SC_HIP(ctx, hipGetLastError());
     const double *p0 = tp, *p1 = tp + P, *v0 = tp + 2 * (size_t)P, *v1 = tp + 3 * (size_t)P;
@@ -302,12 +334,25 @@ extern "C" int sc_smooth_paths_limited_batch(sc_ctx* ctx, const float* path, con
                       length, offsets, status, needed, time, pos, vel, acc, pts, curvature, ang_vel, tpar, seg, &lt);
 }
 
-// the host form of both; lt (host pointers) NULL: sc_smooth_paths_batch_host
+extern "C" int sc_smooth_paths_clear_batch(sc_ctx* ctx, const float* path, const int32_t* npts, int P, int n_max, const double* limits,
+                                           float start_angle, const float* lines, int nlines, float dt, int N, int nsub, int64_t sample_capacity,
+                                           float* ctrl, int32_t* seg_off, float* arclength, int32_t* length, int32_t* offsets, int32_t* status,
+                                           int64_t* needed, double* time, float* pos, float* vel, float* acc, float* pts, float* curvature,
+                                           float* ang_vel, float* tpar, int32_t* seg, const double* dyn, int J, const int32_t* d2, int W, int H,
+                                           float x_min, float y_min, float res_x, float res_y, double* vmax_stage, float* min_clear,
+                                           int32_t r2_clear, int max_level, uint8_t* level, int32_t* leg_min_d2, int32_t* rounds) {
+    const sm_limited lt{dyn, J, {d2, W, H, x_min, y_min, res_x, res_y}, vmax_stage, min_clear};
+    const sm_clear cl{r2_clear, max_level, level, leg_min_d2, rounds};
+    return smooth_run(ctx, path, npts, P, n_max, limits, start_angle, lines, nlines, dt, N, nsub, sample_capacity, ctrl, seg_off, arclength,
+                      length, offsets, status, needed, time, pos, vel, acc, pts, curvature, ang_vel, tpar, seg, &lt, &cl);
+}
+
+// the host form of all three; lt (host pointers) NULL: sc_smooth_paths_batch_host; cl (host pointers) only with lt
 static int smooth_run_host(sc_ctx* ctx, const float* path, const int32_t* npts, int P, int n_max, const double* limits, float start_angle,
                            const float* lines, int nlines, float dt, int N, int nsub, int64_t sample_capacity, float* ctrl,
                            int32_t* seg_off, float* arclength, int32_t* length, int32_t* offsets, int32_t* status, int64_t* needed,
                            double* time, float* pos, float* vel, float* acc, float* pts, float* curvature, float* ang_vel, float* tpar,
-                           int32_t* seg, const sm_limited* lt) {
+                           int32_t* seg, const sm_limited* lt, const sm_clear* cl = nullptr) {
     if (!ctx || !path || !npts || !limits || !ctrl || !seg_off || !arclength || !length || !offsets || !status || !needed || !pos || !pts ||
         P <= 0 || P > SC_SMOOTH_MAX_PATHS || n_max < 2 || (long long)P * (n_max - 1) > INT32_MAX / 8 || nlines < 0 || (nlines > 0 && !lines) ||
         sample_capacity < 0 || sample_capacity > INT32_MAX)
@@ -315,6 +360,7 @@ static int smooth_run_host(sc_ctx* ctx, const float* path, const int32_t* npts, 
     if (lt && (N <= 0 || (long long)P * ((long long)N + 1) > INT32_MAX || !sc_speed_args_ok(lt->J, lt->dyn, lt->fr) ||
                !sc_speed_dyn_ok(lt->dyn, P)))
         return SC_ERR_INVALID;
+    if (cl && (!lt || !lt->fr.d2)) return SC_ERR_INVALID;   // smooth_run checks the rest
     SC_HIP(ctx, hipSetDevice(ctx->device));
     const size_t S = (size_t)P * (n_max - 1), M = sample_capacity > 0 ? (size_t)sample_capacity : 1, pb = (size_t)P * 4;
     sc_stage st(ctx);
@@ -330,6 +376,9 @@ static int smooth_run_host(sc_ctx* ctx, const float* path, const int32_t* npts, 
     auto smp = [&](const void* h, size_t elem) { return st.out(nullptr, h ? M * elem : 0); };
     const int o_time = smp(time, 8), o_pos = smp(pos, 4), o_vel = smp(vel, 4), o_acc = smp(acc, 4), o_pts = smp(pts, 8), o_cv = smp(curvature, 4),
               o_ang = smp(ang_vel, 4), o_tpar = smp(tpar, 4), o_seg = smp(seg, 4);
+    // the repair's outputs: per leg and waypoint, downloaded once the counts are known
+    const int o_lv = st.out(nullptr, cl && cl->level ? S + P : 0), o_lm = st.out(nullptr, cl && cl->leg_min ? S * 4 : 0),
+              o_rd = st.out(cl ? cl->rounds : nullptr, cl && cl->rounds ? pb : 0);
     int r = st.upload();
     sm_limited dl{};
     if (lt) {
@@ -339,6 +388,13 @@ static int smooth_run_host(sc_ctx* ctx, const float* path, const int32_t* npts, 
         dl.vmax_stage = lt->vmax_stage ? st.dev<double>(o_vs) : nullptr;
         dl.min_clear = lt->min_clear ? st.dev<float>(o_mc) : nullptr;
     }
+    sm_clear dc{};
+    if (cl) {
+        dc = *cl;
+        dc.level = cl->level ? st.dev<uint8_t>(o_lv) : nullptr;
+        dc.leg_min = cl->leg_min ? st.dev<int32_t>(o_lm) : nullptr;
+        dc.rounds = cl->rounds ? st.dev<int32_t>(o_rd) : nullptr;
+    }
     if (r == SC_OK)
         r = smooth_run(ctx, st.dev<const float>(i_path), st.dev<const int32_t>(i_npts), P, n_max, st.dev<const double>(i_lim), start_angle,
                                   nlines > 0 ? st.dev<const float>(i_l) : nullptr, nlines, dt, N, nsub, sample_capacity, st.dev<float>(o_ctrl),
@@ -346,7 +402,8 @@ static int smooth_run_host(sc_ctx* ctx, const float* path, const int32_t* npts, 
                                   st.dev<int64_t>(o_need), time ? st.dev<double>(o_time) : nullptr, st.dev<float>(o_pos),
                                   vel ? st.dev<float>(o_vel) : nullptr, acc ? st.dev<float>(o_acc) : nullptr, st.dev<float>(o_pts),
                                   curvature ? st.dev<float>(o_cv) : nullptr, ang_vel ? st.dev<float>(o_ang) : nullptr,
-                                  tpar ? st.dev<float>(o_tpar) : nullptr, seg ? st.dev<int32_t>(o_seg) : nullptr, lt ? &dl : nullptr);
+                                  tpar ? st.dev<float>(o_tpar) : nullptr, seg ? st.dev<int32_t>(o_seg) : nullptr, lt ? &dl : nullptr,
+                                  cl ? &dc : nullptr);
     r = st.finish(r);
     if (r != SC_OK) return r;
     // the samples written: up to the first truncated path
@@ -358,6 +415,7 @@ static int smooth_run_host(sc_ctx* ctx, const float* path, const int32_t* npts, 
     st.back(o_time, time, Mw * 8); st.back(o_pos, pos, Mw * 4); st.back(o_vel, vel, Mw * 4); st.back(o_acc, acc, Mw * 4);
     st.back(o_pts, pts, Mw * 8); st.back(o_cv, curvature, Mw * 4); st.back(o_ang, ang_vel, Mw * 4); st.back(o_tpar, tpar, Mw * 4);
     st.back(o_seg, seg, Mw * 4);
+    if (cl) { st.back(o_lv, cl->level, (size_t)seg_off[P] + P); st.back(o_lm, cl->leg_min, (size_t)seg_off[P] * 4); }
     return st.finish(SC_OK);
 }
 
@@ -380,6 +438,20 @@ extern "C" int sc_smooth_paths_limited_batch_host(sc_ctx* ctx, const float* path
     const sm_limited lt{dyn, J, {d2, W, H, x_min, y_min, res_x, res_y}, vmax_stage, min_clear};
     return smooth_run_host(ctx, path, npts, P, n_max, limits, start_angle, lines, nlines, dt, N, nsub, sample_capacity, ctrl, seg_off,
                            arclength, length, offsets, status, needed, time, pos, vel, acc, pts, curvature, ang_vel, tpar, seg, &lt);
+}
+
+extern "C" int sc_smooth_paths_clear_batch_host(sc_ctx* ctx, const float* path, const int32_t* npts, int P, int n_max, const double* limits,
+                                                float start_angle, const float* lines, int nlines, float dt, int N, int nsub,
+                                                int64_t sample_capacity, float* ctrl, int32_t* seg_off, float* arclength, int32_t* length,
+                                                int32_t* offsets, int32_t* status, int64_t* needed, double* time, float* pos, float* vel,
+                                                float* acc, float* pts, float* curvature, float* ang_vel, float* tpar, int32_t* seg,
+                                                const double* dyn, int J, const int32_t* d2, int W, int H, float x_min, float y_min,
+                                                float res_x, float res_y, double* vmax_stage, float* min_clear, int32_t r2_clear,
+                                                int max_level, uint8_t* level, int32_t* leg_min_d2, int32_t* rounds) {
+    const sm_limited lt{dyn, J, {d2, W, H, x_min, y_min, res_x, res_y}, vmax_stage, min_clear};
+    const sm_clear cl{r2_clear, max_level, level, leg_min_d2, rounds};
+    return smooth_run_host(ctx, path, npts, P, n_max, limits, start_angle, lines, nlines, dt, N, nsub, sample_capacity, ctrl, seg_off,
+                           arclength, length, offsets, status, needed, time, pos, vel, acc, pts, curvature, ang_vel, tpar, seg, &lt, &cl);
 }
 
 // cells of sc_path_waypoints_batch -> float points (occupancy_grid::centre_of), one thread per (path, point)

@@ -25,6 +25,8 @@ K_EDT_COLBITS, K_EDT_BAND, K_MOVES, K_ASTAR, K_TOPPRA, K_TOPPRA_SAMPLE, K_BEZIER
 K_WAYPOINTS = 13
 K_SMOOTH = 14
 SMOOTH_OK, SMOOTH_BAD_INPUT, SMOOTH_NONFINITE, SMOOTH_TOPPRA_FAILED, SMOOTH_TRUNCATED, SMOOTH_EMPTY_SEGMENT = range(6)
+SMOOTH_COLLIDES = 6
+CURVE_MAX_LEGS, CURVE_MAX_LEVEL = 1024, 30
 TRAJ_OK, TRAJ_SKIPPED, TRAJ_BAD = range(3)
 TRAJ_MAX_TICKS = 65535
 SLOT_UNRESOLVED, SLOT_NOT_OK, SLOT_UNNAMED = -1, -2, -3
@@ -132,6 +134,14 @@ _SIGNATURES = {
                                       [_vp, _i, _vp, _i, _i] + [C.c_float] * 4 + [_vp, _vp]),
     "sc_smooth_paths_limited_batch_host": (_i, [_vp, _vp, _vp, _i, _i, _vp, C.c_float, _vp, _i, C.c_float, _i, _i, C.c_int64] + [_vp] * 16 +
                                            [_vp, _i, _vp, _i, _i] + [C.c_float] * 4 + [_vp, _vp]),
+    "sc_curve_clearance_batch": (_i, [_vp] * 4 + [_i, _vp, _i, _i] + [C.c_float] * 4 + [C.c_int32] + [_vp] * 5),
+    "sc_curve_clearance_batch_host": (_i, [_vp] * 4 + [_i, _vp, _i, _i] + [C.c_float] * 4 + [C.c_int32] + [_vp] * 5),
+    "sc_curve_clear_batch": (_i, [_vp] * 4 + [_i, _vp, _i, _i] + [C.c_float] * 4 + [C.c_int32, _i] + [_vp] * 5),
+    "sc_curve_clear_batch_host": (_i, [_vp] * 4 + [_i, _vp, _i, _i] + [C.c_float] * 4 + [C.c_int32, _i] + [_vp] * 5),
+    "sc_smooth_paths_clear_batch": (_i, [_vp, _vp, _vp, _i, _i, _vp, C.c_float, _vp, _i, C.c_float, _i, _i, C.c_int64] + [_vp] * 16 +
+                                    [_vp, _i, _vp, _i, _i] + [C.c_float] * 4 + [_vp, _vp] + [C.c_int32, _i] + [_vp] * 3),
+    "sc_smooth_paths_clear_batch_host": (_i, [_vp, _vp, _vp, _i, _i, _vp, C.c_float, _vp, _i, C.c_float, _i, _i, C.c_int64] + [_vp] * 16 +
+                                         [_vp, _i, _vp, _i, _i] + [C.c_float] * 4 + [_vp, _vp] + [C.c_int32, _i] + [_vp] * 3),
     "sc_traj_knots_batch": (_i, [_vp] * 6 + [_i, _vp, _vp, _d, _d, _i, _vp, _vp]),
     "sc_traj_knots_batch_host": (_i, [_vp] * 6 + [_i, _vp, _vp, _d, _d, _i, _vp, _vp]),
     "sc_traj_conflicts_batch": (_i, [_vp] * 3 + [_i, _i, _d, _d, _vp, _vp, _d] + [_vp] * 6),
@@ -551,8 +561,68 @@ class Context:
                  "sc_speed_limits_batch_host")
         return out
 
+    def curve_clearance(self, ctrl, seg_off, d2, frame, r2_clear=0, status=None):
+        """Which cells P curves visit (sc_curve_clearance_batch; the definition is in include/sea_current_hip.h).  GPU tensors:
+        ctrl float32 [S,4,2], seg_off int32 [P+1], d2 int32 [H,W] with frame = (x_min, y_min, res_x, res_y), status int32 [P] or
+        None.  Returns dict(leg_min int32 [S], path_min, hit_legs, hit_leg int32 [P], hit_t float32 [P]); the legs of skipped
+        paths read -1 in leg_min."""
+        import torch
+        P, S, dev = seg_off.shape[0] - 1, ctrl.shape[0], ctrl.device
+        i = lambda n: torch.empty(n, dtype=torch.int32, device=dev)
+        o = dict(leg_min=torch.full((S,), -1, dtype=torch.int32, device=dev), path_min=i(P), hit_legs=i(P), hit_leg=i(P),
+                 hit_t=torch.empty(P, dtype=torch.float32, device=dev))
+        self._ck(self._l.sc_curve_clearance_batch(self._h, _ptr(ctrl), _ptr(seg_off), _ptr(status), P, _ptr(d2), *self._frame(d2, frame),
+                                                  int(r2_clear), *[_ptr(o[k]) for k in ("leg_min", "path_min", "hit_legs", "hit_leg", "hit_t")]),
+                 "sc_curve_clearance_batch")
+        return o
+
+    def curve_clearance_host(self, ctrl, seg_off, d2, frame, r2_clear=0, status=None):
+        """Host form of curve_clearance (numpy in, numpy out)."""
+        ctrl = np.ascontiguousarray(ctrl, dtype=np.float32)
+        seg_off = np.ascontiguousarray(seg_off, dtype=np.int32)
+        d2 = np.ascontiguousarray(d2, dtype=np.int32)
+        status = None if status is None else np.ascontiguousarray(status, dtype=np.int32)
+        P, S = seg_off.shape[0] - 1, ctrl.shape[0]
+        o = dict(leg_min=np.full(S, -1, np.int32), path_min=np.zeros(P, np.int32), hit_legs=np.zeros(P, np.int32),
+                 hit_leg=np.zeros(P, np.int32), hit_t=np.zeros(P, np.float32))
+        self._ck(self._l.sc_curve_clearance_batch_host(self._h, _ptr(ctrl), _ptr(seg_off), _ptr(status), P, _ptr(d2),
+                                                       *self._frame(d2, frame), int(r2_clear),
+                                                       *[_ptr(o[k]) for k in ("leg_min", "path_min", "hit_legs", "hit_leg", "hit_t")]),
+                 "sc_curve_clearance_batch_host")
+        return o
+
+    def curve_clear(self, ctrl, seg_off, d2, frame, r2_clear=0, max_level=6, status=None, inplace=False):
+        """Shrink the tangents of curves that hit the grid until none does (sc_curve_clear_batch).  Arguments as
+        curve_clearance; inplace=True repairs ctrl itself.  Returns dict(ctrl float32 [S,4,2], level uint8 [S+P] (waypoint j of
+        path p at seg_off[p] + p + j), rounds int32 [P], leg_min int32 [S] (-1 on the legs of skipped paths), status int32 [P],
+        SMOOTH_COLLIDES where shrinking did not help)."""
+        import torch
+        P, S, dev = seg_off.shape[0] - 1, ctrl.shape[0], ctrl.device
+        o = dict(ctrl=ctrl if inplace else torch.empty_like(ctrl), level=torch.empty(S + P, dtype=torch.uint8, device=dev),
+                 rounds=torch.empty(P, dtype=torch.int32, device=dev), leg_min=torch.full((S,), -1, dtype=torch.int32, device=dev),
+                 status=torch.empty(P, dtype=torch.int32, device=dev))
+        self._ck(self._l.sc_curve_clear_batch(self._h, _ptr(ctrl), _ptr(seg_off), _ptr(status), P, _ptr(d2), *self._frame(d2, frame),
+                                              int(r2_clear), int(max_level),
+                                              *[_ptr(o[k]) for k in ("ctrl", "level", "rounds", "leg_min", "status")]), "sc_curve_clear_batch")
+        return o
+
+    def curve_clear_host(self, ctrl, seg_off, d2, frame, r2_clear=0, max_level=6, status=None):
+        """Host form of curve_clear (numpy in, numpy out)."""
+        ctrl = np.ascontiguousarray(ctrl, dtype=np.float32)
+        seg_off = np.ascontiguousarray(seg_off, dtype=np.int32)
+        d2 = np.ascontiguousarray(d2, dtype=np.int32)
+        status = None if status is None else np.ascontiguousarray(status, dtype=np.int32)
+        P, S = seg_off.shape[0] - 1, ctrl.shape[0]
+        o = dict(ctrl=np.zeros_like(ctrl), level=np.zeros(S + P, np.uint8), rounds=np.zeros(P, np.int32), leg_min=np.full(S, -1, np.int32),
+                 status=np.zeros(P, np.int32))
+        self._ck(self._l.sc_curve_clear_batch_host(self._h, _ptr(ctrl), _ptr(seg_off), _ptr(status), P, _ptr(d2), *self._frame(d2, frame),
+                                                   int(r2_clear), int(max_level),
+                                                   *[_ptr(o[k]) for k in ("ctrl", "level", "rounds", "leg_min", "status")]),
+                 "sc_curve_clear_batch_host")
+        return o
+
     def smooth_paths(self, wp, npts, limits, dt=0.02, N=100, nsub=100, start_angle=float("nan"), lines=None, capacity=None, out=None,
-                     dyn=None, J=4, d2=None, frame=None):
+                     dyn=None, J=4, d2=None, frame=None, r2_clear=None, max_level=6):
         """The post-planner sequence for a batch of paths in one call (sc_smooth_paths_batch).  wp float32 [P,n_max,2],
         npts int32 [P], limits float64 [P,4] (vel_min, vel_max, acc_min, acc_max) or 4 numbers for every path, lines float32
         [E,4] or None; all on the GPU.  capacity=None: room for an estimate of the samples, the call repeated once with the
@@ -563,10 +633,19 @@ class Context:
         dyn (float64 [P,4] or 4 numbers: omega_max, alat_max, clear_floor, clear_gain) asks for per-stage speed limits from
         curvature and, with d2 int32 [H,W] and frame = (x_min, y_min, res_x, res_y), clearance (sc_smooth_paths_limited_batch,
         J samples to each side of a stage); the dict then also holds vmax_stage float64 [P,N+1] and min_clear float32 [P].
-        With dyn None the call is sc_smooth_paths_batch as before."""
+        With dyn None the call is sc_smooth_paths_batch as before.
+        r2_clear (needs d2; dyn None then means every speed term off) also keeps the curves clear of the grid
+        (sc_smooth_paths_clear_batch): legs that visit a cell with d2 < max(r2_clear, 1) get the tangents at their ends halved,
+        up to max_level times; the dict then also holds level uint8 [P*(n_max-1) + P], leg_min int32 [P*(n_max-1)] and rounds
+        int32 [P], and a path that shrinking cannot fix reads SMOOTH_COLLIDES.  With r2_clear None the calls are those above."""
         import torch
         P, n_max, _ = wp.shape
         dev = wp.device
+        if r2_clear is not None:
+            if d2 is None:
+                raise ValueError("r2_clear needs d2 and frame")
+            if dyn is None:
+                dyn = (float("inf"), float("inf"), float("inf"), 0.0)
         if dyn is None and d2 is not None:
             raise ValueError("d2 without dyn: the grid only enters through the speed limits")
         if dyn is not None:
@@ -597,8 +676,18 @@ class Context:
             if "vmax_stage" not in o or o["vmax_stage"].shape != (P, N + 1):
                 o["vmax_stage"] = torch.empty((P, N + 1), dtype=torch.float64, device=dev)
                 o["min_clear"] = torch.empty(P, dtype=torch.float32, device=dev)
-            self._ck(self._l.sc_smooth_paths_limited_batch(*args, _ptr(dyn), J, _ptr(d2), *fr, _ptr(o["vmax_stage"]), _ptr(o["min_clear"])),
-                     "sc_smooth_paths_limited_batch")
+            if r2_clear is None:
+                self._ck(self._l.sc_smooth_paths_limited_batch(*args, _ptr(dyn), J, _ptr(d2), *fr, _ptr(o["vmax_stage"]), _ptr(o["min_clear"])),
+                         "sc_smooth_paths_limited_batch")
+                return o
+            if "level" not in o:
+                S = P * (n_max - 1)
+                o["level"] = torch.zeros(S + P, dtype=torch.uint8, device=dev)
+                o["leg_min"] = torch.full((S,), -1, dtype=torch.int32, device=dev)
+                o["rounds"] = torch.empty(P, dtype=torch.int32, device=dev)
+            self._ck(self._l.sc_smooth_paths_clear_batch(*args, _ptr(dyn), J, _ptr(d2), *fr, _ptr(o["vmax_stage"]), _ptr(o["min_clear"]),
+                                                         int(r2_clear), int(max_level), _ptr(o["level"]), _ptr(o["leg_min"]), _ptr(o["rounds"])),
+                     "sc_smooth_paths_clear_batch")
             return o
 
         o = run(cap, out)
@@ -610,9 +699,15 @@ class Context:
         return {k: (v[:need] if k in ("time", "pos", "vel", "acc", "pts", "curvature", "ang_vel", "tpar", "seg") else v) for k, v in o.items()}
 
     def smooth_paths_host(self, wp, npts, limits, capacity, dt=0.02, N=100, nsub=100, start_angle=float("nan"), lines=None, dyn=None, J=4,
-                          d2=None, frame=None):
+                          d2=None, frame=None, r2_clear=None, max_level=6):
         """Host form (numpy in, numpy out) of smooth_paths with room for `capacity` samples (sc_smooth_paths_batch_host; with
-        dyn sc_smooth_paths_limited_batch_host, which adds vmax_stage and min_clear)."""
+        dyn sc_smooth_paths_limited_batch_host, which adds vmax_stage and min_clear; with r2_clear
+        sc_smooth_paths_clear_batch_host, which adds level, leg_min and rounds)."""
+        if r2_clear is not None:
+            if d2 is None:
+                raise ValueError("r2_clear needs d2 and frame")
+            if dyn is None:
+                dyn = (float("inf"), float("inf"), float("inf"), 0.0)
         wp = np.ascontiguousarray(wp, dtype=np.float32)
         npts = np.ascontiguousarray(npts, dtype=np.int32)
         P, n_max, _ = wp.shape
@@ -637,8 +732,15 @@ class Context:
         d2 = None if d2 is None else np.ascontiguousarray(d2, dtype=np.int32)
         o["vmax_stage"] = np.zeros((P, N + 1))
         o["min_clear"] = np.zeros(P, np.float32)
-        self._ck(self._l.sc_smooth_paths_limited_batch_host(*args, _ptr(dyn), J, _ptr(d2), *self._frame(d2, frame), _ptr(o["vmax_stage"]),
-                                                            _ptr(o["min_clear"])), "sc_smooth_paths_limited_batch_host")
+        if r2_clear is None:
+            self._ck(self._l.sc_smooth_paths_limited_batch_host(*args, _ptr(dyn), J, _ptr(d2), *self._frame(d2, frame), _ptr(o["vmax_stage"]),
+                                                                _ptr(o["min_clear"])), "sc_smooth_paths_limited_batch_host")
+            return o
+        S = P * (n_max - 1)
+        o["level"], o["leg_min"], o["rounds"] = np.zeros(S + P, np.uint8), np.full(S, -1, np.int32), np.zeros(P, np.int32)
+        self._ck(self._l.sc_smooth_paths_clear_batch_host(*args, _ptr(dyn), J, _ptr(d2), *self._frame(d2, frame), _ptr(o["vmax_stage"]),
+                                                          _ptr(o["min_clear"]), int(r2_clear), int(max_level), _ptr(o["level"]),
+                                                          _ptr(o["leg_min"]), _ptr(o["rounds"])), "sc_smooth_paths_clear_batch_host")
         return o
 
     # ---- conflicts between timed paths (sc_traj_knots_batch, sc_traj_conflicts_batch, sc_fleet_conflicts_batch) ----

@@ -1419,6 +1419,13 @@ velocity_profile gen_vel_prof(const VectorNd<N>& pos_end, const VectorNd<N>& pos
 // that takes an occupancy_grid with its d2, the speed near obstacles (v <= clear_floor + clear_gain * clearance).  +inf
 // switches a term off; with every term off and no grid the call is sc_smooth_paths_batch_host as before.  vmax_stage then
 // holds the limit TOPP-RA ran with at each of its SC_TOPPRA_GRID + 1 stages, min_clear the smallest sampled clearance.
+//
+// Curves clear of the grid (sc_smooth_paths_clear_batch; the definition, its guarantee and what it does not guarantee are in
+// sea_current_hip.h): when any request of a batch sets clear_r2 >= 0, the overload that takes an occupancy_grid checks which
+// cells every Bezier leg visits and halves the tangents at the ends of legs that visit a cell with d2 < max(clear_r2, 1), up
+// to clear_levels times.  The call takes one clearance and one depth for the batch: the largest clear_r2 and the largest
+// clear_levels among the requests that ask.  tangent_level then holds the level of every waypoint, leg_min_d2 the smallest
+// d2 under every leg of the final curve, rounds the repair rounds; a path shrinking cannot fix reads SC_SMOOTH_COLLIDES.
 struct smooth_request {
     std::vector<Vector2f> path;
     double vel_min, vel_max, acc_min, acc_max;
@@ -1426,6 +1433,8 @@ struct smooth_request {
     double alat_max = std::numeric_limits<double>::infinity();
     double clear_floor = std::numeric_limits<double>::infinity();
     double clear_gain = 0.0;
+    int clear_r2 = -1;      // >= 0: keep the curve out of cells with d2 < max(clear_r2, 1) (needs the grid overload); -1: off
+    int clear_levels = 6;   // halvings of a tangent at the most, 1 .. SC_CURVE_MAX_LEVEL
 };
 struct smooth_result {
     int status = SC_SMOOTH_BAD_INPUT;
@@ -1435,6 +1444,9 @@ struct smooth_result {
     std::vector<float> ang_vel;
     std::vector<double> vmax_stage;   // [SC_TOPPRA_GRID + 1] when limits were asked for, else empty
     float min_clear = std::numeric_limits<float>::infinity();
+    std::vector<uint8_t> tangent_level;   // [waypoints] when the batch asked for clear curves, else empty
+    std::vector<int32_t> leg_min_d2;      // [legs], likewise
+    int rounds = 0;
 };
 constexpr int SC_SPEED_SAMPLES = 4;   // J: samples to each side of a stage
 inline std::vector<smooth_result> smooth_paths_batch_impl(const std::vector<smooth_request>& requests, const planning_space& space,
@@ -1449,12 +1461,14 @@ inline std::vector<smooth_result> smooth_paths_batch_impl(const std::vector<smoo
     std::vector<double> lim((size_t)P * 4), dyn((size_t)P * 4), vstage;
     std::vector<float> min_clear;
     bool limited = grid != nullptr;
+    int clear_r2 = -1, clear_levels = 0;
     int64_t cap = 0;
     for (int p = 0; p < P; ++p) {
         const auto& r = requests[p];
         const double inf = std::numeric_limits<double>::infinity();
         dyn[4 * (size_t)p] = r.omega_max; dyn[4 * (size_t)p + 1] = r.alat_max; dyn[4 * (size_t)p + 2] = r.clear_floor; dyn[4 * (size_t)p + 3] = r.clear_gain;
         limited = limited || r.omega_max != inf || r.alat_max != inf || r.clear_floor != inf;
+        if (grid && r.clear_r2 >= 0) { clear_r2 = std::max(clear_r2, r.clear_r2); clear_levels = std::max(clear_levels, r.clear_levels); }
         npts[p] = (int32_t)r.path.size();
         float poly = 0;
         for (size_t i = 0; i < r.path.size(); ++i) {
@@ -1475,6 +1489,9 @@ inline std::vector<smooth_result> smooth_paths_batch_impl(const std::vector<smoo
     std::vector<double> times;
     int64_t needed = 0;
     if (limited) { vstage.resize((size_t)P * (SC_TOPPRA_GRID + 1)); min_clear.resize(P); }
+    std::vector<uint8_t> level;
+    std::vector<int32_t> leg_min, rounds;
+    if (clear_r2 >= 0) { level.resize((size_t)S + P); leg_min.resize(S); rounds.resize(P); }
     if (grid) { SC_ASSERT(grid->d2.size() == grid->occ.size() && !grid->d2.empty(), "the grid's d2 is missing: call edt() first"); }
     for (int attempt = 0; attempt < 2; ++attempt) {
         cap = std::min<int64_t>(std::max<int64_t>(cap, 1), INT32_MAX);
@@ -1486,6 +1503,16 @@ inline std::vector<smooth_result> smooth_paths_batch_impl(const std::vector<smoo
                                                  length.data(), offsets.data(), status.data(), &needed, times.data(), pos.data(), vel.data(),
                                                  acc.data(), pts.data(), nullptr, ang.data(), tpar.data(), seg.data()),
                       "sc_smooth_paths_batch_host");
+        else if (clear_r2 >= 0)
+            ctx.check(sc_smooth_paths_clear_batch_host(
+                          ctx.get(), xy.data(), npts.data(), P, n_max, lim.data(), NAN, lines.empty() ? nullptr : lines.data(),
+                          (int)(lines.size() / 4), dt, SC_TOPPRA_GRID, nsub, cap, ctrl.data(), seg_off.data(), al.data(), length.data(),
+                          offsets.data(), status.data(), &needed, times.data(), pos.data(), vel.data(), acc.data(), pts.data(), nullptr,
+                          ang.data(), tpar.data(), seg.data(), dyn.data(), SC_SPEED_SAMPLES, grid->d2.data(), grid->W, grid->H,
+                          grid->bound_rect.x_min, grid->bound_rect.y_min, grid->resolution,
+                          (grid->bound_rect.y_max - grid->bound_rect.y_min) / (float)grid->H, vstage.data(), min_clear.data(), clear_r2,
+                          clear_levels, level.data(), leg_min.data(), rounds.data()),
+                      "sc_smooth_paths_clear_batch_host");
         else
             ctx.check(sc_smooth_paths_limited_batch_host(
                           ctx.get(), xy.data(), npts.data(), P, n_max, lim.data(), NAN, lines.empty() ? nullptr : lines.data(),
@@ -1506,6 +1533,11 @@ inline std::vector<smooth_result> smooth_paths_batch_impl(const std::vector<smoo
         if (limited) {
             res.vmax_stage.assign(vstage.begin() + (size_t)p * (SC_TOPPRA_GRID + 1), vstage.begin() + (size_t)(p + 1) * (SC_TOPPRA_GRID + 1));
             res.min_clear = min_clear[p];
+        }
+        if (clear_r2 >= 0 && seg_off[p + 1] > seg_off[p]) {
+            res.tangent_level.assign(level.begin() + seg_off[p] + p, level.begin() + seg_off[p + 1] + p + 1);
+            res.leg_min_d2.assign(leg_min.begin() + seg_off[p], leg_min.begin() + seg_off[p + 1]);
+            res.rounds = rounds[p];
         }
         if (status[p] != SC_SMOOTH_OK) continue;
         const int s0 = seg_off[p], ns = seg_off[p + 1] - s0, o = offsets[p], L = length[p];

@@ -1,0 +1,39 @@
+"""Curves clear of the grid through the C++ successor header (tests/cpp/test_curve.cpp): the program compiles as C++17 and
+C++20, its new members default to "off", and it fails loudly without a GPU; on the GPU requests with clear_r2 come back with
+levels and leg minima, and paths that needed no shrinking equal the limited call."""
+import os
+import subprocess
+
+import pytest
+
+import sea_current_amd as sc
+
+SRC = os.path.join(sc.REPO_ROOT, "tests", "cpp", "test_curve.cpp")
+
+
+def _build(tmp_path, std):
+    sc.build()
+    exe = str(tmp_path / f"test_curve_{std}")
+    subprocess.check_call(["g++", f"-std={std}", "-O1", "-Wall", "-Werror=return-type", "-o", exe, SRC,
+                           "-L", sc.NATIVE_DIR, "-lsea_current_hip", f"-Wl,-rpath,{sc.NATIVE_DIR}"])
+    return exe
+
+
+@pytest.mark.parametrize("std", ["c++17", "c++20"])
+def test_curve_program_compiles_and_fails_loudly_without_gpu(tmp_path, std):
+    import torch
+    exe = _build(tmp_path, std)
+    if torch.cuda.is_available():
+        pytest.skip("GPU present: covered by the gpu test")
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode != 0
+    assert "FAIL" not in r.stdout                                     # the defaults hold before the GPU is touched
+    assert "no CPU fallback" in r.stderr
+
+
+@pytest.mark.gpu
+def test_curve_program_on_gpu(tmp_path):
+    exe = _build(tmp_path, "c++20")
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "curve clear OK" in r.stdout
