@@ -56,7 +56,8 @@
 #define NBUCKET 32
 // The LDS ring of the current f level holds CQ entries (a power of two) and is refilled from the level's HBM ring CQ / 2
 // entries at a time, RU x 64 loads under way at once.  Two builds of the two-wavefront kernel (astar_run picks):
-//   throughput  CQ 1024, RU 4: 13.1 KiB of LDS and <= 80 VGPRs, 12 searches per CU -- batches larger than the chip holds;
+//   throughput  CQ 1024, RU 4: 13.1 KiB of LDS and <= 80 VGPRs, 12 searches per CU -- batches larger than the chip holds
+//               (wavefront 1 stores g non-temporally in this build, see there);
 //   latency     CQ 2048, RU 8: 17.2 KiB and 81 VGPRs, 9 per CU -- every search of the batch resident at once, where
 //               the call lasts as long as its longest search and a refill of a wide level is half as many round trips.
 #define ASTAR_CQ_THROUGHPUT 1024
@@ -477,7 +478,14 @@ __device__ __forceinline__ void astar_query(const astar_args& a, const int q, co
             dirty = true;
             const int x = xy & 0xFFFF, y = xy >> 16;
             const int hc = octile(x, y, gx, gy);
-            if (valid) g[gidx<GT>(x, y, tw)] = (GT)(f - (uint32_t)hc);
+            // Throughput build: the g byte is stored non-temporally.  On a full chip the nodes of one f level lie scattered over
+            // the whole expanded region, a g tile gets its bytes many levels apart and each byte is a partial write of its own
+            // whatever the cache does; as an ordinary store it also takes an L2 line from the bitmap and legal-move lines
+            // wavefront 0 is waiting for.  Nobody reads g before the parent-chain extraction, which reads it from L2 or beyond.
+            if (valid) {
+                if (CQ == ASTAR_CQ_THROUGHPUT) __builtin_nontemporal_store((GT)(f - (uint32_t)hc), &g[gidx<GT>(x, y, tw)]);
+                else g[gidx<GT>(x, y, tw)] = (GT)(f - (uint32_t)hc);
+            }
             if (__ballot(valid && x == gx && y == gy) && lane == 0) __hip_atomic_store(&hq_found, 1, __ATOMIC_RELAXED, SCOPE);   // the goal has been expanded
             uint32_t mv = m & 0xFFu;
             nd_xy[lane] = xy;
