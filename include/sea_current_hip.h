@@ -1009,6 +1009,86 @@ int sc_fleet_assign_batch(sc_ctx* ctx, const int32_t* g, int F, int W, int H, co
 int sc_fleet_assign_batch_host(sc_ctx* ctx, const int32_t* g, int F, int W, int H, const int32_t* cell, int R, const int32_t* col_cost,
                                int32_t* cost, int32_t* col_of, int32_t* row_of, int64_t* u, int64_t* v, int64_t* info);
 
+/* ---- exploration frontiers: known space, clusters, costs, a goal per robot ----------------------------------------
+ * Every planner above takes the map as known.  These calls add a planner-visible notion of "known", find the frontier --
+ * the known, traversable cells that touch unknown space -- grouped into clusters, and give the robots x clusters cost matrix
+ * in the form sc_assign_batch takes, so that one stream carries known -> EDT -> field per robot -> frontiers -> matrix ->
+ * matching -> paths with no host hop.  The reference's counterpart is planner::pick_next_goal_point (sea_current.hpp:433-519,
+ * unfinished there: no parity claim).  DESIGN.md section 22.  Everything is integer and uniquely defined; tests/frontier_twin.py
+ * states it in NumPy, tests/cpp/frontier_ref.c in C, and every output equals them bit for bit.  Cells are c = y*W + x.
+ *
+ * sc_known_from_discs: known[c] = (base ? base[c] != 0 : 0) | exists disc: (x-cx)^2 + (y-cy)^2 <= r2, in int64, written as 0 / 1.
+ *   discs int32 [R][3] = (cx, cy, r2); a disc with r2 < 0 is ignored; R == 0 copies base or clears (discs may then be NULL).
+ *   base uint8 [H][W] may be NULL or alias known.  One grid, one kernel, timed as SC_K_MOVES: the sibling of sc_occ_from_rects.
+ * sc_d2_known_i32: d2k[c] = known[c] ? d2[c] : 0 over [G][H][W]; d2k may alias d2.  With d2 the EDT of the observed obstacles,
+ *   every planner run on d2k (A*, fields, components, space-time plans) moves through known free space only, while clearance is
+ *   still measured from real obstacles, not from the edge of the unknown.  One kernel, timed as SC_K_MOVES.
+ *
+ * sc_frontier_batch: d2 int32 and known uint8 [G][H][W]; thr = max(r2_clear, 1).
+ *   Frontier cell: Fr(c) <=> known[c] != 0 and d2[c] >= thr and some orthogonal neighbour n inside the grid has known[n] == 0.
+ *     Cells outside the grid are not unknown.
+ *   Cluster: an 8-connected set of frontier cells (frontier cells along a slanted boundary touch only diagonally, so the
+ *     4-connected labelling of sc_components_batch would shatter them).  Its representative is its smallest cell index.
+ *   label int32 [G][H][W], may be NULL: the representative of the cell's cluster, -1 where !Fr(c).
+ *   Listed clusters: those of at least min_size cells, in ascending order of representative; L their number.
+ *   ncl int32 [G][2] = {L, the number of all clusters}; L is reported in full even when L > Cmax.
+ *   For k < min(L, Cmax): rep[g][k] the representative, csize[g][k] the cell count, cbox[g][k] = {x0, y0, x1, y1} inclusive
+ *     (int32 [G][Cmax][4], may be NULL), csum[g][k] = {sum x, sum y} (int64 [G][Cmax][2], may be NULL: the caller's centroid).
+ *     Rows k >= min(L, Cmax) read -1 / 0 / zeros.  rep and csize are int32 [G][Cmax].
+ *   slot int32 [G][H][W], may be NULL: the column k of the cell's cluster, -1 where the cell is no frontier cell or its
+ *     cluster is not listed (too small, or beyond Cmax).
+ *   1 <= Cmax <= SC_FRONTIER_MAX_CLUSTERS, min_size >= 1.
+ *   Only enqueues: at most eight kernels whatever the map (one wavefront per 64 x 64 tile labels it in registers, a lock-free
+ *   union across tile edges, a flatten, a two-level count and scan for the ranks), no workgroup waits for another, integer
+ *   atomics only, every output independent of execution order.  Timed as SC_K_MOVES.  Scratch: G * W * H * 4 B (8 B when
+ *   label is NULL) + G * ceil(W * H / 256) * 4 B; grows only.
+ *
+ * sc_frontier_cost_matrix: g int32 [F][H][W] is any field array (plain, weighted, multi-source) rooted at the robots and
+ *   computed on d2k; field f lives on grid fgrid[f] (int32 [F]; NULL only with G == 1; out of range: the whole row
+ *   SC_FIELD_INF / -1).  slot and csize are what sc_frontier_batch wrote with the same G, W, H, Cmax.  For column k:
+ *   m = min g[f][c] over the cells of f's grid with slot == k.  No such cell, or m == SC_FIELD_INF: cost[f][k] = SC_FIELD_INF
+ *   and cell[f][k] = -1.  Otherwise cell[f][k] = the smallest c attaining m and
+ *   cost[f][k] = min(m + gain * (size_cap - min(csize[k], size_cap)), INT32_MAX - 1), in int64.
+ *   gain == 0 is the nearest-frontier rule; gain > 0 prefers large clusters and keeps the costs non-negative, as
+ *   sc_assign_batch requires.  cost and cell are int32 [F][Cmax]: sc_assign_batch's layout with B = 1, R = F, C = Cmax.
+ *   Three launches (key fill, 64-bit atomicMin of g << 32 | c per frontier cell and field, read-out), timed as SC_K_ASTAR.
+ *   Scratch: F * Cmax * 8 B.
+ *
+ * sc_fleet_explore_batch: one grid; sc_frontier_batch -> the matrix (robot r = field r) -> sc_assign_batch -> per robot
+ *   goal[r] = cell[r][col_of[r]], or -1 when unmatched; gcost[r] = g[r][goal[r]], or -1.  Matched robots get pairwise
+ *   different clusters.  label, slot, ncl, rep, csize, cbox, csum, cost, cell, col_of, row_of (int32 [Cmax]) and info
+ *   (int64 [4], sc_assign_batch's) may each be NULL: what the chain needs of them then lives in context scratch.
+ *   sc_field_paths_batch(..., qfield = r, target = goal[r], to_root = 0) then yields the paths; a -1 target reads
+ *   SC_Q_BAD_ENDPOINT by the existing rule.  Timed as its parts.
+ *
+ * Device pointers; the calls only enqueue on the context's stream.  The _host forms take host pointers, check the data
+ * before any launch (a g value below 0: SC_ERR_INVALID), copy, run, copy back and synchronise.
+ * Errors: SC_ERR_INVALID for NULL mandatory pointers (everything not called optional above), W or H outside 1..SC_MAX_DIM,
+ *   G <= 0, R < 0, F < 1, min_size < 1, Cmax outside 1..SC_FRONTIER_MAX_CLUSTERS (1..SC_ASSIGN_MAX_DIM, like F, in
+ *   sc_fleet_explore_batch), F * Cmax > 2^30, gain < 0, size_cap < 0, gain * size_cap > 2^30, fgrid NULL with G > 1. */
+#define SC_FRONTIER_MAX_CLUSTERS 65536
+int sc_known_from_discs(sc_ctx* ctx, const uint8_t* base, const int32_t* discs, int R, int W, int H, uint8_t* known);
+int sc_known_from_discs_host(sc_ctx* ctx, const uint8_t* base, const int32_t* discs, int R, int W, int H, uint8_t* known);
+int sc_d2_known_i32(sc_ctx* ctx, const int32_t* d2, const uint8_t* known, int G, int W, int H, int32_t* d2k);
+int sc_d2_known_i32_host(sc_ctx* ctx, const int32_t* d2, const uint8_t* known, int G, int W, int H, int32_t* d2k);
+int sc_frontier_batch(sc_ctx* ctx, const int32_t* d2, const uint8_t* known, int G, int W, int H, int32_t r2_clear, int min_size, int Cmax,
+                      int32_t* label, int32_t* slot, int32_t* ncl, int32_t* rep, int32_t* csize, int32_t* cbox, int64_t* csum);
+int sc_frontier_batch_host(sc_ctx* ctx, const int32_t* d2, const uint8_t* known, int G, int W, int H, int32_t r2_clear, int min_size,
+                           int Cmax, int32_t* label, int32_t* slot, int32_t* ncl, int32_t* rep, int32_t* csize, int32_t* cbox,
+                           int64_t* csum);
+int sc_frontier_cost_matrix(sc_ctx* ctx, const int32_t* g, int F, const int32_t* fgrid, const int32_t* slot, const int32_t* csize, int G,
+                            int W, int H, int Cmax, int32_t gain, int32_t size_cap, int32_t* cost, int32_t* cell);
+int sc_frontier_cost_matrix_host(sc_ctx* ctx, const int32_t* g, int F, const int32_t* fgrid, const int32_t* slot, const int32_t* csize,
+                                 int G, int W, int H, int Cmax, int32_t gain, int32_t size_cap, int32_t* cost, int32_t* cell);
+int sc_fleet_explore_batch(sc_ctx* ctx, const int32_t* d2, const uint8_t* known, int W, int H, int32_t r2_clear, int min_size, int Cmax,
+                           const int32_t* g, int F, int32_t gain, int32_t size_cap, int32_t* label, int32_t* slot, int32_t* ncl,
+                           int32_t* rep, int32_t* csize, int32_t* cbox, int64_t* csum, int32_t* cost, int32_t* cell, int32_t* col_of,
+                           int32_t* row_of, int64_t* info, int32_t* goal, int32_t* gcost);
+int sc_fleet_explore_batch_host(sc_ctx* ctx, const int32_t* d2, const uint8_t* known, int W, int H, int32_t r2_clear, int min_size,
+                                int Cmax, const int32_t* g, int F, int32_t gain, int32_t size_cap, int32_t* label, int32_t* slot,
+                                int32_t* ncl, int32_t* rep, int32_t* csize, int32_t* cbox, int64_t* csum, int32_t* cost, int32_t* cell,
+                                int32_t* col_of, int32_t* row_of, int64_t* info, int32_t* goal, int32_t* gcost);
+
 /* ---- re-planning in space-time around the scheduled fleet -------------------------------------------------------
  * sc_fleet_schedule_batch only delays: a path that finds no free slot comes back SC_SLOT_UNRESOLVED.  These calls plan such a
  * robot again in (cell, time): the paths that did get a slot are rasterised into reservations, and an exact earliest-arrival

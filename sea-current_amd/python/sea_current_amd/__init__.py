@@ -170,6 +170,16 @@ _SIGNATURES = {
     "sc_assign_batch_host": (_i, [_vp, _vp, _i, _i, _i] + [_vp] * 5),
     "sc_fleet_assign_batch": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp] + [_vp] * 6),
     "sc_fleet_assign_batch_host": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp] + [_vp] * 6),
+    "sc_known_from_discs": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
+    "sc_known_from_discs_host": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
+    "sc_d2_known_i32": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
+    "sc_d2_known_i32_host": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
+    "sc_frontier_batch": (_i, [_vp, _vp, _vp, _i, _i, _i, C.c_int32, _i, _i] + [_vp] * 7),
+    "sc_frontier_batch_host": (_i, [_vp, _vp, _vp, _i, _i, _i, C.c_int32, _i, _i] + [_vp] * 7),
+    "sc_frontier_cost_matrix": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, C.c_int32, C.c_int32, _vp, _vp]),
+    "sc_frontier_cost_matrix_host": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, C.c_int32, C.c_int32, _vp, _vp]),
+    "sc_fleet_explore_batch": (_i, [_vp, _vp, _vp, _i, _i, C.c_int32, _i, _i, _vp, _i, C.c_int32, C.c_int32] + [_vp] * 14),
+    "sc_fleet_explore_batch_host": (_i, [_vp, _vp, _vp, _i, _i, C.c_int32, _i, _i, _vp, _i, C.c_int32, C.c_int32] + [_vp] * 14),
     "sc_rank_range": (None, [_i, _i, _i, C.POINTER(_i), C.POINTER(_i)]),
     "sc_comm_unique_id": (_i, [_vp]),
     "sc_comm_init": (_i, [_vp, _vp, _i, _i]),
@@ -1269,6 +1279,135 @@ class Context:
         self._ck(self._l.sc_fleet_assign_batch_host(self._h, _ptr(g), F, W, H, _ptr(cells), R, _ptr(col_cost), _ptr(out.get("cost")),
                                                     _ptr(out["col_of"]), _ptr(out["row_of"]), _ptr(out["u"]), _ptr(out["v"]),
                                                     _ptr(out["info"])), "sc_fleet_assign_batch_host")
+        return out
+
+    # ---- exploration frontiers (sc_known_from_discs, sc_d2_known_i32, sc_frontier_batch, sc_frontier_cost_matrix,
+    #      sc_fleet_explore_batch) ----
+    def known_from_discs(self, discs, W, H, base=None, out=None):
+        """The known-space mask of sensing discs (sc_known_from_discs): discs int32 [R,3] = (cx, cy, r2) on the GPU, base uint8
+        [H,W] or None (may be `out`).  Returns uint8 [H,W], 1 where base is set or a disc covers the cell.  Only enqueues."""
+        import torch
+        if out is None:
+            out = torch.empty((H, W), dtype=torch.uint8, device=discs.device)
+        self._ck(self._l.sc_known_from_discs(self._h, _ptr(base), _ptr(discs), discs.shape[0], W, H, _ptr(out)), "sc_known_from_discs")
+        return out
+
+    def d2_known(self, d2, known, out=None):
+        """d2 where known, 0 elsewhere (sc_d2_known_i32): d2 int32 and known uint8, [H,W] or [G,H,W] on the GPU; every planner
+        run on the result moves through known free space only.  out may be d2.  Only enqueues."""
+        import torch
+        G, H, W = _ghw(d2)
+        if out is None:
+            out = torch.empty_like(d2)
+        self._ck(self._l.sc_d2_known_i32(self._h, _ptr(d2), _ptr(known), G, W, H, _ptr(out)), "sc_d2_known_i32")
+        return out
+
+    @staticmethod
+    def _frontier_out(shape, G, Cmax, empty, i32, i64, want_label=True, want_slot=True, want_stats=True):
+        return dict(label=empty(shape, i32) if want_label else None, slot=empty(shape, i32) if want_slot else None,
+                    ncl=empty((G, 2), i32), rep=empty((G, Cmax), i32), csize=empty((G, Cmax), i32),
+                    cbox=empty((G, Cmax, 4), i32) if want_stats else None, csum=empty((G, Cmax, 2), i64) if want_stats else None)
+
+    def frontiers(self, d2, known, r2=0, min_size=1, Cmax=128, want_label=True, want_slot=True, want_stats=True, out=None):
+        """Frontier cells and their 8-connected clusters (sc_frontier_batch; the definition is in include/sea_current_hip.h).
+        d2 int32 and known uint8, [H,W] or [G,H,W] on the GPU.  Returns dict(label, slot int32 shaped like d2 (None without
+        want_label / want_slot), ncl int32 [G,2] = (listed, all), rep, csize int32 [G,Cmax], cbox int32 [G,Cmax,4] and csum int64
+        [G,Cmax,2] (None without want_stats)).  `out`: the dict of an earlier call with the same shapes.  Only enqueues."""
+        import torch
+        G, H, W = _ghw(d2)
+        if out is None:
+            out = self._frontier_out(tuple(d2.shape), G, Cmax, lambda s, t: torch.empty(s, dtype=t, device=d2.device), torch.int32, torch.int64,
+                                     want_label, want_slot, want_stats)
+        self._ck(self._l.sc_frontier_batch(self._h, _ptr(d2), _ptr(known), G, W, H, r2, min_size, Cmax, _ptr(out["label"]), _ptr(out["slot"]),
+                                           _ptr(out["ncl"]), _ptr(out["rep"]), _ptr(out["csize"]), _ptr(out["cbox"]), _ptr(out["csum"])),
+                 "sc_frontier_batch")
+        return out
+
+    def frontier_cost_matrix(self, g, fr, gain=0, size_cap=0, fgrid=None):
+        """The robots x clusters matrix (sc_frontier_cost_matrix): g int32 [F,H,W] fields rooted at the robots, fr the dict of
+        frontiers (its slot and csize), fgrid int32 [F] (None only with one grid).  Returns dict(cost, cell int32 [F,Cmax]):
+        assign's layout.  Only enqueues."""
+        import torch
+        F, H, W = g.shape
+        G, Cmax = fr["csize"].shape
+        out = dict(cost=torch.empty((F, Cmax), dtype=torch.int32, device=g.device), cell=torch.empty((F, Cmax), dtype=torch.int32, device=g.device))
+        self._ck(self._l.sc_frontier_cost_matrix(self._h, _ptr(g), F, _ptr(fgrid), _ptr(fr["slot"]), _ptr(fr["csize"]), G, W, H, Cmax, gain,
+                                                 size_cap, _ptr(out["cost"]), _ptr(out["cell"])), "sc_frontier_cost_matrix")
+        return out
+
+    def fleet_explore(self, d2, known, g, r2=0, min_size=1, Cmax=128, gain=0, size_cap=0, want_all=False):
+        """A frontier goal per robot (sc_fleet_explore_batch): frontiers of (d2, known) [H,W], the matrix of the robots' fields g
+        int32 [F,H,W], an optimal matching.  Returns dict(goal int32 [F]: the cell to drive to or -1, gcost int32 [F]); with
+        want_all also every intermediate array (frontiers' without the leading G, cost, cell, col_of, row_of, info).  goal is what
+        field_paths takes as targets with qfield = arange(F).  Only enqueues."""
+        import torch
+        H, W = d2.shape
+        F = g.shape[0]
+        dev = d2.device
+        e = lambda s, t=torch.int32: torch.empty(s, dtype=t, device=dev)
+        out = dict(goal=e(F), gcost=e(F))
+        if want_all:
+            out.update(label=e((H, W)), slot=e((H, W)), ncl=e(2), rep=e(Cmax), csize=e(Cmax), cbox=e((Cmax, 4)), csum=e((Cmax, 2), torch.int64),
+                       cost=e((F, Cmax)), cell=e((F, Cmax)), col_of=e(F), row_of=e(Cmax), info=e(4, torch.int64))
+        self._ck(self._l.sc_fleet_explore_batch(self._h, _ptr(d2), _ptr(known), W, H, r2, min_size, Cmax, _ptr(g), F, gain, size_cap,
+                                                *(_ptr(out.get(k)) for k in ("label", "slot", "ncl", "rep", "csize", "cbox", "csum", "cost",
+                                                                             "cell", "col_of", "row_of", "info")),
+                                                _ptr(out["goal"]), _ptr(out["gcost"])), "sc_fleet_explore_batch")
+        return out
+
+    def known_from_discs_host(self, discs, W, H, base=None):
+        """Host form of known_from_discs (numpy in, numpy out)."""
+        discs = np.ascontiguousarray(discs, dtype=np.int32).reshape(-1, 3)
+        base = None if base is None else np.ascontiguousarray(base, dtype=np.uint8)
+        out = np.zeros((H, W), np.uint8)
+        self._ck(self._l.sc_known_from_discs_host(self._h, _ptr(base), _ptr(discs), discs.shape[0], W, H, _ptr(out)), "sc_known_from_discs_host")
+        return out
+
+    def d2_known_host(self, d2, known):
+        """Host form of d2_known (numpy in, numpy out)."""
+        d2, known = np.ascontiguousarray(d2, dtype=np.int32), np.ascontiguousarray(known, dtype=np.uint8)
+        G, H, W = _ghw(d2)
+        out = np.zeros_like(d2)
+        self._ck(self._l.sc_d2_known_i32_host(self._h, _ptr(d2), _ptr(known), G, W, H, _ptr(out)), "sc_d2_known_i32_host")
+        return out
+
+    def frontiers_host(self, d2, known, r2=0, min_size=1, Cmax=128, want_label=True, want_slot=True, want_stats=True):
+        """Host form of frontiers (numpy in, numpy out)."""
+        d2, known = np.ascontiguousarray(d2, dtype=np.int32), np.ascontiguousarray(known, dtype=np.uint8)
+        G, H, W = _ghw(d2)
+        out = self._frontier_out(d2.shape, G, Cmax, lambda s, t: np.zeros(s, t), np.int32, np.int64, want_label, want_slot, want_stats)
+        self._ck(self._l.sc_frontier_batch_host(self._h, _ptr(d2), _ptr(known), G, W, H, r2, min_size, Cmax, _ptr(out["label"]),
+                                                _ptr(out["slot"]), _ptr(out["ncl"]), _ptr(out["rep"]), _ptr(out["csize"]), _ptr(out["cbox"]),
+                                                _ptr(out["csum"])), "sc_frontier_batch_host")
+        return out
+
+    def frontier_cost_matrix_host(self, g, fr, gain=0, size_cap=0, fgrid=None):
+        """Host form of frontier_cost_matrix (numpy in, numpy out)."""
+        g = np.ascontiguousarray(g, dtype=np.int32)
+        slot, csize = np.ascontiguousarray(fr["slot"], dtype=np.int32), np.ascontiguousarray(fr["csize"], dtype=np.int32)
+        fgrid = None if fgrid is None else np.ascontiguousarray(fgrid, dtype=np.int32)
+        F, H, W = g.shape
+        G, Cmax = csize.shape
+        out = dict(cost=np.zeros((F, Cmax), np.int32), cell=np.zeros((F, Cmax), np.int32))
+        self._ck(self._l.sc_frontier_cost_matrix_host(self._h, _ptr(g), F, _ptr(fgrid), _ptr(slot), _ptr(csize), G, W, H, Cmax, gain, size_cap,
+                                                      _ptr(out["cost"]), _ptr(out["cell"])), "sc_frontier_cost_matrix_host")
+        return out
+
+    def fleet_explore_host(self, d2, known, g, r2=0, min_size=1, Cmax=128, gain=0, size_cap=0, want_all=False):
+        """Host form of fleet_explore (numpy in, numpy out)."""
+        d2, known = np.ascontiguousarray(d2, dtype=np.int32), np.ascontiguousarray(known, dtype=np.uint8)
+        g = np.ascontiguousarray(g, dtype=np.int32)
+        H, W = d2.shape
+        F = g.shape[0]
+        z = lambda s, t=np.int32: np.zeros(s, t)
+        out = dict(goal=z(F), gcost=z(F))
+        if want_all:
+            out.update(label=z((H, W)), slot=z((H, W)), ncl=z(2), rep=z(Cmax), csize=z(Cmax), cbox=z((Cmax, 4)), csum=z((Cmax, 2), np.int64),
+                       cost=z((F, Cmax)), cell=z((F, Cmax)), col_of=z(F), row_of=z(Cmax), info=z(4, np.int64))
+        self._ck(self._l.sc_fleet_explore_batch_host(self._h, _ptr(d2), _ptr(known), W, H, r2, min_size, Cmax, _ptr(g), F, gain, size_cap,
+                                                     *(_ptr(out.get(k)) for k in ("label", "slot", "ncl", "rep", "csize", "cbox", "csum",
+                                                                                  "cost", "cell", "col_of", "row_of", "info")),
+                                                     _ptr(out["goal"]), _ptr(out["gcost"])), "sc_fleet_explore_batch_host")
         return out
 
     # ---- multi-GPU gather (RCCL through the C ABI) ----

@@ -32,6 +32,10 @@
 //   (new) fleet_schedule: start slots by priority that let the lower-priority path wait until it meets nobody
 //   (new) fleet_replan: the paths no slot was free for, planned again in (cell, tick) around the scheduled ones
 //   (new) planning_space::plan_assigned: one goal per robot, the cheapest such assignment, from fields rooted at the goals
+//   planner (ps, goal_point_cache, past_id) :433-441      same members
+//   planner::pick_next_goal_point      :465-519           same signature; unfinished there ("TODO: fix condition"), so no
+//                                                         parity: frontier clusters of the known space on the GPU
+//   (new) occupancy_grid::frontiers / explore_goals, planning_space::known_grid: exploration frontiers, a goal per robot
 //
 // Differences that are deliberate: obstacle::closed is initialised (the reference leaves it
 // uninitialised, :197); library code never prints or calls std::exit (SC_ASSERT throws in DEBUG);
@@ -59,6 +63,7 @@
 #include <functional>
 #include <limits>
 #include <optional>
+#include <stack>
 #include <stdexcept>
 #include <string>
 #include <tuple>
@@ -584,6 +589,68 @@ public:
                   "sc_path_waypoints_batch_host");
         return r;
     }
+    // Exploration frontiers (sc_frontier_batch): `known` is [H][W], != 0 where the map has been seen.  A frontier cell is
+    // known, has d2 >= max(r2_clear, 1) and touches an unknown cell orthogonally; clusters are 8-connected.  label[c] = the
+    // smallest cell of c's cluster (-1 off the frontier), slot[c] = its column among the listed clusters (at least min_size
+    // cells, ascending by representative, at most Cmax) or -1; rep / csize / cbox {x0, y0, x1, y1} / csum {sum x, sum y} per
+    // column; listed and total count the clusters, listed in full even beyond Cmax.
+    struct frontier_result {
+        std::vector<int32_t> label, slot, rep, csize, cbox;
+        std::vector<int64_t> csum;
+        int32_t listed = 0, total = 0;
+        int Cmax = 0;
+    };
+    frontier_result frontiers(const std::vector<uint8_t>& known, int32_t r2_clear = 0, int min_size = 1, int Cmax = 128,
+                              gpu_context& ctx = default_context()) {
+        if (known.size() != occ.size()) throw std::invalid_argument("occupancy_grid::frontiers: known is not [H][W]");
+        if (d2.size() != occ.size()) edt(ctx);
+        frontier_result r;
+        r.Cmax = Cmax;
+        r.label.assign(occ.size(), -1); r.slot.assign(occ.size(), -1);
+        r.rep.assign((size_t)std::max(Cmax, 0), -1); r.csize.assign(r.rep.size(), 0); r.cbox.assign(4 * r.rep.size(), 0); r.csum.assign(2 * r.rep.size(), 0);
+        if (occ.empty()) return r;
+        int32_t ncl[2] = {0, 0};
+        ctx.check(sc_frontier_batch_host(ctx.get(), d2.data(), known.data(), 1, W, H, r2_clear, min_size, Cmax, r.label.data(), r.slot.data(), ncl,
+                                         r.rep.data(), r.csize.data(), r.cbox.data(), r.csum.data()), "sc_frontier_batch_host");
+        r.listed = ncl[0]; r.total = ncl[1];
+        return r;
+    }
+    // A frontier goal per robot (sc_d2_known_i32, sc_cost_field_batch, sc_fleet_explore_batch): the robots stand on the cells
+    // `robots`; their cost fields run through known free space only; cost / cell [R][Cmax] is the robots x clusters matrix
+    // (cost = the cheapest cell of the cluster + gain * (size_cap - min(size, size_cap)), SC_FIELD_INF when out of reach), an
+    // optimal matching gives every robot a cluster of its own: goal[r] = the cell to drive to, -1 without one, gcost[r] its
+    // cost-to-come, col_of[r] the cluster's column.  1 <= robots, Cmax <= SC_ASSIGN_MAX_DIM.
+    struct explore_result {
+        std::vector<int32_t> goal, gcost, col_of, cost, cell;
+        frontier_result fr;
+    };
+    explore_result explore_goals(const std::vector<uint8_t>& known, const std::vector<int32_t>& robots, int32_t r2_clear = 0, int min_size = 1,
+                                 int Cmax = 128, int32_t gain = 0, int32_t size_cap = 0, gpu_context& ctx = default_context()) {
+        if (known.size() != occ.size()) throw std::invalid_argument("occupancy_grid::explore_goals: known is not [H][W]");
+        if (d2.size() != occ.size()) edt(ctx);
+        const int R = (int)robots.size();
+        explore_result r;
+        frontier_result& f = r.fr;
+        f.Cmax = Cmax;
+        const size_t C = (size_t)std::max(Cmax, 0);
+        f.label.assign(occ.size(), -1); f.slot.assign(occ.size(), -1);
+        f.rep.assign(C, -1); f.csize.assign(C, 0); f.cbox.assign(4 * C, 0); f.csum.assign(2 * C, 0);
+        r.goal.assign(R, -1); r.gcost.assign(R, -1); r.col_of.assign(R, -1);
+        r.cost.assign((size_t)R * C, SC_FIELD_INF); r.cell.assign((size_t)R * C, -1);
+        if (R == 0 || occ.empty()) return r;
+        std::vector<int32_t> d2k(occ.size()), g((size_t)R * occ.size()), fstatus(R);
+        ctx.check(sc_d2_known_i32_host(ctx.get(), d2.data(), known.data(), 1, W, H, d2k.data()), "sc_d2_known_i32_host");
+        ctx.check(sc_cost_field_batch_host(ctx.get(), d2k.data(), 1, nullptr, W, H, r2_clear, robots.data(), R, -1, g.data(), fstatus.data()),
+                  "sc_cost_field_batch_host");
+        int32_t ncl[2] = {0, 0};
+        int64_t info[4] = {0, 0, 0, 0};
+        ctx.check(sc_fleet_explore_batch_host(ctx.get(), d2k.data(), known.data(), W, H, r2_clear, min_size, Cmax, g.data(), R, gain, size_cap,
+                                              f.label.data(), f.slot.data(), ncl, f.rep.data(), f.csize.data(), f.cbox.data(), f.csum.data(),
+                                              r.cost.data(), r.cell.data(), r.col_of.data(), nullptr, info, r.goal.data(), r.gcost.data()),
+                  "sc_fleet_explore_batch_host");
+        f.listed = ncl[0]; f.total = ncl[1];
+        return r;
+    }
 private:
     // both cost_fields overloads; pen NULL: the unweighted fields
     field_result cost_fields_with(const std::vector<int32_t>& roots, const std::vector<uint8_t>* pen, int pen_cap, int32_t r2_clear, int rounds,
@@ -761,6 +828,14 @@ public:
         const float wx = bound_rect.x_max - bound_rect.x_min, wy = bound_rect.y_max - bound_rect.y_min;
         const float res = std::max(wx, wy) / (float)grid_cells;
         return occupancy_grid(bound_rect, std::max(1, (int)std::ceil(wx / res)), std::max(1, (int)std::ceil(wy / res)));
+    }
+    // The known-space mask of a W x H grid over bound_rect: 1 where a free-space allocation holds the cell's centre.  The
+    // allocations are std::functions, so this is evaluated on the host; occupancy_grid::frontiers / explore_goals take it.
+    std::vector<uint8_t> known_grid(int W, int H) {
+        const occupancy_grid g(bound_rect, W, H);
+        std::vector<uint8_t> known((size_t)W * H);
+        for (int32_t c = 0; c < W * H; ++c) known[(size_t)c] = is_free_space_allocated(g.centre_of(c)) ? 1 : 0;
+        return known;
     }
     // Same role and result type as the reference's FMT* planner: start -> goal waypoint list, nullopt if
     // no path.  `n` and `rn` (sample count, connection radius) are accepted for source compatibility;
@@ -940,6 +1015,7 @@ public:
     }
 
 private:
+    friend class planner;
     int32_t clearance_r2(const occupancy_grid& g) const {
         const float cc = clearance / g.resolution;
         return (int32_t)std::ceil(cc * cc);
@@ -984,6 +1060,48 @@ private:
             out[q] = std::move(wp);
         }
         return out;
+    }
+};
+
+// ---- planner (sea_current.hpp:433-441, 465-519): where to drive next to see more ---------------------
+// The reference's members and signature.  Its pick_next_goal_point is unfinished (it traces a circle around the origin with
+// a condition marked "TODO: fix", never fills the cache and reads an empty stack when it finds nothing), so there is nothing
+// to be equal to; this one does what its comments aim at, on the grid:
+//   the disc of search_radius around start is allocated as known space (ps.free_space_allocations, as the reference's
+//   comment says: "our local area of known space will be circular"); the obstacles inside the known space are what the robot
+//   has observed; the frontier clusters of the grid (occupancy_grid::explore_goals, at most n of them listed, gain 0) are
+//   ranked by the cost of the robot's path to their cheapest cell; the cheapest is returned, the other clusters' best cells
+//   are pushed onto goal_point_cache, cheapest on top.  Without a reachable frontier the top of the cache is returned and
+//   popped; with the cache empty as well it throws std::runtime_error.
+class planner {
+public:
+    planning_space ps;
+    std::stack<Vector2f> goal_point_cache;
+    int64_t past_id = 0;
+
+    explicit planner(const planning_space& space) : ps(space) {}
+
+    Vector2f pick_next_goal_point(const Vector2f& start, const int n, const float search_radius, gpu_context& ctx = default_context()) {
+        ps.free_space_allocations.push_back([start, search_radius](Vector2f p) { return pt_dist(p, start) <= search_radius; });
+        occupancy_grid g = ps.make_grid(ctx);
+        const std::vector<uint8_t> known = ps.known_grid(g.W, g.H);
+        for (size_t c = 0; c < known.size(); ++c)
+            if (!known[c]) g.occ[c] = 0;                       // an obstacle the robot has not seen is not on its map
+        g.edt(ctx);
+        const int Cmax = std::clamp(n, 1, SC_ASSIGN_MAX_DIM);
+        const auto ex = g.explore_goals(known, {g.cell_of(start)}, ps.clearance_r2(g), 1, Cmax, 0, 0, ctx);
+        if (ex.goal[0] >= 0) {
+            std::vector<std::pair<int32_t, int32_t>> rest;     // (cost, cell) of the clusters not chosen
+            for (int k = 0; k < Cmax; ++k)
+                if (k != ex.col_of[0] && ex.cost[(size_t)k] != SC_FIELD_INF) rest.push_back({ex.cost[(size_t)k], ex.cell[(size_t)k]});
+            std::sort(rest.begin(), rest.end());
+            for (auto it = rest.rbegin(); it != rest.rend(); ++it) goal_point_cache.push(g.centre_of(it->second));
+            return g.centre_of(ex.goal[0]);
+        }
+        if (goal_point_cache.empty()) throw std::runtime_error("planner::pick_next_goal_point: no reachable frontier and no cached goal");
+        const Vector2f next = goal_point_cache.top();
+        goal_point_cache.pop();
+        return next;
     }
 };
 
