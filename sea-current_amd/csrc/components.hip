@@ -9,31 +9,24 @@
 //   8-connected reachability under the no-corner-cutting rule equals 4-connected reachability.  Hence for two traversable
 //   cells sc_astar_batch finds a path (SC_Q_OK or SC_Q_TRUNCATED) iff their labels are equal.  DESIGN.md section 15.
 //
-// Kernels: a constant number of launches on one stream, no workgroup waits for another, integer atomics only.
+// Kernels: a constant number of launches on one stream, no workgroup waits for another, integer atomics only.  The labelling
+// routines are those of tile_label.h, shared with frontier.hip.
 //   1. comp_tile_kernel: one wavefront per 64 x 64 tile, lane = column.  It reads its 64 x 64 cells of d2 into one 64-bit
-//      traversability mask per lane, keeps the column's 64 labels (tile-local indices y * 64 + x) in registers and sweeps the
-//      rows down and up in turn -- every row takes the minimum with the row before it, then a segmented min-scan across the
-//      lanes closes each horizontal run -- until a sweep, not the first, changed nothing.  Labels only fall and the cell that
-//      holds a local component's minimum keeps it, so the fixed point is that minimum on every cell.  It stores the global
-//      index of each cell's local minimum (a forest: label[c] = r with label[r] == r) and, at each local minimum, the cell
-//      count of the local component (an LDS histogram, one add per horizontal run).
+//      traversability mask per lane, runs the 4-connected tile labeller on it (sweeps to the fixed point, labels in
+//      registers) and stores the global index of each cell's local minimum (a forest: label[c] = r with label[r] == r) and,
+//      at each local minimum, the cell count of the local component.
 //   2. comp_border_kernel: one thread per pair of cells that face each other across a tile edge.  Where both are
-//      traversable it unites their trees with the lock-free union-find of Komura / Playne: find both roots, atomicMin the
-//      smaller into the larger root's slot, go on with what the atomicMin displaced.  Parents only fall, a cell's parent is
-//      always a cell of its own component with an index no larger than its own, so every interleaving ends in one tree per
-//      component whose root is the component's minimum.  All reads of a launch-shared word are relaxed agent-scope atomic
-//      loads, all writes atomicMin.
-//   3. comp_flatten_kernel: every cell follows its parents to the root (atomic loads) and stores it (atomic store: a
-//      reader sees the old parent or the root, both ancestors); a local minimum that is not the root adds its local count
-//      to the root's (atomicAdd) and clears its own; roots are counted per wavefront (ballot) into ncomp.
+//      traversable it unites their trees (the lock-free union-find: one tree per component, rooted at its minimum).
+//   3. comp_flatten_kernel: every cell follows its parents to the root and stores it; a local minimum that is not the root
+//      adds its local count to the root's and clears its own; roots are counted per wavefront (ballot) into ncomp.
 //   4. comp_largest_kernel (only when `largest` is asked for): 64-bit atomicMax of size << 32 | ~index over the roots, one
 //      per wavefront; comp_largest_out_kernel turns the key into the index.
-#include "sc_internal.h"
+#include "tile_label.h"
 
 namespace {
 
-constexpr int CT = 64;                     // tile edge (= wavefront width: lane = column)
-constexpr uint32_t CINF = 0xFFFFFFFFu;     // label of a blocked cell inside the tile kernel
+using tl::ld_agent;
+constexpr int CT = tl::T;   // tile edge
 
 struct comp_args {
     const int32_t* d2;   // [G][H][W]
@@ -42,62 +35,6 @@ struct comp_args {
     int G, W, H, TX, TY;
     int32_t thr;
 };
-
-__device__ __forceinline__ uint32_t cshup(uint32_t v, int s) { return (uint32_t)__shfl_up((int)v, s, 64); }
-__device__ __forceinline__ uint32_t cshdn(uint32_t v, int s) { return (uint32_t)__shfl_down((int)v, s, 64); }
-
-__device__ __forceinline__ int32_t ld_agent(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void st_agent(int32_t* p, int32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// minimum of v over each run of traversable lanes (tmask = ballot of T in this row): segmented min-scans left-to-right then
-// right-to-left
-__device__ __forceinline__ uint32_t seg_min(uint32_t v, uint64_t tmask, bool tc, int lane) {
-    const uint64_t blocked = ~tmask;
-    const uint64_t below = blocked & ((1ull << lane) - 1ull);
-    const int rs = below ? 64 - __clzll((long long)below) : 0;
-    const uint64_t above = lane == 63 ? 0ull : (blocked & (~0ull << (lane + 1)));
-    const int re = above ? __ffsll((long long)above) - 2 : 63;
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) {
-        const uint32_t o = cshup(v, s);
-        if (tc && lane - s >= rs) v = min(v, o);
-    }
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) {
-        const uint32_t o = cshdn(v, s);
-        if (tc && lane + s <= re) v = min(v, o);
-    }
-    return v;
-}
-
-// one row step of a sweep: row y takes the minimum with row yp = y -/+ 1 where both cells are traversable, then closes its
-// runs; returns whether it changed.  Called from fully unrolled loops only: every index of lab is a constant.
-__device__ __forceinline__ bool comp_row_step(uint32_t (&lab)[CT], uint64_t m, int y, int yp, int lane, bool force) {
-    const bool tc = ((m >> y) & 1ull) != 0;
-    const uint32_t old = lab[y];
-    uint32_t v = old;
-    if (yp >= 0 && yp < CT) {
-        if (tc && ((m >> yp) & 1ull)) v = min(v, lab[yp]);
-    }
-    if (__ballot(v < old) != 0ull || force) {
-        const uint64_t tm = __ballot(tc);
-        if (tm != 0ull) v = seg_min(v, tm, tc, lane);
-    }
-    lab[y] = v;
-    return __ballot(v < old) != 0ull;
-}
-
-__device__ __forceinline__ bool comp_sweep(uint32_t (&lab)[CT], uint64_t m, bool down, int lane, bool force) {
-    bool c = false;
-    if (down) {
-#pragma unroll
-        for (int y = 0; y < CT; ++y) c |= comp_row_step(lab, m, y, y - 1, lane, force);
-    } else {
-#pragma unroll
-        for (int y = CT - 1; y >= 0; --y) c |= comp_row_step(lab, m, y, y + 1, lane, force);
-    }
-    return c;
-}
 
 // grid (tiles, grids): grids strided
 __global__ __launch_bounds__(64) void comp_tile_kernel(comp_args a) {
@@ -121,64 +58,9 @@ __global__ __launch_bounds__(64) void comp_tile_kernel(comp_args a) {
             m |= (uint64_t)t << y;
         }
         uint32_t lab[CT];
-#pragma unroll
-        for (int y = 0; y < CT; ++y) lab[y] = ((m >> y) & 1ull) ? (uint32_t)(y * CT + lane) : CINF;
-        if (__ballot(m != 0ull) != 0ull) {
-            bool down = true;
-            for (int k = 0;; ++k) {
-                const bool c = comp_sweep(lab, m, down, lane, k == 0);
-                if (!c && k >= 1) break;
-                down = !down;
-            }
-        }
-        if (S) {
-            for (int i = lane; i < CT * CT; i += 64) cnt[i] = 0;
-            wave_lds_sync();
-            // one add per horizontal run: its cells share a label
-#pragma unroll
-            for (int y = 0; y < CT; ++y) {
-                const bool tc = ((m >> y) & 1ull) != 0;
-                const uint64_t tm = __ballot(tc);
-                if (tc && (lane == 0 || !((tm >> (lane - 1)) & 1ull))) {
-                    const uint64_t r = ~(tm >> lane);
-                    atomicAdd(&cnt[lab[y]], r ? __ffsll((long long)r) - 1 : 64);
-                }
-            }
-            wave_lds_sync();
-        }
-#pragma unroll
-        for (int y = 0; y < CT; ++y) {
-            if (colin && y < th) {
-                const size_t c = (size_t)(y0 + y) * W + cx;
-                const uint32_t l = lab[y];
-                const bool tc = l != CINF;
-                L[c] = tc ? (int32_t)((y0 + (int)(l >> 6)) * W + x0 + (int)(l & 63u)) : -1;
-                if (S) S[c] = (tc && l == (uint32_t)(y * CT + lane)) ? cnt[l] : 0;
-            }
-        }
-        wave_lds_sync();   // cnt is reused by the next grid
-    }
-}
-
-__device__ __forceinline__ int32_t comp_find(const int32_t* L, int32_t x) {
-    for (;;) {
-        const int32_t p = ld_agent(L + x);
-        if (p == x) return x;
-        x = p;
-    }
-}
-
-// unite the trees of a and b (cells of one grid): the larger root is linked to the smaller; when the atomicMin finds the
-// larger root linked meanwhile, the link it displaced (or the one it lost to) is united in turn
-__device__ __forceinline__ void comp_unite(int32_t* L, int32_t a, int32_t b) {
-    for (;;) {
-        a = comp_find(L, a);
-        b = comp_find(L, b);
-        if (a == b) return;
-        if (a < b) { const int32_t t = a; a = b; b = t; }
-        const int32_t old = atomicMin(L + a, b);
-        if (old == a) return;
-        a = old;
+        tl::label_tile<false>(lab, m, lane);
+        if (S) tl::count_runs(cnt, lab, m, lane);
+        tl::store_forest(L, S, cnt, lab, W, x0, y0, th, colin, lane);
     }
 }
 
@@ -191,22 +73,13 @@ __global__ __launch_bounds__(256) void comp_border_kernel(int32_t* label, int G,
     for (int gi = blockIdx.y; gi < G; gi += gridDim.y) {
         int32_t* L = label + (size_t)gi * n;
         for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < ne; i += (size_t)gridDim.x * blockDim.x) {
-            int a, b, step;
-            bool first;
-            if (i < ne_h) {
-                const int t = (int)(i / W) + 1, x = (int)(i % W);
-                a = (t * CT - 1) * W + x; b = a + W; step = 1; first = (x % CT) == 0;
-            } else {
-                const size_t j = i - ne_h;
-                const int t = (int)(j / H) + 1, y = (int)(j % H);
-                a = y * W + t * CT - 1; b = a + 1; step = W; first = (y % CT) == 0;
-            }
-            const int32_t la = ld_agent(L + a);
+            const tl::edge e = tl::edge_decode(i, ne_h, W, H);
+            const int32_t la = ld_agent(L + e.a);
             if (la < 0) continue;
-            const int32_t lb = ld_agent(L + b);
+            const int32_t lb = ld_agent(L + e.b);
             if (lb < 0) continue;
-            if (!first && ld_agent(L + a - step) >= 0 && ld_agent(L + b - step) >= 0) continue;
-            comp_unite(L, la, lb);
+            if (e.pos % CT != 0 && ld_agent(L + e.a - e.step) >= 0 && ld_agent(L + e.b - e.step) >= 0) continue;
+            tl::unite(L, la, lb);
         }
     }
 }
@@ -216,25 +89,7 @@ __global__ __launch_bounds__(256) void comp_flatten_kernel(int32_t* label, int32
     const size_t n = (size_t)W * H;
     const size_t c = (size_t)blockIdx.x * 256 + threadIdx.x;
     for (int gi = blockIdx.y; gi < G; gi += gridDim.y) {
-        int32_t* L = label + (size_t)gi * n;
-        bool root = false;
-        if (c < n) {
-            const int32_t l = ld_agent(L + c);
-            if (l >= 0) {
-                const int32_t r = comp_find(L, l);
-                if (r != l) st_agent(L + c, r);
-                root = r == (int32_t)c;
-                if (sz && !root) {
-                    // a cell that is not a root receives no adds: its count is what the tile kernel stored
-                    int32_t* S = sz + (size_t)gi * n;
-                    const int32_t s = S[c];
-                    if (s) {
-                        atomicAdd(S + r, s);
-                        S[c] = 0;
-                    }
-                }
-            }
-        }
+        const bool root = c < n && tl::flatten_cell(label + (size_t)gi * n, sz ? sz + (size_t)gi * n : nullptr, c);
         if (ncomp) {
             const int k = __popcll(__ballot(root));
             if ((threadIdx.x & 63) == 0 && k) atomicAdd(ncomp + gi, k);

@@ -41,7 +41,7 @@
 //   Read-out: field_paths_kernel with the end cell seed[owner[target]] in place of the root.
 #include <type_traits>
 
-#include "sc_internal.h"
+#include "tile_label.h"   // the wave shuffles
 
 namespace {
 
@@ -72,14 +72,7 @@ struct field_args_w : field_args {
     uint32_t cap;            // pen_cap
 };
 
-__device__ __forceinline__ uint32_t shup(uint32_t v, int s) { return (uint32_t)__shfl_up((int)v, s, 64); }
-__device__ __forceinline__ uint32_t shdn(uint32_t v, int s) { return (uint32_t)__shfl_down((int)v, s, 64); }
-__device__ __forceinline__ uint64_t shup64(uint64_t v) {
-    return ((uint64_t)shup((uint32_t)(v >> 32), 1) << 32) | shup((uint32_t)v, 1);
-}
-__device__ __forceinline__ uint64_t shdn64(uint64_t v) {
-    return ((uint64_t)shdn((uint32_t)(v >> 32), 1) << 32) | shdn((uint32_t)v, 1);
-}
+using tl::shup, tl::shdn, tl::shup64, tl::shdn64;
 __device__ __forceinline__ uint32_t rdl(uint32_t v, int l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, l); }
 
 // traversability of row y (-1 .. 64) of a column: m = rows 0..63, ex bit 0 = row -1, bit 1 = row 64

@@ -12,16 +12,12 @@
 //   2. fr_tile_kernel: one wavefront per 64 x 64 tile, lane = column.  The unknown cells of the column, of the rows above and
 //      below the tile (one byte per lane) and of the columns left and right of it (lane = row, one ballot each) give the
 //      known cells that touch unknown space; d2 is read for those only.  A tile with none leaves after that ballot (it
-//      still writes its -1 labels).  Otherwise the labels (tile-local y * 64 + x) stay in registers and the rows are swept
-//      down and up in turn: a row takes the minimum with the three cells of the row before it (the vertical one and, with two
-//      shuffles, the diagonal ones), then a segmented min-scan closes each horizontal run -- until a sweep, not the first,
-//      changed nothing.  A sweep leaves every cell <= its three neighbours in the row it came from and every run closed, so
-//      a state that the opposite sweep leaves unchanged has every cell <= all of its eight neighbours: constant on every
-//      8-connected set; labels only fall and stay indices of cells of the own cluster, so that constant is the minimum.
-//      It stores the forest (global index of the tile-local minimum) and, at each local minimum, the local cell count.
+//      still writes its -1 labels).  Otherwise the 8-connected tile labeller of tile_label.h runs on the mask (sweeps to the
+//      fixed point, labels in registers) and stores the forest (global index of the tile-local minimum) and, at each local
+//      minimum, the local cell count.
 //   3. fr_border_kernel: one thread per cell along the near side of a tile edge; where it is a frontier cell it unites its
 //      tree with those of the (up to three) cells it touches across the edge, diagonal ones and tile corners included:
-//      the lock-free union-find of components.hip (atomicMin of the smaller root into the larger root's slot).
+//      the lock-free union-find of tile_label.h (atomicMin of the smaller root into the larger root's slot).
 //   4. fr_flatten_kernel: every cell follows its parents to the root and stores it; local counts are added to the root's;
 //      roots are counted into ncl[g][1].
 //   5. fr_count_kernel / 6. fr_scan_kernel / 7. fr_rank_kernel: the listed clusters (size >= min_size) in ascending order of
@@ -30,12 +26,12 @@
 //      box of its own cell, and its column into the size scratch.
 //   8. fr_slot_kernel (only when slot, cbox or csum is asked for): every frontier cell reads its root's column, stores it,
 //      and adds itself to the box (atomicMin / atomicMax) and to the coordinate sums (64-bit atomicAdd).
-#include "sc_internal.h"
+#include "tile_label.h"
 
 namespace {
 
-constexpr int FT = 64;                     // tile edge (= wavefront width: lane = column)
-constexpr uint32_t FINF = 0xFFFFFFFFu;     // label of a cell that is no frontier cell inside the tile kernel
+using tl::ld_agent;
+constexpr int FT = tl::T;                  // tile edge
 constexpr int FR_BLOCK = 256;              // cells per block of the count / rank kernels
 constexpr int FR_SCAN = 1024;              // threads of the scan kernel
 
@@ -47,69 +43,6 @@ struct fr_args {
     int G, W, H, TX, TY;
     int32_t thr;
 };
-
-__device__ __forceinline__ uint32_t fshup(uint32_t v, int s) { return (uint32_t)__shfl_up((int)v, s, 64); }
-__device__ __forceinline__ uint32_t fshdn(uint32_t v, int s) { return (uint32_t)__shfl_down((int)v, s, 64); }
-__device__ __forceinline__ uint64_t fshup64(uint64_t v) {
-    return ((uint64_t)fshup((uint32_t)(v >> 32), 1) << 32) | fshup((uint32_t)v, 1);
-}
-__device__ __forceinline__ uint64_t fshdn64(uint64_t v) {
-    return ((uint64_t)fshdn((uint32_t)(v >> 32), 1) << 32) | fshdn((uint32_t)v, 1);
-}
-
-__device__ __forceinline__ int32_t fr_ld(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void fr_st(int32_t* p, int32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// minimum of v over each run of frontier lanes (tmask = ballot of the row's frontier cells): segmented min-scans left-to-right
-// then right-to-left
-__device__ __forceinline__ uint32_t fr_seg_min(uint32_t v, uint64_t tmask, bool tc, int lane) {
-    const uint64_t blocked = ~tmask;
-    const uint64_t below = blocked & ((1ull << lane) - 1ull);
-    const int rs = below ? 64 - __clzll((long long)below) : 0;
-    const uint64_t above = lane == 63 ? 0ull : (blocked & (~0ull << (lane + 1)));
-    const int re = above ? __ffsll((long long)above) - 2 : 63;
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) {
-        const uint32_t o = fshup(v, s);
-        if (tc && lane - s >= rs) v = min(v, o);
-    }
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) {
-        const uint32_t o = fshdn(v, s);
-        if (tc && lane + s <= re) v = min(v, o);
-    }
-    return v;
-}
-
-// one row step of a sweep: row y takes the minimum with the three cells of row yp = y -/+ 1 it touches (a cell that is no
-// frontier cell holds FINF), then closes its runs; returns whether it changed.  rows: bit y set where row y of the tile
-// has a frontier cell (wave-uniform).  Called from fully unrolled loops only: every index of lab is a constant.
-__device__ __forceinline__ bool fr_row_step(uint32_t (&lab)[FT], uint64_t m, uint64_t rows, int y, int yp, int lane, bool force) {
-    if (!((rows >> y) & 1ull)) return false;
-    const bool tc = ((m >> y) & 1ull) != 0;
-    const uint32_t old = lab[y];
-    uint32_t v = old;
-    if (yp >= 0 && yp < FT && ((rows >> yp) & 1ull)) {
-        const uint32_t p = lab[yp];
-        const uint32_t pl = fshup(p, 1), pr = fshdn(p, 1);   // lanes 0 / 63 receive their own p
-        if (tc) v = min(v, min(p, min(pl, pr)));
-    }
-    if (__ballot(v < old) != 0ull || force) v = fr_seg_min(v, __ballot(tc), tc, lane);
-    lab[y] = v;
-    return __ballot(v < old) != 0ull;
-}
-
-__device__ __forceinline__ bool fr_sweep(uint32_t (&lab)[FT], uint64_t m, uint64_t rows, bool down, int lane, bool force) {
-    bool c = false;
-    if (down) {
-#pragma unroll
-        for (int y = 0; y < FT; ++y) c |= fr_row_step(lab, m, rows, y, y - 1, lane, force);
-    } else {
-#pragma unroll
-        for (int y = FT - 1; y >= 0; --y) c |= fr_row_step(lab, m, rows, y, y + 1, lane, force);
-    }
-    return c;
-}
 
 // grid (tiles, grids): grids strided
 __global__ __launch_bounds__(64) void fr_tile_kernel(fr_args a) {
@@ -141,7 +74,7 @@ __global__ __launch_bounds__(64) void fr_tile_kernel(fr_args a) {
         const bool ubelow = colin && y0 + FT < H && K[(size_t)(y0 + FT) * W + cx] == 0;
         const uint64_t lcol = __ballot(x0 > 0 && lane < th && K[(size_t)(y0 + lane) * W + x0 - 1] == 0);        // lane = row
         const uint64_t rcol = __ballot(x0 + FT < W && lane < th && K[(size_t)(y0 + lane) * W + x0 + FT] == 0);
-        uint64_t lm = fshup64(unk), rm = fshdn64(unk);
+        uint64_t lm = tl::shup64(unk), rm = tl::shdn64(unk);
         if (lane == 0) lm = lcol;
         if (lane == 63) rm = rcol;
         const uint64_t nb = (unk << 1) | (uint64_t)uabove | (unk >> 1) | ((uint64_t)ubelow << 63) | lm | rm;
@@ -164,64 +97,10 @@ __global__ __launch_bounds__(64) void fr_tile_kernel(fr_args a) {
             }
             continue;
         }
-        uint64_t rows = 0;
-#pragma unroll
-        for (int y = 0; y < FT; ++y) rows |= (uint64_t)(__ballot((m >> y) & 1ull) != 0ull) << y;
         uint32_t lab[FT];
-#pragma unroll
-        for (int y = 0; y < FT; ++y) lab[y] = ((m >> y) & 1ull) ? (uint32_t)(y * FT + lane) : FINF;
-        bool down = true;
-        for (int k = 0;; ++k) {
-            const bool c = fr_sweep(lab, m, rows, down, lane, k == 0);
-            if (!c && k >= 1) break;
-            down = !down;
-        }
-        for (int i = lane; i < FT * FT; i += 64) cnt[i] = 0;
-        wave_lds_sync();
-        // one add per horizontal run: its cells share a label
-#pragma unroll
-        for (int y = 0; y < FT; ++y) {
-            const bool tc = ((m >> y) & 1ull) != 0;
-            const uint64_t tm = __ballot(tc);
-            if (tc && (lane == 0 || !((tm >> (lane - 1)) & 1ull))) {
-                const uint64_t r = ~(tm >> lane);
-                atomicAdd(&cnt[lab[y]], r ? __ffsll((long long)r) - 1 : 64);
-            }
-        }
-        wave_lds_sync();
-#pragma unroll
-        for (int y = 0; y < FT; ++y) {
-            if (colin && y < th) {
-                const size_t c = (size_t)(y0 + y) * W + cx;
-                const uint32_t l = lab[y];
-                const bool tc = l != FINF;
-                L[c] = tc ? (int32_t)((y0 + (int)(l >> 6)) * W + x0 + (int)(l & 63u)) : -1;
-                S[c] = (tc && l == (uint32_t)(y * FT + lane)) ? cnt[l] : 0;
-            }
-        }
-        wave_lds_sync();   // cnt is reused by the next grid
-    }
-}
-
-__device__ __forceinline__ int32_t fr_find(const int32_t* L, int32_t x) {
-    for (;;) {
-        const int32_t p = fr_ld(L + x);
-        if (p == x) return x;
-        x = p;
-    }
-}
-
-// unite the trees of a and b (cells of one grid): the larger root is linked to the smaller; when the atomicMin finds the
-// larger root linked meanwhile, the link it displaced (or the one it lost to) is united in turn
-__device__ __forceinline__ void fr_unite(int32_t* L, int32_t a, int32_t b) {
-    for (;;) {
-        a = fr_find(L, a);
-        b = fr_find(L, b);
-        if (a == b) return;
-        if (a < b) { const int32_t t = a; a = b; b = t; }
-        const int32_t old = atomicMin(L + a, b);
-        if (old == a) return;
-        a = old;
+        tl::label_tile<true>(lab, m, lane);
+        tl::count_runs(cnt, lab, m, lane);
+        tl::store_forest(L, S, cnt, lab, W, x0, y0, th, colin, lane);
     }
 }
 
@@ -236,22 +115,14 @@ __global__ __launch_bounds__(256) void fr_border_kernel(int32_t* label, int G, i
     for (int gi = blockIdx.y; gi < G; gi += gridDim.y) {
         int32_t* L = label + (size_t)gi * n;
         for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < ne; i += (size_t)gridDim.x * blockDim.x) {
-            int a, b, step;
-            bool lo, hi;   // the diagonal partners b - step / b + step are inside the grid
-            if (i < ne_h) {
-                const int t = (int)(i / W) + 1, x = (int)(i % W);
-                a = (t * FT - 1) * W + x; b = a + W; step = 1; lo = x > 0; hi = x + 1 < W;
-            } else {
-                const size_t j = i - ne_h;
-                const int t = (int)(j / H) + 1, y = (int)(j % H);
-                a = y * W + t * FT - 1; b = a + 1; step = W; lo = y > 0; hi = y + 1 < H;
-            }
-            const int32_t la = fr_ld(L + a);
+            const tl::edge e = tl::edge_decode(i, ne_h, W, H);
+            const int32_t la = ld_agent(L + e.a);
             if (la < 0) continue;
-            int32_t lb = fr_ld(L + b);
-            if (lb >= 0) fr_unite(L, la, lb);
-            if (lo && (lb = fr_ld(L + b - step)) >= 0) fr_unite(L, la, lb);
-            if (hi && (lb = fr_ld(L + b + step)) >= 0) fr_unite(L, la, lb);
+            int32_t lb = ld_agent(L + e.b);
+            if (lb >= 0) tl::unite(L, la, lb);
+            // the diagonal partners, where they are inside the grid
+            if (e.pos > 0 && (lb = ld_agent(L + e.b - e.step)) >= 0) tl::unite(L, la, lb);
+            if (e.pos + 1 < e.len && (lb = ld_agent(L + e.b + e.step)) >= 0) tl::unite(L, la, lb);
         }
     }
 }
@@ -261,25 +132,7 @@ __global__ __launch_bounds__(256) void fr_flatten_kernel(int32_t* label, int32_t
     const size_t n = (size_t)W * H;
     const size_t c = (size_t)blockIdx.x * 256 + threadIdx.x;
     for (int gi = blockIdx.y; gi < G; gi += gridDim.y) {
-        int32_t* L = label + (size_t)gi * n;
-        int32_t* S = sz + (size_t)gi * n;
-        bool root = false;
-        if (c < n) {
-            const int32_t l = fr_ld(L + c);
-            if (l >= 0) {
-                const int32_t r = fr_find(L, l);
-                if (r != l) fr_st(L + c, r);
-                root = r == (int32_t)c;
-                if (!root) {
-                    // a cell that is not a root receives no adds: its count is what the tile kernel stored
-                    const int32_t s = S[c];
-                    if (s) {
-                        atomicAdd(S + r, s);
-                        S[c] = 0;
-                    }
-                }
-            }
-        }
+        const bool root = c < n && tl::flatten_cell(label + (size_t)gi * n, sz + (size_t)gi * n, c);
         const int k = __popcll(__ballot(root));
         if ((threadIdx.x & 63) == 0 && k) atomicAdd(ncl + 2 * gi + 1, k);
     }
