@@ -230,8 +230,7 @@ __global__ void __launch_bounds__(CV_THREADS) curve_clear_kernel(cv_clear_args a
 }
 
 int sc_curve_grid_ok(const sc_speed_frame& fr, int32_t r2_clear) {
-    return fr.d2 && r2_clear >= 0 && fr.W >= 1 && fr.W <= SC_MAX_DIM && fr.H >= 1 && fr.H <= SC_MAX_DIM && isfinite(fr.x_min) &&
-           isfinite(fr.y_min) && fr.res_x > 0.f && isfinite(fr.res_x) && fr.res_y > 0.f && isfinite(fr.res_y);
+    return fr.d2 && r2_clear >= 0 && sc_frame_ok(fr);
 }
 
 static cv_grid cv_make_grid(const sc_speed_frame& fr, int32_t r2_clear) {

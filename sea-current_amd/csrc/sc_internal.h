@@ -1,6 +1,7 @@
 // sc_internal.h -- context, scratch and launch-timing plumbing shared by the HIP sources.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
@@ -185,6 +186,11 @@ struct sc_speed_frame {
     int W, H;
     float x_min, y_min, res_x, res_y;
 };
+// the frames every call accepts: dimensions 1 .. SC_MAX_DIM, a finite origin, finite resolutions > 0 (d2 is the caller's matter)
+static inline bool sc_frame_ok(const sc_speed_frame& fr) {
+    return fr.W >= 1 && fr.W <= SC_MAX_DIM && fr.H >= 1 && fr.H <= SC_MAX_DIM && isfinite(fr.x_min) && isfinite(fr.y_min) &&
+           isfinite(fr.res_x) && fr.res_x > 0.f && isfinite(fr.res_y) && fr.res_y > 0.f;
+}
 // ns_bound: an upper bound of the legs of one path (sizes the LDS the kernel stages a path's tables in), <= 0: not known.
 // vlo (may be NULL) receives vel_min per stage, vhi_copy (may be NULL) a second copy of vhi.
 int sc_launch_speed_limits(sc_ctx* ctx, const float* ctrl, const float* cum, const int32_t* seg_off, const float* arclength,
@@ -220,17 +226,8 @@ __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_wave_barrier();
 }
 
-// m2 of the path conflicts (the definition in include/sea_current_hip.h): the squared closest approach on one interval of two
-// motions whose difference goes from d0 to d1, in the order of operations of traj.hip's pair kernel (compile without contraction)
-__device__ __forceinline__ double sc_traj_m2(double d0x, double d0y, double d1x, double d1y) {
-    const double ex = d1x - d0x, ey = d1y - d0y;
-    const double aa = ex * ex + ey * ey;
-    const double bb = d0x * ex + d0y * ey;
-    const double q = -bb / aa;
-    const double lam = aa > 0.0 ? (q < 0.0 ? 0.0 : (q > 1.0 ? 1.0 : q)) : 0.0;
-    const double px = d0x + lam * ex, py = d0y + lam * ey;
-    return px * px + py * py;
-}
+// the float32 centre of cell i of an axis with origin o and resolution r (occupancy_grid::centre_of), rounding by rounding
+__device__ __forceinline__ float sc_cell_centre(int i, float o, float r) { return __fadd_rn(o, __fmul_rn(__fadd_rn((float)i, 0.5f), r)); }
 
 // point (order 0), hodograph (1) or second derivative (2) of the cubic Bezier c [4][2] at parameter s, in fp64
 __device__ __forceinline__ void bez_eval(const float* c, double s, int order, double& ox, double& oy) {

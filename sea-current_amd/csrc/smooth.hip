@@ -474,8 +474,8 @@ cells_to_points_kernel(const int32_t* __restrict__ wp, const int32_t* __restrict
     else if (ends && i == np - 1) { x = goals[2 * (size_t)q]; y = goals[2 * (size_t)q + 1]; }
     else {
         const int c = wp[(size_t)q * Wmax + i];
-        x = __fadd_rn(x_min, __fmul_rn(__fadd_rn((float)(c % W), 0.5f), res_x));
-        y = __fadd_rn(y_min, __fmul_rn(__fadd_rn((float)(c / W), 0.5f), res_y));
+        x = sc_cell_centre(c % W, x_min, res_x);
+        y = sc_cell_centre(c / W, y_min, res_y);
     }
     path[((size_t)q * Wmax + i) * 2] = x;
     path[((size_t)q * Wmax + i) * 2 + 1] = y;

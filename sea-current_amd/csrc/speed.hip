@@ -204,9 +204,7 @@ __global__ void __launch_bounds__(SP_THREADS) speed_limits_kernel(sp_args a) {
 
 int sc_speed_args_ok(int J, const double* dyn, const sc_speed_frame& fr) {
     if (!dyn || J < 1 || J > SC_SPEED_MAX_J) return 0;
-    if (fr.d2 && (fr.W < 1 || fr.W > SC_MAX_DIM || fr.H < 1 || fr.H > SC_MAX_DIM || !isfinite(fr.x_min) || !isfinite(fr.y_min) ||
-                  !(fr.res_x > 0.f) || !isfinite(fr.res_x) || !(fr.res_y > 0.f) || !isfinite(fr.res_y)))
-        return 0;
+    if (fr.d2 && !sc_frame_ok(fr)) return 0;
     return 1;
 }
 

@@ -3,7 +3,7 @@
 // sc_fleet_replan_batch; the definition is in include/sea_current_hip.h and DESIGN.md section 20).
 //
 // Reserve: a wavefront per (path, interval).  It clips the capsule's cell box to the grid, widens it to whole 32-cell words,
-// and walks it two words at a time: lane = cell, the predicate of the path conflicts (sc_traj_m2) per cell, __ballot, and the
+// and walks it two words at a time: lane = cell, the predicate of the path conflicts (sc_traj_closest) per cell, __ballot, and the
 // lanes 0 and 32 OR their halves into layers k and k+1.  The box is a superset of the hit cells (its margin covers the
 // float32 rounding of the cell centres), so the result equals the definition, which tests every cell.
 // Planes: one pass over the move bytes, __ballot per direction: plane d = the cells with bit d of the move byte set.
@@ -19,10 +19,8 @@
 // is larger than the launch's base layer), so every layer up to the arrival is complete.
 // Read-out: one thread per query walks back from (goal, arrive), waits first, then the directions in order.
 //
-// Compiled with -ffp-contract=off: the reservation predicate is the one of traj.hip, without fused multiply-adds.
-#include "sc_internal.h"
-
-#include <math.h>
+// Compiled with -ffp-contract=off: the reservation predicate is the one of traj.hip (sc_traj_closest of traj_common.h), without fused multiply-adds.
+#include "traj_common.h"
 
 #define TP_TW 8                      // interior words of a tile (256 cells)
 #define TP_TH 64                     // interior rows of a tile
@@ -42,8 +40,6 @@ struct tp_q {
     int32_t status;
 };
 
-__device__ __forceinline__ float tp_centre(int i, float o, float r) { return __fadd_rn(o, __fmul_rn(__fadd_rn((float)i, 0.5f), r)); }
-
 // ---- reserve ---------------------------------------------------------------------------------------------------------
 struct tp_reserve_args {
     const double* knots;
@@ -52,12 +48,10 @@ struct tp_reserve_args {
     const int32_t* select;     // may be NULL: all
     int P, K;
     double pad;
-    int W, H, Wq, margin;
-    float x_min, y_min, res_x, res_y;
+    sc_speed_frame fr;         // d2 is not read
+    int Wq, margin;
     uint32_t* res;
 };
-
-__device__ __forceinline__ double tp_clampd(double x, double lo, double hi) { return x < lo ? lo : (x > hi ? hi : x); }
 
 __global__ void __launch_bounds__(256) tplan_reserve_kernel(tp_reserve_args a) {
     const int lane = threadIdx.x & 63;
@@ -65,27 +59,26 @@ __global__ void __launch_bounds__(256) tplan_reserve_kernel(tp_reserve_args a) {
     if (item >= (long long)a.P * a.K) return;
     const int q = (int)(item / a.K), k = (int)(item % a.K);
     const double r = a.radius[q];
-    const bool r_ok = isfinite(r) && r >= 0.0;
-    const int st = a.tstatus ? a.tstatus[q] : SC_TRAJ_OK;
-    if (!r_ok) {
-        if (a.tstatus && k == 0 && lane == 0 && st == SC_TRAJ_OK) a.tstatus[q] = SC_TRAJ_BAD;   // every wavefront of q leaves on r_ok alone
+    if (!sc_traj_radius_ok(r)) {   // every wavefront of q leaves on the radius alone
+        if (a.tstatus && k == 0 && lane == 0) sc_traj_mark_radius(a.tstatus, q, r);
         return;
     }
-    if (st != SC_TRAJ_OK || (a.select && a.select[q] == 0)) return;
+    if ((a.tstatus && a.tstatus[q] != SC_TRAJ_OK) || (a.select && a.select[q] == 0)) return;
     const double* kn = a.knots + ((size_t)q * (a.K + 1) + k) * 2;
     const double ax = kn[0], ay = kn[1], bx = kn[2], by = kn[3];
     if (isnan(ax) || isnan(ay) || isnan(bx) || isnan(by)) return;
     const double R = r + a.pad, RR = R * R;
     // the cell box: centres within R of the segment's box, `margin` cells wider than the exact one
-    const double fx0 = ((fmin(ax, bx) - R) - (double)a.x_min) / (double)a.res_x - 0.5, fx1 = ((fmax(ax, bx) + R) - (double)a.x_min) / (double)a.res_x - 0.5;
-    const double fy0 = ((fmin(ay, by) - R) - (double)a.y_min) / (double)a.res_y - 0.5, fy1 = ((fmax(ay, by) + R) - (double)a.y_min) / (double)a.res_y - 0.5;
+    const sc_speed_frame& f = a.fr;
+    const double fx0 = ((fmin(ax, bx) - R) - (double)f.x_min) / (double)f.res_x - 0.5, fx1 = ((fmax(ax, bx) + R) - (double)f.x_min) / (double)f.res_x - 0.5;
+    const double fy0 = ((fmin(ay, by) - R) - (double)f.y_min) / (double)f.res_y - 0.5, fy1 = ((fmax(ay, by) + R) - (double)f.y_min) / (double)f.res_y - 0.5;
     if (!(fx1 >= fx0) || !(fy1 >= fy0)) return;   // not finite
-    const int x0 = (int)tp_clampd(floor(fx0) - a.margin, 0.0, (double)a.W), x1 = (int)tp_clampd(ceil(fx1) + a.margin, -1.0, (double)(a.W - 1));
-    const int y0 = (int)tp_clampd(floor(fy0) - a.margin, 0.0, (double)a.H), y1 = (int)tp_clampd(ceil(fy1) + a.margin, -1.0, (double)(a.H - 1));
+    const int x0 = (int)sc_clampd(floor(fx0) - a.margin, 0.0, (double)f.W), x1 = (int)sc_clampd(ceil(fx1) + a.margin, -1.0, (double)(f.W - 1));
+    const int y0 = (int)sc_clampd(floor(fy0) - a.margin, 0.0, (double)f.H), y1 = (int)sc_clampd(ceil(fy1) + a.margin, -1.0, (double)(f.H - 1));
     if (x1 < x0 || y1 < y0) return;
     const int w0 = x0 >> 5, nw = (x1 >> 5) - w0 + 1;        // words of a box row
     const int np = (nw + 1) >> 1;                           // word pairs of a box row
-    const size_t layer = (size_t)a.H * a.Wq;
+    const size_t layer = (size_t)f.H * a.Wq;
     uint32_t* l0 = a.res + (size_t)k * layer;
     const long long n = (long long)(y1 - y0 + 1) * np;
     for (long long i = 0; i < n; ++i) {                     // wavefront-uniform
@@ -93,8 +86,8 @@ __global__ void __launch_bounds__(256) tplan_reserve_kernel(tp_reserve_args a) {
         const int x = w * 32 + (lane & 31);
         bool hit = false;
         if (x >= x0 && x <= x1) {
-            const double cx = (double)tp_centre(x, a.x_min, a.res_x), cy = (double)tp_centre(y, a.y_min, a.res_y);
-            hit = sc_traj_m2(ax - cx, ay - cy, bx - cx, by - cy) < RR;
+            const double cx = (double)sc_cell_centre(x, f.x_min, f.res_x), cy = (double)sc_cell_centre(y, f.y_min, f.res_y);
+            hit = sc_traj_closest(ax - cx, ay - cy, bx - cx, by - cy).m2 < RR;
         }
         const unsigned long long m = __ballot(hit);
         const uint32_t word = (uint32_t)(m >> (lane & 32));
@@ -315,8 +308,8 @@ __global__ void __launch_bounds__(64) tplan_read_kernel(tp_read_args a) {
 struct tp_knots_args {
     const tp_q* qs;
     const int32_t* path;
-    int W, L, B, hold;
-    float x_min, y_min, res_x, res_y;
+    int L, B, hold;
+    sc_speed_frame fr;
     double* knots_out;
 };
 
@@ -331,36 +324,31 @@ __global__ void __launch_bounds__(256) tplan_knots_kernel(tp_knots_args a) {
         else if (a.hold) c = q.goal;
     }
     double x = NAN, y = NAN;
-    if (c >= 0) { x = (double)tp_centre(c % a.W, a.x_min, a.res_x); y = (double)tp_centre(c / a.W, a.y_min, a.res_y); }
+    if (c >= 0) { x = (double)sc_cell_centre(c % a.fr.W, a.fr.x_min, a.fr.res_x); y = (double)sc_cell_centre(c / a.fr.W, a.fr.y_min, a.fr.res_y); }
     a.knots_out[2 * i] = x;
     a.knots_out[2 * i + 1] = y;
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------
-static bool tp_frame_invalid(int W, int H, float x_min, float y_min, float res_x, float res_y) {
-    return W < 1 || H < 1 || W > SC_MAX_DIM || H > SC_MAX_DIM || !isfinite(x_min) || !isfinite(y_min) || !isfinite(res_x) || !isfinite(res_y) ||
-           !(res_x > 0.f) || !(res_y > 0.f);
+// the grid of a call is a sc_speed_frame: a reservation reads no d2, a plan the origin and the resolutions only for knots_out
+static bool tp_reserve_invalid(sc_ctx* ctx, const double* knots, int P, int K, const double* radius, double pad, const sc_speed_frame& fr,
+                               const uint32_t* res) {
+    return !ctx || !knots || !radius || !res || !sc_traj_size_ok(P, K) || !isfinite(pad) || pad < 0.0 || !sc_frame_ok(fr);
 }
 
-static bool tp_reserve_invalid(sc_ctx* ctx, const double* knots, int P, int K, const double* radius, double pad, int W, int H, float x_min,
-                               float y_min, float res_x, float res_y, const uint32_t* res) {
-    return !ctx || !knots || !radius || !res || P < 1 || P > 16384 || K < 1 || K > 65535 || (long long)P * ((long long)K + 1) > (1ll << 26) ||
-           !isfinite(pad) || pad < 0.0 || tp_frame_invalid(W, H, x_min, y_min, res_x, res_y);
-}
-
-static bool tp_plan_invalid(sc_ctx* ctx, const int32_t* d2, int W, int H, int L, const int32_t* start, const int32_t* goal, int B,
-                            const int32_t* status, const double* knots_out, float x_min, float y_min, float res_x, float res_y) {
-    return !ctx || !d2 || !start || !goal || !status || W < 1 || H < 1 || W > SC_MAX_DIM || H > SC_MAX_DIM || L < 1 || L > TP_MAX_L || B < 1 ||
-           B > TP_MAX_B || (knots_out && tp_frame_invalid(W, H, x_min, y_min, res_x, res_y));
+static bool tp_plan_invalid(sc_ctx* ctx, const sc_speed_frame& fr, int L, const int32_t* start, const int32_t* goal, int B,
+                            const int32_t* status, const double* knots_out) {
+    return !ctx || !fr.d2 || !start || !goal || !status || fr.W < 1 || fr.H < 1 || fr.W > SC_MAX_DIM || fr.H > SC_MAX_DIM || L < 1 ||
+           L > TP_MAX_L || B < 1 || B > TP_MAX_B || (knots_out && !sc_frame_ok(fr));
 }
 
 static int tp_launch_reserve(sc_ctx* ctx, const double* knots, int32_t* tstatus, int P, int K, const double* radius, const int32_t* select,
-                             double pad, int W, int H, float x_min, float y_min, float res_x, float res_y, uint32_t* res) {
+                             double pad, const sc_speed_frame& fr, uint32_t* res) {
     // cells the float32 rounding of a centre can move it by, plus one for floor / ceil and one to spare
-    const double span_x = fabs((double)x_min) + (double)W * res_x, span_y = fabs((double)y_min) + (double)H * res_y;
-    double m = fmax(span_x / res_x, span_y / res_y) * 0x1p-22 + 2.0;
+    const double span_x = fabs((double)fr.x_min) + (double)fr.W * fr.res_x, span_y = fabs((double)fr.y_min) + (double)fr.H * fr.res_y;
+    double m = fmax(span_x / fr.res_x, span_y / fr.res_y) * 0x1p-22 + 2.0;
     if (!(m < 16384.0)) m = 16384.0;
-    tp_reserve_args a{knots, tstatus, radius, select, P, K, pad, W, H, (W + 31) / 32, (int)ceil(m), x_min, y_min, res_x, res_y, res};
+    tp_reserve_args a{knots, tstatus, radius, select, P, K, pad, fr, (fr.W + 31) / 32, (int)ceil(m), res};
     const long long items = (long long)P * K;
     int tk = sc_time_begin(ctx, SC_K_ASTAR);
     hipLaunchKernelGGL(tplan_reserve_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, ctx->stream, a);
@@ -370,12 +358,12 @@ static int tp_launch_reserve(sc_ctx* ctx, const double* knots, int32_t* tstatus,
 }
 
 // moves and planes of (d2, r2_clear) into the context's scratch
-static int tp_prepare_grid(sc_ctx* ctx, const int32_t* d2, int W, int H, int32_t r2_clear) {
-    const int Wq = (W + 31) / 32;
+static int tp_prepare_grid(sc_ctx* ctx, const sc_speed_frame& fr, int32_t r2_clear) {
+    const int W = fr.W, H = fr.H, Wq = (W + 31) / 32;
     int r = sc_scratch_reserve(ctx, &ctx->moves, (size_t)W * H);
     if (r == SC_OK) r = sc_scratch_reserve(ctx, &ctx->tp_planes, (size_t)8 * H * Wq * 4);
     if (r != SC_OK) return r;
-    r = sc_launch_moves(ctx, d2, W, H, H, r2_clear, (uint8_t*)ctx->moves.p);
+    r = sc_launch_moves(ctx, fr.d2, W, H, H, r2_clear, (uint8_t*)ctx->moves.p);
     if (r != SC_OK) return r;
     int tk = sc_time_begin(ctx, SC_K_ASTAR);
     hipLaunchKernelGGL(tplan_planes_kernel, dim3((W + 255) / 256, H), dim3(256), 0, ctx->stream, (const uint8_t*)ctx->moves.p, W, H, Wq,
@@ -407,14 +395,14 @@ static int tp_group_size(sc_ctx* ctx, int W, int H, int L, int B, bool own_reach
 }
 
 // the search of queries [0, Bg) with their layers at `reach`; tp_prepare_grid has run.  path may be NULL unless knots_out is given.
-static int tp_launch_group(sc_ctx* ctx, const int32_t* d2, int W, int H, int32_t r2_clear, const uint32_t* res, int L, const int32_t* start,
+static int tp_launch_group(sc_ctx* ctx, const sc_speed_frame& fr, int32_t r2_clear, const uint32_t* res, int L, const int32_t* start,
                            const int32_t* goal, const int32_t* t_start, int Bg, int hold, int32_t* path, int32_t* len, int32_t* arrive,
-                           int32_t* status, double* knots_out, float x_min, float y_min, float res_x, float res_y, uint32_t* reach, tp_q* qs) {
-    const int Wq = (W + 31) / 32, h = ctx->tplan_layers;
+                           int32_t* status, double* knots_out, uint32_t* reach, tp_q* qs) {
+    const int W = fr.W, H = fr.H, Wq = (W + 31) / 32, h = ctx->tplan_layers;
     const size_t layer = (size_t)H * Wq;
     const int tiles_x = (Wq + TP_TW - 1) / TP_TW, tiles_y = (H + TP_TH - 1) / TP_TH;
     int tk = sc_time_begin(ctx, SC_K_ASTAR);
-    tp_init_args ia{d2, W, H, Wq, L, r2_clear > 1 ? r2_clear : 1, res, start, goal, t_start, hold, qs};
+    tp_init_args ia{fr.d2, W, H, Wq, L, r2_clear > 1 ? r2_clear : 1, res, start, goal, t_start, hold, qs};
     hipLaunchKernelGGL(tplan_init_kernel, dim3(Bg), dim3(256), 0, ctx->stream, ia);
     hipLaunchKernelGGL(tplan_seed_kernel, dim3((unsigned)((layer + 255) / 256), Bg), dim3(256), 0, ctx->stream, (const tp_q*)qs, W, layer, L, reach);
     for (int t0 = 0; t0 < L - 1; t0 += h) {
@@ -424,7 +412,7 @@ static int tp_launch_group(sc_ctx* ctx, const int32_t* d2, int W, int H, int32_t
     tp_read_args ra{qs, reach, (const uint8_t*)ctx->moves.p, W, H, Wq, L, Bg, path, len, arrive, status};
     hipLaunchKernelGGL(tplan_read_kernel, dim3((Bg + 63) / 64), dim3(64), 0, ctx->stream, ra);
     if (knots_out) {
-        tp_knots_args ka{qs, path, W, L, Bg, hold, x_min, y_min, res_x, res_y, knots_out};
+        tp_knots_args ka{qs, path, L, Bg, hold, fr, knots_out};
         hipLaunchKernelGGL(tplan_knots_kernel, dim3((unsigned)(((long long)Bg * L + 255) / 256)), dim3(256), 0, ctx->stream, ka);
     }
     sc_time_end(ctx, tk);
@@ -460,35 +448,36 @@ static int tp_make_scratch(sc_ctx* ctx, int W, int H, int L, int B, bool seq, ui
 }
 
 // queries [b0, b0 + n) of a call, n <= s.Bg
-static int tp_run(sc_ctx* ctx, const tp_scratch& s, const int32_t* d2, int W, int H, int32_t r2_clear, const uint32_t* res, int L,
+static int tp_run(sc_ctx* ctx, const tp_scratch& s, const sc_speed_frame& fr, int32_t r2_clear, const uint32_t* res, int L,
                   const int32_t* start, const int32_t* goal, const int32_t* t_start, int b0, int n, int hold, int32_t* path, int32_t* len,
-                  int32_t* arrive, int32_t* status, double* knots_out, float x_min, float y_min, float res_x, float res_y) {
-    const size_t per_q = (size_t)L * H * ((W + 31) / 32);
-    return tp_launch_group(ctx, d2, W, H, r2_clear, res, L, start + b0, goal + b0, t_start ? t_start + b0 : nullptr, n, hold,
+                  int32_t* arrive, int32_t* status, double* knots_out) {
+    const size_t per_q = (size_t)L * fr.H * ((fr.W + 31) / 32);
+    return tp_launch_group(ctx, fr, r2_clear, res, L, start + b0, goal + b0, t_start ? t_start + b0 : nullptr, n, hold,
                            path ? path + (size_t)b0 * L : s.path, len ? len + b0 : nullptr, arrive ? arrive + b0 : nullptr, status + b0,
-                           knots_out ? knots_out + (size_t)b0 * L * 2 : nullptr, x_min, y_min, res_x, res_y,
-                           s.own_reach ? s.reach : s.reach + (size_t)b0 * per_q, s.qs);
+                           knots_out ? knots_out + (size_t)b0 * L * 2 : nullptr, s.own_reach ? s.reach : s.reach + (size_t)b0 * per_q, s.qs);
 }
 
 extern "C" int sc_traj_reserve_batch(sc_ctx* ctx, const double* knots, int32_t* tstatus, int P, int K, const double* radius,
                                      const int32_t* select, double pad, int W, int H, float x_min, float y_min, float res_x, float res_y,
                                      uint32_t* res) {
-    if (tp_reserve_invalid(ctx, knots, P, K, radius, pad, W, H, x_min, y_min, res_x, res_y, res)) return SC_ERR_INVALID;
+    const sc_speed_frame fr{nullptr, W, H, x_min, y_min, res_x, res_y};
+    if (tp_reserve_invalid(ctx, knots, P, K, radius, pad, fr, res)) return SC_ERR_INVALID;
     SC_HIP(ctx, hipSetDevice(ctx->device));
-    return tp_launch_reserve(ctx, knots, tstatus, P, K, radius, select, pad, W, H, x_min, y_min, res_x, res_y, res);
+    return tp_launch_reserve(ctx, knots, tstatus, P, K, radius, select, pad, fr, res);
 }
 
 extern "C" int sc_tplan_batch(sc_ctx* ctx, const int32_t* d2, int W, int H, int32_t r2_clear, const uint32_t* res, int L, const int32_t* start,
                               const int32_t* goal, const int32_t* t_start, int B, int hold, int32_t* path, int32_t* len, int32_t* arrive,
                               int32_t* status, double* knots_out, float x_min, float y_min, float res_x, float res_y, uint32_t* reach) {
-    if (tp_plan_invalid(ctx, d2, W, H, L, start, goal, B, status, knots_out, x_min, y_min, res_x, res_y)) return SC_ERR_INVALID;
+    const sc_speed_frame fr{d2, W, H, x_min, y_min, res_x, res_y};
+    if (tp_plan_invalid(ctx, fr, L, start, goal, B, status, knots_out)) return SC_ERR_INVALID;
     SC_HIP(ctx, hipSetDevice(ctx->device));
     tp_scratch s;
     int r = tp_make_scratch(ctx, W, H, L, B, false, reach, knots_out && !path, &s);
-    if (r == SC_OK) r = tp_prepare_grid(ctx, d2, W, H, r2_clear);
+    if (r == SC_OK) r = tp_prepare_grid(ctx, fr, r2_clear);
     for (int b0 = 0; r == SC_OK && b0 < B; b0 += s.Bg)
-        r = tp_run(ctx, s, d2, W, H, r2_clear, res, L, start, goal, t_start, b0, B - b0 < s.Bg ? B - b0 : s.Bg, hold != 0, path, len, arrive, status,
-                   knots_out, x_min, y_min, res_x, res_y);
+        r = tp_run(ctx, s, fr, r2_clear, res, L, start, goal, t_start, b0, B - b0 < s.Bg ? B - b0 : s.Bg, hold != 0, path, len, arrive, status,
+                   knots_out);
     return r;
 }
 
@@ -497,39 +486,32 @@ extern "C" int sc_fleet_replan_batch(sc_ctx* ctx, const double* knots, int32_t* 
                                      uint32_t* res, const int32_t* d2, int32_t r2_clear, int L, const int32_t* start, const int32_t* goal,
                                      const int32_t* t_start, int B, int hold, int32_t* path, int32_t* len, int32_t* arrive, int32_t* status,
                                      double* knots_out, uint32_t* reach, const double* r_new, int sequential) {
-    if (tp_reserve_invalid(ctx, knots, P, K, radius, pad, W, H, x_min, y_min, res_x, res_y, res) ||
-        tp_plan_invalid(ctx, d2, W, H, L, start, goal, B, status, knots_out, x_min, y_min, res_x, res_y) || L != K + 1 ||
-        (sequential && (!r_new || !knots_out)))
+    const sc_speed_frame fr{d2, W, H, x_min, y_min, res_x, res_y};
+    if (tp_reserve_invalid(ctx, knots, P, K, radius, pad, fr, res) || tp_plan_invalid(ctx, fr, L, start, goal, B, status, knots_out) ||
+        L != K + 1 || (sequential && (!r_new || !knots_out)))
         return SC_ERR_INVALID;
     SC_HIP(ctx, hipSetDevice(ctx->device));
     tp_scratch s;
     int r = tp_make_scratch(ctx, W, H, L, B, sequential != 0, reach, knots_out && !path, &s);
-    if (r == SC_OK) r = tp_prepare_grid(ctx, d2, W, H, r2_clear);
-    if (r == SC_OK) r = tp_launch_reserve(ctx, knots, tstatus, P, K, radius, select, pad, W, H, x_min, y_min, res_x, res_y, res);
+    if (r == SC_OK) r = tp_prepare_grid(ctx, fr, r2_clear);
+    if (r == SC_OK) r = tp_launch_reserve(ctx, knots, tstatus, P, K, radius, select, pad, fr, res);
     const int step = sequential ? 1 : s.Bg;
     for (int b0 = 0; r == SC_OK && b0 < B; b0 += step) {
-        r = tp_run(ctx, s, d2, W, H, r2_clear, res, L, start, goal, t_start, b0, B - b0 < step ? B - b0 : step, hold != 0, path, len, arrive,
-                   status, knots_out, x_min, y_min, res_x, res_y);
+        r = tp_run(ctx, s, fr, r2_clear, res, L, start, goal, t_start, b0, B - b0 < step ? B - b0 : step, hold != 0, path, len, arrive, status,
+                   knots_out);
         // prioritised planning: robot b0's row joins the reservations (a failed plan is NaN rows and reserves nothing)
         if (r == SC_OK && sequential)
-            r = tp_launch_reserve(ctx, knots_out + (size_t)b0 * L * 2, nullptr, 1, K, r_new + b0, nullptr, pad, W, H, x_min, y_min, res_x, res_y,
-                                  res);
+            r = tp_launch_reserve(ctx, knots_out + (size_t)b0 * L * 2, nullptr, 1, K, r_new + b0, nullptr, pad, fr, res);
     }
     return r;
 }
 
 // ---- host forms ----
-static bool tp_radius_outside(const double* radius, int P) {
-    for (int p = 0; p < P; ++p)
-        if (!(isfinite(radius[p]) && radius[p] >= 0.0)) return true;
-    return false;
-}
-
 extern "C" int sc_traj_reserve_batch_host(sc_ctx* ctx, const double* knots, int32_t* tstatus, int P, int K, const double* radius,
                                           const int32_t* select, double pad, int W, int H, float x_min, float y_min, float res_x, float res_y,
                                           uint32_t* res) {
-    if (tp_reserve_invalid(ctx, knots, P, K, radius, pad, W, H, x_min, y_min, res_x, res_y, res) || tp_radius_outside(radius, P))
-        return SC_ERR_INVALID;
+    const sc_speed_frame fr{nullptr, W, H, x_min, y_min, res_x, res_y};
+    if (tp_reserve_invalid(ctx, knots, P, K, radius, pad, fr, res) || sc_traj_radius_outside(radius, P)) return SC_ERR_INVALID;
     SC_HIP(ctx, hipSetDevice(ctx->device));
     const size_t pb = (size_t)P * 4, rb = (size_t)(K + 1) * H * ((W + 31) / 32) * 4;
     sc_stage st(ctx);
@@ -540,7 +522,7 @@ extern "C" int sc_traj_reserve_batch_host(sc_ctx* ctx, const double* knots, int3
     int r = st.upload();
     if (r == SC_OK)
         r = tp_launch_reserve(ctx, st.dev<const double>(i_k), tstatus ? st.dev<int32_t>(i_s) : nullptr, P, K, st.dev<const double>(i_r),
-                              select ? st.dev<const int32_t>(i_sel) : nullptr, pad, W, H, x_min, y_min, res_x, res_y, st.dev<uint32_t>(i_res));
+                              select ? st.dev<const int32_t>(i_sel) : nullptr, pad, fr, st.dev<uint32_t>(i_res));
     return st.finish(r);
 }
 
@@ -548,7 +530,7 @@ extern "C" int sc_tplan_batch_host(sc_ctx* ctx, const int32_t* d2, int W, int H,
                                    const int32_t* start, const int32_t* goal, const int32_t* t_start, int B, int hold, int32_t* path,
                                    int32_t* len, int32_t* arrive, int32_t* status, double* knots_out, float x_min, float y_min, float res_x,
                                    float res_y, uint32_t* reach) {
-    if (tp_plan_invalid(ctx, d2, W, H, L, start, goal, B, status, knots_out, x_min, y_min, res_x, res_y)) return SC_ERR_INVALID;
+    if (tp_plan_invalid(ctx, sc_speed_frame{d2, W, H, x_min, y_min, res_x, res_y}, L, start, goal, B, status, knots_out)) return SC_ERR_INVALID;
     SC_HIP(ctx, hipSetDevice(ctx->device));
     const size_t bb = (size_t)B * 4, layer = (size_t)H * ((W + 31) / 32) * 4;
     sc_stage st(ctx);
@@ -571,9 +553,10 @@ extern "C" int sc_fleet_replan_batch_host(sc_ctx* ctx, const double* knots, int3
                                           uint32_t* res, const int32_t* d2, int32_t r2_clear, int L, const int32_t* start, const int32_t* goal,
                                           const int32_t* t_start, int B, int hold, int32_t* path, int32_t* len, int32_t* arrive,
                                           int32_t* status, double* knots_out, uint32_t* reach, const double* r_new, int sequential) {
-    if (tp_reserve_invalid(ctx, knots, P, K, radius, pad, W, H, x_min, y_min, res_x, res_y, res) ||
-        tp_plan_invalid(ctx, d2, W, H, L, start, goal, B, status, knots_out, x_min, y_min, res_x, res_y) || L != K + 1 ||
-        (sequential && (!r_new || !knots_out)) || tp_radius_outside(radius, P) || (r_new && tp_radius_outside(r_new, B)))
+    const sc_speed_frame fr{d2, W, H, x_min, y_min, res_x, res_y};
+    if (tp_reserve_invalid(ctx, knots, P, K, radius, pad, fr, res) || tp_plan_invalid(ctx, fr, L, start, goal, B, status, knots_out) ||
+        L != K + 1 || (sequential && (!r_new || !knots_out)) || sc_traj_radius_outside(radius, P) ||
+        (r_new && sc_traj_radius_outside(r_new, B)))
         return SC_ERR_INVALID;
     SC_HIP(ctx, hipSetDevice(ctx->device));
     const size_t pb = (size_t)P * 4, bb = (size_t)B * 4, layer = (size_t)H * ((W + 31) / 32) * 4;

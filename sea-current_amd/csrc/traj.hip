@@ -15,11 +15,10 @@
 // execution.
 //
 // Compiled with -ffp-contract=off: the NumPy twin of the tests states the same products and sums without fused
-// multiply-adds.
-#include "sc_internal.h"
+// multiply-adds.  The predicate, the radius contract, the limits and the packed paths are traj_common.h's.
+#include "traj_common.h"
 
 #include <limits.h>
-#include <math.h>
 
 #define TJ_KN_THREADS 256
 #define TJ_ROWS 64          // row paths of a workgroup: the lanes of its one wavefront
@@ -27,35 +26,22 @@
 #define TJ_CHUNK 16         // intervals of a chunk: 4 * (TJ_CHUNK + 1) registers of row knots per lane, no scratch
 // (the workgroups a launch aims for, 4096 = 16 per CU unless SC_TRAJ_WORKGROUPS says otherwise, are ctx->traj_wg_target:
 // columns and tick chunks are split to reach it)
-#define TJ_MAX_PATHS 16384
-#define TJ_MAX_TICKS 65535
-#define TJ_MAX_KNOTS (1ll << 26)
 
 struct tj_part {   // what one workgroup found for one row path
     double first, sep2;
     int32_t first_with, sep_with;   // INT_MAX: none
 };
 
-struct tj_knots_args {
-    const double* time;
-    const float* pts;
-    const int32_t *offsets, *length, *status;
-    const double* t0;
-    const int32_t* flags;
-    double T0, dt_c;
-    int K;
-    double* knots;
-    int32_t* tstatus;
-};
+struct tj_knots_args { sc_traj_paths pa; sc_traj_clock ck; double* knots; int32_t* tstatus; };
 
 __global__ void __launch_bounds__(TJ_KN_THREADS) traj_knots_kernel(tj_knots_args a) {
-    const int p = blockIdx.y, tid = threadIdx.x, K = a.K;
-    const int n = a.length[p];
-    int st = ((a.status && a.status[p] != SC_SMOOTH_OK) || n < 1) ? SC_TRAJ_SKIPPED : SC_TRAJ_OK;
-    const size_t o = st == SC_TRAJ_OK ? (size_t)a.offsets[p] : 0;
-    const double* t = a.time + o;
-    const float* xy = a.pts + 2 * o;
-    const double d = a.t0 ? a.t0[p] : 0.0;
+    const int p = blockIdx.y, tid = threadIdx.x, K = a.ck.K;
+    const int n = a.pa.length[p];
+    int st = ((a.pa.status && a.pa.status[p] != SC_SMOOTH_OK) || n < 1) ? SC_TRAJ_SKIPPED : SC_TRAJ_OK;
+    const size_t o = st == SC_TRAJ_OK ? (size_t)a.pa.offsets[p] : 0;
+    const double* t = a.pa.time + o;
+    const float* xy = a.pa.pts + 2 * o;
+    const double d = a.pa.t0 ? a.pa.t0[p] : 0.0;
     int bad = 0;
     if (st == SC_TRAJ_OK) {
         if (!isfinite(d)) bad = 1;
@@ -71,8 +57,8 @@ __global__ void __launch_bounds__(TJ_KN_THREADS) traj_knots_kernel(tj_knots_args
     if (k > K) return;
     double x = NAN, y = NAN;
     if (st == SC_TRAJ_OK) {
-        const int fl = a.flags ? a.flags[p] : 3;
-        const double tau = a.T0 + (double)k * a.dt_c;
+        const int fl = a.pa.flags ? a.pa.flags[p] : 3;
+        const double tau = a.ck.T0 + (double)k * a.ck.dt_c;
         const double u = tau - d;
         if (u < t[0]) {
             if (fl & 1) { x = (double)xy[0]; y = (double)xy[1]; }
@@ -102,8 +88,8 @@ struct tj_pair_args {
     const int32_t* tstatus;
     const double* radius;
     const int32_t* group;
-    int P, K;
-    double T0, dt_c;
+    int P;
+    sc_traj_clock ck;
     int coltiles, G, chunks_per_split, slots;   // grid: (G column shares, row tiles, tick splits); slots = G * splits
     tj_part* part;      // [P][slots]
     uint32_t* matrix;   // [P][nw], zeroed; may be NULL
@@ -111,17 +97,14 @@ struct tj_pair_args {
 };
 
 __device__ __forceinline__ bool tj_path_ok(const tj_pair_args& a, int p) {
-    const double r = a.radius[p];
-    return a.tstatus[p] == SC_TRAJ_OK && isfinite(r) && r >= 0.0;
+    return a.tstatus[p] == SC_TRAJ_OK && sc_traj_radius_ok(a.radius[p]);
 }
-
-__device__ __forceinline__ double tj_clamp(double x, double lo, double hi) { return x < lo ? lo : (x > hi ? hi : x); }
 
 __global__ void __launch_bounds__(TJ_ROWS) traj_pairs_kernel(tj_pair_args a) {
     __shared__ double2 s_col[TJ_COLS][TJ_CHUNK + 1];
     __shared__ double s_rad[TJ_COLS];
     __shared__ int32_t s_grp[TJ_COLS], s_ok[TJ_COLS];
-    const int lane = threadIdx.x, P = a.P, K = a.K;
+    const int lane = threadIdx.x, P = a.P, K = a.ck.K;
     const int row = blockIdx.y * TJ_ROWS + lane;
     const bool row_ok = row < P && tj_path_ok(a, row);
     const double rrad = row_ok ? a.radius[row] : 0.0;
@@ -172,23 +155,18 @@ __global__ void __launch_bounds__(TJ_ROWS) traj_pairs_kernel(tj_pair_args a) {
                 for (int i = 0; i < TJ_CHUNK; ++i) {
                     ck = s_col[c][i + 1];
                     const double d1x = ck.x - rx[i + 1], d1y = ck.y - ry[i + 1];
-                    const double ex = d1x - d0x, ey = d1y - d0y;
-                    const double aa = ex * ex + ey * ey;
-                    const double bb = d0x * ex + d0y * ey;
-                    const double lam = aa > 0.0 ? tj_clamp(-bb / aa, 0.0, 1.0) : 0.0;
-                    const double px = d0x + lam * ex, py = d0y + lam * ey;
-                    const double m2 = px * px + py * py;
-                    if (m2 < m2min) m2min = m2;
-                    if (m2 < RR) {   // rare: the entry time of the conflict
+                    const sc_traj_approach ap = sc_traj_closest(d0x, d0y, d1x, d1y);
+                    if (ap.m2 < m2min) m2min = ap.m2;
+                    if (ap.m2 < RR) {   // rare: the entry time of the conflict
                         const double cc = d0x * d0x + d0y * d0y;
                         double lc = 0.0;
                         if (!(cc < RR)) {
-                            double disc = bb * bb - aa * (cc - RR);
+                            double disc = ap.bb * ap.bb - ap.aa * (cc - RR);
                             disc = disc > 0.0 ? disc : 0.0;
-                            lc = tj_clamp((-bb - sqrt(disc)) / aa, 0.0, lam);
+                            lc = sc_clampd((-ap.bb - sqrt(disc)) / ap.aa, 0.0, ap.lam);
                         }
-                        const double tau = a.T0 + (double)(kc + i) * a.dt_c;
-                        const double tt = tau + lc * a.dt_c;
+                        const double tau = a.ck.T0 + (double)(kc + i) * a.ck.dt_c;
+                        const double tt = tau + lc * a.ck.dt_c;
                         if (tt < tfirst) tfirst = tt;
                     }
                     d0x = d1x;
@@ -213,6 +191,13 @@ __global__ void __launch_bounds__(TJ_ROWS) traj_pairs_kernel(tj_pair_args a) {
     }
 }
 
+// what a conflicts call reports; each may be NULL
+struct tj_report {
+    double *first_t, *min_sep;
+    int32_t *first_with, *min_with, *n_conf;
+    uint32_t* conflict;   // [P][ceil(P / TJ_COLS)]
+};
+
 struct tj_reduce_args {
     const tj_part* part;
     int slots;
@@ -221,8 +206,7 @@ struct tj_reduce_args {
     const double* radius;
     double sep_cap;
     int32_t* tstatus;
-    double *first_t, *min_sep;
-    int32_t *first_with, *min_with, *n_conf;
+    tj_report o;   // conflict is not read: matrix is it, or scratch
 };
 
 // lexicographic minimum of (value, partner) across the wavefront
@@ -251,37 +235,24 @@ __global__ void __launch_bounds__(64) traj_reduce_kernel(tj_reduce_args a) {
 #pragma unroll
     for (int s = 32; s >= 1; s >>= 1) cnt += __shfl_xor(cnt, s);
     if (lane != 0) return;
-    const double r = a.radius[p];
-    if (a.tstatus[p] == SC_TRAJ_OK && !(isfinite(r) && r >= 0.0)) a.tstatus[p] = SC_TRAJ_BAD;
+    sc_traj_mark_radius(a.tstatus, p, a.radius[p]);
     const double ms = sqrt(bs);
     const bool rep = ms < a.sep_cap;
-    if (a.first_t) a.first_t[p] = bf;
-    if (a.first_with) a.first_with[p] = bf < INFINITY ? bfw : -1;
-    if (a.min_sep) a.min_sep[p] = rep ? ms : INFINITY;
-    if (a.min_with) a.min_with[p] = rep ? bsw : -1;
-    if (a.n_conf) a.n_conf[p] = cnt;
+    if (a.o.first_t) a.o.first_t[p] = bf;
+    if (a.o.first_with) a.o.first_with[p] = bf < INFINITY ? bfw : -1;
+    if (a.o.min_sep) a.o.min_sep[p] = rep ? ms : INFINITY;
+    if (a.o.min_with) a.o.min_with[p] = rep ? bsw : -1;
+    if (a.o.n_conf) a.o.n_conf[p] = cnt;
 }
 
-static bool tj_clock_invalid(int P, int K, double T0, double dt_c) {
-    return P < 1 || P > TJ_MAX_PATHS || K < 1 || K > TJ_MAX_TICKS || (long long)P * ((long long)K + 1) > TJ_MAX_KNOTS || !isfinite(dt_c) ||
-           !(dt_c > 0.0) || !isfinite(T0);
+static bool tj_conf_invalid(sc_ctx* ctx, int P, const sc_traj_clock& ck, const double* radius, double sep_cap) {
+    return !ctx || !radius || !sc_traj_size_ok(P, ck.K) || !sc_traj_clock_ok(ck) || isnan(sep_cap) || !(sep_cap > 0.0);
 }
 
-static bool tj_knots_invalid(sc_ctx* ctx, const double* time, const float* pts, const int32_t* offsets, const int32_t* length, int P,
-                             double T0, double dt_c, int K) {
-    return !ctx || !time || !pts || !offsets || !length || tj_clock_invalid(P, K, T0, dt_c);
-}
-
-static bool tj_conf_invalid(sc_ctx* ctx, int P, int K, double T0, double dt_c, const double* radius, double sep_cap) {
-    return !ctx || !radius || tj_clock_invalid(P, K, T0, dt_c) || isnan(sep_cap) || !(sep_cap > 0.0);
-}
-
-static int tj_launch_knots(sc_ctx* ctx, const double* time, const float* pts, const int32_t* offsets, const int32_t* length,
-                           const int32_t* status, int P, const double* t0, const int32_t* flags, double T0, double dt_c, int K,
-                           double* knots, int32_t* tstatus) {
-    tj_knots_args a{time, pts, offsets, length, status, t0, flags, T0, dt_c, K, knots, tstatus};
+int sc_traj_launch_knots(sc_ctx* ctx, const sc_traj_paths& pa, const sc_traj_clock& ck, double* knots, int32_t* tstatus) {
+    tj_knots_args a{pa, ck, knots, tstatus};
     int tk = sc_time_begin(ctx, SC_K_SMOOTH);
-    hipLaunchKernelGGL(traj_knots_kernel, dim3((K + TJ_KN_THREADS) / TJ_KN_THREADS, P), dim3(TJ_KN_THREADS), 0, ctx->stream, a);
+    hipLaunchKernelGGL(traj_knots_kernel, dim3((ck.K + TJ_KN_THREADS) / TJ_KN_THREADS, pa.P), dim3(TJ_KN_THREADS), 0, ctx->stream, a);
     sc_time_end(ctx, tk);
     SC_HIP(ctx, hipGetLastError());
     return SC_OK;
@@ -311,17 +282,19 @@ static tj_plan tj_make_plan(const sc_ctx* ctx, int P, int K, bool own_matrix) {
     return pl;
 }
 
-// scratch: ctx->traj_part, reserved by the caller to plan.part_bytes + plan.matrix_bytes
-static int tj_launch_conflicts(sc_ctx* ctx, const tj_plan& pl, const double* knots, int32_t* tstatus, int P, int K, double T0, double dt_c,
-                               const double* radius, const int32_t* group, double sep_cap, double* first_t, int32_t* first_with,
-                               double* min_sep, int32_t* min_with, int32_t* n_conf, uint32_t* conflict) {
+// the pair and the reduce kernel behind a report; scratch: ctx->traj_part
+static int tj_launch_conflicts(sc_ctx* ctx, const double* knots, int32_t* tstatus, int P, const sc_traj_clock& ck, const double* radius,
+                               const int32_t* group, double sep_cap, const tj_report& o) {
+    const tj_plan pl = tj_make_plan(ctx, P, ck.K, !o.conflict && o.n_conf);
+    const int reserved = sc_scratch_reserve(ctx, &ctx->traj_part, pl.part_bytes + pl.matrix_bytes);
+    if (reserved != SC_OK) return reserved;
     tj_part* part = (tj_part*)ctx->traj_part.p;
-    uint32_t* matrix = conflict ? conflict : (n_conf ? (uint32_t*)((char*)ctx->traj_part.p + pl.part_bytes) : nullptr);
+    uint32_t* matrix = o.conflict ? o.conflict : (o.n_conf ? (uint32_t*)((char*)ctx->traj_part.p + pl.part_bytes) : nullptr);
     if (matrix) SC_HIP(ctx, hipMemsetAsync(matrix, 0, (size_t)P * pl.nw * 4, ctx->stream));
     int tk = sc_time_begin(ctx, SC_K_SMOOTH);
-    tj_pair_args a{knots, tstatus, radius, group, P, K, T0, dt_c, pl.coltiles, pl.G, pl.chunks_per_split, pl.slots, part, matrix, pl.nw};
+    tj_pair_args a{knots, tstatus, radius, group, P, ck, pl.coltiles, pl.G, pl.chunks_per_split, pl.slots, part, matrix, pl.nw};
     hipLaunchKernelGGL(traj_pairs_kernel, dim3(pl.G, pl.rowtiles, pl.splits), dim3(TJ_ROWS), 0, ctx->stream, a);
-    tj_reduce_args r{part, pl.slots, matrix, pl.nw, radius, sep_cap, tstatus, first_t, min_sep, first_with, min_with, n_conf};
+    tj_reduce_args r{part, pl.slots, matrix, pl.nw, radius, sep_cap, tstatus, o};
     hipLaunchKernelGGL(traj_reduce_kernel, dim3(P), dim3(64), 0, ctx->stream, r);
     sc_time_end(ctx, tk);
     SC_HIP(ctx, hipGetLastError());
@@ -331,21 +304,20 @@ static int tj_launch_conflicts(sc_ctx* ctx, const tj_plan& pl, const double* kno
 extern "C" int sc_traj_knots_batch(sc_ctx* ctx, const double* time, const float* pts, const int32_t* offsets, const int32_t* length,
                                    const int32_t* status, int P, const double* t0, const int32_t* flags, double T0, double dt_c, int K,
                                    double* knots, int32_t* tstatus) {
-    if (tj_knots_invalid(ctx, time, pts, offsets, length, P, T0, dt_c, K) || !knots || !tstatus) return SC_ERR_INVALID;
+    const sc_traj_paths pa{time, pts, offsets, length, status, t0, flags, P};
+    const sc_traj_clock ck{T0, dt_c, K};
+    if (sc_traj_input_invalid(ctx, pa, ck) || !knots || !tstatus) return SC_ERR_INVALID;
     SC_HIP(ctx, hipSetDevice(ctx->device));
-    return tj_launch_knots(ctx, time, pts, offsets, length, status, P, t0, flags, T0, dt_c, K, knots, tstatus);
+    return sc_traj_launch_knots(ctx, pa, ck, knots, tstatus);
 }
 
 extern "C" int sc_traj_conflicts_batch(sc_ctx* ctx, const double* knots, int32_t* tstatus, int P, int K, double T0, double dt_c,
                                        const double* radius, const int32_t* group, double sep_cap, double* first_t, int32_t* first_with,
                                        double* min_sep, int32_t* min_with, int32_t* n_conf, uint32_t* conflict) {
-    if (tj_conf_invalid(ctx, P, K, T0, dt_c, radius, sep_cap) || !knots || !tstatus) return SC_ERR_INVALID;
+    const sc_traj_clock ck{T0, dt_c, K};
+    if (tj_conf_invalid(ctx, P, ck, radius, sep_cap) || !knots || !tstatus) return SC_ERR_INVALID;
     SC_HIP(ctx, hipSetDevice(ctx->device));
-    const tj_plan pl = tj_make_plan(ctx, P, K, !conflict && n_conf);
-    int r = sc_scratch_reserve(ctx, &ctx->traj_part, pl.part_bytes + pl.matrix_bytes);
-    if (r != SC_OK) return r;
-    return tj_launch_conflicts(ctx, pl, knots, tstatus, P, K, T0, dt_c, radius, group, sep_cap, first_t, first_with, min_sep, min_with,
-                               n_conf, conflict);
+    return tj_launch_conflicts(ctx, knots, tstatus, P, ck, radius, group, sep_cap, tj_report{first_t, min_sep, first_with, min_with, n_conf, conflict});
 }
 
 extern "C" int sc_fleet_conflicts_batch(sc_ctx* ctx, const double* time, const float* pts, const int32_t* offsets, const int32_t* length,
@@ -353,89 +325,64 @@ extern "C" int sc_fleet_conflicts_batch(sc_ctx* ctx, const double* time, const f
                                         double* knots, int32_t* tstatus, const double* radius, const int32_t* group, double sep_cap,
                                         double* first_t, int32_t* first_with, double* min_sep, int32_t* min_with, int32_t* n_conf,
                                         uint32_t* conflict) {
-    if (tj_knots_invalid(ctx, time, pts, offsets, length, P, T0, dt_c, K) || tj_conf_invalid(ctx, P, K, T0, dt_c, radius, sep_cap))
-        return SC_ERR_INVALID;
+    const sc_traj_paths pa{time, pts, offsets, length, status, t0, flags, P};
+    const sc_traj_clock ck{T0, dt_c, K};
+    if (sc_traj_input_invalid(ctx, pa, ck) || tj_conf_invalid(ctx, P, ck, radius, sep_cap)) return SC_ERR_INVALID;
     SC_HIP(ctx, hipSetDevice(ctx->device));
-    const tj_plan pl = tj_make_plan(ctx, P, K, !conflict && n_conf);
-    int r = sc_scratch_reserve(ctx, &ctx->traj_part, pl.part_bytes + pl.matrix_bytes);
+    int r = sc_traj_scratch_knots(ctx, P, K, &knots, &tstatus);
+    if (r == SC_OK) r = sc_traj_launch_knots(ctx, pa, ck, knots, tstatus);
     if (r != SC_OK) return r;
-    const size_t kb = knots ? 0 : al256((size_t)P * (K + 1) * 16), sb = tstatus ? 0 : al256((size_t)P * 4);
-    if (kb + sb) {
-        r = sc_scratch_reserve(ctx, &ctx->traj_knots, kb + sb);
-        if (r != SC_OK) return r;
-        if (!knots) knots = (double*)ctx->traj_knots.p;
-        if (!tstatus) tstatus = (int32_t*)((char*)ctx->traj_knots.p + kb);
-    }
-    r = tj_launch_knots(ctx, time, pts, offsets, length, status, P, t0, flags, T0, dt_c, K, knots, tstatus);
-    if (r != SC_OK) return r;
-    return tj_launch_conflicts(ctx, pl, knots, tstatus, P, K, T0, dt_c, radius, group, sep_cap, first_t, first_with, min_sep, min_with,
-                               n_conf, conflict);
+    return tj_launch_conflicts(ctx, knots, tstatus, P, ck, radius, group, sep_cap, tj_report{first_t, min_sep, first_with, min_with, n_conf, conflict});
 }
 
 // ---- host forms ----
-// what a device form would read out of range, or mark SC_TRAJ_BAD from the per-path arguments alone
-static bool tj_paths_outside(const int32_t* offsets, const int32_t* length, const int32_t* status, int P, const double* t0,
-                             const int32_t* flags) {
-    if (offsets[0] < 0) return true;
-    for (int p = 0; p < P; ++p) {
-        if (offsets[p + 1] < offsets[p]) return true;
-        if (t0 && !isfinite(t0[p])) return true;
-        if (flags && (flags[p] < 0 || flags[p] > 3)) return true;
-    }
-    for (int p = 0; p < P; ++p)
-        if ((!status || status[p] == SC_SMOOTH_OK) && length[p] >= 1 && (long long)offsets[p] + length[p] > offsets[P]) return true;
-    return false;
+// a report's slots in a stage, in the order of its members; tj_report_dev, after st.upload(): the report on the device
+static int tj_stage_report(sc_stage& st, const tj_report& h, int P) {
+    const size_t pb = (size_t)P * 4;
+    const int first = st.out(h.first_t, h.first_t ? pb * 2 : 0);
+    st.out(h.min_sep, h.min_sep ? pb * 2 : 0), st.out(h.first_with, h.first_with ? pb : 0), st.out(h.min_with, h.min_with ? pb : 0);
+    st.out(h.n_conf, h.n_conf ? pb : 0), st.out(h.conflict, h.conflict ? (size_t)P * ((P + TJ_COLS - 1) / TJ_COLS) * 4 : 0);
+    return first;
 }
 
-static bool tj_radius_outside(const double* radius, int P) {
-    for (int p = 0; p < P; ++p)
-        if (!(isfinite(radius[p]) && radius[p] >= 0.0)) return true;
-    return false;
+static tj_report tj_report_dev(const sc_stage& st, int i, const tj_report& h) {
+    return tj_report{h.first_t ? st.dev<double>(i) : nullptr,         h.min_sep ? st.dev<double>(i + 1) : nullptr,
+                     h.first_with ? st.dev<int32_t>(i + 2) : nullptr, h.min_with ? st.dev<int32_t>(i + 3) : nullptr,
+                     h.n_conf ? st.dev<int32_t>(i + 4) : nullptr,     h.conflict ? st.dev<uint32_t>(i + 5) : nullptr};
 }
 
 extern "C" int sc_traj_knots_batch_host(sc_ctx* ctx, const double* time, const float* pts, const int32_t* offsets, const int32_t* length,
                                         const int32_t* status, int P, const double* t0, const int32_t* flags, double T0, double dt_c,
                                         int K, double* knots, int32_t* tstatus) {
-    if (tj_knots_invalid(ctx, time, pts, offsets, length, P, T0, dt_c, K) || !knots || !tstatus) return SC_ERR_INVALID;
-    if (tj_paths_outside(offsets, length, status, P, t0, flags)) return SC_ERR_INVALID;
+    const sc_traj_paths pa{time, pts, offsets, length, status, t0, flags, P};
+    const sc_traj_clock ck{T0, dt_c, K};
+    if (sc_traj_input_invalid(ctx, pa, ck) || !knots || !tstatus || sc_traj_paths_outside(pa)) return SC_ERR_INVALID;
     SC_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t M = (size_t)offsets[P], pb = (size_t)P * 4;
     sc_stage st(ctx);
-    const int i_t = st.in(time, M * 8), i_p = st.in(pts, M * 8), i_o = st.in(offsets, pb + 4), i_l = st.in(length, pb),
-              i_s = st.in(status, status ? pb : 0), i_d = st.in(t0, t0 ? pb * 2 : 0), i_f = st.in(flags, flags ? pb : 0);
-    const int o_k = st.out(knots, (size_t)P * (K + 1) * 16), o_s = st.out(tstatus, pb);
+    const int i_pa = sc_traj_stage_paths(st, pa);
+    const int o_k = st.out(knots, (size_t)P * (K + 1) * 16), o_s = st.out(tstatus, (size_t)P * 4);
     int r = st.upload();
-    if (r == SC_OK)
-        r = tj_launch_knots(ctx, st.dev<const double>(i_t), st.dev<const float>(i_p), st.dev<const int32_t>(i_o), st.dev<const int32_t>(i_l),
-                            status ? st.dev<const int32_t>(i_s) : nullptr, P, t0 ? st.dev<const double>(i_d) : nullptr,
-                            flags ? st.dev<const int32_t>(i_f) : nullptr, T0, dt_c, K, st.dev<double>(o_k), st.dev<int32_t>(o_s));
+    if (r == SC_OK) r = sc_traj_launch_knots(ctx, sc_traj_staged_paths(st, i_pa, pa), ck, st.dev<double>(o_k), st.dev<int32_t>(o_s));
     return st.finish(r);
 }
 
 extern "C" int sc_traj_conflicts_batch_host(sc_ctx* ctx, const double* knots, int32_t* tstatus, int P, int K, double T0, double dt_c,
                                             const double* radius, const int32_t* group, double sep_cap, double* first_t,
                                             int32_t* first_with, double* min_sep, int32_t* min_with, int32_t* n_conf, uint32_t* conflict) {
-    if (tj_conf_invalid(ctx, P, K, T0, dt_c, radius, sep_cap) || !knots || !tstatus) return SC_ERR_INVALID;
-    if (tj_radius_outside(radius, P)) return SC_ERR_INVALID;
+    const sc_traj_clock ck{T0, dt_c, K};
+    const tj_report out{first_t, min_sep, first_with, min_with, n_conf, conflict};
+    if (tj_conf_invalid(ctx, P, ck, radius, sep_cap) || !knots || !tstatus || sc_traj_radius_outside(radius, P)) return SC_ERR_INVALID;
     SC_HIP(ctx, hipSetDevice(ctx->device));
-    const tj_plan pl = tj_make_plan(ctx, P, K, !conflict && n_conf);
-    int r = sc_scratch_reserve(ctx, &ctx->traj_part, pl.part_bytes + pl.matrix_bytes);
-    if (r != SC_OK) return r;
     const size_t pb = (size_t)P * 4;
     sc_stage st(ctx);
     const int i_k = st.in(knots, (size_t)P * (K + 1) * 16), i_s = st.in(tstatus, pb), i_r = st.in(radius, pb * 2),
               i_g = st.in(group, group ? pb : 0);
     st.back(i_s, tstatus, pb);
-    const int o_ft = st.out(first_t, first_t ? pb * 2 : 0), o_fw = st.out(first_with, first_with ? pb : 0),
-              o_ms = st.out(min_sep, min_sep ? pb * 2 : 0), o_mw = st.out(min_with, min_with ? pb : 0),
-              o_nc = st.out(n_conf, n_conf ? pb : 0), o_cf = st.out(conflict, conflict ? (size_t)P * pl.nw * 4 : 0);
-    r = st.upload();
+    const int o_rep = tj_stage_report(st, out, P);
+    int r = st.upload();
     if (r == SC_OK)
-        r = tj_launch_conflicts(ctx, pl, st.dev<const double>(i_k), st.dev<int32_t>(i_s), P, K, T0, dt_c, st.dev<const double>(i_r),
-                                group ? st.dev<const int32_t>(i_g) : nullptr, sep_cap, first_t ? st.dev<double>(o_ft) : nullptr,
-                                first_with ? st.dev<int32_t>(o_fw) : nullptr, min_sep ? st.dev<double>(o_ms) : nullptr,
-                                min_with ? st.dev<int32_t>(o_mw) : nullptr, n_conf ? st.dev<int32_t>(o_nc) : nullptr,
-                                conflict ? st.dev<uint32_t>(o_cf) : nullptr);
+        r = tj_launch_conflicts(ctx, st.dev<const double>(i_k), st.dev<int32_t>(i_s), P, ck, st.dev<const double>(i_r),
+                                group ? st.dev<const int32_t>(i_g) : nullptr, sep_cap, tj_report_dev(st, o_rep, out));
     return st.finish(r);
 }
 
@@ -444,32 +391,22 @@ extern "C" int sc_fleet_conflicts_batch_host(sc_ctx* ctx, const double* time, co
                                              double T0, double dt_c, int K, double* knots, int32_t* tstatus, const double* radius,
                                              const int32_t* group, double sep_cap, double* first_t, int32_t* first_with, double* min_sep,
                                              int32_t* min_with, int32_t* n_conf, uint32_t* conflict) {
-    if (tj_knots_invalid(ctx, time, pts, offsets, length, P, T0, dt_c, K) || tj_conf_invalid(ctx, P, K, T0, dt_c, radius, sep_cap))
-        return SC_ERR_INVALID;
-    if (tj_paths_outside(offsets, length, status, P, t0, flags) || tj_radius_outside(radius, P)) return SC_ERR_INVALID;
+    const sc_traj_paths pa{time, pts, offsets, length, status, t0, flags, P};
+    const sc_traj_clock ck{T0, dt_c, K};
+    const tj_report out{first_t, min_sep, first_with, min_with, n_conf, conflict};
+    if (sc_traj_input_invalid(ctx, pa, ck) || tj_conf_invalid(ctx, P, ck, radius, sep_cap)) return SC_ERR_INVALID;
+    if (sc_traj_paths_outside(pa) || sc_traj_radius_outside(radius, P)) return SC_ERR_INVALID;
     SC_HIP(ctx, hipSetDevice(ctx->device));
-    const tj_plan pl = tj_make_plan(ctx, P, K, !conflict && n_conf);
-    int r = sc_scratch_reserve(ctx, &ctx->traj_part, pl.part_bytes + pl.matrix_bytes);
-    if (r != SC_OK) return r;
-    const size_t M = (size_t)offsets[P], pb = (size_t)P * 4;
+    const size_t pb = (size_t)P * 4;
     sc_stage st(ctx);
-    const int i_t = st.in(time, M * 8), i_p = st.in(pts, M * 8), i_o = st.in(offsets, pb + 4), i_l = st.in(length, pb),
-              i_s = st.in(status, status ? pb : 0), i_d = st.in(t0, t0 ? pb * 2 : 0), i_f = st.in(flags, flags ? pb : 0),
-              i_r = st.in(radius, pb * 2), i_g = st.in(group, group ? pb : 0);
+    const int i_pa = sc_traj_stage_paths(st, pa);
+    const int i_r = st.in(radius, pb * 2), i_g = st.in(group, group ? pb : 0);
     const int o_k = st.out(knots, (size_t)P * (K + 1) * 16), o_s = st.out(tstatus, pb);   // slots even when not copied back
-    const int o_ft = st.out(first_t, first_t ? pb * 2 : 0), o_fw = st.out(first_with, first_with ? pb : 0),
-              o_ms = st.out(min_sep, min_sep ? pb * 2 : 0), o_mw = st.out(min_with, min_with ? pb : 0),
-              o_nc = st.out(n_conf, n_conf ? pb : 0), o_cf = st.out(conflict, conflict ? (size_t)P * pl.nw * 4 : 0);
-    r = st.upload();
+    const int o_rep = tj_stage_report(st, out, P);
+    int r = st.upload();
+    if (r == SC_OK) r = sc_traj_launch_knots(ctx, sc_traj_staged_paths(st, i_pa, pa), ck, st.dev<double>(o_k), st.dev<int32_t>(o_s));
     if (r == SC_OK)
-        r = tj_launch_knots(ctx, st.dev<const double>(i_t), st.dev<const float>(i_p), st.dev<const int32_t>(i_o), st.dev<const int32_t>(i_l),
-                            status ? st.dev<const int32_t>(i_s) : nullptr, P, t0 ? st.dev<const double>(i_d) : nullptr,
-                            flags ? st.dev<const int32_t>(i_f) : nullptr, T0, dt_c, K, st.dev<double>(o_k), st.dev<int32_t>(o_s));
-    if (r == SC_OK)
-        r = tj_launch_conflicts(ctx, pl, st.dev<const double>(o_k), st.dev<int32_t>(o_s), P, K, T0, dt_c, st.dev<const double>(i_r),
-                                group ? st.dev<const int32_t>(i_g) : nullptr, sep_cap, first_t ? st.dev<double>(o_ft) : nullptr,
-                                first_with ? st.dev<int32_t>(o_fw) : nullptr, min_sep ? st.dev<double>(o_ms) : nullptr,
-                                min_with ? st.dev<int32_t>(o_mw) : nullptr, n_conf ? st.dev<int32_t>(o_nc) : nullptr,
-                                conflict ? st.dev<uint32_t>(o_cf) : nullptr);
+        r = tj_launch_conflicts(ctx, st.dev<const double>(o_k), st.dev<int32_t>(o_s), P, ck, st.dev<const double>(i_r),
+                                group ? st.dev<const int32_t>(i_g) : nullptr, sep_cap, tj_report_dev(st, o_rep, out));
     return st.finish(r);
 }

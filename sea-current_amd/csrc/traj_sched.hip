@@ -17,14 +17,10 @@
 // wave reduction and an LDS combine follow, thread 0 takes the lowest free bit.  The next row is loaded before the current
 // one reduces (its address does not depend on the decision).
 //
-// Compiled with -ffp-contract=off: the predicate is section 17's, product by product.
-#include "sc_internal.h"
+// Compiled with -ffp-contract=off: the predicate is section 17's, product by product (sc_traj_closest of traj_common.h).
+#include "traj_common.h"
 
-#include <math.h>
-
-#define TS_MAX_PATHS 8192
-#define TS_MAX_TICKS 65535
-#define TS_MAX_KNOTS (1ll << 26)
+#define TS_MAX_PATHS SC_TRAJ_SCHED_MAX_PATHS
 #define TS_CHUNK 64             // intervals of a chunk
 #define TS_HALO_LDS 512         // the largest (D-1) * stride the LDS path takes: 4 rows * 2 * 8 B * 596 slots = 37.3 KiB
 #define TS_LDS_BYTES 49152      // what a launch takes at most: four pairs per wavefront become two when their rows need more
@@ -62,8 +58,7 @@ __global__ void __launch_bounds__(64) traj_box_kernel(ts_box_args a) {
         y0 = ay0 < y0 ? ay0 : y0; y1 = ay1 > y1 ? ay1 : y1;
     }
     if (lane != 0) return;
-    const double r = a.radius[p];
-    if (a.tstatus[p] == SC_TRAJ_OK && !(isfinite(r) && r >= 0.0)) a.tstatus[p] = SC_TRAJ_BAD;
+    sc_traj_mark_radius(a.tstatus, p, a.radius[p]);
     a.box[p] = ts_box{x0, x1, y0, y1};
     a.table[(size_t)p * a.P + p] = 0;
 }
@@ -107,8 +102,6 @@ __device__ __forceinline__ void ts_pair(long long t, int& lo, int& hi) {
     hi = h;
     lo = (int)(t - (long long)h * (h - 1) / 2);
 }
-
-__device__ __forceinline__ double ts_clamp01(double x) { return x < 0.0 ? 0.0 : (x > 1.0 ? 1.0 : x); }
 
 template <bool LDS>
 __global__ void __launch_bounds__(64) traj_shift_table_kernel(ts_table_args a) {
@@ -175,13 +168,7 @@ __global__ void __launch_bounds__(64) traj_shift_table_kernel(ts_table_args a) {
                             hx = khi[2 * (size_t)ih]; hy = khi[2 * (size_t)ih + 1];
                         }
                         const double d1x = hx - lx, d1y = hy - ly;
-                        const double ex = d1x - d0x, ey = d1y - d0y;
-                        const double aa = ex * ex + ey * ey;
-                        const double bb = d0x * ex + d0y * ey;
-                        const double lam = aa > 0.0 ? ts_clamp01(-bb / aa) : 0.0;
-                        const double px = d0x + lam * ex, py = d0y + lam * ey;
-                        const double m2 = px * px + py * py;
-                        hit |= m2 < RR;
+                        hit |= sc_traj_closest(d0x, d0y, d1x, d1y).m2 < RR;
                         d0x = d1x;
                         d0y = d1y;
                     }
@@ -298,9 +285,7 @@ __global__ void __launch_bounds__(TS_KN_THREADS) traj_shift_knots_kernel(const d
 }
 
 // ---- launches ----
-static bool ts_size_invalid(int P, int K) {
-    return P < 1 || P > TS_MAX_PATHS || K < 1 || K > TS_MAX_TICKS || (long long)P * ((long long)K + 1) > TS_MAX_KNOTS;
-}
+static bool ts_size_invalid(int P, int K) { return !sc_traj_size_ok(P, K, TS_MAX_PATHS); }
 
 static bool ts_slots_invalid(int D, int stride, int K) {
     return D < 1 || D > 32 || stride < 1 || (long long)(D - 1) * stride > K;
@@ -352,13 +337,6 @@ static int ts_launch_shift(sc_ctx* ctx, const double* knots, int P, int K, const
     return SC_OK;
 }
 
-static bool ts_fleet_invalid(sc_ctx* ctx, const double* time, const float* pts, const int32_t* offsets, const int32_t* length, int P,
-                             double T0, double dt_c, int K, const double* radius, int D, int stride, const int32_t* slot,
-                             const int32_t* counts) {
-    return !ctx || !time || !pts || !offsets || !length || !radius || !slot || !counts || ts_size_invalid(P, K) || ts_slots_invalid(D, stride, K) ||
-           !isfinite(dt_c) || !(dt_c > 0.0) || !isfinite(T0);
-}
-
 extern "C" int sc_traj_shift_table_batch(sc_ctx* ctx, const double* knots, int32_t* tstatus, int P, int K, const double* radius,
                                          const int32_t* group, int D, int stride, uint64_t* table) {
     if (!ctx || !knots || !tstatus || !radius || !table || ts_size_invalid(P, K) || ts_slots_invalid(D, stride, K)) return SC_ERR_INVALID;
@@ -379,15 +357,19 @@ extern "C" int sc_traj_shift_knots_batch(sc_ctx* ctx, const double* knots, int P
     return ts_launch_shift(ctx, knots, P, K, slot, stride, knots_out);
 }
 
-// the three launches behind the knots; every pointer is a device pointer and present, except knots_out
-static int ts_launch_fleet(sc_ctx* ctx, const double* time, const float* pts, const int32_t* offsets, const int32_t* length,
-                           const int32_t* status, int P, const double* t0, const int32_t* flags, double T0, double dt_c, int K, double* knots,
-                           int32_t* tstatus, const double* radius, const int32_t* group, int D, int stride, uint64_t* table,
-                           const int32_t* order, const int32_t* jmax, int32_t* slot, int32_t* counts, double* knots_out) {
-    int r = sc_traj_knots_batch(ctx, time, pts, offsets, length, status, P, t0, flags, T0, dt_c, K, knots, tstatus);
-    if (r == SC_OK) r = ts_launch_table(ctx, knots, tstatus, P, K, radius, group, D, stride, table);
-    if (r == SC_OK) r = ts_launch_schedule(ctx, table, tstatus, P, D, order, jmax, slot, counts);
-    if (r == SC_OK && knots_out) r = ts_launch_shift(ctx, knots, P, K, slot, stride, knots_out);
+static bool ts_fleet_invalid(sc_ctx* ctx, const sc_traj_paths& pa, const sc_traj_clock& ck, const double* radius, int D, int stride,
+                             const int32_t* slot, const int32_t* counts) {
+    return sc_traj_input_invalid(ctx, pa, ck, TS_MAX_PATHS) || !radius || !slot || !counts || ts_slots_invalid(D, stride, ck.K);
+}
+
+// the four launches; every pointer is a device pointer and present, except knots_out (ts_fleet_invalid covers sc_traj_knots_batch's checks)
+static int ts_launch_fleet(sc_ctx* ctx, const sc_traj_paths& pa, const sc_traj_clock& ck, double* knots, int32_t* tstatus, const double* radius,
+                           const int32_t* group, int D, int stride, uint64_t* table, const int32_t* order, const int32_t* jmax, int32_t* slot,
+                           int32_t* counts, double* knots_out) {
+    int r = sc_traj_launch_knots(ctx, pa, ck, knots, tstatus);
+    if (r == SC_OK) r = ts_launch_table(ctx, knots, tstatus, pa.P, ck.K, radius, group, D, stride, table);
+    if (r == SC_OK) r = ts_launch_schedule(ctx, table, tstatus, pa.P, D, order, jmax, slot, counts);
+    if (r == SC_OK && knots_out) r = ts_launch_shift(ctx, knots, pa.P, ck.K, slot, stride, knots_out);
     return r;
 }
 
@@ -396,35 +378,22 @@ extern "C" int sc_fleet_schedule_batch(sc_ctx* ctx, const double* time, const fl
                                        double* knots, int32_t* tstatus, const double* radius, const int32_t* group, int D, int stride,
                                        uint64_t* table, const int32_t* order, const int32_t* jmax, int32_t* slot, int32_t* counts,
                                        double* knots_out) {
-    if (ts_fleet_invalid(ctx, time, pts, offsets, length, P, T0, dt_c, K, radius, D, stride, slot, counts)) return SC_ERR_INVALID;
+    const sc_traj_paths pa{time, pts, offsets, length, status, t0, flags, P};
+    const sc_traj_clock ck{T0, dt_c, K};
+    if (ts_fleet_invalid(ctx, pa, ck, radius, D, stride, slot, counts)) return SC_ERR_INVALID;
     SC_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t kb = knots ? 0 : al256((size_t)P * (K + 1) * 16), sb = tstatus ? 0 : al256((size_t)P * 4);
-    if (kb + sb) {
-        int r = sc_scratch_reserve(ctx, &ctx->traj_knots, kb + sb);
-        if (r != SC_OK) return r;
-        if (!knots) knots = (double*)ctx->traj_knots.p;
-        if (!tstatus) tstatus = (int32_t*)((char*)ctx->traj_knots.p + kb);
-    }
-    if (!table) {
-        int r = sc_scratch_reserve(ctx, &ctx->traj_table, al256((size_t)P * P * 8));
-        if (r != SC_OK) return r;
-        table = (uint64_t*)ctx->traj_table.p;
-    }
-    return ts_launch_fleet(ctx, time, pts, offsets, length, status, P, t0, flags, T0, dt_c, K, knots, tstatus, radius, group, D, stride, table,
-                           order, jmax, slot, counts, knots_out);
+    int r = sc_traj_scratch_knots(ctx, P, K, &knots, &tstatus);
+    if (r == SC_OK && !table) r = sc_scratch_reserve(ctx, &ctx->traj_table, al256((size_t)P * P * 8));
+    if (r != SC_OK) return r;
+    if (!table) table = (uint64_t*)ctx->traj_table.p;
+    return ts_launch_fleet(ctx, pa, ck, knots, tstatus, radius, group, D, stride, table, order, jmax, slot, counts, knots_out);
 }
 
 // ---- host forms ----
-static bool ts_radius_outside(const double* radius, int P) {
-    for (int p = 0; p < P; ++p)
-        if (!(isfinite(radius[p]) && radius[p] >= 0.0)) return true;
-    return false;
-}
-
 extern "C" int sc_traj_shift_table_batch_host(sc_ctx* ctx, const double* knots, int32_t* tstatus, int P, int K, const double* radius,
                                               const int32_t* group, int D, int stride, uint64_t* table) {
     if (!ctx || !knots || !tstatus || !radius || !table || ts_size_invalid(P, K) || ts_slots_invalid(D, stride, K)) return SC_ERR_INVALID;
-    if (ts_radius_outside(radius, P)) return SC_ERR_INVALID;
+    if (sc_traj_radius_outside(radius, P)) return SC_ERR_INVALID;
     SC_HIP(ctx, hipSetDevice(ctx->device));
     const size_t pb = (size_t)P * 4;
     sc_stage st(ctx);
@@ -472,28 +441,22 @@ extern "C" int sc_fleet_schedule_batch_host(sc_ctx* ctx, const double* time, con
                                             int K, double* knots, int32_t* tstatus, const double* radius, const int32_t* group, int D,
                                             int stride, uint64_t* table, const int32_t* order, const int32_t* jmax, int32_t* slot,
                                             int32_t* counts, double* knots_out) {
-    if (ts_fleet_invalid(ctx, time, pts, offsets, length, P, T0, dt_c, K, radius, D, stride, slot, counts)) return SC_ERR_INVALID;
-    if (ts_radius_outside(radius, P)) return SC_ERR_INVALID;
-    if (offsets[0] < 0) return SC_ERR_INVALID;
-    for (int p = 0; p < P; ++p)
-        if (offsets[p + 1] < offsets[p] || (t0 && !isfinite(t0[p])) || (flags && (flags[p] < 0 || flags[p] > 3))) return SC_ERR_INVALID;
-    for (int p = 0; p < P; ++p)
-        if ((!status || status[p] == SC_SMOOTH_OK) && length[p] >= 1 && (long long)offsets[p] + length[p] > offsets[P]) return SC_ERR_INVALID;
+    const sc_traj_paths pa{time, pts, offsets, length, status, t0, flags, P};
+    const sc_traj_clock ck{T0, dt_c, K};
+    if (ts_fleet_invalid(ctx, pa, ck, radius, D, stride, slot, counts)) return SC_ERR_INVALID;
+    if (sc_traj_radius_outside(radius, P) || sc_traj_paths_outside(pa)) return SC_ERR_INVALID;
     SC_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t M = (size_t)offsets[P], pb = (size_t)P * 4, kb = (size_t)P * (K + 1) * 16;
+    const size_t pb = (size_t)P * 4, kb = (size_t)P * (K + 1) * 16;
     sc_stage st(ctx);
-    const int i_t = st.in(time, M * 8), i_p = st.in(pts, M * 8), i_o = st.in(offsets, pb + 4), i_l = st.in(length, pb),
-              i_s = st.in(status, status ? pb : 0), i_d = st.in(t0, t0 ? pb * 2 : 0), i_f = st.in(flags, flags ? pb : 0),
-              i_r = st.in(radius, pb * 2), i_g = st.in(group, group ? pb : 0), i_or = st.in(order, order ? pb : 0),
+    const int i_pa = sc_traj_stage_paths(st, pa);
+    const int i_r = st.in(radius, pb * 2), i_g = st.in(group, group ? pb : 0), i_or = st.in(order, order ? pb : 0),
               i_j = st.in(jmax, jmax ? pb : 0);
     const int o_k = st.out(knots, kb), o_s = st.out(tstatus, pb), o_t = st.out(table, (size_t)P * P * 8);   // slots even when not copied back
     const int o_sl = st.out(slot, pb), o_c = st.out(counts, 16), o_ko = st.out(knots_out, knots_out ? kb : 0);
     int r = st.upload();
     if (r == SC_OK)
-        r = ts_launch_fleet(ctx, st.dev<const double>(i_t), st.dev<const float>(i_p), st.dev<const int32_t>(i_o), st.dev<const int32_t>(i_l),
-                            status ? st.dev<const int32_t>(i_s) : nullptr, P, t0 ? st.dev<const double>(i_d) : nullptr,
-                            flags ? st.dev<const int32_t>(i_f) : nullptr, T0, dt_c, K, st.dev<double>(o_k), st.dev<int32_t>(o_s),
-                            st.dev<const double>(i_r), group ? st.dev<const int32_t>(i_g) : nullptr, D, stride, st.dev<uint64_t>(o_t),
+        r = ts_launch_fleet(ctx, sc_traj_staged_paths(st, i_pa, pa), ck, st.dev<double>(o_k), st.dev<int32_t>(o_s), st.dev<const double>(i_r),
+                            group ? st.dev<const int32_t>(i_g) : nullptr, D, stride, st.dev<uint64_t>(o_t),
                             order ? st.dev<const int32_t>(i_or) : nullptr, jmax ? st.dev<const int32_t>(i_j) : nullptr, st.dev<int32_t>(o_sl),
                             st.dev<int32_t>(o_c), knots_out ? st.dev<double>(o_ko) : nullptr);
     return st.finish(r);

@@ -172,6 +172,29 @@ def test_entry_points_agree(ctx):
     assert np.array_equal(prefilled.cpu().numpy().view(np.uint64), ref["table"])
 
 
+@pytest.mark.parametrize("P,K,box,D,stride", [(70, 70, 12.0, 4, 3), (33, 17, 6.0, 8, 1)])
+def test_unshifted_bit_is_the_conflict_matrix(ctx, P, K, box, D, stride):
+    """The table kernel and the pair kernel evaluate one predicate (sc_traj_closest): on the same knots, tstatus, radius and
+    group, bit D-1 of table[p][q] (nobody shifted) is bit q % 32 of word q // 32 of traj_conflicts' matrix, and both calls leave
+    the same tstatus.  The smallest sizes that cross the pair kernel's 64-row and 32-column tiles and 16-tick chunks and the
+    table kernel's 64-tick chunk; D = 4 packs four pairs into a wavefront, D = 8 two.  On the two twins the identity holds with
+    328 of 4900 and 130 of 1089 bits set and 5 paths BAD."""
+    c = tc.random_fleet(seed=tc.FLEET_SEED + P + K, P=P, K=K, dt_c=75.0 / K, box=box)
+    kn = ctx.traj_knots(_sm(c), t0=_t(c["t0"]), flags=_t(c["flags"]), T0=c["T0"], dt_c=c["dt_c"], K=K)
+    tb = ctx.traj_shift_table(kn["knots"], kn["tstatus"].clone(), _t(c["radius"]), group=_t(c["group"]), D=D, stride=stride)
+    cf = ctx.traj_conflicts(kn["knots"], kn["tstatus"].clone(), _t(c["radius"]), group=_t(c["group"]), T0=c["T0"], dt_c=c["dt_c"],
+                            want_matrix=True)
+    ctx.synchronize()
+    tb, cf = _np(tb), _np(cf)
+    q = np.arange(P)
+    unshifted = (tb["table"].view(np.uint64) >> np.uint64(D - 1)) & np.uint64(1)
+    matrix = (cf["conflict"].view(np.uint32)[:, q // 32] >> (q % 32).astype(np.uint32)) & np.uint32(1)
+    print("bits set: table", int(unshifted.sum()), "matrix", int(matrix.sum()), "of", P * P, "BAD", int((tb["tstatus"] == 2).sum()))
+    assert np.array_equal(unshifted, matrix)
+    assert np.array_equal(tb["tstatus"], cf["tstatus"])
+    assert matrix.any() and not matrix.all()
+
+
 def test_residual_report_is_empty(ctx):
     """traj_conflicts on knots_out: no conflict among the scheduled paths (every path rests where the shifts end), and the
     unscheduled ones are absent."""
