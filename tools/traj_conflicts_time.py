@@ -96,7 +96,7 @@ def main():
     K = ctx._traj_ticks(sm, None, T0, dt_c)
     kn = ctx.traj_knots(sm, T0=T0, dt_c=dt_c, K=K)
     l, h, p = ctx._l, ctx._h, sc._ptr
-    out = ctx._traj_out(P, "cuda", False)
+    out = sc._on("cuda").traj_out(P, False)
     outs = [p(out[k]) for k in ("first_t", "first_with", "min_sep", "min_with", "n_conf")]
 
     def knots():

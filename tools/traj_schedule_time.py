@@ -110,7 +110,7 @@ def main():
         slot = torch.empty(P, dtype=torch.int32, device="cuda")
         counts = torch.empty(4, dtype=torch.int32, device="cuda")
         moved = torch.empty_like(kn["knots"])
-        out = ctx._traj_out(P, "cuda", False)
+        out = sc._on("cuda").traj_out(P, False)
         outs = [p(out[k]) for k in ("first_t", "first_with", "min_sep", "min_with", "n_conf")]
 
         def tab(c, t):
