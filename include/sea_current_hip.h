@@ -1089,6 +1089,50 @@ int sc_fleet_explore_batch_host(sc_ctx* ctx, const int32_t* d2, const uint8_t* k
                                 int32_t* ncl, int32_t* rep, int32_t* csize, int32_t* cbox, int64_t* csum, int32_t* cost, int32_t* cell,
                                 int32_t* col_of, int32_t* row_of, int64_t* info, int32_t* goal, int32_t* gcost);
 
+/* ---- line-of-sight sensing: known space that walls block, and what a pose would reveal ---------------------------
+ * sc_known_from_discs marks a cell known when it lies in a sensing disc, whatever stands between it and the sensor.  These
+ * calls cast one ray per (view, cell of the view's box) instead.  The reference has no counterpart (no parity claim); the
+ * definitions are integer and unique; tests/views_twin.py states them in NumPy, tests/cpp/views_ref.c in C, and every output
+ * equals both bit for bit.  DESIGN.md section 23.  Cells are c = y*W + x.
+ *
+ * Inputs.  occ uint8 [H][W]: the map the sensor meets (in a simulation the true map, for a prediction the observed one).
+ *   views int32 [R][3] = (cx, cy, r2), the layout of discs.  A view with r2 < 0, or with its centre outside the grid, is
+ *   ignored.
+ * Clear(a, b): sc_path_waypoints_batch's Visible(a, b) with the cell test occ == 0 in place of T: every cell whose closed unit
+ *   square meets the closed segment between the centres of a and b has occ = 0 (the supercover, a and b included; a ray
+ *   through a cell corner needs both side cells: A*'s no-corner-cutting rule).  Integer tests in doubled coordinates, exact
+ *   for every grid the library accepts.
+ * Seen free cell.  vis[c] <=> exists view v: (x-cx)^2 + (y-cy)^2 <= r2 (int64) and Clear(v, c).  vis[c] implies occ[c] = 0;
+ *   a view standing on an occupied cell sees nothing.
+ * Seen surface.  surf[c] <=> occ[c] != 0 and an orthogonal neighbour n inside the grid has vis[n]: the face of a wall that
+ *   bounds the seen free space is observed at any angle (a centre-to-centre ray reaches a wall cell only within 45 degrees of
+ *   its normal, and every free cell along a wall seen obliquely would be a spurious frontier cell).  A surface cell may lie
+ *   one cell outside the disc.
+ *
+ * sc_known_from_views: known[c] = (base ? base[c] != 0 : 0) | vis[c] | surf[c], written as 0 / 1; vis and surf come from
+ *   this call's views only; nothing depends on the order of the views or of execution.  occ_seen[c] = known[c] ? occ[c] : 0
+ *   (may be NULL): the map the EDT of the observed obstacles takes.  base may be NULL or known itself; occ_seen must be
+ *   neither occ nor known.  R == 0 copies base or clears (views may then be NULL).  A memset, one ray kernel per 65535 views
+ *   and one kernel per cell, timed as SC_K_MOVES.  Scratch: W * H bytes; grows only.
+ *   Consequences: with occ == 0 everywhere and all centres in the grid, known equals sc_known_from_discs of the same rows;
+ *   vis lies inside the discs and known \ base inside the discs dilated by one orthogonal step; from a frontier cell with
+ *   r2 >= 1 a view reveals the unknown orthogonal neighbour (free: Clear at distance 1; occupied: surface).
+ * sc_view_gain_batch: gain[i] = #{c : known[c] == 0 and vis_i[c]} (int32 [N]) for view i alone; 0 for an ignored view.
+ *   With occ the observed map (unknown cells read 0) it predicts what pose i would reveal; with occ the true map it is
+ *   exactly the number of free cells sc_known_from_views(known, occ, view i) newly marks.  N == 0 is a no-op.  A memset and
+ *   one kernel per 65535 candidates (one integer atomicAdd per wavefront), timed as SC_K_MOVES.
+ *
+ * Device pointers; the calls only enqueue on the context's stream.  The _host forms take host pointers, copy, run, copy back
+ * and synchronise.  Errors: SC_ERR_INVALID for NULL mandatory pointers, R < 0, N < 0, W or H outside 1..SC_MAX_DIM, occ_seen
+ * equal to occ or to known. */
+int sc_known_from_views(sc_ctx* ctx, const uint8_t* base, const uint8_t* occ, const int32_t* views, int R, int W, int H, uint8_t* known,
+                        uint8_t* occ_seen);
+int sc_known_from_views_host(sc_ctx* ctx, const uint8_t* base, const uint8_t* occ, const int32_t* views, int R, int W, int H,
+                             uint8_t* known, uint8_t* occ_seen);
+int sc_view_gain_batch(sc_ctx* ctx, const uint8_t* occ, const uint8_t* known, const int32_t* views, int N, int W, int H, int32_t* gain);
+int sc_view_gain_batch_host(sc_ctx* ctx, const uint8_t* occ, const uint8_t* known, const int32_t* views, int N, int W, int H,
+                            int32_t* gain);
+
 /* ---- re-planning in space-time around the scheduled fleet -------------------------------------------------------
  * sc_fleet_schedule_batch only delays: a path that finds no free slot comes back SC_SLOT_UNRESOLVED.  These calls plan such a
  * robot again in (cell, time): the paths that did get a slot are rasterised into reservations, and an exact earliest-arrival

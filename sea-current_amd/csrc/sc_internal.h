@@ -92,6 +92,7 @@ struct __attribute__((visibility("hidden"))) sc_ctx {
     sc_scratch fr_state;    // frontiers: int32 [G][H][W] labels when the caller passes none | int32 [G][H][W] sizes, then slots, at the roots | int32 [G][blocks] listed roots per 256 cells
     sc_scratch fr_key;      // frontier cost matrix: uint64 [F][Cmax] keys g << 32 | cell
     sc_scratch fr_fleet;    // sc_fleet_explore_batch: the intermediate arrays the caller passes none of
+    sc_scratch vw_vis;      // line-of-sight sensing: uint8 [H][W], 1 where a view of the call sees the free cell
     int astar_cap = 1 << 16;         // ring entries per bucket (power of two)
     size_t astar_slot_budget = (size_t)96 << 30;  // bytes of g + bitmap + ring scratch this context may take (SC_ASTAR_SLOT_GB), further bounded by what the device has free; 4096^2: 96 GiB = 1966 slots measured best (48: -34 %, 160: -17 %)
     int traj_wg_target = 4096;      // path conflicts: workgroups a launch of the pair kernel aims for (16 per CU; SC_TRAJ_WORKGROUPS)

@@ -1209,6 +1209,46 @@ class Context:
                                                 "info")), _ptr(out["goal"]), _ptr(out["gcost"]))
         return out
 
+    # ---- line-of-sight sensing (sc_known_from_views, sc_view_gain_batch) ----
+    def known_from_views(self, views, occ, base=None, out=None, occ_seen=None):
+        """The known-space mask of views that walls block (sc_known_from_views): views int32 [R,3] = (cx, cy, r2) and occ uint8
+        [H,W] (the map the sensor meets) on the GPU, base uint8 [H,W] or None (may be `out`).  Returns known uint8 [H,W]: base,
+        the free cells a view sees along a clear ray, and the occupied cells that border one.  occ_seen: a uint8 [H,W] tensor,
+        or True to have it allocated; then (known, occ_seen) is returned, occ_seen = occ where known, 0 elsewhere.  Only
+        enqueues."""
+        return self._known_from_views(_on(occ.device), views, occ, base, out, occ_seen)
+
+    def known_from_views_host(self, views, occ, base=None, occ_seen=None):
+        """Host form of known_from_views (numpy in, numpy out)."""
+        return self._known_from_views(_HOST, views, occ, base, None, occ_seen)
+
+    def _known_from_views(self, A, views, occ, base, out, occ_seen):
+        views, occ, base = A.rows(views, A.i32, 3), A.arr(occ, A.u8), A.arr(base, A.u8)
+        H, W = occ.shape
+        if out is None:
+            out = A.new((H, W), A.u8)
+        if occ_seen is True:
+            occ_seen = A.new((H, W), A.u8)
+        self._call("sc_known_from_views" + A.suffix, _ptr(base), _ptr(occ), _ptr(views), views.shape[0], W, H, _ptr(out), _ptr(occ_seen))
+        return out if occ_seen is None else (out, occ_seen)
+
+    def view_gain(self, views, occ, known, out=None):
+        """The unknown cells every candidate pose would see (sc_view_gain_batch): views int32 [N,3], occ and known uint8 [H,W]
+        on the GPU.  Returns gain int32 [N]: for view i alone, the cells with known == 0 it sees.  Only enqueues."""
+        return self._view_gain(_on(occ.device), views, occ, known, out)
+
+    def view_gain_host(self, views, occ, known):
+        """Host form of view_gain (numpy in, numpy out)."""
+        return self._view_gain(_HOST, views, occ, known)
+
+    def _view_gain(self, A, views, occ, known, out=None):
+        views, occ, known = A.rows(views, A.i32, 3), A.arr(occ, A.u8), A.arr(known, A.u8)
+        H, W = occ.shape
+        if out is None:
+            out = A.new(views.shape[0], A.i32)
+        self._call("sc_view_gain_batch" + A.suffix, _ptr(occ), _ptr(known), _ptr(views), views.shape[0], W, H, _ptr(out))
+        return out
+
     # ---- multi-GPU gather (RCCL through the C ABI) ----
     @staticmethod
     def comm_unique_id():

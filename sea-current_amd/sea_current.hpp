@@ -36,6 +36,7 @@
 //   planner::pick_next_goal_point      :465-519           same signature; unfinished there ("TODO: fix condition"), so no
 //                                                         parity: frontier clusters of the known space on the GPU
 //   (new) occupancy_grid::frontiers / explore_goals, planning_space::known_grid: exploration frontiers, a goal per robot
+//   (new) occupancy_grid::known_from_views / view_gain, planner::line_of_sight: sensing that walls block
 //
 // Differences that are deliberate: obstacle::closed is initialised (the reference leaves it
 // uninitialised, :197); library code never prints or calls std::exit (SC_ASSERT throws in DEBUG);
@@ -53,6 +54,7 @@
 #pragma once
 
 #include <algorithm>
+#include <array>
 #include <cfloat>
 #include <cmath>
 #include <complex>
@@ -651,6 +653,35 @@ public:
         f.listed = ncl[0]; f.total = ncl[1];
         return r;
     }
+    // Line-of-sight sensing (sc_known_from_views): `views` are (cx, cy, r2) in cells, one std::array<int32_t, 3> each -- the
+    // rows of the C call; this grid's occ is the map the sensor meets.  A free cell is seen when it lies in a view's disc and
+    // every cell the segment from the view's centre touches is free; an occupied cell is known when it borders a seen free
+    // cell.  known = base (empty: nothing known before) | seen | surface; occ_seen = occ where known, 0 elsewhere: the map the
+    // robot has observed.  A view with r2 < 0, off the grid or on an occupied cell sees nothing.
+    struct view_result {
+        std::vector<uint8_t> known, occ_seen;
+    };
+    view_result known_from_views(const std::vector<std::array<int32_t, 3>>& views, const std::vector<uint8_t>& base = {},
+                                 gpu_context& ctx = default_context()) const {
+        if (!base.empty() && base.size() != occ.size()) throw std::invalid_argument("occupancy_grid::known_from_views: base is not [H][W]");
+        view_result r;
+        r.known.assign(occ.size(), 0); r.occ_seen.assign(occ.size(), 0);
+        if (occ.empty()) return r;
+        ctx.check(sc_known_from_views_host(ctx.get(), base.empty() ? nullptr : base.data(), occ.data(), views.empty() ? nullptr : views[0].data(),
+                                           (int)views.size(), W, H, r.known.data(), r.occ_seen.data()), "sc_known_from_views_host");
+        return r;
+    }
+    // The unknown cells every candidate pose would see (sc_view_gain_batch): gain[i] = the cells with known == 0 that view i
+    // alone sees on this grid's occ.  With occ the observed map (occ_seen) it predicts what driving to pose i would reveal.
+    std::vector<int32_t> view_gain(const std::vector<uint8_t>& known, const std::vector<std::array<int32_t, 3>>& views,
+                                   gpu_context& ctx = default_context()) const {
+        if (known.size() != occ.size()) throw std::invalid_argument("occupancy_grid::view_gain: known is not [H][W]");
+        std::vector<int32_t> gain(views.size(), 0);
+        if (views.empty() || occ.empty()) return gain;
+        ctx.check(sc_view_gain_batch_host(ctx.get(), occ.data(), known.data(), views[0].data(), (int)views.size(), W, H, gain.data()),
+                  "sc_view_gain_batch_host");
+        return gain;
+    }
 private:
     // both cost_fields overloads; pen NULL: the unweighted fields
     field_result cost_fields_with(const std::vector<int32_t>& roots, const std::vector<uint8_t>* pen, int pen_cap, int32_t r2_clear, int rounds,
@@ -1073,18 +1104,32 @@ private:
 //   ranked by the cost of the robot's path to their cheapest cell; the cheapest is returned, the other clusters' best cells
 //   are pushed onto goal_point_cache, cheapest on top.  Without a reachable frontier the top of the cache is returned and
 //   popped; with the cache empty as well it throws std::runtime_error.
+// line_of_sight (false: the above, unchanged).  With it set the disc is not allocated; instead the robot senses the true grid
+//   (ps.make_grid) along clear rays: seen = occupancy_grid::known_from_views(one view at start's cell, base = seen), with
+//   r2 = (int32_t)((search_radius / g.resolution)^2), the squared radius in cells truncated to an integer.  `seen` is the
+//   known mask kept between calls ([H][W], sized and zeroed on first use); the grid the frontiers are taken on is occ_seen.
 class planner {
 public:
     planning_space ps;
     std::stack<Vector2f> goal_point_cache;
     int64_t past_id = 0;
+    bool line_of_sight = false;
+    std::vector<uint8_t> seen;
 
     explicit planner(const planning_space& space) : ps(space) {}
 
     Vector2f pick_next_goal_point(const Vector2f& start, const int n, const float search_radius, gpu_context& ctx = default_context()) {
-        ps.free_space_allocations.push_back([start, search_radius](Vector2f p) { return pt_dist(p, start) <= search_radius; });
+        if (!line_of_sight) ps.free_space_allocations.push_back([start, search_radius](Vector2f p) { return pt_dist(p, start) <= search_radius; });
         occupancy_grid g = ps.make_grid(ctx);
-        const std::vector<uint8_t> known = ps.known_grid(g.W, g.H);
+        if (line_of_sight) {
+            if (seen.size() != g.occ.size()) seen.assign(g.occ.size(), 0);
+            const int32_t sc = g.cell_of(start);
+            const float rc = search_radius / g.resolution;
+            auto view = g.known_from_views({{sc % g.W, sc / g.W, (int32_t)(rc * rc)}}, seen, ctx);
+            seen = std::move(view.known);
+            g.occ = std::move(view.occ_seen);
+        }
+        const std::vector<uint8_t> known = line_of_sight ? seen : ps.known_grid(g.W, g.H);
         for (size_t c = 0; c < known.size(); ++c)
             if (!known[c]) g.occ[c] = 0;                       // an obstacle the robot has not seen is not on its map
         g.edt(ctx);
