@@ -1133,6 +1133,63 @@ int sc_view_gain_batch(sc_ctx* ctx, const uint8_t* occ, const uint8_t* known, co
 int sc_view_gain_batch_host(sc_ctx* ctx, const uint8_t* occ, const uint8_t* known, const int32_t* views, int N, int W, int H,
                             int32_t* gain);
 
+/* ---- occupancy from range scans: beam casts and log-odds maps ------------------------------------------------------
+ * The calls above take the map to be sensed and hand back a mask.  These two take measurements: a beam has an origin, an end
+ * and either the cell where it stopped or no return.  sc_scan_cast_batch is the simulated range sensor (it casts beams through
+ * a true map), sc_logodds_update the standard occupancy-grid update from beams: free along the beam, occupied at its end, as
+ * clamped integer log-odds that accumulate over calls and can take a cell back.  The reference has no counterpart (no parity
+ * claim); the definitions are integer and unique; tests/scan_twin.py states them in NumPy, tests/cpp/scan_ref.c in C, and
+ * every output equals both bit for bit.  DESIGN.md section 24.  Cells are c = y*W + x.
+ *
+ * Walk(a, b): the supercover of the segment between the centres of cells a and b (every cell whose closed unit square meets
+ *   the closed segment; a ray through a cell corner touches both side cells) as a SEQUENCE: column i = 0 .. D of the major
+ *   axis (D = max(|dx|, |dy|), m = min(|dx|, |dy|), the x axis is the major one when |dx| >= |dy|), and inside a column the
+ *   rows rlo(i) .. rhi(i) counted away from a,
+ *     rhi(i) = min(floor(((2i+1) m + D) / 2D), m),   rlo(i) = ceil(((2i-1) m - D) / 2D) for i >= 1, 0 for i = 0.
+ *   a = b is the one cell a.  a lies inside the grid; b may lie outside: the sequence ends before its first cell outside the
+ *   grid (the segment leaves the grid once; a cell inside the grid that the segment only touches at a corner after that
+ *   point is not part of the walk).  At an exact corner crossing the cell on the near column (the larger row of column i)
+ *   comes before the cell of the next column.
+ * Rays int32 [N][4] = (ax, ay, bx, by), aligned as int32 (no more is needed).  A ray is IGNORED when a lies outside the
+ *   grid or |bx - ax| or |by - ay| exceeds SC_SCAN_MAX_REACH (then (2D+1) m + D < 2^30: the walk's products stay in int32).
+ *
+ * sc_scan_cast_batch: hit int32 [N].  hit[k] = SC_SCAN_IGNORED for an ignored ray or occ[a] != 0 (a sensor standing in an
+ *   obstacle sees nothing); else the first cell of Walk(a, b), in sequence order, with occ != 0; else SC_SCAN_NO_RETURN.
+ *   Consequence: for b inside the grid, hit = SC_SCAN_NO_RETURN <=> Clear(a, b) of the section above.  N == 0 is a no-op.
+ *   One kernel, one lane per ray in ceil(N / 256) workgroups, timed as SC_K_MOVES.
+ * sc_logodds_update: L int32 [H][W] (NULL: a fresh map of zeros; may be Lout), hit[k] what the cast wrote -- for recorded data
+ *   the cell of the beam's end with b that cell, or SC_SCAN_NO_RETURN with b at maximum range.  A beam is ignored when its
+ *   ray is, or hit[k] = SC_SCAN_IGNORED (the device form also ignores a hit below -2 or >= W*H; the _host form returns
+ *   SC_ERR_INVALID for one before any launch).  For every other beam the cells of Walk(a, b) before the first occurrence of
+ *   cell hit[k] are MISSED (all of them when hit[k] = -1 or the cell is not on the walk), and cell hit[k] >= 0 is HIT.  With M
+ *   the cells missed and S the cells hit by some beam of this call,
+ *     Lout[c] = clamp(L[c] + (c in S ? l_hit : c in M ? -l_miss : 0), -l_clamp, l_clamp)      (the sum in 64 bits).
+ *   One update per cell and call however many beams cross it; a hit wins over a miss within a call (a wall cell that
+ *   neighbouring beams graze is not eroded); nothing depends on the order of the beams or of execution.  Several scans that
+ *   should each count are several calls.  Optional outputs (either or both NULL), written as 0 / 1:
+ *     occ_est[c] = Lout[c] >= t_occ,   known[c] = Lout[c] >= t_occ or Lout[c] <= -t_free:
+ *   the (known, occ_seen) pair of the calls above; unknown cells read 0 in occ_est.  N == 0 applies no beam, still clamps and
+ *   writes the outputs (a stored map -> masks; rays and hit may then be NULL).
+ *   Consequence (soundness): fed the cast's hit of a true map with the same rays, every missed cell has occ = 0 and every hit
+ *   cell occ != 0; with l_hit >= t_occ and l_miss >= t_free occ_est never contradicts the true map.
+ *   One kernel per beam batch (plain byte stores of 1 into two flag maps) and one kernel per cell, timed as SC_K_MOVES.
+ *   Scratch: 2 * W * H bytes; grows only.
+ *
+ * Device pointers; the calls only enqueue on the context's stream.  The _host forms take host pointers, copy, run, copy back
+ * and synchronise.  Errors: SC_ERR_INVALID for NULL mandatory pointers (Lout; occ and hit of the cast; rays and hit when
+ * N > 0), N < 0, W or H outside 1..SC_MAX_DIM, l_hit < 0, l_miss < 0, l_clamp outside 0..2^30, t_occ < 1, t_free < 1, occ_est
+ * or known equal to each other or to L or Lout. */
+#define SC_SCAN_NO_RETURN (-1)  /* hit: the beam met no occupied cell */
+#define SC_SCAN_IGNORED (-2)    /* hit: the ray was ignored, or the sensor stands on an occupied cell */
+#define SC_SCAN_MAX_REACH 16384 /* |bx - ax|, |by - ay| of a ray that is not ignored */
+int sc_scan_cast_batch(sc_ctx* ctx, const uint8_t* occ, const int32_t* rays, int N, int W, int H, int32_t* hit);
+int sc_scan_cast_batch_host(sc_ctx* ctx, const uint8_t* occ, const int32_t* rays, int N, int W, int H, int32_t* hit);
+int sc_logodds_update(sc_ctx* ctx, const int32_t* L, const int32_t* rays, const int32_t* hit, int N, int W, int H, int32_t l_hit,
+                      int32_t l_miss, int32_t l_clamp, int32_t t_occ, int32_t t_free, int32_t* Lout, uint8_t* occ_est, uint8_t* known);
+int sc_logodds_update_host(sc_ctx* ctx, const int32_t* L, const int32_t* rays, const int32_t* hit, int N, int W, int H, int32_t l_hit,
+                           int32_t l_miss, int32_t l_clamp, int32_t t_occ, int32_t t_free, int32_t* Lout, uint8_t* occ_est,
+                           uint8_t* known);
+
 /* ---- re-planning in space-time around the scheduled fleet -------------------------------------------------------
  * sc_fleet_schedule_batch only delays: a path that finds no free slot comes back SC_SLOT_UNRESOLVED.  These calls plan such a
  * robot again in (cell, time): the paths that did get a slot are rasterised into reservations, and an exact earliest-arrival

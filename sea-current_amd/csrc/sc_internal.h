@@ -93,12 +93,14 @@ struct __attribute__((visibility("hidden"))) sc_ctx {
     sc_scratch fr_key;      // frontier cost matrix: uint64 [F][Cmax] keys g << 32 | cell
     sc_scratch fr_fleet;    // sc_fleet_explore_batch: the intermediate arrays the caller passes none of
     sc_scratch vw_vis;      // line-of-sight sensing: uint8 [H][W], 1 where a view of the call sees the free cell
+    sc_scratch sn_flags;    // range scans: uint8 [2][al256(W H)] miss and hit flags of one sc_logodds_update; all zero between calls
     int astar_cap = 1 << 16;         // ring entries per bucket (power of two)
     size_t astar_slot_budget = (size_t)96 << 30;  // bytes of g + bitmap + ring scratch this context may take (SC_ASTAR_SLOT_GB), further bounded by what the device has free; 4096^2: 96 GiB = 1966 slots measured best (48: -34 %, 160: -17 %)
     int traj_wg_target = 4096;      // path conflicts: workgroups a launch of the pair kernel aims for (16 per CU; SC_TRAJ_WORKGROUPS)
     bool traj_sched_noskip = false; // delay schedules: evaluate the pairs the box test would skip (SC_TRAJ_SCHED_NOSKIP=1; the tests prove the skip exact with it)
     size_t tplan_budget = (size_t)8 << 30;   // space-time plans: bytes of tp_reach a group of queries may take (SC_TPLAN_GB, 1 .. 64)
     int tplan_layers = 16;          // space-time plans: layers a launch of the step kernel advances, 1 .. 16 (SC_TPLAN_LAYERS); no output depends on it
+    bool sn_flags_zeroed = false;   // range scans: the memset of the current sn_flags buffer has been enqueued
     int last_Q = 0;
     void* comm = nullptr;           // ncclComm_t of sc_allgather_paths
     bool comm_owned = false;

@@ -41,6 +41,8 @@ TP_OK, TP_NO_PATH, TP_BAD_ENDPOINT, TP_START_BLOCKED = range(4)
 ASSIGN_MAX_DIM = 1024
 ASSIGN_BIG = 1 << 42
 ASSIGN_OK, ASSIGN_BAD = 0, 1
+SCAN_NO_RETURN, SCAN_IGNORED, SCAN_MAX_REACH = -1, -2, 16384
+LOGODDS_HIT, LOGODDS_MISS, LOGODDS_CLAMP, LOGODDS_T_OCC, LOGODDS_T_FREE = 2, 1, 8, 2, 1   # logodds_update's defaults
 
 _lib = None
 
@@ -113,6 +115,18 @@ def _ptr(t):
         return t.ctypes.data
     assert t.is_contiguous()
     return t.data_ptr()
+
+
+def _count(x):
+    """Elements of a torch tensor or numpy array."""
+    return int(x.size) if isinstance(x, np.ndarray) else int(x.numel())
+
+
+def _sized(what, x, n):
+    """x (may be None) has n elements: the calls whose grid size is an argument, not a tensor's shape, check it here, since
+    the library would write W * H elements whatever the tensor holds."""
+    if x is not None and _count(x) != n:
+        raise SeaCurrentError(f"{what} has {_count(x)} elements, the call needs {n}")
 
 
 def _ghw(d2):
@@ -1248,6 +1262,66 @@ class Context:
             out = A.new(views.shape[0], A.i32)
         self._call("sc_view_gain_batch" + A.suffix, _ptr(occ), _ptr(known), _ptr(views), views.shape[0], W, H, _ptr(out))
         return out
+
+    # ---- occupancy from range scans (sc_scan_cast_batch, sc_logodds_update) ----
+    def scan_cast(self, rays, occ, out=None):
+        """The simulated range sensor (sc_scan_cast_batch): rays int32 [N,4] = (ax, ay, bx, by) and occ uint8 [H,W] (the true
+        map) on the GPU.  Returns hit int32 [N]: the first occupied cell of the walk from a to b, SCAN_NO_RETURN when there is
+        none, SCAN_IGNORED for a ray that is ignored (a outside the grid, a reach above SCAN_MAX_REACH) or whose sensor stands
+        on an occupied cell.  b may lie outside the grid.  Only enqueues."""
+        return self._scan_cast(_on(occ.device), rays, occ, out)
+
+    def scan_cast_host(self, rays, occ):
+        """Host form of scan_cast (numpy in, numpy out)."""
+        return self._scan_cast(_HOST, rays, occ)
+
+    def _scan_cast(self, A, rays, occ, out=None):
+        rays, occ = A.rows(rays, A.i32, 4), A.arr(occ, A.u8)
+        H, W = occ.shape
+        if out is None:
+            out = A.new(rays.shape[0], A.i32)
+        _sized("scan_cast: rays", rays, 4 * rays.shape[0])
+        _sized("scan_cast: out", out, rays.shape[0])
+        self._call("sc_scan_cast_batch" + A.suffix, _ptr(occ), _ptr(rays), rays.shape[0], W, H, _ptr(out))
+        return out
+
+    def logodds_update(self, rays, hit, W, H, L=None, l_hit=LOGODDS_HIT, l_miss=LOGODDS_MISS, l_clamp=LOGODDS_CLAMP, t_occ=LOGODDS_T_OCC,
+                       t_free=LOGODDS_T_FREE, out=None, occ_est=None, known=None):
+        """The occupancy-grid update from beams (sc_logodds_update): rays int32 [N,4] and hit int32 [N] (what scan_cast wrote, or
+        recorded ends) on the GPU, L int32 [H,W] the map so far (None: all zeros; may be `out`).  Every cell some beam hits
+        gains l_hit, every other cell some beam passes loses l_miss -- once per call however many beams cross it -- and the
+        result is clamped to +-l_clamp.  occ_est / known: a uint8 [H,W] tensor, or True to have one allocated; occ_est = L >=
+        t_occ, known = occ_est or L <= -t_free: the (occ_seen, known) pair the exploration calls take.  Returns L alone, or a
+        tuple in the order (L, occ_est, known) of those requested.  rays and hit may be None (or empty): no beam, the stored
+        map is clamped and turned into masks.  The defaults make one look decide a cell (l_hit >= t_occ, l_miss >= t_free: the
+        estimate never contradicts a static true map) and the clamp four hits or eight misses deep, so that a cell that
+        changed is taken back after a few scans.  Only enqueues."""
+        src = next((x for x in (L, rays, out) if x is not None), None)
+        A = _on(src.device if src is not None else "cuda:%d" % self.device)
+        return self._logodds_update(A, rays, hit, W, H, L, l_hit, l_miss, l_clamp, t_occ, t_free, out, occ_est, known)
+
+    def logodds_update_host(self, rays, hit, W, H, L=None, l_hit=LOGODDS_HIT, l_miss=LOGODDS_MISS, l_clamp=LOGODDS_CLAMP,
+                            t_occ=LOGODDS_T_OCC, t_free=LOGODDS_T_FREE, occ_est=None, known=None):
+        """Host form of logodds_update (numpy in, numpy out); a hit below SCAN_IGNORED or >= W * H is an error."""
+        return self._logodds_update(_HOST, rays, hit, W, H, L, l_hit, l_miss, l_clamp, t_occ, t_free, None, occ_est, known)
+
+    def _logodds_update(self, A, rays, hit, W, H, L, l_hit, l_miss, l_clamp, t_occ, t_free, out, occ_est, known):
+        rays, hit, L = A.rows(rays, A.i32, 4), A.arr(hit, A.i32), A.arr(L, A.i32)
+        N = 0 if rays is None else rays.shape[0]
+        if out is None:
+            out = A.new((H, W), A.i32)
+        if occ_est is True:
+            occ_est = A.new((H, W), A.u8)
+        if known is True:
+            known = A.new((H, W), A.u8)
+        for what, x in (("L", L), ("out", out), ("occ_est", occ_est), ("known", known)):
+            _sized("logodds_update: " + what, x, W * H)
+        _sized("logodds_update: rays", rays, 4 * N)
+        _sized("logodds_update: hit", hit if N else None, N)
+        self._call("sc_logodds_update" + A.suffix, _ptr(L), _ptr(rays) if N else None, _ptr(hit) if N else None, N, W, H, l_hit, l_miss, l_clamp,
+                   t_occ, t_free, _ptr(out), _ptr(occ_est), _ptr(known))
+        res = (out,) + tuple(x for x in (occ_est, known) if x is not None)
+        return out if len(res) == 1 else res
 
     # ---- multi-GPU gather (RCCL through the C ABI) ----
     @staticmethod

@@ -37,6 +37,8 @@
 //                                                         parity: frontier clusters of the known space on the GPU
 //   (new) occupancy_grid::frontiers / explore_goals, planning_space::known_grid: exploration frontiers, a goal per robot
 //   (new) occupancy_grid::known_from_views / view_gain, planner::line_of_sight: sensing that walls block
+//   (new) occupancy_grid::scan_cast, logodds_grid, beams_from_ranges, square_fan, planner::range_scan: range beams in, a
+//         log-odds occupancy map out
 //
 // Differences that are deliberate: obstacle::closed is initialised (the reference leaves it
 // uninitialised, :197); library code never prints or calls std::exit (SC_ASSERT throws in DEBUG);
@@ -682,6 +684,16 @@ public:
                   "sc_view_gain_batch_host");
         return gain;
     }
+    // The simulated range sensor (sc_scan_cast_batch): `rays` are (ax, ay, bx, by) in cells, one std::array<int32_t, 4> each;
+    // this grid's occ is the true map.  hit[k] = the first occupied cell the beam from a towards b meets, SC_SCAN_NO_RETURN
+    // when there is none before b or the edge of the grid (b may lie outside it), SC_SCAN_IGNORED for a beam whose origin lies
+    // off the grid or on an occupied cell or whose reach exceeds SC_SCAN_MAX_REACH.  logodds_grid::update takes rays and hit.
+    std::vector<int32_t> scan_cast(const std::vector<std::array<int32_t, 4>>& rays, gpu_context& ctx = default_context()) const {
+        std::vector<int32_t> hit(rays.size(), SC_SCAN_IGNORED);
+        if (rays.empty() || occ.empty()) return hit;
+        ctx.check(sc_scan_cast_batch_host(ctx.get(), occ.data(), rays[0].data(), (int)rays.size(), W, H, hit.data()), "sc_scan_cast_batch_host");
+        return hit;
+    }
 private:
     // both cost_fields overloads; pen NULL: the unweighted fields
     field_result cost_fields_with(const std::vector<int32_t>& roots, const std::vector<uint8_t>* pen, int pen_cap, int32_t r2_clear, int rounds,
@@ -703,6 +715,86 @@ private:
         return r;
     }
 };
+
+// ---- occupancy from range scans (new; the reference has no counterpart) -----------------------------
+// The increments, the clamp and the two thresholds of logodds_grid (sc_logodds_update).  The defaults let one look decide a
+// cell (l_hit >= t_occ, l_miss >= t_free: the estimate never contradicts a static true map) and make the clamp four hits or
+// eight misses deep, so a cell that changed is taken back after a few scans.
+struct logodds_params {
+    int32_t l_hit = 2, l_miss = 1, l_clamp = 8, t_occ = 2, t_free = 1;
+};
+
+// A log-odds occupancy map that accumulates beams: every cell some beam of a call hits gains l_hit, every other cell some beam
+// passes loses l_miss (once per call however many beams cross it), clamped to +-l_clamp.  occ_est = L >= t_occ and known =
+// occ_est or L <= -t_free are the (occ_seen, known) pair occupancy_grid::explore_goals and the planners take.
+class logodds_grid {
+public:
+    int W = 0, H = 0;
+    std::vector<int32_t> L;
+
+    struct masks_result {
+        std::vector<uint8_t> occ_est, known;
+    };
+
+    logodds_grid() = default;
+    logodds_grid(int cells_x, int cells_y) : W(cells_x), H(cells_y), L((size_t)cells_x * cells_y, 0) {}
+
+    // one scan: `rays` as occupancy_grid::scan_cast takes them, hit[k] what it returned -- or, for recorded data, the cell of
+    // the beam's end (with b that cell) and SC_SCAN_NO_RETURN for a beam that returned nothing (with b at maximum range)
+    masks_result update(const std::vector<std::array<int32_t, 4>>& rays, const std::vector<int32_t>& hit, const logodds_params& p = {},
+                        gpu_context& ctx = default_context()) {
+        if (hit.size() != rays.size()) throw std::invalid_argument("logodds_grid::update: one hit per ray");
+        masks_result r;
+        r.occ_est.assign(L.size(), 0); r.known.assign(L.size(), 0);
+        if (L.empty()) return r;
+        ctx.check(sc_logodds_update_host(ctx.get(), L.data(), rays.empty() ? nullptr : rays[0].data(), rays.empty() ? nullptr : hit.data(),
+                                         (int)rays.size(), W, H, p.l_hit, p.l_miss, p.l_clamp, p.t_occ, p.t_free, L.data(), r.occ_est.data(),
+                                         r.known.data()), "sc_logodds_update_host");
+        return r;
+    }
+    // the masks of the stored map (the call with no beams; it also clamps L to p.l_clamp)
+    masks_result masks(const logodds_params& p = {}, gpu_context& ctx = default_context()) { return update({}, {}, p, ctx); }
+};
+
+// The 8 r rays from cell (cx, cy) to every cell on the perimeter of the square of half-side r around it, going round once: a
+// full scan without trigonometry.  On a free grid they pass exactly the cells of that square.
+inline std::vector<std::array<int32_t, 4>> square_fan(int32_t cx, int32_t cy, int r) {
+    std::vector<std::array<int32_t, 4>> rays;
+    for (int t = -r; t < r; ++t) rays.push_back({cx, cy, cx + t, cy - r});
+    for (int t = -r; t < r; ++t) rays.push_back({cx, cy, cx + r, cy + t});
+    for (int t = -r; t < r; ++t) rays.push_back({cx, cy, cx - t, cy + r});
+    for (int t = -r; t < r; ++t) rays.push_back({cx, cy, cx - r, cy - t});
+    return rays;
+}
+
+// A range scan in world coordinates -> what logodds_grid::update takes.  Beam k leaves `origin` at angle bearings[k] (radians,
+// from +x towards +y) and returned ranges[k]; a range that is not finite, negative, or >= max_range is no return.  A cell
+// is floor((p - min) / resolution) per axis, NOT clamped: an end may lie outside the grid, and the beam then counts up to the
+// edge.  A return outside the grid marks no cell.  Float arithmetic on the host: no bit-exactness is claimed for oblique beams.
+struct scan_beams {
+    std::vector<std::array<int32_t, 4>> rays;
+    std::vector<int32_t> hit;
+};
+inline scan_beams beams_from_ranges(const occupancy_grid& g, const Vector2f& origin, const std::vector<float>& bearings,
+                                    const std::vector<float>& ranges, float max_range) {
+    if (bearings.size() != ranges.size()) throw std::invalid_argument("beams_from_ranges: one range per bearing");
+    const float ry = (g.bound_rect.y_max - g.bound_rect.y_min) / (float)g.H;
+    // a cell coordinate, floored; a point so far out that the beam would be ignored anyway is held at that distance, so the
+    // conversion to int32 is always defined (NaN becomes the far end too)
+    constexpr float far = (float)(SC_MAX_DIM + SC_SCAN_MAX_REACH + 1);
+    auto cell = [&](float v) { const float c = std::floor(v); return (int32_t)(c >= -far && c <= far ? c : (c < 0.0f ? -far : far)); };
+    auto cx = [&](float x) { return cell((x - g.bound_rect.x_min) / g.resolution); };
+    auto cy = [&](float y) { return cell((y - g.bound_rect.y_min) / ry); };
+    scan_beams b;
+    for (size_t k = 0; k < bearings.size(); ++k) {
+        const bool ret = std::isfinite(ranges[k]) && ranges[k] >= 0.0f && ranges[k] < max_range;
+        const float d = ret ? ranges[k] : max_range;
+        const int32_t ex = cx(origin.x() + d * std::cos(bearings[k])), ey = cy(origin.y() + d * std::sin(bearings[k]));
+        b.rays.push_back({cx(origin.x()), cy(origin.y()), ex, ey});
+        b.hit.push_back(ret && ex >= 0 && ey >= 0 && ex < g.W && ey < g.H ? ey * g.W + ex : SC_SCAN_NO_RETURN);
+    }
+    return b;
+}
 
 // ---- planning_space (sea_current.hpp:298-319, 1272-1407) --------------------------------------------
 // ---- sampling helpers of the reference's planner (sea_current.hpp:90-132, 287-296) ----------------
@@ -1108,6 +1200,11 @@ private:
 //   (ps.make_grid) along clear rays: seen = occupancy_grid::known_from_views(one view at start's cell, base = seen), with
 //   r2 = (int32_t)((search_radius / g.resolution)^2), the squared radius in cells truncated to an integer.  `seen` is the
 //   known mask kept between calls ([H][W], sized and zeroed on first use); the grid the frontiers are taken on is occ_seen.
+// range_scan (false: the above, unchanged; setting both flags throws std::logic_error).  With it set the disc is not
+//   allocated; the robot casts square_fan(start's cell, max(1, (int)(search_radius / g.resolution))) on the true grid
+//   (occupancy_grid::scan_cast) and updates `map` with scan_params (logodds_grid::update; sized and zeroed on first use).
+//   `seen` is the map's known mask, the grid the frontiers are taken on its occ_est: the robot explores on what its beams
+//   have accumulated, not on a mask handed to it.
 class planner {
 public:
     planning_space ps;
@@ -1115,12 +1212,25 @@ public:
     int64_t past_id = 0;
     bool line_of_sight = false;
     std::vector<uint8_t> seen;
+    bool range_scan = false;
+    logodds_grid map;
+    logodds_params scan_params;
 
     explicit planner(const planning_space& space) : ps(space) {}
 
     Vector2f pick_next_goal_point(const Vector2f& start, const int n, const float search_radius, gpu_context& ctx = default_context()) {
-        if (!line_of_sight) ps.free_space_allocations.push_back([start, search_radius](Vector2f p) { return pt_dist(p, start) <= search_radius; });
+        if (line_of_sight && range_scan) throw std::logic_error("planner::pick_next_goal_point: line_of_sight and range_scan are both set");
+        if (!line_of_sight && !range_scan)
+            ps.free_space_allocations.push_back([start, search_radius](Vector2f p) { return pt_dist(p, start) <= search_radius; });
         occupancy_grid g = ps.make_grid(ctx);
+        if (range_scan) {
+            if (map.W != g.W || map.H != g.H) map = logodds_grid(g.W, g.H);
+            const int32_t sc = g.cell_of(start);
+            const auto rays = square_fan(sc % g.W, sc / g.W, std::max(1, (int)(search_radius / g.resolution)));
+            auto m = map.update(rays, g.scan_cast(rays, ctx), scan_params, ctx);
+            seen = std::move(m.known);
+            g.occ = std::move(m.occ_est);
+        }
         if (line_of_sight) {
             if (seen.size() != g.occ.size()) seen.assign(g.occ.size(), 0);
             const int32_t sc = g.cell_of(start);
@@ -1129,7 +1239,7 @@ public:
             seen = std::move(view.known);
             g.occ = std::move(view.occ_seen);
         }
-        const std::vector<uint8_t> known = line_of_sight ? seen : ps.known_grid(g.W, g.H);
+        const std::vector<uint8_t> known = (line_of_sight || range_scan) ? seen : ps.known_grid(g.W, g.H);
         for (size_t c = 0; c < known.size(); ++c)
             if (!known[c]) g.occ[c] = 0;                       // an obstacle the robot has not seen is not on its map
         g.edt(ctx);
