@@ -17,7 +17,9 @@
  *     (sea_current.hpp:1191-1265).  PINNED for dof=1 by the reference's only
  *     recorded output, examples/output.json (tests/golden/toppra_1dof_*.npz):
  *     duration, vel, acc reproduce to float32 round-off.  dof>1 / varying
- *     limits: parity unpinned.
+ *     limits: pinned to the definition by the exact stage certificate, the
+ *     scaled replicas of the recording and the dense-solve spline of
+ *     tests/toppra_cert.py (see toppra_oracle.c).
  */
 #ifndef SC_ORACLE_H
 #define SC_ORACLE_H

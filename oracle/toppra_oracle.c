@@ -14,8 +14,15 @@
  *     LinearJointAcceleration with DiscretizationType::Interpolation (:1209-1210)
  *   - computePathParametrization(0, 0)                              (:1225)
  *   - parametrizer::Spline + uniform sampling at dt                 (:1233-1243)
- * PINNED for dof = 1 by examples/output.json (tests/test_oracle_toppra.py);
- * dof > 1: parity unpinned.
+ * PINNED for dof = 1 by examples/output.json (tests/test_oracle_toppra.py).
+ * dof > 1 has no recorded output; it is pinned to the definition below by
+ * tests/toppra_cert.py (tests/test_toppra_cert.py): an exact stage certificate
+ * (rational arithmetic, vertex enumeration of every stage polygon; measured
+ * residual of this file at most 1.4e-14, bar 1e-10), scaled replicas of the
+ * recording (joint k = the recorded joint times c_k: K, x, u, t bit-equal to
+ * the 1-dof result for signed power-of-two c_k, 1e-12 otherwise; the recorded
+ * times bit-equal, profiles within 2e-7), and for sco_toppra_sample a
+ * dense-solve clamped spline (5.8e-8, float32 round-off).
  *
  * Stage LP (variables u = sddot, x = sdot^2), rows  alpha*u + beta*x <= gamma:
  *   accel, collocation at i      :  +-(a_i u + b_i x) <= +-alim, a_i = q'(s_i), b_i = q''(s_i)
