@@ -1190,6 +1190,59 @@ int sc_logodds_update_host(sc_ctx* ctx, const int32_t* L, const int32_t* rays, c
                            int32_t l_miss, int32_t l_clamp, int32_t t_occ, int32_t t_free, int32_t* Lout, uint8_t* occ_est,
                            uint8_t* known);
 
+/* ---- scan matching: a scan's pose against the map -----------------------------------------------------------------
+ * The calls above take the sensor's cell as given.  sc_scan_match_batch asks the opposite question: given a scan's end points
+ * and the map so far, where was the sensor?  It scores every pose of a window around a prior against the likelihood field of
+ * the map (the exact EDT of occ_est, capped) and returns the best one, with the number of poses that tie with it.  The
+ * reference has no counterpart (no parity claim); the definition is integer and unique; tests/match_twin.py states it in
+ * NumPy, tests/cpp/match_ref.c in C, and every output equals both bit for bit.  DESIGN.md section 25.  Cells are c = y*W + x.
+ *
+ * Inputs.  d2 int32 [H][W] from sc_edt_u8_i32, normally of occ_est (a grid without obstacles reads SC_EDT_INF).
+ *   known uint8 [H][W], optional: NULL means that every cell of the grid is known.
+ *   pts int32 [S][R][N][2] = (px, py): the scan's end points as cell offsets from the sensor cell, one set per scan s and
+ *     candidate rotation r.  The caller rotates the points; the kernels know no angles.  A point is ABSENT when px or py lies
+ *     outside -SC_SCAN_MAX_REACH .. SC_SCAN_MAX_REACH; SC_MATCH_ABSENT is the value the helpers write (a no-return beam has
+ *     no end point).
+ *   centre int32 [S][2] = (cx, cy), the prior sensor cell.  A scan is IGNORED when cx or cy lies outside
+ *     -SC_SCAN_MAX_REACH .. SC_MAX_DIM + SC_SCAN_MAX_REACH: every sum of coordinates then stays far inside int32.
+ *   wx, wy in 0 .. SC_MATCH_MAX_HALF, d2_cap in 1 .. 32767, unk in 0 .. d2_cap, N in 1 .. SC_MATCH_MAX_POINTS, R in
+ *     1 .. SC_MATCH_MAX_ROT.
+ * Cost of a cell.  cost(x, y) = unk when (x, y) lies outside the grid or known[c] = 0, else min(d2[c], d2_cap).
+ * Score, for dy in [-wy, wy] and dx in [-wx, wx]:
+ *     score[s][r][dy][dx] = sum over the present points k of cost(cx + dx + px_k, cy + dy + py_k).
+ *   It is at most 32767 * 65536 = 2 147 418 112 < 2^31: an int32.
+ * Best pose of scan s: the candidate with the lexicographically smallest (score, dx^2 + dy^2, r, dy, dx).  Ties go to the
+ *   smallest displacement, then to the earliest rotation: a caller who has a prior heading puts it first.  Rotations with
+ *   different numbers of present points are compared as they are (a rotation that loses points scores less); giving every
+ *   rotation the same points is the caller's business.
+ * Outputs.  best int32 [S][6] = (r, dx, dy, score, n_points, n_ties): n_points the present points of rotation r, n_ties the
+ *   number of candidates of the whole volume whose score equals the best.  An ignored scan reads (SC_MATCH_IGNORED, 0, 0, 0,
+ *   0, 0).  score int32 [S][R][2 wy + 1][2 wx + 1], optional (NULL allowed): the whole volume, for callers who want a
+ *   covariance; an ignored scan's part is written as zeros.  With score NULL nothing of the volume's size is written.
+ * Consequences.  All points absent: score 0 everywhere, best = (0, 0, 0, 0, 0, R (2 wx + 1)(2 wy + 1)).  If the points are
+ *   the hits of sc_scan_cast_batch on a true map from cell a, and d2 is that map's, the candidate that puts the sensor at a
+ *   scores 0; if it lies in the window and n_ties = 1, best is that candidate.
+ *
+ * Three kernels, timed as SC_K_MOVES, no atomics and no float operations: a cost pass (one thread per cell: the uint16 cost
+ * map with a border of unk), the score kernel (256 candidates per workgroup, its 4 or 16 wavefronts share the points and
+ * add their partial sums in LDS; it leaves its smallest key and the candidates at that score) and a pick kernel (one workgroup
+ * per scan).  Scratch: 2 (W + 2)(H + 2) + 2 bytes and 16 S R ceil((2 wx + 1)(2 wy + 1) / 256) bytes; grows only.
+ *
+ * Device pointers; the call only enqueues on the context's stream (... -> sc_logodds_update -> sc_edt_u8_i32 ->
+ * sc_scan_match_batch runs on one stream).  The _host form takes host pointers, copies, runs, copies back and synchronises;
+ * it returns SC_ERR_INVALID for an ignored centre before any launch (the device form writes the ignored row).  Errors:
+ * SC_ERR_INVALID for NULL d2, pts, centre or best, S < 0, R, N, W, H, wx, wy, d2_cap or unk outside their ranges, score equal
+ * to best.  S == 0 is a no-op. */
+#define SC_MATCH_ABSENT INT32_MIN  /* pts: the value the helpers write for a point that is not there */
+#define SC_MATCH_IGNORED (-1)      /* best[s][0] of an ignored scan */
+#define SC_MATCH_MAX_HALF 64       /* wx, wy */
+#define SC_MATCH_MAX_POINTS 65536  /* N */
+#define SC_MATCH_MAX_ROT 256       /* R */
+int sc_scan_match_batch(sc_ctx* ctx, const int32_t* d2, const uint8_t* known, const int32_t* pts, const int32_t* centre, int S, int R,
+                        int N, int W, int H, int wx, int wy, int32_t d2_cap, int32_t unk, int32_t* best, int32_t* score);
+int sc_scan_match_batch_host(sc_ctx* ctx, const int32_t* d2, const uint8_t* known, const int32_t* pts, const int32_t* centre, int S,
+                             int R, int N, int W, int H, int wx, int wy, int32_t d2_cap, int32_t unk, int32_t* best, int32_t* score);
+
 /* ---- re-planning in space-time around the scheduled fleet -------------------------------------------------------
  * sc_fleet_schedule_batch only delays: a path that finds no free slot comes back SC_SLOT_UNRESOLVED.  These calls plan such a
  * robot again in (cell, time): the paths that did get a slot are rasterised into reservations, and an exact earliest-arrival

@@ -94,6 +94,8 @@ struct __attribute__((visibility("hidden"))) sc_ctx {
     sc_scratch fr_fleet;    // sc_fleet_explore_batch: the intermediate arrays the caller passes none of
     sc_scratch vw_vis;      // line-of-sight sensing: uint8 [H][W], 1 where a view of the call sees the free cell
     sc_scratch sn_flags;    // range scans: uint8 [2][al256(W H)] miss and hit flags of one sc_logodds_update; all zero between calls
+    sc_scratch mt_cost;     // scan matching: uint16 [H+2][W+2] + 1, the cost map of one call inside a border of unk, then a cell of 0
+    sc_scratch mt_part;     // scan matching: {uint64 key, int32 count, pad} [S][R][tiles of 256 candidates]
     int astar_cap = 1 << 16;         // ring entries per bucket (power of two)
     size_t astar_slot_budget = (size_t)96 << 30;  // bytes of g + bitmap + ring scratch this context may take (SC_ASTAR_SLOT_GB), further bounded by what the device has free; 4096^2: 96 GiB = 1966 slots measured best (48: -34 %, 160: -17 %)
     int traj_wg_target = 4096;      // path conflicts: workgroups a launch of the pair kernel aims for (16 per CU; SC_TRAJ_WORKGROUPS)

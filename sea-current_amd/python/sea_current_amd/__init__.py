@@ -43,6 +43,7 @@ ASSIGN_BIG = 1 << 42
 ASSIGN_OK, ASSIGN_BAD = 0, 1
 SCAN_NO_RETURN, SCAN_IGNORED, SCAN_MAX_REACH = -1, -2, 16384
 LOGODDS_HIT, LOGODDS_MISS, LOGODDS_CLAMP, LOGODDS_T_OCC, LOGODDS_T_FREE = 2, 1, 8, 2, 1   # logodds_update's defaults
+SCAN_MATCH_ABSENT, SCAN_MATCH_IGNORED, SCAN_MATCH_MAX_HALF, SCAN_MATCH_MAX_POINTS, SCAN_MATCH_MAX_ROT = -2**31, -1, 64, 65536, 256
 
 _lib = None
 
@@ -1323,6 +1324,41 @@ class Context:
         res = (out,) + tuple(x for x in (occ_est, known) if x is not None)
         return out if len(res) == 1 else res
 
+    # ---- scan matching (sc_scan_match_batch) ----
+    def scan_match(self, pts, centre, d2, known=None, wx=8, wy=8, d2_cap=64, unk=1, out=None, score=None):
+        """The pose of a scan against the map (sc_scan_match_batch): pts int32 [S,R,N,2], the scan's end points as cell offsets
+        from the sensor, one set per scan and candidate rotation (points_from_hits, rotate_points; SCAN_MATCH_ABSENT where a
+        beam has no end), centre int32 [S,2] the prior sensor cell, d2 int32 [H,W] the EDT of the estimated obstacles and
+        known uint8 [H,W] (None: every cell), all on the GPU.  A cell costs min(d2, d2_cap), or unk where it is unknown or
+        outside the grid; a pose scores the sum over its points.  Returns best int32 [S,6] = (r, dx, dy, score, n_points,
+        n_ties): the smallest (score, dx^2 + dy^2, r, dy, dx) over the window +-wx, +-wy, and how many poses reach that score
+        (1: the answer is unique); a scan whose centre is out of range reads (SCAN_MATCH_IGNORED, 0, ...).  score: an int32
+        [S,R,2wy+1,2wx+1] tensor, or True to have one allocated; then the result is (best, score).  Only enqueues."""
+        return self._scan_match(_on(d2.device), pts, centre, d2, known, wx, wy, d2_cap, unk, out, score)
+
+    def scan_match_host(self, pts, centre, d2, known=None, wx=8, wy=8, d2_cap=64, unk=1, score=None):
+        """Host form of scan_match (numpy in, numpy out); a centre out of range is an error."""
+        return self._scan_match(_HOST, pts, centre, d2, known, wx, wy, d2_cap, unk, None, score)
+
+    def _scan_match(self, A, pts, centre, d2, known, wx, wy, d2_cap, unk, out, score):
+        pts, centre, d2, known = A.arr(pts, A.i32), A.rows(centre, A.i32, 2), A.arr(d2, A.i32), A.arr(known, A.u8)
+        if len(pts.shape) != 4 or pts.shape[3] != 2 or len(d2.shape) != 2:
+            raise SeaCurrentError(f"scan_match: pts is [S,R,N,2] and d2 [H,W], got {tuple(pts.shape)} and {tuple(d2.shape)}")
+        S, R, N = (int(v) for v in pts.shape[:3])
+        H, W = d2.shape
+        vol = S * R * (2 * wy + 1) * (2 * wx + 1)
+        if out is None:
+            out = A.new((S, 6), A.i32)
+        if score is True:
+            score = A.new((S, R, 2 * wy + 1, 2 * wx + 1), A.i32)
+        _sized("scan_match: centre", centre, 2 * S)
+        _sized("scan_match: known", known, W * H)
+        _sized("scan_match: out", out, 6 * S)
+        _sized("scan_match: score", score, vol)
+        self._call("sc_scan_match_batch" + A.suffix, _ptr(d2), _ptr(known), _ptr(pts), _ptr(centre), S, R, N, W, H, wx, wy, d2_cap, unk,
+                   _ptr(out), _ptr(score))
+        return out if score is None else (out, score)
+
     # ---- multi-GPU gather (RCCL through the C ABI) ----
     @staticmethod
     def comm_unique_id():
@@ -1577,3 +1613,33 @@ class Context:
                                                   _ptr(out["seg"]), _ptr(out["curvature"]) if want_curvature else None,
                                                   _ptr(out["status"])), "sc_bezier_resample_batch")
         return out
+
+
+# ---- host helpers of scan matching (numpy) ----
+def points_from_hits(rays, hit, W):
+    """scan_cast's output as scan_match's points: int32 [N,2], the hit cell of every beam as a cell offset from its ray's
+    origin (rays int32 [N,4], hit int32 [N], W the grid's width).  Integer and exact.  A beam without a return or an ignored
+    one (hit < 0) becomes SCAN_MATCH_ABSENT."""
+    rays, hit = np.asarray(rays, dtype=np.int64).reshape(-1, 4), np.asarray(hit, dtype=np.int64).reshape(-1)
+    if len(rays) != len(hit):
+        raise SeaCurrentError(f"points_from_hits: {len(rays)} rays and {len(hit)} hits")
+    out = np.full((len(hit), 2), SCAN_MATCH_ABSENT, np.int64)
+    ok = hit >= 0
+    out[ok, 0], out[ok, 1] = hit[ok] % W - rays[ok, 0], hit[ok] // W - rays[ok, 1]
+    return out.astype(np.int32)
+
+
+def rotate_points(pts, angles):
+    """Candidate rotations of a scan: pts int32 [..., N, 2] and angles [R] in radians -> int32 [..., R, N, 2], every point
+    turned by each angle about the sensor ((x, y) -> (x cos a - y sin a, x sin a + y cos a), in float64 on the host) and
+    rounded to the nearest cell.  Absent points stay SCAN_MATCH_ABSENT.  No bit-exactness is claimed but at multiples of a
+    quarter turn, where the result is the integer rotation (x, y) -> (-y, x) applied that many times."""
+    p = np.asarray(pts, dtype=np.int64)
+    a = np.asarray(angles, dtype=np.float64).reshape(-1)
+    ok = (np.abs(p) <= SCAN_MAX_REACH).all(-1)
+    x, y = np.where(ok, p[..., 0], 0).astype(np.float64)[..., None, :], np.where(ok, p[..., 1], 0).astype(np.float64)[..., None, :]
+    # at a multiple of a quarter turn cos and sin are within 1e-15 of 0 and +-1 and |x|, |y| <= 2^14: the sums lie within
+    # 1e-10 of the integers they stand for, and rounding gives exactly those
+    c, s = np.cos(a)[:, None], np.sin(a)[:, None]
+    out = np.stack([np.rint(x * c - y * s), np.rint(x * s + y * c)], -1).astype(np.int64)
+    return np.where(ok[..., None, :, None], out, SCAN_MATCH_ABSENT).astype(np.int32)

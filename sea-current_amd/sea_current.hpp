@@ -39,6 +39,7 @@
 //   (new) occupancy_grid::known_from_views / view_gain, planner::line_of_sight: sensing that walls block
 //   (new) occupancy_grid::scan_cast, logodds_grid, beams_from_ranges, square_fan, planner::range_scan: range beams in, a
 //         log-odds occupancy map out
+//   (new) occupancy_grid::scan_match, logodds_grid::match, points_from_hits, rotate_points: a scan's pose against the map
 //
 // Differences that are deliberate: obstacle::closed is initialised (the reference leaves it
 // uninitialised, :197); library code never prints or calls std::exit (SC_ASSERT throws in DEBUG);
@@ -332,6 +333,17 @@ struct obstacle {
         }
         return inside;
     }
+};
+
+// ---- scan matching (new; the reference has no counterpart) ------------------------------------------
+// A scan's end points as cell offsets (px, py) from the sensor cell; SC_MATCH_ABSENT in both for a beam without an end point.
+using scan_points = std::vector<std::array<int32_t, 2>>;
+// The window (+-wx, +-wy cells around the prior), the cap of the squared distance a point can cost, what a point on an unknown
+// cell or outside the grid costs, and the number of candidate rotations the points come in (sc_scan_match_batch).
+struct match_params {
+    int wx = 8, wy = 8;
+    int32_t d2_cap = 64, unk = 1;
+    int rotations = 1;
 };
 
 // ---- occupancy grid (new): the world model the GPU path works on ----------------------------------
@@ -694,6 +706,28 @@ public:
         ctx.check(sc_scan_cast_batch_host(ctx.get(), occ.data(), rays[0].data(), (int)rays.size(), W, H, hit.data()), "sc_scan_cast_batch_host");
         return hit;
     }
+    // Where was the sensor (sc_scan_match_batch)?  `pts` holds [S][p.rotations][N] points, S = centres.size() scans with
+    // their candidate rotations (points_from_hits, rotate_points), `centres` the prior sensor cell of each scan; this grid's
+    // d2 (of occ, normally an estimate: computed if it is not there) is the likelihood field, `known` (empty: every cell)
+    // says which cells may be scored.  Returns per scan (r, dx, dy, score, n_points, n_ties): the best rotation and shift of
+    // the prior, and how many poses of the window score as well (1: unique).  Throws for a centre further than
+    // SC_SCAN_MAX_REACH outside the largest grid.  `score` (optional) receives the volume [S][R][2 wy + 1][2 wx + 1].
+    std::vector<std::array<int32_t, 6>> scan_match(const scan_points& pts, const std::vector<std::array<int32_t, 2>>& centres,
+                                                   const match_params& p = {}, gpu_context& ctx = default_context(),
+                                                   const std::vector<uint8_t>& known = {}, std::vector<int32_t>* score = nullptr) {
+        const size_t S = centres.size(), per_scan = S ? pts.size() / S : 0;
+        if (p.rotations < 1 || (S && (pts.size() % S || per_scan % (size_t)p.rotations || per_scan == 0)))
+            throw std::invalid_argument("occupancy_grid::scan_match: pts is not [S][rotations][N]");
+        if (!known.empty() && known.size() != occ.size()) throw std::invalid_argument("occupancy_grid::scan_match: known is not [H][W]");
+        std::vector<std::array<int32_t, 6>> best(S, std::array<int32_t, 6>{SC_MATCH_IGNORED, 0, 0, 0, 0, 0});
+        if (score) score->assign(S * (size_t)p.rotations * (2 * p.wy + 1) * (2 * p.wx + 1), 0);
+        if (S == 0 || occ.empty()) return best;
+        if (d2.size() != occ.size()) edt(ctx);
+        ctx.check(sc_scan_match_batch_host(ctx.get(), d2.data(), known.empty() ? nullptr : known.data(), pts[0].data(), centres[0].data(), (int)S,
+                                           p.rotations, (int)(per_scan / (size_t)p.rotations), W, H, p.wx, p.wy, p.d2_cap, p.unk, best[0].data(),
+                                           score ? score->data() : nullptr), "sc_scan_match_batch_host");
+        return best;
+    }
 private:
     // both cost_fields overloads; pen NULL: the unweighted fields
     field_result cost_fields_with(const std::vector<int32_t>& roots, const std::vector<uint8_t>* pen, int pen_cap, int32_t r2_clear, int rounds,
@@ -754,6 +788,17 @@ public:
     }
     // the masks of the stored map (the call with no beams; it also clamps L to p.l_clamp)
     masks_result masks(const logodds_params& p = {}, gpu_context& ctx = default_context()) { return update({}, {}, p, ctx); }
+    // The pose of one scan against the map so far: masks -> the EDT of occ_est -> occupancy_grid::scan_match with known, three
+    // calls on the context's stream.  `pts` holds [m.rotations][N] points, `centre` the prior sensor cell.  Returns the best row
+    // (r, dx, dy, score, n_points, n_ties); like masks() it clamps L to p.l_clamp.
+    std::array<int32_t, 6> match(const scan_points& pts, const std::array<int32_t, 2>& centre, const match_params& m = {},
+                                 const logodds_params& p = {}, gpu_context& ctx = default_context()) {
+        masks_result k = masks(p, ctx);
+        occupancy_grid est;
+        est.W = W; est.H = H;
+        est.occ = std::move(k.occ_est);
+        return est.scan_match(pts, {centre}, m, ctx, k.known)[0];
+    }
 };
 
 // The 8 r rays from cell (cx, cy) to every cell on the perimeter of the square of half-side r around it, going round once: a
@@ -794,6 +839,33 @@ inline scan_beams beams_from_ranges(const occupancy_grid& g, const Vector2f& ori
         b.hit.push_back(ret && ex >= 0 && ey >= 0 && ex < g.W && ey < g.H ? ey * g.W + ex : SC_SCAN_NO_RETURN);
     }
     return b;
+}
+
+// scan_cast's output -> scan_match's points: the hit cell of every beam as a cell offset from its ray's origin (W the grid's
+// width).  Integer and exact.  A beam without a return, or an ignored one (hit < 0), becomes SC_MATCH_ABSENT.
+inline scan_points points_from_hits(const std::vector<std::array<int32_t, 4>>& rays, const std::vector<int32_t>& hit, int W) {
+    if (hit.size() != rays.size()) throw std::invalid_argument("points_from_hits: one hit per ray");
+    scan_points pts(hit.size(), {SC_MATCH_ABSENT, SC_MATCH_ABSENT});
+    for (size_t k = 0; k < hit.size(); ++k)
+        if (hit[k] >= 0) pts[k] = {hit[k] % W - rays[k][0], hit[k] / W - rays[k][1]};
+    return pts;
+}
+
+// Candidate rotations of a scan: [N] points and R angles (radians, from +x towards +y) -> [R][N] points, every point turned
+// about the sensor in double precision and rounded to the nearest cell; absent points stay absent.  No bit-exactness is
+// claimed but at multiples of a quarter turn, where the result is the integer rotation (x, y) -> (-y, x) applied that often.
+inline scan_points rotate_points(const scan_points& pts, const std::vector<double>& angles) {
+    scan_points out;
+    out.reserve(pts.size() * angles.size());
+    auto absent = [](int32_t v) { return v < -SC_SCAN_MAX_REACH || v > SC_SCAN_MAX_REACH; };
+    for (double a : angles) {
+        const double c = std::cos(a), s = std::sin(a);
+        for (const auto& q : pts) {
+            if (absent(q[0]) || absent(q[1])) out.push_back({SC_MATCH_ABSENT, SC_MATCH_ABSENT});
+            else out.push_back({(int32_t)std::lrint(q[0] * c - q[1] * s), (int32_t)std::lrint(q[0] * s + q[1] * c)});
+        }
+    }
+    return out;
 }
 
 // ---- planning_space (sea_current.hpp:298-319, 1272-1407) --------------------------------------------
