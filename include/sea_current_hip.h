@@ -1243,6 +1243,72 @@ int sc_scan_match_batch(sc_ctx* ctx, const int32_t* d2, const uint8_t* known, co
 int sc_scan_match_batch_host(sc_ctx* ctx, const int32_t* d2, const uint8_t* known, const int32_t* pts, const int32_t* centre, int S,
                              int R, int N, int W, int H, int wx, int wy, int32_t d2_cap, int32_t unk, int32_t* best, int32_t* score);
 
+/* ---- wide-window scan matching: an exact pruned search over a cost pyramid ----------------------------------------
+ * sc_scan_match_batch scores every pose of a window of at most +-64 cells.  A robot that has lost its pose, or that comes
+ * back to a mapped place after a long loop, needs windows of hundreds or thousands of cells, where only one pose wins and
+ * most of the volume is wasted.  sc_scan_match_wide_batch searches such a window with lower bounds from a min-pooled pyramid
+ * of the same cost map and opens only the blocks of poses whose bound does not exceed a score already in hand.  Only blocks
+ * with bound > U are dropped, so the result is the same `best` row, ties included, as the dense volume.  Integer and unique;
+ * tests/match_wide_twin.py states it in NumPy, tests/cpp/match_wide_ref.c in C, and every output equals both bit for bit.
+ * DESIGN.md section 26.
+ *
+ * Inputs.  d2, known (optional), pts [S][R][N][2], centre [S][2], d2_cap, unk: those of sc_scan_match_batch, with the same
+ *   rules for absent points and ignored scans, and cost(x, y) the same function over the whole plane (unk outside the grid
+ *   or where known is 0).
+ *   wx, wy in 0 .. SC_MATCH_WIDE_MAX_HALF (2048).  top in 0 .. SC_MATCH_WIDE_MAX_TOP (5).  max_nodes in
+ *   SC_MATCH_WIDE_MIN_NODES (64) .. SC_MATCH_WIDE_MAX_NODES (2^22), with S max_nodes <= SC_MATCH_WIDE_MAX_TOTAL (2^26).
+ *   R (2 wx + 1)(2 wy + 1) <= INT32_MAX, since n_ties is an int32.
+ * Pooled cost, bounds and nodes.  P_m(x, y) = min over 0 <= i, j < m of cost(x + i, y + j) for m = 4^j, and P_1 = cost.
+ *   A node (r, dx0, dy0) of size m stands for the candidates dx0 <= dx < dx0 + m, dy0 <= dy < dy0 + m of rotation r that lie
+ *   in the window.  Its bound is B_m = sum over the present points k of P_m(cx + dx0 + px_k, cy + dy0 + py_k).  It is at
+ *   most the score of every candidate the node stands for; it is an int32 by the argument of sc_scan_match_batch, and for
+ *   m = 1 it is the score itself.  Its children are the up to 16 nodes of size m/4 at (dx0 + a m/4, dy0 + b m/4),
+ *   a, b in 0 .. 3, with dx0' <= wx and dy0' <= wy.
+ * Procedure per scan (part of the definition, because its counts are outputs).
+ *   1. An ignored scan reads (SC_MATCH_IGNORED, 0, 0, 0, 0, 0) and has zero stats.
+ *   2. If no rotation has a present point, the result is best = (0, 0, 0, 0, 0, R (2 wx + 1)(2 wy + 1)) and zero stats: the
+ *      closed form of sc_scan_match_batch; no search runs.
+ *   3. Start: U = min over r of score(r, 0, 0).  The nodes of size m = 4^top are (r, -wx + i m, -wy + j m) for all r and all
+ *      i, j with dx0 <= wx and dy0 <= wy.  If their count exceeds max_nodes, the call returns SC_ERR_INVALID (the host tests
+ *      this before anything runs).
+ *   4. Level of size m: bound every node, and set n_j to the number of nodes bounded, with m = 4^j.  If m = 1, go to step 5.
+ *      Otherwise run one dive per rotation r: among r's nodes take the smallest (B, dy0, dx0); if its B exceeds the U of the
+ *      start of this level, r does not dive; else bound its children and take the smallest (B, dy0, dx0) among them, and
+ *      repeat down to size 1: the last B is a true score v_r.  n_dive counts every child bounded in dives.  After the dives,
+ *      U <- min(U, all v_r).  Survivors are the nodes with B <= U; the next level's nodes are their children.  If the next
+ *      level has more than max_nodes nodes, the scan reads (SC_MATCH_OVERFLOW, 0, 0, 0, 0, 0); its n_j are filled down to
+ *      the level just bounded, the levels below are 0, and n_dive and U are what they were at that point.
+ *   5. Over the leaves, best is the smallest (score, dx^2 + dy^2, r, dy, dx); n_ties is the number of leaves whose score
+ *      equals the best score; n_points is as in sc_scan_match_batch.
+ * Why the result equals the dense search.  A candidate whose score equals the best has every ancestor at B <= best <= U, so
+ *   all tying candidates reach the leaves.  The minimum and the ties do not depend on U, on the dives or on any order of
+ *   execution; the counts depend only on the stated procedure.
+ * Outputs.  best int32 [S][6], as sc_scan_match_batch.  stats int32 [S][8] = (n_0, .., n_5, n_dive, U), optional (NULL
+ *   allowed).  There is no score volume.
+ *
+ * Kernels, timed as SC_K_MOVES, integer only: the cost pass of sc_scan_match_batch, two pooling passes per level, an init
+ * kernel, per level a bound kernel (a wave takes four parents and bounds their 64 children), a dive kernel (one workgroup
+ * per scan and rotation) and an expand kernel (wave-aggregated appends), and a pick kernel: 4 + 5 top launches and three
+ * memsets.  Scratch, grows only: the pooled maps, 2 (W + m + 1)(H + m + 1) bytes per level m = 4 .. 4^top and one of
+ * m = 4^top / 2; 20 S max_nodes + 8 S R + 96 S bytes of lists, bounds, keys and counters.
+ *
+ * Device pointers; the call only enqueues on the context's stream and never synchronises.  The _host form takes host
+ * pointers, copies, runs, copies back and synchronises; it returns SC_ERR_INVALID for an ignored centre before any launch.
+ * Errors: SC_ERR_INVALID for NULL d2, pts, centre or best, S < 0, R, N, W, H, wx, wy, d2_cap, unk, top or max_nodes outside
+ * their ranges, too many nodes at the top level, stats equal to best.  S == 0 is a no-op. */
+#define SC_MATCH_OVERFLOW (-2)              /* best[s][0] of a scan whose next level had more than max_nodes nodes */
+#define SC_MATCH_WIDE_MAX_HALF 2048         /* wx, wy */
+#define SC_MATCH_WIDE_MAX_TOP 5             /* top: nodes of up to 1024 x 1024 candidates */
+#define SC_MATCH_WIDE_MIN_NODES 64          /* max_nodes */
+#define SC_MATCH_WIDE_MAX_NODES (1 << 22)   /* max_nodes */
+#define SC_MATCH_WIDE_MAX_TOTAL (1 << 26)   /* S * max_nodes */
+int sc_scan_match_wide_batch(sc_ctx* ctx, const int32_t* d2, const uint8_t* known, const int32_t* pts, const int32_t* centre, int S,
+                             int R, int N, int W, int H, int wx, int wy, int32_t d2_cap, int32_t unk, int top, int max_nodes,
+                             int32_t* best, int32_t* stats);
+int sc_scan_match_wide_batch_host(sc_ctx* ctx, const int32_t* d2, const uint8_t* known, const int32_t* pts, const int32_t* centre,
+                                  int S, int R, int N, int W, int H, int wx, int wy, int32_t d2_cap, int32_t unk, int top,
+                                  int max_nodes, int32_t* best, int32_t* stats);
+
 /* ---- re-planning in space-time around the scheduled fleet -------------------------------------------------------
  * sc_fleet_schedule_batch only delays: a path that finds no free slot comes back SC_SLOT_UNRESOLVED.  These calls plan such a
  * robot again in (cell, time): the paths that did get a slot are rasterised into reservations, and an exact earliest-arrival

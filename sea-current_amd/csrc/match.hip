@@ -3,7 +3,7 @@
 //
 // The work is S R (2wx+1)(2wy+1) N cell lookups, each read by exactly one candidate: nothing to stage, only coalescing and
 // parallelism.  Kernels, all integer, no atomics:
-//   1. mt_cost_kernel: one thread per cell of the padded cost map, uint16 [H+2][W+2] plus one cell that holds 0: the grid's
+//   1. mt_cost_kernel (match_common.h, shared with match_wide.hip): one thread per cell of the padded cost map, uint16 [H+2][W+2] plus one cell that holds 0: the grid's
 //      cost (min(d2, cap), unk where unknown) inside a one-cell border of unk.  The score kernel clamps a coordinate to the
 //      border, so it has no off-grid branch and every load lies inside the map by construction; an absent point reads the
 //      zero cell.
@@ -16,7 +16,7 @@
 //      16 below that.  The workgroup then leaves its smallest key and the number of its candidates at that score.
 //   3. mt_pick_kernel: one workgroup per scan: the smallest key over rotations and tiles, the ties (a partial's count only
 //      counts when its score is the minimum) and the present points of the chosen rotation.
-#include "sc_internal.h"
+#include "match_common.h"
 
 namespace {
 
@@ -26,26 +26,6 @@ constexpr int MT_UNROLL = 4;     // points whose loads are in flight together
 constexpr size_t MT_FEW = 512;   // workgroups below which a launch leaves most of the machine idle (2 per compute unit)
 
 struct mt_part { unsigned long long key; int32_t count; int32_t pad; };   // key = score << 32 | (dx^2 + dy^2) << 16 | dyi << 8 | dxi
-
-__device__ __host__ __forceinline__ bool mt_absent(int p) { return p < -SC_SCAN_MAX_REACH || p > SC_SCAN_MAX_REACH; }
-__device__ __host__ __forceinline__ bool mt_centre_ok(int c) { return c >= -SC_SCAN_MAX_REACH && c <= SC_MAX_DIM + SC_SCAN_MAX_REACH; }
-
-__global__ __launch_bounds__(256) void mt_cost_kernel(const int32_t* __restrict__ d2, const uint8_t* __restrict__ known, int W, int H,
-                                                      int32_t d2_cap, int32_t unk, uint16_t* __restrict__ cost) {
-    const int Wp = W + 2, total = Wp * (H + 2) + 1;   // (SC_MAX_DIM + 2)^2 + 1 < 2^27
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= total) return;
-    int v = 0;   // the last entry: what an absent point reads
-    if (i < total - 1) {
-        const int x = i % Wp - 1, y = i / Wp - 1;
-        v = unk;
-        if ((unsigned)x < (unsigned)W && (unsigned)y < (unsigned)H) {
-            const int c = y * W + x;
-            if (!known || known[c] != 0) v = min(d2[c], d2_cap);
-        }
-    }
-    cost[i] = (uint16_t)v;
-}
 
 // WAVES wavefronts share the points of one tile of candidates: 4 when the launch fills the machine without it, 16 when it has
 // few workgroups (one scan of a mapping loop), where the time is the chain of a wave's rounds of loads.
@@ -137,10 +117,6 @@ __global__ __launch_bounds__(WAVES * 64) void mt_score_kernel(const uint16_t* __
     const int n_min = __syncthreads_count(reducer && total == (uint32_t)(best >> 32));
     if (tid == 0) part[srg * tiles + tile] = {best, n_min, 0};
 }
-
-// lexicographic (score, displacement, r, dy, dx): k1 = score << 32 | disp << 8 | r, k2 = dyi << 8 | dxi
-struct mt_key { unsigned long long k1; uint32_t k2; };
-__device__ __forceinline__ bool mt_less(const mt_key& a, const mt_key& b) { return a.k1 < b.k1 || (a.k1 == b.k1 && a.k2 < b.k2); }
 
 __global__ __launch_bounds__(256) void mt_pick_kernel(const mt_part* __restrict__ part, const int32_t* __restrict__ pts,
                                                       const int32_t* __restrict__ centre, int R, int N, int wx, int wy, int tiles,

@@ -96,6 +96,8 @@ struct __attribute__((visibility("hidden"))) sc_ctx {
     sc_scratch sn_flags;    // range scans: uint8 [2][al256(W H)] miss and hit flags of one sc_logodds_update; all zero between calls
     sc_scratch mt_cost;     // scan matching: uint16 [H+2][W+2] + 1, the cost map of one call inside a border of unk, then a cell of 0
     sc_scratch mt_part;     // scan matching: {uint64 key, int32 count, pad} [S][R][tiles of 256 candidates]
+    sc_scratch mw_pyr;      // wide scan matching: the pooled cost maps of levels 1 .. top, uint16 [H+m+1][W+m+1] each, and the half-way map of a level
+    sc_scratch mw_state;    // wide scan matching: uint64 parents [2][S][max_nodes] | int32 bounds [S][max_nodes] | uint64 keys [S][R] | int32 counts [S][16] | int32 U [S][8]
     int astar_cap = 1 << 16;         // ring entries per bucket (power of two)
     size_t astar_slot_budget = (size_t)96 << 30;  // bytes of g + bitmap + ring scratch this context may take (SC_ASTAR_SLOT_GB), further bounded by what the device has free; 4096^2: 96 GiB = 1966 slots measured best (48: -34 %, 160: -17 %)
     int traj_wg_target = 4096;      // path conflicts: workgroups a launch of the pair kernel aims for (16 per CU; SC_TRAJ_WORKGROUPS)

@@ -44,6 +44,7 @@ ASSIGN_OK, ASSIGN_BAD = 0, 1
 SCAN_NO_RETURN, SCAN_IGNORED, SCAN_MAX_REACH = -1, -2, 16384
 LOGODDS_HIT, LOGODDS_MISS, LOGODDS_CLAMP, LOGODDS_T_OCC, LOGODDS_T_FREE = 2, 1, 8, 2, 1   # logodds_update's defaults
 SCAN_MATCH_ABSENT, SCAN_MATCH_IGNORED, SCAN_MATCH_MAX_HALF, SCAN_MATCH_MAX_POINTS, SCAN_MATCH_MAX_ROT = -2**31, -1, 64, 65536, 256
+SCAN_MATCH_OVERFLOW, SCAN_MATCH_WIDE_MAX_HALF, SCAN_MATCH_WIDE_MAX_TOP = -2, 2048, 5
 
 _lib = None
 
@@ -1358,6 +1359,38 @@ class Context:
         self._call("sc_scan_match_batch" + A.suffix, _ptr(d2), _ptr(known), _ptr(pts), _ptr(centre), S, R, N, W, H, wx, wy, d2_cap, unk,
                    _ptr(out), _ptr(score))
         return out if score is None else (out, score)
+
+    # ---- wide-window scan matching (sc_scan_match_wide_batch) ----
+    def scan_match_wide(self, pts, centre, d2, known=None, wx=256, wy=256, d2_cap=64, unk=1, top=3, max_nodes=1 << 16, out=None, stats=None):
+        """The pose of a scan in a wide window (sc_scan_match_wide_batch): the inputs and the result best int32 [S,6] of
+        scan_match, for windows of up to +-SCAN_MATCH_WIDE_MAX_HALF cells, by an exact pruned search over a min-pooled
+        pyramid of the cost map whose top nodes stand for 4^top x 4^top poses; best equals what the dense volume would give,
+        ties included.  A scan whose search needs more than max_nodes nodes at a level reads (SCAN_MATCH_OVERFLOW, 0, ...).
+        stats: an int32 [S,8] tensor = (n_0 .. n_5 nodes bounded per level, n_dive, U), or True to have one allocated; then
+        the result is (best, stats).  Only enqueues."""
+        return self._scan_match_wide(_on(d2.device), pts, centre, d2, known, wx, wy, d2_cap, unk, top, max_nodes, out, stats)
+
+    def scan_match_wide_host(self, pts, centre, d2, known=None, wx=256, wy=256, d2_cap=64, unk=1, top=3, max_nodes=1 << 16, stats=None):
+        """Host form of scan_match_wide (numpy in, numpy out); a centre out of range is an error."""
+        return self._scan_match_wide(_HOST, pts, centre, d2, known, wx, wy, d2_cap, unk, top, max_nodes, None, stats)
+
+    def _scan_match_wide(self, A, pts, centre, d2, known, wx, wy, d2_cap, unk, top, max_nodes, out, stats):
+        pts, centre, d2, known = A.arr(pts, A.i32), A.rows(centre, A.i32, 2), A.arr(d2, A.i32), A.arr(known, A.u8)
+        if len(pts.shape) != 4 or pts.shape[3] != 2 or len(d2.shape) != 2:
+            raise SeaCurrentError(f"scan_match_wide: pts is [S,R,N,2] and d2 [H,W], got {tuple(pts.shape)} and {tuple(d2.shape)}")
+        S, R, N = (int(v) for v in pts.shape[:3])
+        H, W = d2.shape
+        if out is None:
+            out = A.new((S, 6), A.i32)
+        if stats is True:
+            stats = A.new((S, 8), A.i32)
+        _sized("scan_match_wide: centre", centre, 2 * S)
+        _sized("scan_match_wide: known", known, W * H)
+        _sized("scan_match_wide: out", out, 6 * S)
+        _sized("scan_match_wide: stats", stats, 8 * S)
+        self._call("sc_scan_match_wide_batch" + A.suffix, _ptr(d2), _ptr(known), _ptr(pts), _ptr(centre), S, R, N, W, H, wx, wy, d2_cap, unk,
+                   top, max_nodes, _ptr(out), _ptr(stats))
+        return out if stats is None else (out, stats)
 
     # ---- multi-GPU gather (RCCL through the C ABI) ----
     @staticmethod

@@ -40,6 +40,7 @@
 //   (new) occupancy_grid::scan_cast, logodds_grid, beams_from_ranges, square_fan, planner::range_scan: range beams in, a
 //         log-odds occupancy map out
 //   (new) occupancy_grid::scan_match, logodds_grid::match, points_from_hits, rotate_points: a scan's pose against the map
+//   (new) occupancy_grid::scan_match_wide, logodds_grid::relocalise: the same over windows of thousands of cells, pruned
 //
 // Differences that are deliberate: obstacle::closed is initialised (the reference leaves it
 // uninitialised, :197); library code never prints or calls std::exit (SC_ASSERT throws in DEBUG);
@@ -344,6 +345,14 @@ struct match_params {
     int wx = 8, wy = 8;
     int32_t d2_cap = 64, unk = 1;
     int rotations = 1;
+};
+// The same for a wide window (sc_scan_match_wide_batch): +-wx, +-wy up to SC_MATCH_WIDE_MAX_HALF cells, searched from nodes
+// of 4^top x 4^top poses down, with room for max_nodes nodes per scan and level.
+struct wide_match_params {
+    int wx = 256, wy = 256;
+    int32_t d2_cap = 64, unk = 1;
+    int rotations = 1;
+    int top = 3, max_nodes = 1 << 16;
 };
 
 // ---- occupancy grid (new): the world model the GPU path works on ----------------------------------
@@ -728,6 +737,28 @@ public:
                                            score ? score->data() : nullptr), "sc_scan_match_batch_host");
         return best;
     }
+    // The same question over a wide window (sc_scan_match_wide_batch): the arguments and the result of scan_match, found by
+    // an exact pruned search, so a row equals what the dense volume would give, ties included; a scan that needed more than
+    // p.max_nodes nodes at a level reads (SC_MATCH_OVERFLOW, 0, 0, 0, 0, 0).  `stats` (optional) receives per scan
+    // (n_0 .. n_5, n_dive, U): the nodes bounded per level, the children bounded in dives and the last upper bound.
+    std::vector<std::array<int32_t, 6>> scan_match_wide(const scan_points& pts, const std::vector<std::array<int32_t, 2>>& centres,
+                                                        const wide_match_params& p = {}, gpu_context& ctx = default_context(),
+                                                        const std::vector<uint8_t>& known = {},
+                                                        std::vector<std::array<int32_t, 8>>* stats = nullptr) {
+        const size_t S = centres.size(), per_scan = S ? pts.size() / S : 0;
+        if (p.rotations < 1 || (S && (pts.size() % S || per_scan % (size_t)p.rotations || per_scan == 0)))
+            throw std::invalid_argument("occupancy_grid::scan_match_wide: pts is not [S][rotations][N]");
+        if (!known.empty() && known.size() != occ.size()) throw std::invalid_argument("occupancy_grid::scan_match_wide: known is not [H][W]");
+        std::vector<std::array<int32_t, 6>> best(S, std::array<int32_t, 6>{SC_MATCH_IGNORED, 0, 0, 0, 0, 0});
+        if (stats) stats->assign(S, std::array<int32_t, 8>{0, 0, 0, 0, 0, 0, 0, 0});
+        if (S == 0 || occ.empty()) return best;
+        if (d2.size() != occ.size()) edt(ctx);
+        ctx.check(sc_scan_match_wide_batch_host(ctx.get(), d2.data(), known.empty() ? nullptr : known.data(), pts[0].data(), centres[0].data(),
+                                                (int)S, p.rotations, (int)(per_scan / (size_t)p.rotations), W, H, p.wx, p.wy, p.d2_cap, p.unk,
+                                                p.top, p.max_nodes, best[0].data(), stats ? (*stats)[0].data() : nullptr),
+                  "sc_scan_match_wide_batch_host");
+        return best;
+    }
 private:
     // both cost_fields overloads; pen NULL: the unweighted fields
     field_result cost_fields_with(const std::vector<int32_t>& roots, const std::vector<uint8_t>* pen, int pen_cap, int32_t r2_clear, int rounds,
@@ -798,6 +829,16 @@ public:
         est.W = W; est.H = H;
         est.occ = std::move(k.occ_est);
         return est.scan_match(pts, {centre}, m, ctx, k.known)[0];
+    }
+    // The same chain with the wide-window search at its end: where is a robot that has lost its pose, or that comes back to
+    // a mapped place after a long loop?  masks -> the EDT of occ_est -> occupancy_grid::scan_match_wide with known.
+    std::array<int32_t, 6> relocalise(const scan_points& pts, const std::array<int32_t, 2>& centre, const wide_match_params& m = {},
+                                      const logodds_params& p = {}, gpu_context& ctx = default_context()) {
+        masks_result k = masks(p, ctx);
+        occupancy_grid est;
+        est.W = W; est.H = H;
+        est.occ = std::move(k.occ_est);
+        return est.scan_match_wide(pts, {centre}, m, ctx, k.known)[0];
     }
 };
 
