@@ -1133,6 +1133,74 @@ int sc_view_gain_batch(sc_ctx* ctx, const uint8_t* occ, const uint8_t* known, co
 int sc_view_gain_batch_host(sc_ctx* ctx, const uint8_t* occ, const uint8_t* known, const int32_t* views, int N, int W, int H,
                             int32_t* gain);
 
+/* ---- sensors with a field of view: sector views and the gain of every heading --------------------------------------
+ * The calls above see a full circle.  These give a view a sector, tell for a candidate pose what every heading would reveal
+ * at the cost of one pass of rays, and turn goal cells into view rows on the stream.  The reference has no counterpart (no
+ * parity claim); the definitions are integer and unique; tests/sectors_twin.py states them in NumPy, tests/cpp/sectors_ref.c
+ * in C, and every output equals both bit for bit.  DESIGN.md section 27.  Cells are c = y*W + x.  cross(p, q) = px*qy - py*qx,
+ * dot is the usual; d is a cell's offset from the view's centre.
+ *
+ * Half-open sector In(d; a, b): the sector counter-clockwise from direction a (inclusive) to direction b (exclusive).  a and b
+ *   are int32 pairs whose components lie in -32767 .. 32767.
+ *   d = (0, 0): true.  The centre belongs to every sector.
+ *   a = b = (0, 0): true.  This is the full circle.
+ *   Otherwise let s = cross(a, b):
+ *     s > 0: cross(a, d) >= 0 and cross(d, b) > 0.
+ *     s < 0 (more than half a turn): not (cross(b, d) >= 0 and cross(d, a) > 0).
+ *     s = 0 and dot(a, b) < 0 (exactly half a turn): cross(a, d) > 0 or (cross(a, d) = 0 and dot(a, d) > 0).
+ *     s = 0 and dot(a, b) > 0, exactly one of a, b zero, or a component out of range: the view is IGNORED.  It sees nothing
+ *       and its gain is 0, like r2 < 0.
+ *   With W, H <= SC_MAX_DIM every product is below 2^30, so int32 suffices in the kernel; the twin and the C statement use
+ *   int64.
+ * Sector view.  sviews int32 [R][7] = (cx, cy, r2, ax, ay, bx, by).  vis[c] and surf[c] are the section above's, with
+ *   "and In(c - centre; a, b)" added to the disc test of vis.  The surf rule is unchanged: an occupied cell with a seen
+ *   orthogonal neighbour, which may lie just outside the sector as it may lie outside the disc.  A row with a = b = 0 is
+ *   exactly the view (cx, cy, r2).
+ * Heading table.  dirs int32 [B][2], a HOST pointer in both call forms (a small parameter table, validated before any launch
+ *   and handed to the kernel as an argument).  It is valid iff 3 <= B <= SC_VIEW_MAX_BINS; every component lies in
+ *   -32767 .. 32767; cross(u_b, u_{(b+1) mod B}) > 0 for every b; and exactly one b has u_b in the upper half-open plane
+ *   (y > 0 or (y = 0 and x > 0)) and its successor not in it (one turn, not several).  Bin b is In(d; u_b, u_{b+1}) for d != 0.
+ *   The bins of a valid table partition the offsets; the centre is in no bin.
+ * Gain per heading.  For view i = (cx, cy, r2):
+ *   hist[i][b] = #{c != centre : known[c] = 0 and vis_i[c] and bin(c - centre) = b},
+ *   c0[i] = [known[centre] = 0 and vis_i[centre]],
+ *   gainh[i][h] = c0[i] + sum over j < span of hist[i][(h + j) mod B], 1 <= span <= B,
+ *   best[i] = (max over h of gainh[i][h], the smallest h attaining it).  An ignored view gives zeros and best = (0, 0).
+ *   Identities: sum_b hist[i][b] + c0[i] = sc_view_gain_batch's gain[i]; for span < B, gainh[i][h] is the sector gain of
+ *   (cx, cy, r2, u_h, u_{(h+span) mod B}); at span = B it is gain[i].
+ *
+ * sc_known_from_sectors: sc_known_from_views over sector rows; the aliasing and the R == 0 rule are that call's.  A memset,
+ *   one ray kernel per 65535 rows and one kernel per cell, timed as SC_K_MOVES.  Scratch: W * H bytes (shared with
+ *   sc_known_from_views); grows only.
+ * sc_sector_gain_batch: gain[i] = #{c : known[c] == 0 and vis_i[c]} (int32 [N]) for sector row i alone; 0 for an ignored row.
+ *   N == 0 is a no-op.
+ * sc_view_gain_headings_batch: views int32 [N][3]; best int32 [N][2], mandatory; hist and gainh int32 [N][B], each may be
+ *   NULL (hist then lives in context scratch, which only grows: 4 N (B + 1) bytes).  N == 0 is a no-op.  Two memsets, one ray
+ *   kernel per 65535 candidates (integer atomicAdds only; nothing depends on the order of execution) and one kernel with a
+ *   wavefront per candidate, timed as SC_K_MOVES.
+ * sc_views_from_cells: views[i] = (cell[i] % W, cell[i] / W, r2) (cell int32 [N], views int32 [N][3]); a cell outside
+ *   0 .. W*H - 1 gives (0, 0, -1), an ignored view: this covers the -1 of sc_fleet_explore_batch's unmatched robot, so its
+ *   goal feeds the gain calls with no host hop.  N == 0 is a no-op.
+ *
+ * Device pointers, except dirs; the calls only enqueue on the context's stream.  The _host forms take host pointers, copy,
+ * run, copy back and synchronise.  Errors: SC_ERR_INVALID for NULL mandatory pointers (best included), R < 0, N < 0, W or H
+ * outside 1..SC_MAX_DIM, occ_seen equal to occ or to known, a dirs table that is not valid, span outside 1 .. B,
+ * N * B > 2^30. */
+#define SC_VIEW_MAX_BINS 64
+int sc_known_from_sectors(sc_ctx* ctx, const uint8_t* base, const uint8_t* occ, const int32_t* sviews, int R, int W, int H, uint8_t* known,
+                          uint8_t* occ_seen);
+int sc_known_from_sectors_host(sc_ctx* ctx, const uint8_t* base, const uint8_t* occ, const int32_t* sviews, int R, int W, int H,
+                               uint8_t* known, uint8_t* occ_seen);
+int sc_sector_gain_batch(sc_ctx* ctx, const uint8_t* occ, const uint8_t* known, const int32_t* sviews, int N, int W, int H, int32_t* gain);
+int sc_sector_gain_batch_host(sc_ctx* ctx, const uint8_t* occ, const uint8_t* known, const int32_t* sviews, int N, int W, int H,
+                              int32_t* gain);
+int sc_view_gain_headings_batch(sc_ctx* ctx, const uint8_t* occ, const uint8_t* known, const int32_t* views, int N, int W, int H,
+                                const int32_t* dirs, int B, int span, int32_t* hist, int32_t* gainh, int32_t* best);
+int sc_view_gain_headings_batch_host(sc_ctx* ctx, const uint8_t* occ, const uint8_t* known, const int32_t* views, int N, int W, int H,
+                                     const int32_t* dirs, int B, int span, int32_t* hist, int32_t* gainh, int32_t* best);
+int sc_views_from_cells(sc_ctx* ctx, const int32_t* cell, int N, int W, int H, int32_t r2, int32_t* views);
+int sc_views_from_cells_host(sc_ctx* ctx, const int32_t* cell, int N, int W, int H, int32_t r2, int32_t* views);
+
 /* ---- occupancy from range scans: beam casts and log-odds maps ------------------------------------------------------
  * The calls above take the map to be sensed and hand back a mask.  These two take measurements: a beam has an origin, an end
  * and either the cell where it stopped or no return.  sc_scan_cast_batch is the simulated range sensor (it casts beams through

@@ -93,6 +93,7 @@ struct __attribute__((visibility("hidden"))) sc_ctx {
     sc_scratch fr_key;      // frontier cost matrix: uint64 [F][Cmax] keys g << 32 | cell
     sc_scratch fr_fleet;    // sc_fleet_explore_batch: the intermediate arrays the caller passes none of
     sc_scratch vw_vis;      // line-of-sight sensing: uint8 [H][W], 1 where a view of the call sees the free cell
+    sc_scratch vs_state;    // gain per heading: int32 c0 [N] | int32 hist [N][B] when the caller passes none
     sc_scratch sn_flags;    // range scans: uint8 [2][al256(W H)] miss and hit flags of one sc_logodds_update; all zero between calls
     sc_scratch mt_cost;     // scan matching: uint16 [H+2][W+2] + 1, the cost map of one call inside a border of unk, then a cell of 0
     sc_scratch mt_part;     // scan matching: {uint64 key, int32 count, pad} [S][R][tiles of 256 candidates]

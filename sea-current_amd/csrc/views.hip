@@ -9,129 +9,22 @@
 // Kernels.  One ray per (view, cell of the view's clipped bounding box); nothing loops over views per grid cell.
 //   1. vw_view_kernel: grid (tile slots, views).  A workgroup of 256 takes 16 x 16 tiles of its view's box, strided by the
 //      tile slots; a wavefront is an 8 x 8 quarter of the tile, so its 64 rays have nearly the same length and direction.  A
-//      lane walks its ray from the centre outward (vw_ray, below), leaves at its first blocked cell, and the wave leaves when
-//      all lanes have.  A visible target stores 1 into the zeroed vis bytes: plain stores, every writer stores the same value.
+//      lane walks its ray from the centre outward (vw_ray, views_common.h), leaves at its first blocked cell, and the wave
+//      leaves when all lanes have.  A visible target stores 1 into the zeroed vis bytes: plain stores, every writer stores
+//      the same value.
 //   2. vw_combine_kernel: one thread per cell; reads base[c] and writes known[c] of its own cell only (in place is safe).
 //   3. vw_gain_kernel: grid (tile slots, candidates), the same ray routine; a wave counts known == 0 and Clear by ballot and
 //      popcount over its tiles and adds once into gain[i] (integer atomicAdd; gain was zeroed on the stream before).
 // Where occ is read.  Every ray reads its bytes from global memory (L2).  A form that first packed the view's box into a bit
 // map in LDS and tested bits there was built and measured: it lost at every size and is not kept.
 //
-// The walker restates section 9's (waypoints.hip) rather than sharing it: that one tests d2 >= thr on int32 and divides per
-// column; this one tests bytes and carries quotient and remainder from column to column (no division in the loop).  With
-// W, H <= SC_MAX_DIM = 8192 every product fits int32: (2 D + 1) m + D <= 2 * 8191^2 + 3 * 8191 < 2^28.
-#include "sc_internal.h"
+// The walker (views_common.h, shared with sectors.hip) restates section 9's (waypoints.hip) rather than sharing it: that one
+// tests d2 >= thr on int32 and divides per column; this one tests bytes and carries quotient and remainder from column to
+// column (no division in the loop).  With W, H <= SC_MAX_DIM = 8192 every product fits int32: (2 D + 1) m + D <=
+// 2 * 8191^2 + 3 * 8191 < 2^28.
+#include "views_common.h"
 
 namespace {
-
-constexpr int VW_TILE = 16;       // tile edge of a workgroup; a wavefront takes an 8 x 8 quarter
-constexpr int VW_COLS = 4;        // columns whose loads are in flight together
-constexpr int VW_SLOTS = 2048;    // workgroups per view at most (tiles are strided over them)
-
-// The supercover of the segment from a (cell index ca, always free) to a target, column by column of the major axis.
-// Column i, doubled coordinates relative to a: t in [max(2i-1, 0), min(2i+1, 2D)], rows
-//   rhi(i) = min(floor(((2i+1) m + D) / 2D), m),   rlo(i) = ceil(((2i-1) m - D) / 2D) for i >= 1, 0 for i = 0.
-// With n(i) = (2i+1) m + D = q(i) * 2D + rem(i):  rhi(i) = min(q(i), m), and (2i-1) m - D = n(i-1) - 2D gives
-// rlo(i) = q(i-1) - (rem(i-1) == 0).  n(i+1) = n(i) + 2m with 2m <= 2D: q grows by at most one per column.  rhi - rlo <= 2.
-struct vw_ray {
-    int ca, D, m, twoD, sM, sm;
-    int i, q, rem, rlo;   // column i: q, rem of n(i); rlo of column i
-    __device__ void init(int W, int ax, int ay, int bx, int by) {
-        const int dx = bx - ax, dy = by - ay;
-        const bool xmajor = abs(dx) >= abs(dy);
-        D = xmajor ? abs(dx) : abs(dy);
-        m = xmajor ? abs(dy) : abs(dx);
-        const int smaj = (xmajor ? dx : dy) < 0 ? -1 : 1, smin = (xmajor ? dy : dx) < 0 ? -1 : 1;
-        sM = xmajor ? smaj : smaj * W;
-        sm = xmajor ? smin * W : smin;
-        twoD = 2 * D;
-        ca = ay * W + ax;
-        i = 0;
-        // n(0) = m + D < 2D unless m == D (then q = 1, rem = 0); D == 0: one column, row 0
-        q = (D > 0 && m == D) ? 1 : 0;
-        rem = (D > 0 && m == D) ? 0 : m + D;
-        rlo = 0;
-    }
-    __device__ bool finished() const { return i > D; }
-    // VW_COLS columns, every load issued before any test.  Columns past D and unused rows repeat the centre cell, which is
-    // free.  Every cell lies in the bounding box of the two endpoints, hence in the grid; the index guard only keeps a broken
-    // invariant from reading outside occ.
-    __device__ bool step(const uint8_t* __restrict__ occ, int cells) {
-        uint32_t v[VW_COLS][3];
-#pragma unroll
-        for (int c = 0; c < VW_COLS; ++c) {
-            const bool live = i <= D;
-            const int rhi = min(q, m);
-            const int base = ca + i * sM;
-#pragma unroll
-            for (int r = 0; r < 3; ++r) {
-                const int idx = (live && rlo + r <= rhi) ? base + (rlo + r) * sm : ca;
-                v[c][r] = (unsigned)idx < (unsigned)cells ? occ[idx] : 1u;
-            }
-            // to column i + 1
-            rlo = q - (rem == 0 ? 1 : 0);
-            rem += 2 * m;
-            if (rem >= twoD && twoD > 0) { rem -= twoD; ++q; }
-            ++i;
-        }
-        unsigned any = 0;
-#pragma unroll
-        for (int c = 0; c < VW_COLS; ++c)
-#pragma unroll
-            for (int r = 0; r < 3; ++r) any |= v[c][r];
-        return any == 0;
-    }
-};
-
-struct vw_box {
-    int cx, cy, x0, y0, tx, ntiles;   // ntiles == 0: the view sees nothing
-    long long r2;
-};
-
-// floor(sqrt(v)) for 0 <= v < 2^31, exact: the float estimate is corrected in integers
-__device__ __forceinline__ int vw_isqrt(long long v) {
-    long long r = (long long)sqrtf((float)v);
-    while (r * r > v) --r;
-    while ((r + 1) * (r + 1) <= v) ++r;
-    return (int)r;
-}
-
-// the clipped box of view v; uniform across the workgroup
-__device__ __forceinline__ vw_box vw_view_box(const uint8_t* __restrict__ occ, const int32_t* __restrict__ views, int v, int W, int H) {
-    vw_box b;
-    b.cx = views[3 * v];
-    b.cy = views[3 * v + 1];
-    b.r2 = views[3 * v + 2];
-    b.x0 = b.y0 = b.tx = b.ntiles = 0;
-    if (b.r2 < 0 || b.cx < 0 || b.cy < 0 || b.cx >= W || b.cy >= H) return b;   // ignored
-    if (occ[b.cy * W + b.cx] != 0) return b;                                      // stands on an occupied cell
-    const int r = vw_isqrt(b.r2);                                                 // <= 46340
-    b.x0 = max(b.cx - r, 0);
-    b.y0 = max(b.cy - r, 0);
-    const int x1 = (int)min((long long)b.cx + r, (long long)W - 1), y1 = (int)min((long long)b.cy + r, (long long)H - 1);
-    b.tx = (x1 - b.x0) / VW_TILE + 1;
-    b.ntiles = b.tx * ((y1 - b.y0) / VW_TILE + 1);
-    return b;
-}
-
-// this thread's target in tile t of the box: wave w of the workgroup is the 8 x 8 quarter (w & 1, w >> 1); -1 when the
-// target lies outside the grid or the disc
-__device__ __forceinline__ int vw_target(const vw_box& b, int t, int W, int H, int& x, int& y) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    x = b.x0 + (t % b.tx) * VW_TILE + (wv & 1) * 8 + (lane & 7);
-    y = b.y0 + (t / b.tx) * VW_TILE + (wv >> 1) * 8 + (lane >> 3);
-    if (x >= W || y >= H) return -1;
-    const long long dx = x - b.cx, dy = y - b.cy;
-    return dx * dx + dy * dy <= b.r2 ? y * W + x : -1;
-}
-
-__device__ __forceinline__ bool vw_clear(const uint8_t* __restrict__ occ, int W, int cells, const vw_box& b, int x, int y) {
-    vw_ray ray;
-    ray.init(W, b.cx, b.cy, x, y);
-    bool ok = true;
-    while (ok && !ray.finished()) ok = ray.step(occ, cells);
-    return ok;
-}
 
 __global__ __launch_bounds__(256) void vw_view_kernel(const uint8_t* __restrict__ occ, const int32_t* __restrict__ views, int W, int H,
                                                       uint8_t* __restrict__ vis) {
@@ -173,7 +66,13 @@ __global__ __launch_bounds__(256) void vw_gain_kernel(const uint8_t* __restrict_
 
 }  // namespace
 
-static bool vw_dims_ok(int W, int H) { return W >= 1 && W <= SC_MAX_DIM && H >= 1 && H <= SC_MAX_DIM; }
+// sectors.hip ends its known-space call with the same kernel
+int sc_launch_view_combine(sc_ctx* ctx, const uint8_t* base, const uint8_t* occ, const uint8_t* vis, int W, int H, uint8_t* known,
+                           uint8_t* occ_seen) {
+    const size_t n = (size_t)W * H;
+    hipLaunchKernelGGL(vw_combine_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, base, occ, vis, W, H, known, occ_seen);
+    return SC_OK;
+}
 
 static bool views_args_ok(const sc_ctx* ctx, const uint8_t* occ, const int32_t* views, int R, int W, int H, const uint8_t* known,
                           const uint8_t* occ_seen) {
@@ -183,12 +82,6 @@ static bool views_args_ok(const sc_ctx* ctx, const uint8_t* occ, const int32_t* 
 static bool gain_args_ok(const sc_ctx* ctx, const uint8_t* occ, const uint8_t* known, const int32_t* views, int N, int W, int H,
                          const int32_t* gain) {
     return ctx && occ && known && N >= 0 && ((views && gain) || N == 0) && vw_dims_ok(W, H);
-}
-
-// tile slots of a launch: the tiles of a box that covers the grid, VW_SLOTS at most
-static unsigned vw_slots(int W, int H, int cap) {
-    const long long t = (long long)((W + VW_TILE - 1) / VW_TILE) * ((H + VW_TILE - 1) / VW_TILE);
-    return (unsigned)(t < cap ? t : cap);
 }
 
 extern "C" int sc_known_from_views(sc_ctx* ctx, const uint8_t* base, const uint8_t* occ, const int32_t* views, int R, int W, int H,

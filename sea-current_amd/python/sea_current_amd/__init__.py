@@ -45,6 +45,7 @@ SCAN_NO_RETURN, SCAN_IGNORED, SCAN_MAX_REACH = -1, -2, 16384
 LOGODDS_HIT, LOGODDS_MISS, LOGODDS_CLAMP, LOGODDS_T_OCC, LOGODDS_T_FREE = 2, 1, 8, 2, 1   # logodds_update's defaults
 SCAN_MATCH_ABSENT, SCAN_MATCH_IGNORED, SCAN_MATCH_MAX_HALF, SCAN_MATCH_MAX_POINTS, SCAN_MATCH_MAX_ROT = -2**31, -1, 64, 65536, 256
 SCAN_MATCH_OVERFLOW, SCAN_MATCH_WIDE_MAX_HALF, SCAN_MATCH_WIDE_MAX_TOP = -2, 2048, 5
+VIEW_MAX_BINS = 64
 
 _lib = None
 
@@ -1265,6 +1266,108 @@ class Context:
         self._call("sc_view_gain_batch" + A.suffix, _ptr(occ), _ptr(known), _ptr(views), views.shape[0], W, H, _ptr(out))
         return out
 
+    # ---- sensors with a field of view (sc_known_from_sectors, sc_sector_gain_batch, sc_view_gain_headings_batch) ----
+    def known_from_sectors(self, sviews, occ, base=None, out=None, occ_seen=None):
+        """known_from_views for sector views (sc_known_from_sectors): sviews int32 [R,7] = (cx, cy, r2, ax, ay, bx, by), the
+        sector counter-clockwise from direction a (inclusive) to b (exclusive); a = b = 0 is the full circle.  The other
+        arguments and the result are known_from_views'.  Only enqueues."""
+        return self._known_from_sectors(_on(occ.device), sviews, occ, base, out, occ_seen)
+
+    def known_from_sectors_host(self, sviews, occ, base=None, occ_seen=None):
+        """Host form of known_from_sectors (numpy in, numpy out)."""
+        return self._known_from_sectors(_HOST, sviews, occ, base, None, occ_seen)
+
+    def _known_from_sectors(self, A, sviews, occ, base, out, occ_seen):
+        sviews, occ, base = A.rows(sviews, A.i32, 7), A.arr(occ, A.u8), A.arr(base, A.u8)
+        H, W = occ.shape
+        if out is None:
+            out = A.new((H, W), A.u8)
+        if occ_seen is True:
+            occ_seen = A.new((H, W), A.u8)
+        for what, x in (("base", base), ("out", out), ("occ_seen", occ_seen)):
+            _sized(what, x, W * H)
+        _sized("sviews", sviews, 7 * sviews.shape[0])
+        self._call("sc_known_from_sectors" + A.suffix, _ptr(base), _ptr(occ), _ptr(sviews), sviews.shape[0], W, H, _ptr(out), _ptr(occ_seen))
+        return out if occ_seen is None else (out, occ_seen)
+
+    def sector_gain(self, sviews, occ, known, out=None):
+        """The unknown cells every sector pose would see (sc_sector_gain_batch): sviews int32 [N,7], occ and known uint8 [H,W]
+        on the GPU.  Returns gain int32 [N].  Only enqueues."""
+        return self._sector_gain(_on(occ.device), sviews, occ, known, out)
+
+    def sector_gain_host(self, sviews, occ, known):
+        """Host form of sector_gain (numpy in, numpy out)."""
+        return self._sector_gain(_HOST, sviews, occ, known)
+
+    def _sector_gain(self, A, sviews, occ, known, out=None):
+        sviews, occ, known = A.rows(sviews, A.i32, 7), A.arr(occ, A.u8), A.arr(known, A.u8)
+        H, W = occ.shape
+        N = sviews.shape[0]
+        if out is None:
+            out = A.new(N, A.i32)
+        _sized("known", known, W * H)
+        _sized("sviews", sviews, 7 * N)
+        _sized("out", out, N)
+        self._call("sc_sector_gain_batch" + A.suffix, _ptr(occ), _ptr(known), _ptr(sviews), N, W, H, _ptr(out))
+        return out
+
+    def view_gain_headings(self, views, occ, known, dirs, span, hist=None, gainh=None, out=None):
+        """The gain of every heading of every candidate pose at the cost of one pass of rays (sc_view_gain_headings_batch):
+        views int32 [N,3], occ and known uint8 [H,W] on the GPU; dirs int32 [B,2] on the HOST (heading_dirs(B)), the table whose
+        consecutive entries bound the bins; span: the bins a sensor covers.  Returns best int32 [N,2] = (the largest gain over
+        the headings, the smallest heading that attains it); heading h is the sector from dirs[h] to dirs[(h + span) % B].
+        hist / gainh: an int32 [N,B] tensor, or True to have it allocated; then dict(best, hist, gainh) with what was asked for
+        is returned.  Only enqueues."""
+        return self._view_gain_headings(_on(occ.device), views, occ, known, dirs, span, hist, gainh, out)
+
+    def view_gain_headings_host(self, views, occ, known, dirs, span, hist=None, gainh=None):
+        """Host form of view_gain_headings (numpy in, numpy out)."""
+        return self._view_gain_headings(_HOST, views, occ, known, dirs, span, hist, gainh)
+
+    def _view_gain_headings(self, A, views, occ, known, dirs, span, hist, gainh, out=None):
+        views, occ, known = A.rows(views, A.i32, 3), A.arr(occ, A.u8), A.arr(known, A.u8)
+        dirs = np.ascontiguousarray(dirs, dtype=np.int32).reshape(-1, 2)         # a host table in both forms
+        H, W = occ.shape
+        N, B = views.shape[0], dirs.shape[0]
+        if out is None:
+            out = A.new((N, 2), A.i32)
+        plain = hist is None and gainh is None
+        hist = A.new((N, B), A.i32) if hist is True else hist
+        gainh = A.new((N, B), A.i32) if gainh is True else gainh
+        _sized("known", known, W * H)
+        _sized("views", views, 3 * N)
+        _sized("out", out, 2 * N)
+        _sized("hist", hist, N * B)
+        _sized("gainh", gainh, N * B)
+        self._call("sc_view_gain_headings_batch" + A.suffix, _ptr(occ), _ptr(known), _ptr(views), N, W, H, _ptr(dirs), B, int(span), _ptr(hist),
+                   _ptr(gainh), _ptr(out))
+        if plain:
+            return out
+        res = dict(best=out)
+        if hist is not None:
+            res["hist"] = hist
+        if gainh is not None:
+            res["gainh"] = gainh
+        return res
+
+    def views_from_cells(self, cell, W, H, r2, out=None):
+        """View rows from cells (sc_views_from_cells): cell int32 [N] on the GPU -> views int32 [N,3] = (cell % W, cell // W, r2),
+        (0, 0, -1), an ignored view, for a cell outside the grid (the -1 of fleet_explore's unmatched robot).  Only enqueues."""
+        return self._views_from_cells(_on(cell.device), cell, W, H, r2, out)
+
+    def views_from_cells_host(self, cell, W, H, r2):
+        """Host form of views_from_cells (numpy in, numpy out)."""
+        return self._views_from_cells(_HOST, cell, W, H, r2)
+
+    def _views_from_cells(self, A, cell, W, H, r2, out=None):
+        cell = A.arr(cell, A.i32)
+        N = _count(cell)
+        if out is None:
+            out = A.new((N, 3), A.i32)
+        _sized("out", out, 3 * N)
+        self._call("sc_views_from_cells" + A.suffix, _ptr(cell), N, W, H, r2, _ptr(out))
+        return out
+
     # ---- occupancy from range scans (sc_scan_cast_batch, sc_logodds_update) ----
     def scan_cast(self, rays, occ, out=None):
         """The simulated range sensor (sc_scan_cast_batch): rays int32 [N,4] = (ax, ay, bx, by) and occ uint8 [H,W] (the true
@@ -1676,3 +1779,30 @@ def rotate_points(pts, angles):
     c, s = np.cos(a)[:, None], np.sin(a)[:, None]
     out = np.stack([np.rint(x * c - y * s), np.rint(x * s + y * c)], -1).astype(np.int64)
     return np.where(ok[..., None, :, None], out, SCAN_MATCH_ABSENT).astype(np.int32)
+
+
+# ---- host helpers of sensors with a field of view (numpy) ----
+def heading_dirs(B, phase=0.0):
+    """The heading table of B evenly spaced directions, counter-clockwise: int32 [B,2] =
+    round(32767 (cos, sin)(2 pi (b + phase) / B)), 3 <= B <= VIEW_MAX_BINS, computed in float64.  Valid for
+    view_gain_headings; no bit claim beyond that."""
+    if not 3 <= int(B) <= VIEW_MAX_BINS:
+        raise SeaCurrentError(f"heading_dirs: B = {B} outside 3 .. {VIEW_MAX_BINS}")
+    t = 2.0 * np.pi * (np.arange(int(B), dtype=np.float64) + float(phase)) / int(B)
+    return np.rint(32767.0 * np.stack([np.cos(t), np.sin(t)], 1)).astype(np.int32)
+
+
+def sector_views(views, dirs, h, span):
+    """Views with a heading as sector rows: views int32 [N,3], dirs int32 [B,2], h a heading or [N] headings, span the bins the
+    sensor covers -> int32 [N,7] = (cx, cy, r2, dirs[h], dirs[(h + span) % B]); span == B gives a = b = 0, the full circle."""
+    views = np.asarray(views, dtype=np.int32).reshape(-1, 3)
+    dirs = np.asarray(dirs, dtype=np.int32).reshape(-1, 2)
+    B = len(dirs)
+    if not 1 <= int(span) <= B:
+        raise SeaCurrentError(f"sector_views: span = {span} outside 1 .. {B}")
+    h = np.broadcast_to(np.asarray(h, dtype=np.int64), (len(views),)) % B
+    out = np.zeros((len(views), 7), np.int32)
+    out[:, :3] = views
+    if int(span) < B:
+        out[:, 3:5], out[:, 5:7] = dirs[h], dirs[(h + int(span)) % B]
+    return out

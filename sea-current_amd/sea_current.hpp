@@ -37,6 +37,8 @@
 //                                                         parity: frontier clusters of the known space on the GPU
 //   (new) occupancy_grid::frontiers / explore_goals, planning_space::known_grid: exploration frontiers, a goal per robot
 //   (new) occupancy_grid::known_from_views / view_gain, planner::line_of_sight: sensing that walls block
+//   (new) heading_dirs, occupancy_grid::known_from_sectors / sector_gain / view_gain_headings, planner::fov_span: sensors
+//         with a field of view, and the heading that reveals most
 //   (new) occupancy_grid::scan_cast, logodds_grid, beams_from_ranges, square_fan, planner::range_scan: range beams in, a
 //         log-odds occupancy map out
 //   (new) occupancy_grid::scan_match, logodds_grid::match, points_from_hits, rotate_points: a scan's pose against the map
@@ -354,6 +356,32 @@ struct wide_match_params {
     int rotations = 1;
     int top = 3, max_nodes = 1 << 16;
 };
+
+// A heading table of B evenly spaced directions, counter-clockwise: round(32767 (cos, sin)(2 pi (b + phase) / B)),
+// 3 <= B <= SC_VIEW_MAX_BINS (sc_view_gain_headings_batch's dirs).  Consecutive entries bound the bins; heading h of a sensor that
+// covers `span` bins is the sector from entry h to entry (h + span) % B.  Computed in double; valid, no bit claim beyond that.
+using heading_table = std::vector<std::array<int32_t, 2>>;
+inline heading_table heading_dirs(int B, double phase = 0.0) {
+    if (B < 3 || B > SC_VIEW_MAX_BINS) throw std::invalid_argument("heading_dirs: B outside 3 .. SC_VIEW_MAX_BINS");
+    heading_table d((size_t)B);
+    const double turn = 2.0 * std::acos(-1.0);
+    for (int b = 0; b < B; ++b) {
+        const double t = turn * (b + phase) / B;
+        d[(size_t)b] = {(int32_t)std::nearbyint(32767.0 * std::cos(t)), (int32_t)std::nearbyint(32767.0 * std::sin(t))};
+    }
+    return d;
+}
+// A view with a heading as a sector row (cx, cy, r2, a, b) of sc_known_from_sectors; span == B: a = b = 0, the full circle.
+inline std::array<int32_t, 7> sector_view(const std::array<int32_t, 3>& view, const heading_table& dirs, int h, int span) {
+    const int B = (int)dirs.size();
+    if (B < 1 || span < 1 || span > B) throw std::invalid_argument("sector_view: span outside 1 .. B");
+    std::array<int32_t, 7> r{view[0], view[1], view[2], 0, 0, 0, 0};
+    if (span < B) {
+        const auto &a = dirs[(size_t)(((h % B) + B) % B)], &b = dirs[(size_t)(((h % B) + B + span) % B)];
+        r[3] = a[0]; r[4] = a[1]; r[5] = b[0]; r[6] = b[1];
+    }
+    return r;
+}
 
 // ---- occupancy grid (new): the world model the GPU path works on ----------------------------------
 // Row-major uint8 occupancy over a bounding_rect; cell (ix, iy) covers
@@ -704,6 +732,52 @@ public:
         ctx.check(sc_view_gain_batch_host(ctx.get(), occ.data(), known.data(), views[0].data(), (int)views.size(), W, H, gain.data()),
                   "sc_view_gain_batch_host");
         return gain;
+    }
+    // Sensors with a field of view (sc_known_from_sectors): known_from_views for rows (cx, cy, r2, ax, ay, bx, by); a row sees
+    // what its view sees inside the sector counter-clockwise from direction a (inclusive) to b (exclusive); a = b = 0 is the
+    // full circle (sector_view builds rows from a heading table).
+    view_result known_from_sectors(const std::vector<std::array<int32_t, 7>>& sviews, const std::vector<uint8_t>& base = {},
+                                   gpu_context& ctx = default_context()) const {
+        if (!base.empty() && base.size() != occ.size()) throw std::invalid_argument("occupancy_grid::known_from_sectors: base is not [H][W]");
+        view_result r;
+        r.known.assign(occ.size(), 0); r.occ_seen.assign(occ.size(), 0);
+        if (occ.empty()) return r;
+        ctx.check(sc_known_from_sectors_host(ctx.get(), base.empty() ? nullptr : base.data(), occ.data(),
+                                             sviews.empty() ? nullptr : sviews[0].data(), (int)sviews.size(), W, H, r.known.data(),
+                                             r.occ_seen.data()), "sc_known_from_sectors_host");
+        return r;
+    }
+    // The unknown cells every sector pose would see (sc_sector_gain_batch).
+    std::vector<int32_t> sector_gain(const std::vector<uint8_t>& known, const std::vector<std::array<int32_t, 7>>& sviews,
+                                     gpu_context& ctx = default_context()) const {
+        if (known.size() != occ.size()) throw std::invalid_argument("occupancy_grid::sector_gain: known is not [H][W]");
+        std::vector<int32_t> gain(sviews.size(), 0);
+        if (sviews.empty() || occ.empty()) return gain;
+        ctx.check(sc_sector_gain_batch_host(ctx.get(), occ.data(), known.data(), sviews[0].data(), (int)sviews.size(), W, H, gain.data()),
+                  "sc_sector_gain_batch_host");
+        return gain;
+    }
+    // The gain of every heading of every candidate pose, from one pass of rays (sc_view_gain_headings_batch): hist [N][B] the
+    // unknown cells pose i sees in bin b of the table, gainh [N][B] what a sensor of `span` bins sees at heading h, best [N]
+    // = (the largest of them, the smallest heading that attains it).
+    struct heading_result {
+        int B = 0;
+        std::vector<std::array<int32_t, 2>> best;
+        std::vector<int32_t> hist, gainh;
+    };
+    heading_result view_gain_headings(const std::vector<uint8_t>& known, const std::vector<std::array<int32_t, 3>>& views,
+                                      const heading_table& dirs, int span, gpu_context& ctx = default_context()) const {
+        if (known.size() != occ.size()) throw std::invalid_argument("occupancy_grid::view_gain_headings: known is not [H][W]");
+        heading_result r;
+        r.B = (int)dirs.size();
+        r.best.assign(views.size(), {0, 0});
+        r.hist.assign(views.size() * dirs.size(), 0);
+        r.gainh.assign(views.size() * dirs.size(), 0);
+        if (views.empty() || occ.empty()) return r;
+        ctx.check(sc_view_gain_headings_batch_host(ctx.get(), occ.data(), known.data(), views[0].data(), (int)views.size(), W, H,
+                                                   dirs.empty() ? nullptr : dirs[0].data(), r.B, span, r.hist.data(), r.gainh.data(),
+                                                   r.best[0].data()), "sc_view_gain_headings_batch_host");
+        return r;
     }
     // The simulated range sensor (sc_scan_cast_batch): `rays` are (ax, ay, bx, by) in cells, one std::array<int32_t, 4> each;
     // this grid's occ is the true map.  hit[k] = the first occupied cell the beam from a towards b meets, SC_SCAN_NO_RETURN
@@ -1318,6 +1392,13 @@ private:
 //   (occupancy_grid::scan_cast) and updates `map` with scan_params (logodds_grid::update; sized and zeroed on first use).
 //   `seen` is the map's known mask, the grid the frontiers are taken on its occ_est: the robot explores on what its beams
 //   have accumulated, not on a mask handed to it.
+// fov_span (0: off; every path above runs unchanged and nothing new is allocated).  With fov_span > 0 the sensor covers
+//   fov_span bins of heading_dirs(headings); line_of_sight must be set, else std::logic_error.  The robot senses at its cell
+//   with the sector of `heading` (-1: the heading of largest predicted gain there on the map observed so far, ties to the
+//   smallest; `heading` receives the one used, so set it again before the next call: to goal_heading once the robot stands at
+//   the goal, or to -1); if that look adds no known cell it senses the full circle once, a turn on the
+//   spot, so a look from a frontier cell always adds one.  After the goal is picked, goal_heading is view_gain_headings' best
+//   heading at the goal on the observed map (-1 when the goal came from the cache).
 class planner {
 public:
     planning_space ps;
@@ -1328,11 +1409,16 @@ public:
     bool range_scan = false;
     logodds_grid map;
     logodds_params scan_params;
+    int fov_span = 0;
+    int headings = 16;
+    int heading = -1;
+    int goal_heading = -1;
 
     explicit planner(const planning_space& space) : ps(space) {}
 
     Vector2f pick_next_goal_point(const Vector2f& start, const int n, const float search_radius, gpu_context& ctx = default_context()) {
         if (line_of_sight && range_scan) throw std::logic_error("planner::pick_next_goal_point: line_of_sight and range_scan are both set");
+        if (fov_span > 0 && !line_of_sight) throw std::logic_error("planner::pick_next_goal_point: fov_span needs line_of_sight");
         if (!line_of_sight && !range_scan)
             ps.free_space_allocations.push_back([start, search_radius](Vector2f p) { return pt_dist(p, start) <= search_radius; });
         occupancy_grid g = ps.make_grid(ctx);
@@ -1348,7 +1434,8 @@ public:
             if (seen.size() != g.occ.size()) seen.assign(g.occ.size(), 0);
             const int32_t sc = g.cell_of(start);
             const float rc = search_radius / g.resolution;
-            auto view = g.known_from_views({{sc % g.W, sc / g.W, (int32_t)(rc * rc)}}, seen, ctx);
+            const std::array<int32_t, 3> here{sc % g.W, sc / g.W, (int32_t)(rc * rc)};
+            auto view = fov_span > 0 ? look_with_sector(g, here, ctx) : g.known_from_views({here}, seen, ctx);
             seen = std::move(view.known);
             g.occ = std::move(view.occ_seen);
         }
@@ -1364,12 +1451,38 @@ public:
                 if (k != ex.col_of[0] && ex.cost[(size_t)k] != SC_FIELD_INF) rest.push_back({ex.cost[(size_t)k], ex.cell[(size_t)k]});
             std::sort(rest.begin(), rest.end());
             for (auto it = rest.rbegin(); it != rest.rend(); ++it) goal_point_cache.push(g.centre_of(it->second));
+            if (fov_span > 0) {
+                const float rc = search_radius / g.resolution;
+                goal_heading = g.view_gain_headings(known, {{ex.goal[0] % g.W, ex.goal[0] / g.W, (int32_t)(rc * rc)}}, heading_dirs(headings),
+                                                    fov_span, ctx).best[0][1];
+            }
             return g.centre_of(ex.goal[0]);
         }
+        goal_heading = -1;
         if (goal_point_cache.empty()) throw std::runtime_error("planner::pick_next_goal_point: no reachable frontier and no cached goal");
         const Vector2f next = goal_point_cache.top();
         goal_point_cache.pop();
         return next;
+    }
+
+private:
+    // One look of a sensor of fov_span bins from `here` on the true grid g, on top of `seen`: the sector of `heading`, or of the
+    // heading of largest predicted gain on the observed map; the full circle when the sector adds nothing.
+    occupancy_grid::view_result look_with_sector(const occupancy_grid& g, const std::array<int32_t, 3>& here, gpu_context& ctx) {
+        const heading_table dirs = heading_dirs(headings);
+        if (fov_span > headings) throw std::invalid_argument("planner::pick_next_goal_point: fov_span exceeds headings");
+        if (heading < 0 || heading >= headings) {
+            occupancy_grid observed = g;
+            for (size_t c = 0; c < seen.size(); ++c)
+                if (!seen[c]) observed.occ[c] = 0;
+            heading = observed.view_gain_headings(seen, {here}, dirs, fov_span, ctx).best[0][1];
+        }
+        size_t before = 0, after = 0;
+        for (uint8_t k : seen) before += k != 0;
+        auto view = g.known_from_sectors({sector_view(here, dirs, heading, fov_span)}, seen, ctx);
+        for (uint8_t k : view.known) after += k != 0;
+        if (after == before) view = g.known_from_views({here}, seen, ctx);
+        return view;
     }
 };
 
