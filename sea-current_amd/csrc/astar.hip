@@ -24,7 +24,8 @@
 // equal-f chains towards the goal) are appended to that ring by wavefront-ballot compaction
 // (consecutive slots by mbcnt rank of the ballot); successors of other levels take their slot in
 // the HBM ring of their level with one LDS atomic add.  When the LDS ring runs empty it is refilled
-// from the level's HBM ring with coalesced loads, so every pop is an LDS read.
+// from the level's HBM ring with coalesced loads, so every pop is an LDS read.  (The throughput build of the two-wavefront
+// kernel groups a refill chunk by the tile of its nodes, see the refill in astar_query: the order inside a level is free.)
 // Lane layout of the one-wavefront kernel (astar_kernel; the two-wavefront kernel's steps are described
 // in astar_query): frontiers of <= 8 nodes use 8 lanes per node (one per move); wider ones one lane per
 // node for the pop, then the legal successors of all nodes are compacted into a list and pushed 64 at
@@ -165,6 +166,11 @@ __device__ __forceinline__ uint32_t entry_prune(uint32_t e) {
     if (e & E_RUN) prune |= 1u << d;                   // its continuation was queued together with it
     return (e & 0x3E000u) == E_START ? 0u : prune;
 }
+
+// Bin of a queue entry for the tile-ordered refill of the throughput build: row and column of its node's closed-bitmap
+// tile (32 x 16 cells) modulo 8, ((y >> 4) & 7) << 3 | ((x >> 5) & 7) -- 64 bins, one per lane.  Tiles 8 apart share a
+// bin; a level's nodes in one chunk rarely span that far, and an alias costs locality only.
+__device__ __forceinline__ uint32_t tile_bin(uint32_t e) { return ((e >> 20) & 0x38u) | ((e >> 5) & 7u); }
 
 // Returning atomic OR on the lanes whose operand is not 0 only, without a branch: hipcc drains vmcnt in front of a
 // divergent `if (...) atomic`, which would put the load issued beside it on a round trip of its own.  The caller
@@ -533,6 +539,15 @@ __device__ __forceinline__ void astar_query(const astar_args& a, const int q, co
                 const int tl = __builtin_amdgcn_readfirstlane(__hip_atomic_load(&s_tail[b], __ATOMIC_RELAXED, SCOPE));
                 if (hd == tl) break;
                 const int n = min(tl - hd, REFILL);
+                // Throughput build, a chunk of more than one step: the chunk goes into the ring grouped by the closed-bitmap
+                // tile of its nodes (tile_bin), so that the lanes of a step share closed, legal-move and g lines instead of
+                // touching one each -- on a full chip the scattered 32-64 B requests are what bounds the kernel, and the order
+                // of pops inside a level is free (E, g and the parent chain do not depend on it).  The ring is empty here, so
+                // the chunk (<= CQ / 2) is staged in ring order in the half of the ring beyond its destination, counted per
+                // bin in the spare words (nothing live there between steps), and moved to its place by a returning LDS add on
+                // its bin's offset; the order inside a bin is whatever the adds give.
+                const bool binned = DUAL && CQ == ASTAR_CQ_THROUGHPUT && n > 64;
+                const int stage = binned ? REFILL : 0;
                 // REFILL_UNROLL loads under way before the first is waited for (one after the other, a chunk of 512 entries
                 // was eight dependent round trips)
                 for (int base = lane; base < n; base += 64 * REFILL_UNROLL) {
@@ -542,7 +557,35 @@ __device__ __forceinline__ void astar_query(const astar_args& a, const int q, co
                         if (base + 64 * k < n) chunk[k] = bq[(hd + base + 64 * k) & capm];
 #pragma unroll
                     for (int k = 0; k < REFILL_UNROLL; ++k)
-                        if (base + 64 * k < n) qe[(lt + base + 64 * k) & (CQ - 1)] = chunk[k];
+                        if (base + 64 * k < n) qe[(lt + stage + base + 64 * k) & (CQ - 1)] = chunk[k];
+                }
+                if constexpr (DUAL && CQ == ASTAR_CQ_THROUGHPUT) {
+                    if (binned) {
+                        // one entry per lane at a time from here on: the block is cold, and registers held over it would
+                        // count against the step loop's 80
+                        qe[CQ + lane] = 0u;
+                        wave_lds_sync();
+#pragma unroll 1
+                        for (int i = lane; i < n; i += 64)
+                            __hip_atomic_fetch_add(&qe[CQ + tile_bin(qe[(lt + REFILL + i) & (CQ - 1)])], 1u, __ATOMIC_RELAXED, SCOPE);
+                        wave_lds_sync();
+                        // exclusive prefix of the 64 bin counts, one bin per lane
+                        const uint32_t cnt = qe[CQ + lane];
+                        uint32_t off = 0;   // from ten ballots (a count is at most REFILL = 512): nothing lane-dependent to keep live
+#pragma unroll
+                        for (int bb = 0; bb < 10; ++bb) {
+                            const unsigned long long m = __ballot((cnt >> bb) & 1u);
+                            off += (uint32_t)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)) << bb;
+                        }
+                        qe[CQ + lane] = off;
+                        wave_lds_sync();
+#pragma unroll 1
+                        for (int i = lane; i < n; i += 64) {
+                            const uint32_t e = qe[(lt + REFILL + i) & (CQ - 1)];
+                            const uint32_t slot = __hip_atomic_fetch_add(&qe[CQ + tile_bin(e)], 1u, __ATOMIC_RELAXED, SCOPE);
+                            qe[(lt + (int)slot) & (CQ - 1)] = e;   // slot < n <= REFILL: never a staged entry's place
+                        }
+                    }
                 }
                 lt += n;
                 if (lane == 0) __hip_atomic_store(&s_head[b], hd + n, __ATOMIC_RELAXED, SCOPE);
