@@ -1201,6 +1201,97 @@ int sc_view_gain_headings_batch_host(sc_ctx* ctx, const uint8_t* occ, const uint
 int sc_views_from_cells(sc_ctx* ctx, const int32_t* cell, int N, int W, int H, int32_t r2, int32_t* views);
 int sc_views_from_cells_host(sc_ctx* ctx, const int32_t* cell, int N, int W, int H, int32_t r2, int32_t* views);
 
+/* ---- planning in poses: heading fields with turn costs and oriented footprints --------------------------------------
+ * The planners above plan for a disc without a heading: a state is a cell, turning is free, a goal carries no orientation.
+ * These calls plan over poses (cell, heading): a per-heading collision mask of a rectangular body, exact cost fields over
+ * the 8 W H poses with a price for turning and for reversing, and their read-out.  The reference has no counterpart (no parity
+ * claim); the definitions are integer and unique; tests/pose_twin.py states them in NumPy, tests/cpp/pose_ref.c in C, and
+ * every output equals both bit for bit.  DESIGN.md section 28.  Cells are c = y*W + x.
+ *
+ * Headings.  There are SC_POSE_HEADINGS = 8, counter-clockwise in (x, y): hx = {1,1,0,-1,-1,-1,0,1}, hy = {0,1,1,1,0,-1,-1,-1}.
+ *   Heading k is A*'s move index {0,4,2,5,1,7,3,6}[k].  w_k is 10 for even k and 14 for odd k.
+ *   T(c) <=> d2[c] >= max(r2_clear, 1) as everywhere.
+ * Footprint mask (sc_footprint_mask_u8).  hmask is uint8 [batch][H][W].  The body is a rectangle in the robot's frame.  Its
+ *   extents are whole cells, 0 <= front, back, left, right <= SC_FOOTPRINT_MAX = 32, with left counter-clockwise of the
+ *   heading.  The rectangle is inflated by the disc that r2_clear already stands for.  Let n = hx^2 + hy^2,
+ *   u = dx*hx + dy*hy and v = -dx*hy + dy*hx.  Offset (dx, dy) is covered at heading k iff both of these hold:
+ *     u >= 0 ? u^2 <= n*front^2 : u^2 <= n*back^2
+ *     v >= 0 ? v^2 <= n*left^2 : v^2 <= n*right^2
+ *   In words, the cell's centre lies in the closed rectangle, decided exactly for the diagonals.
+ *   Bit k of hmask[c] is set iff T(c + o) holds for every covered offset o that lands in the grid.  Offsets outside the
+ *   grid are free, as the disc's are today.  Anchor: with all four extents 0, hmask[c] = T(c) ? 0xFF : 0.
+ *   Not modelled: cells partly covered whose centre is outside, and the corners' sweep during a 45 degree turn.  The caller
+ *   pads the extents.
+ * Pose graph.  Pose (c, k) is valid iff T(c) and (hmask == NULL or bit k of hmask[c]).  Edges out of (c, k):
+ *   Forward to (c + h_k, k), cost w_k.  It is legal iff A*'s move c -> c + h_k is legal and both poses are valid.  A*'s
+ *     rule means in grid, both cells T, and for a diagonal both side cells T.
+ *   Reverse to (c - h_k, k), cost w_k + rev_cost, with the same legality.  It exists only when rev_cost >= 0.
+ *     rev_cost = -1 means no reversing, and other negative values are SC_ERR_INVALID.
+ *   Turn on the spot to (c, k +- 1 mod 8), cost turn_cost >= 0.  It is legal iff both poses are valid.
+ *   No arc moves (forward while turning) and no costmap.
+ * Field (sc_pose_field_batch).  gp is int32 [F][8][H][W].  With toward = 0, gp[f][k][c] is the exact optimal cost from the
+ *   root pose to (c, k).  It is SC_FIELD_INF where (c, k) is invalid or unreachable.  rhead[f] in 0..7 seeds that pose at
+ *   0.  rhead[f] = -1 seeds every valid heading of the root cell at 0.  The whole field is SC_FIELD_INF with status
+ *   SC_Q_BAD_ENDPOINT in four cases: the root cell is out of range; the root pose is invalid (for -1: no valid heading);
+ *   rhead is outside -1..7; fgrid is out of range.
+ *   toward = 1 gives the cost from (c, k) to the root pose.  It is needed because reversing makes the graph asymmetric.  By
+ *   definition it is the toward = 0 field of root heading rhead + 4 with its layers renamed k -> k + 4 (and the bits of
+ *   hmask renamed with them: layer j of the renamed search is valid where bit j + 4 is set).  Transposing the graph swaps
+ *   the roles of forward and reverse, which is what negating every heading vector does.  The twin checks this identity
+ *   against a Dijkstra on the transposed graph.
+ *   Before any launch or allocation, SC_ERR_INVALID unless 0 <= turn_cost <= 255, -1 <= rev_cost <= 255 and, in 64 bits,
+ *   max(14 + max(rev_cost, 0), turn_cost) * (8*W*H - 1) <= INT32_MAX - 1.  An optimal path visits every state at most once.
+ * Read-out (sc_pose_paths_batch).  turn_cost = 0 is SC_ERR_INVALID here: zero-cost turn cycles have no unique walk.  The
+ *   field call accepts 0.  thead[q] in 0..7, or -1 for the cheapest heading at the target, smallest k on a tie (k as the
+ *   caller numbers the layers of gp).  The walk goes from the target pose back to a seeded state, on the toward = 0
+ *   numbering.  For a toward field, rename as above and rename the written headings back.  From (c, k) with
+ *   v = gp[k][c] > 0 or not a seed, take the first candidate whose edge is legal and whose gp + edge cost == v:
+ *     1. The forward predecessor (c - h_k, k).
+ *     2. The reverse predecessor (c + h_k, k), only if rev_cost >= 0.
+ *     3. The turn from k - 1.
+ *     4. The turn from k + 1.
+ *   Every edge is positive, so g falls strictly and the walk ends.  Legality is read from d2 and hmask, not inferred from g.
+ *   One entry per state is written: path int32 [Q][Lmax] cells and head uint8 [Q][Lmax].  to_root = 0 writes root..target
+ *   and to_root = 1 writes target..root.  For a toward field, to_root = 1 is the driving order.
+ *   cells_only = 1 drops every entry whose cell equals the previous written entry's cell.  The first state of each cell (in
+ *   the order written) stays.  path is then an 8-connected cell path that sc_path_waypoints_batch takes.  len counts what is
+ *   written.
+ *   Statuses, len, cost and truncation past Lmax follow sc_field_paths_batch: SC_Q_OK; SC_Q_BAD_ENDPOINT (qfield, the field's
+ *   grid, its root cell or rhead out of range, the root pose or the target pose invalid, thead outside -1..7, thead = -1 on
+ *   a target cell that is not T), len 0 and cost -1; SC_Q_NO_PATH (gp at the target pose is SC_FIELD_INF, or no candidate
+ *   matches: gp is not the field of these arguments), len 0 and cost -1; SC_Q_TRUNCATED with len = the needed count and the
+ *   cost (path and head unspecified).
+ * Device pointers; the calls only enqueue on the context's stream, so sc_edt_u8_i32 -> sc_footprint_mask_u8 ->
+ * sc_pose_field_batch -> sc_pose_paths_batch -> sc_path_waypoints_batch runs with one synchronise.  hmask of the pose calls is
+ * uint8 [G][H][W] or NULL.  rounds: chip-wide relaxation launches before the per-field finisher; the result is identical for
+ * every value; rounds < 0 = the library default 4 * (ceil(W/32) + ceil(H/32)) + 16.  Errors: SC_ERR_INVALID for NULL mandatory
+ * pointers (hmask, fgrid with G == 1 and fstatus may be NULL), W or H outside 1..SC_MAX_DIM, batch, G, F <= 0, Q < 0
+ * (Q == 0 is a no-op), Lmax <= 0, an extent outside 0..SC_FOOTPRINT_MAX, and the cost rules above.  The _host forms take host
+ * pointers, check the data (sc_pose_paths_batch_host: every gp value >= 0), copy, run, copy back and synchronise.  Scratch
+ * grows only: the mask keeps two summed-area tables of one grid, 4 (W+1) (H+1) + 4 (W+H)^2 bytes; the field about 12 B per
+ * (field, 32 x 32 tile).  The field and the read-out are timed as SC_K_ASTAR, the mask as SC_K_MOVES. */
+#define SC_POSE_HEADINGS 8
+#define SC_FOOTPRINT_MAX 32
+int sc_footprint_mask_u8(sc_ctx* ctx, const int32_t* d2, int W, int H, int batch, int32_t r2_clear, int front, int back, int left,
+                         int right, uint8_t* hmask);
+int sc_footprint_mask_u8_host(sc_ctx* ctx, const int32_t* d2, int W, int H, int batch, int32_t r2_clear, int front, int back, int left,
+                              int right, uint8_t* hmask);
+int sc_pose_field_batch(sc_ctx* ctx, const int32_t* d2, const uint8_t* hmask, int G, const int32_t* fgrid, int W, int H,
+                        int32_t r2_clear, int turn_cost, int rev_cost, int toward, const int32_t* root, const int32_t* rhead, int F,
+                        int rounds, int32_t* gp, int32_t* fstatus);
+int sc_pose_field_batch_host(sc_ctx* ctx, const int32_t* d2, const uint8_t* hmask, int G, const int32_t* fgrid, int W, int H,
+                             int32_t r2_clear, int turn_cost, int rev_cost, int toward, const int32_t* root, const int32_t* rhead,
+                             int F, int rounds, int32_t* gp, int32_t* fstatus);
+int sc_pose_paths_batch(sc_ctx* ctx, const int32_t* d2, const uint8_t* hmask, int G, const int32_t* fgrid, int W, int H,
+                        int32_t r2_clear, int turn_cost, int rev_cost, int toward, const int32_t* gp, const int32_t* root,
+                        const int32_t* rhead, int F, const int32_t* qfield, const int32_t* target, const int32_t* thead, int Q, int Lmax,
+                        int to_root, int cells_only, int32_t* path, uint8_t* head, int32_t* len, int32_t* cost, int32_t* status);
+int sc_pose_paths_batch_host(sc_ctx* ctx, const int32_t* d2, const uint8_t* hmask, int G, const int32_t* fgrid, int W, int H,
+                             int32_t r2_clear, int turn_cost, int rev_cost, int toward, const int32_t* gp, const int32_t* root,
+                             const int32_t* rhead, int F, const int32_t* qfield, const int32_t* target, const int32_t* thead, int Q,
+                             int Lmax, int to_root, int cells_only, int32_t* path, uint8_t* head, int32_t* len, int32_t* cost,
+                             int32_t* status);
+
 /* ---- occupancy from range scans: beam casts and log-odds maps ------------------------------------------------------
  * The calls above take the map to be sensed and hand back a mask.  These two take measurements: a beam has an origin, an end
  * and either the cell where it stopped or no return.  sc_scan_cast_batch is the simulated range sensor (it casts beams through

@@ -99,6 +99,8 @@ struct __attribute__((visibility("hidden"))) sc_ctx {
     sc_scratch mt_part;     // scan matching: {uint64 key, int32 count, pad} [S][R][tiles of 256 candidates]
     sc_scratch mw_pyr;      // wide scan matching: the pooled cost maps of levels 1 .. top, uint16 [H+m+1][W+m+1] each, and the half-way map of a level
     sc_scratch mw_state;    // wide scan matching: uint64 parents [2][S][max_nodes] | int32 bounds [S][max_nodes] | uint64 keys [S][R] | int32 counts [S][16] | int32 U [S][8]
+    sc_scratch fp_sat;      // footprint mask: int32 [H+1][W+1] | int32 [W+H][W+H], the summed-area tables of one grid's blocked cells over (x, y) and over (x + y, y - x)
+    sc_scratch pose_state;  // pose fields: int32 ok [F] | stamp [F][tiles] | list0, list1 [F * tiles] | ctr [rounds + 1]
     int astar_cap = 1 << 16;         // ring entries per bucket (power of two)
     size_t astar_slot_budget = (size_t)96 << 30;  // bytes of g + bitmap + ring scratch this context may take (SC_ASTAR_SLOT_GB), further bounded by what the device has free; 4096^2: 96 GiB = 1966 slots measured best (48: -34 %, 160: -17 %)
     int traj_wg_target = 4096;      // path conflicts: workgroups a launch of the pair kernel aims for (16 per CU; SC_TRAJ_WORKGROUPS)

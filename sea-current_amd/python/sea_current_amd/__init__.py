@@ -46,6 +46,8 @@ LOGODDS_HIT, LOGODDS_MISS, LOGODDS_CLAMP, LOGODDS_T_OCC, LOGODDS_T_FREE = 2, 1, 
 SCAN_MATCH_ABSENT, SCAN_MATCH_IGNORED, SCAN_MATCH_MAX_HALF, SCAN_MATCH_MAX_POINTS, SCAN_MATCH_MAX_ROT = -2**31, -1, 64, 65536, 256
 SCAN_MATCH_OVERFLOW, SCAN_MATCH_WIDE_MAX_HALF, SCAN_MATCH_WIDE_MAX_TOP = -2, 2048, 5
 VIEW_MAX_BINS = 64
+POSE_HEADINGS, FOOTPRINT_MAX = 8, 32
+POSE_HX, POSE_HY = (1, 1, 0, -1, -1, -1, 0, 1), (0, 1, 1, 1, 0, -1, -1, -1)   # heading k, counter-clockwise in (x, y)
 
 _lib = None
 
@@ -1366,6 +1368,93 @@ class Context:
             out = A.new((N, 3), A.i32)
         _sized("out", out, 3 * N)
         self._call("sc_views_from_cells" + A.suffix, _ptr(cell), N, W, H, r2, _ptr(out))
+        return out
+
+    # ---- planning in poses (sc_footprint_mask_u8, sc_pose_field_batch, sc_pose_paths_batch) ----
+    def footprint_mask(self, d2, front, back, left, right, r2=0, out=None):
+        """The per-heading collision mask of a rectangular body (sc_footprint_mask_u8): d2 int32 [H,W] or [B,H,W] on the GPU,
+        the extents in whole cells, 0 .. FOOTPRINT_MAX, left counter-clockwise of the heading.  Returns uint8 shaped like d2:
+        bit k set where the body, at heading k (POSE_HX, POSE_HY) and inflated by the disc r2 stands for, covers no blocked
+        cell.  Only enqueues."""
+        return self._footprint_mask(_on(d2.device), d2, front, back, left, right, r2, out)
+
+    def footprint_mask_host(self, d2, front, back, left, right, r2=0):
+        """Host form of footprint_mask (numpy in, numpy out)."""
+        return self._footprint_mask(_HOST, d2, front, back, left, right, r2)
+
+    def _footprint_mask(self, A, d2, front, back, left, right, r2, out=None):
+        d2 = A.arr(d2, A.i32)
+        B, H, W = _ghw(d2)
+        if out is None:
+            out = A.new(tuple(d2.shape), A.u8)
+        _sized("out", out, B * H * W)
+        self._call("sc_footprint_mask_u8" + A.suffix, _ptr(d2), W, H, B, r2, int(front), int(back), int(left), int(right), _ptr(out))
+        return out
+
+    def pose_fields(self, d2, roots, rhead, turn_cost, rev_cost=-1, toward=False, r2=0, hmask=None, fgrid=None, rounds=-1, out=None):
+        """Cost fields over poses (sc_pose_field_batch): field f is rooted at the pose (roots[f], rhead[f]) (rhead -1: every
+        valid heading of the cell) on grid fgrid[f].  d2 int32 [H,W] or [G,H,W], roots / rhead / fgrid int32 [F], hmask uint8
+        shaped like d2 (what footprint_mask returned) or None, all on the GPU.  A forward move costs 10 / 14, a reverse move
+        rev_cost more (-1: none), a turn of 45 degrees on the spot turn_cost.  toward: the cost from every pose to the root
+        pose instead of from it.  Returns dict(gp int32 [F,8,H,W], status int32 [F]).  Only enqueues."""
+        return self._pose_fields(_on(d2.device), d2, roots, rhead, turn_cost, rev_cost, toward, r2, hmask, fgrid, rounds, out)
+
+    def pose_fields_host(self, d2, roots, rhead, turn_cost, rev_cost=-1, toward=False, r2=0, hmask=None, fgrid=None, rounds=-1):
+        """Host form of pose_fields (numpy in, numpy out)."""
+        return self._pose_fields(_HOST, d2, roots, rhead, turn_cost, rev_cost, toward, r2, hmask, fgrid, rounds)
+
+    def _pose_fields(self, A, d2, roots, rhead, turn_cost, rev_cost, toward, r2, hmask, fgrid, rounds, out=None):
+        d2, roots, rhead, fgrid, hmask = A.arr(d2, A.i32), A.arr(roots, A.i32), A.arr(rhead, A.i32), A.arr(fgrid, A.i32), A.arr(hmask, A.u8)
+        G, H, W = _ghw(d2)
+        F = _count(roots)
+        if out is None:
+            out = dict(gp=A.new((F, POSE_HEADINGS, H, W), A.i32), status=A.new(F, A.i32))
+        _sized("rhead", rhead, F)
+        _sized("fgrid", fgrid, F)
+        _sized("hmask", hmask, G * H * W)
+        _sized("out['gp']", out["gp"], F * POSE_HEADINGS * H * W)
+        _sized("out['status']", out["status"], F)
+        self._call("sc_pose_field_batch" + A.suffix, _ptr(d2), _ptr(hmask), G, _ptr(fgrid), W, H, r2, int(turn_cost), int(rev_cost),
+                   int(bool(toward)), _ptr(roots), _ptr(rhead), F, rounds, _ptr(out["gp"]), _ptr(out["status"]))
+        return out
+
+    def pose_paths(self, d2, gp, roots, rhead, qfield, targets, thead, turn_cost, rev_cost=-1, toward=False, r2=0, hmask=None, Lmax=4096,
+                   to_root=False, cells_only=False, fgrid=None, out=None):
+        """Pose paths read from pose fields (sc_pose_paths_batch): query q follows field qfield[q] (gp, roots, rhead and the
+        costs as pose_fields took and returned them) to the pose (targets[q], thead[q]); thead -1: the cheapest heading there.
+        Returns dict(path int32 [Q,Lmax] cells, head uint8 [Q,Lmax] headings, len, cost, status int32 [Q]), one entry per
+        pose; to_root writes target..root (the driving order of a toward field); cells_only keeps the first pose of every
+        cell, which makes path a cell path path_waypoints takes.  turn_cost 0 is refused.  Only enqueues."""
+        return self._pose_paths(_on(d2.device), d2, gp, roots, rhead, qfield, targets, thead, turn_cost, rev_cost, toward, r2, hmask, Lmax,
+                                to_root, cells_only, fgrid, out)
+
+    def pose_paths_host(self, d2, gp, roots, rhead, qfield, targets, thead, turn_cost, rev_cost=-1, toward=False, r2=0, hmask=None, Lmax=4096,
+                        to_root=False, cells_only=False, fgrid=None):
+        """Host form of pose_paths (numpy in, numpy out)."""
+        return self._pose_paths(_HOST, d2, gp, roots, rhead, qfield, targets, thead, turn_cost, rev_cost, toward, r2, hmask, Lmax, to_root,
+                                cells_only, fgrid)
+
+    def _pose_paths(self, A, d2, gp, roots, rhead, qfield, targets, thead, turn_cost, rev_cost, toward, r2, hmask, Lmax, to_root, cells_only,
+                    fgrid, out=None):
+        d2, gp, roots, rhead, qfield, targets, thead, fgrid = (A.arr(a, A.i32) for a in (d2, gp, roots, rhead, qfield, targets, thead, fgrid))
+        hmask = A.arr(hmask, A.u8)
+        G, H, W = _ghw(d2)
+        F, Q = _count(roots), _count(targets)
+        if out is None:
+            out = A.paths_out(Q, Lmax)
+            out["head"] = A.new((Q, Lmax), A.u8)
+        _sized("gp", gp, F * POSE_HEADINGS * H * W)
+        _sized("rhead", rhead, F)
+        _sized("fgrid", fgrid, F)
+        _sized("hmask", hmask, G * H * W)
+        _sized("qfield", qfield, Q)
+        _sized("thead", thead, Q)
+        _sized("out['path']", out["path"], Q * Lmax)
+        _sized("out['head']", out["head"], Q * Lmax)
+        self._call("sc_pose_paths_batch" + A.suffix, _ptr(d2), _ptr(hmask), G, _ptr(fgrid), W, H, r2, int(turn_cost), int(rev_cost),
+                   int(bool(toward)), _ptr(gp), _ptr(roots), _ptr(rhead), F, _ptr(qfield), _ptr(targets), _ptr(thead), Q, Lmax,
+                   int(bool(to_root)), int(bool(cells_only)), _ptr(out["path"]), _ptr(out["head"]), _ptr(out["len"]), _ptr(out["cost"]),
+                   _ptr(out["status"]))
         return out
 
     # ---- occupancy from range scans (sc_scan_cast_batch, sc_logodds_update) ----

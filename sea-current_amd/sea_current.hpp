@@ -43,6 +43,8 @@
 //         log-odds occupancy map out
 //   (new) occupancy_grid::scan_match, logodds_grid::match, points_from_hits, rotate_points: a scan's pose against the map
 //   (new) occupancy_grid::scan_match_wide, logodds_grid::relocalise: the same over windows of thousands of cells, pruned
+//   (new) footprint, occupancy_grid::footprint_mask / pose_fields / pose_paths, planning_space::plan_to_pose: planning in
+//         poses (cell, heading) with a price for turning and reversing and a rectangular body
 //
 // Differences that are deliberate: obstacle::closed is initialised (the reference leaves it
 // uninitialised, :197); library code never prints or calls std::exit (SC_ASSERT throws in DEBUG);
@@ -383,6 +385,12 @@ inline std::array<int32_t, 7> sector_view(const std::array<int32_t, 3>& view, co
     return r;
 }
 
+// A rectangular body in the robot's frame, in whole cells from the reference cell: `left` is counter-clockwise of the heading.
+// Each extent 0 .. SC_FOOTPRINT_MAX.  All zero: the disc that the clearance already stands for.
+struct footprint {
+    int front = 0, back = 0, left = 0, right = 0;
+};
+
 // ---- occupancy grid (new): the world model the GPU path works on ----------------------------------
 // Row-major uint8 occupancy over a bounding_rect; cell (ix, iy) covers
 // [x_min + ix*res, x_min + (ix+1)*res) x [y_min + iy*res, ...).  d2 is the exact squared distance (in
@@ -566,6 +574,71 @@ public:
         };
         if (fr.pen.empty()) ctx.check(call(sc_field_paths_batch_host), "sc_field_paths_batch_host");
         else ctx.check(call(sc_field_paths_weighted_batch_host, fr.pen.data(), fr.pen_cap), "sc_field_paths_weighted_batch_host");
+        return r;
+    }
+    // The per-heading collision mask of a body (sc_footprint_mask_u8): bit k of mask[c] is set iff the body, at heading k
+    // (SC_POSE_HEADINGS = 8, counter-clockwise from +x) and inflated by the disc r2_clear stands for, covers no blocked cell.
+    std::vector<uint8_t> footprint_mask(const footprint& fp, int32_t r2_clear = 0, gpu_context& ctx = default_context()) {
+        if (d2.size() != occ.size()) edt(ctx);
+        std::vector<uint8_t> m(occ.size(), 0);
+        if (occ.empty()) return m;
+        ctx.check(sc_footprint_mask_u8_host(ctx.get(), d2.data(), W, H, 1, r2_clear, fp.front, fp.back, fp.left, fp.right, m.data()),
+                  "sc_footprint_mask_u8_host");
+        return m;
+    }
+    // Cost fields over poses (sc_pose_field_batch): gp[f][k][c] = the optimal cost from the pose (roots[f], rhead[f]) to (c, k)
+    // -- toward: from (c, k) to it -- with forward moves at 10 / 14, reverse moves rev_cost dearer (-1: none) and turns of 45
+    // degrees on the spot at turn_cost; SC_FIELD_INF where there is none.  rhead[f] = -1 roots the field at every heading that
+    // fits.  hmask: what footprint_mask returned, or empty for the disc.  The result remembers what pose_paths needs.
+    struct pose_field_result {
+        std::vector<int32_t> gp, status, roots, rhead;  // gp is [F][8][H][W]
+        std::vector<uint8_t> hmask;
+        int32_t r2 = 0;
+        int turn_cost = 0, rev_cost = -1;
+        bool toward = false;
+    };
+    pose_field_result pose_fields(const std::vector<int32_t>& roots, const std::vector<int32_t>& rhead, int turn_cost, int rev_cost = -1,
+                                  bool toward = false, int32_t r2_clear = 0, const std::vector<uint8_t>& hmask = {}, int rounds = -1,
+                                  gpu_context& ctx = default_context()) {
+        if (roots.size() != rhead.size()) throw std::invalid_argument("occupancy_grid::pose_fields: roots and rhead differ in size");
+        if (!hmask.empty() && hmask.size() != occ.size()) throw std::invalid_argument("occupancy_grid::pose_fields: hmask is not [H][W]");
+        if (d2.size() != occ.size()) edt(ctx);
+        pose_field_result r;
+        r.roots = roots; r.rhead = rhead; r.hmask = hmask; r.r2 = r2_clear; r.turn_cost = turn_cost; r.rev_cost = rev_cost; r.toward = toward;
+        const int F = (int)roots.size();
+        r.gp.assign((size_t)F * SC_POSE_HEADINGS * occ.size(), SC_FIELD_INF); r.status.assign(F, SC_Q_BAD_ENDPOINT);
+        if (F == 0) return r;
+        ctx.check(sc_pose_field_batch_host(ctx.get(), d2.data(), hmask.empty() ? nullptr : hmask.data(), 1, nullptr, W, H, r2_clear, turn_cost,
+                                           rev_cost, toward ? 1 : 0, roots.data(), rhead.data(), F, rounds, r.gp.data(), r.status.data()),
+                  "sc_pose_field_batch_host");
+        return r;
+    }
+    // Pose paths read from pose fields (sc_pose_paths_batch): query q follows field qfield[q] to the pose (targets[q],
+    // thead[q]) (thead -1: the cheapest heading there).  One entry per pose in path and head; to_root writes target..root, the
+    // driving order of a toward field; cells_only keeps the first pose of every cell.
+    struct pose_paths_result {
+        std::vector<int32_t> path, len, cost, status;  // path is [Q][Lmax]
+        std::vector<uint8_t> head;                     // [Q][Lmax]
+        int Lmax = 0;
+    };
+    pose_paths_result pose_paths(const pose_field_result& fr, const std::vector<int32_t>& qfield, const std::vector<int32_t>& targets,
+                                 const std::vector<int32_t>& thead, int Lmax = 0, bool to_root = false, bool cells_only = false,
+                                 gpu_context& ctx = default_context()) {
+        if (qfield.size() != targets.size() || thead.size() != targets.size())
+            throw std::invalid_argument("occupancy_grid::pose_paths: qfield, targets and thead differ in size");
+        if (d2.size() != occ.size()) edt(ctx);
+        pose_paths_result r;
+        const int Q = (int)targets.size(), F = (int)fr.roots.size();
+        r.Lmax = Lmax > 0 ? Lmax : 16 * (W + H);
+        r.path.assign((size_t)Q * r.Lmax, -1); r.head.assign((size_t)Q * r.Lmax, 0);
+        r.len.assign(Q, 0); r.cost.assign(Q, -1); r.status.assign(Q, SC_Q_NO_PATH);
+        if (Q == 0) return r;
+        if (F == 0) { r.status.assign(Q, SC_Q_BAD_ENDPOINT); return r; }
+        ctx.check(sc_pose_paths_batch_host(ctx.get(), d2.data(), fr.hmask.empty() ? nullptr : fr.hmask.data(), 1, nullptr, W, H, fr.r2,
+                                           fr.turn_cost, fr.rev_cost, fr.toward ? 1 : 0, fr.gp.data(), fr.roots.data(), fr.rhead.data(), F,
+                                           qfield.data(), targets.data(), thead.data(), Q, r.Lmax, to_root ? 1 : 0, cells_only ? 1 : 0,
+                                           r.path.data(), r.head.data(), r.len.data(), r.cost.data(), r.status.data()),
+                  "sc_pose_paths_batch_host");
         return r;
     }
     // Multi-source cost fields (sc_cost_field_multi_batch): field f starts from seeds[seed_off[f] .. seed_off[f+1]-1], each
@@ -1231,6 +1304,47 @@ public:
         auto fr = fields_of(g, g.cell_of(goal), r2, ctx);
         auto br = g.field_paths(fr, qf, s, 0, true, ctx);
         return to_points(g, br, r2, starts, std::vector<Vector2f>(starts.size(), goal), "plan_to", ctx);
+    }
+    // Many starts with headings, one goal pose, for a body that turns at a price: one toward pose field rooted at the goal pose
+    // (occupancy_grid::pose_fields over the mask of `body`).  Per start the poses in driving order, first (start cell,
+    // start_heading[q]), last (goal cell, goal_heading); nullopt where there is none (the body does not fit an endpoint, or
+    // no route).  Headings are 0 .. 7 counter-clockwise from +x (SC_POSE_HEADINGS); goal_heading -1: any heading that fits,
+    // start_heading[q] -1: the cheapest.  turn_cost >= 1 per 45 degrees, rev_cost per reverse move (-1: no reversing), both in
+    // the units of the move costs (10 per cell step).  Not smoothed: a cells_only read-out feeds the waypoint chain instead.
+    struct pose {
+        Vector2f position;   // the cell's centre
+        int32_t cell;
+        int heading;
+    };
+    std::vector<std::optional<std::vector<pose>>> plan_to_pose(const std::vector<Vector2f>& starts, const std::vector<int32_t>& start_heading,
+                                                               const Vector2f& goal, int goal_heading, int turn_cost, int rev_cost = -1,
+                                                               const footprint& body = {}, gpu_context& ctx = default_context()) {
+        if (starts.size() != start_heading.size())
+            throw std::invalid_argument("planning_space::plan_to_pose: starts and start_heading differ in size");
+        occupancy_grid g = make_grid(ctx);
+        g.edt(ctx);
+        const int32_t r2 = clearance_r2(g);
+        const bool disc = body.front == 0 && body.back == 0 && body.left == 0 && body.right == 0;
+        auto fr = g.pose_fields({g.cell_of(goal)}, {(int32_t)goal_heading}, turn_cost, rev_cost, true, r2,
+                                disc ? std::vector<uint8_t>{} : g.footprint_mask(body, r2, ctx), -1, ctx);
+        std::vector<int32_t> s(starts.size()), qf(starts.size(), 0);
+        for (size_t i = 0; i < starts.size(); ++i) s[i] = g.cell_of(starts[i]);
+        auto pr = g.pose_paths(fr, qf, s, start_heading, 0, true, false, ctx);
+        int need = 0;                                       // a truncated read-out reports the count it needs: read again with room
+        for (size_t q = 0; q < starts.size(); ++q)
+            if (pr.status[q] == SC_Q_TRUNCATED) need = std::max(need, (int)pr.len[q]);
+        if (need > 0) pr = g.pose_paths(fr, qf, s, start_heading, need, true, false, ctx);
+        std::vector<std::optional<std::vector<pose>>> out(starts.size());
+        for (size_t q = 0; q < starts.size(); ++q) {
+            if (pr.status[q] != SC_Q_OK) continue;
+            std::vector<pose> poses((size_t)pr.len[q]);
+            for (int i = 0; i < pr.len[q]; ++i) {
+                const int32_t c = pr.path[q * (size_t)pr.Lmax + i];
+                poses[(size_t)i] = pose{g.centre_of(c), c, (int)pr.head[q * (size_t)pr.Lmax + i]};
+            }
+            out[q] = std::move(poses);
+        }
+        return out;
     }
     // Many starts, many goals (a fleet where every robot goes to the cheapest of K docks): one multi-source field seeded at
     // all goal cells, goal k with the start cost goal_costs[k] (empty: all 0; in the units of the move costs, 10 per cell
