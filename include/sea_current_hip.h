@@ -1201,6 +1201,90 @@ int sc_view_gain_headings_batch_host(sc_ctx* ctx, const uint8_t* occ, const uint
 int sc_views_from_cells(sc_ctx* ctx, const int32_t* cell, int N, int W, int H, int32_t r2, int32_t* views);
 int sc_views_from_cells_host(sc_ctx* ctx, const int32_t* cell, int N, int W, int H, int32_t r2, int32_t* views);
 
+/* ---- coordinated exploration goals: greedy picks by what each view reveals -----------------------------------------
+ * sc_fleet_explore_batch matches robots to clusters on travel cost and cluster size.  These calls pick (robot, candidate)
+ * pairs greedily by utility = weighted gain of the candidate's view minus weighted travel cost, and discount every other
+ * candidate by the cells a pick has claimed (coordinated next-best-view selection, Burgard et al. / Simmons et al.), all on
+ * the stream.  The reference has no counterpart (no parity claim); the definitions are integer and unique;
+ * tests/explore_gain_twin.py states them in NumPy, tests/cpp/explore_gain_ref.c in C, and every output equals both bit for
+ * bit.  DESIGN.md section 29.  Cells are c = y*W + x.  vis, surf, Clear, In, heading tables, hist, c0 and gainh are those of
+ * the two sections above.
+ *
+ * sc_explore_gain_batch.
+ *   Inputs.  occ uint8 [H][W]: the map the prediction meets (the observed map, unknown cells reading 0).  known uint8 [H][W].
+ *     g int32 [R][H][W]: fields rooted at the robots (any field array, as for sc_frontier_cost_matrix).  cand int32 [N]:
+ *     candidate cells; a candidate is DEAD when its cell lies outside 0 .. W*H - 1 or stands on occ != 0: its gain is 0 and it
+ *     is never picked.  r2 >= 0: the sensing radius squared.  dirs (a HOST pointer, int32 [B][2]) and span: dirs == NULL is the
+ *     full circle (B and span ignored); otherwise a valid heading table and 1 <= span < B.  Weights wg, wc in 0 .. 2^20;
+ *     min_gain >= 0; rounds in 0 .. SC_ASSIGN_MAX_DIM, the cap on picks.
+ *   State.  kw = known (a working copy in context scratch, or known_out when given); all robots free, all candidates untaken.
+ *   Gain of candidate n against kw.  Full circle: gain[n] = #{c : kw[c] == 0 and vis_n[c]} for the view (cand x, cand y, r2),
+ *     its heading -1.  With a table: (gain[n], heading[n]) = best of the view against kw (the largest gainh[n][h], the smallest
+ *     h attaining it).
+ *   Round t = 0, 1, ... while t < min(rounds, R, N).  A pair (r, n) is eligible when r is free, n is alive and untaken,
+ *     g[r][cand[n]] != SC_FIELD_INF and gain[n] >= min_gain.  No eligible pair: stop.  Otherwise take the eligible pair of
+ *     largest score = wg * gain[n] - wc * g[r][cand[n]] (int64); ties go to the smallest r, then the smallest n.  Record
+ *     goal[r] = cand[n], cand_of[r] = n, gcost[r] = g[r][cand[n]], ggain[r] = gain[n], head[r] = heading[n], pick[r] = t; mark
+ *     r assigned and n taken; kw = sc_known_from_views(base = kw, occ, that one view) -- with a table sc_known_from_sectors
+ *     of the row (cx, cy, r2, u_h, u_{(h + span) mod B}) -- so both vis and surf cells become known; recompute every gain.
+ *   Outputs (int32).  goal [R], gcost [R], npick [1] (the number of picks): mandatory.  ggain, head, cand_of, pick [R];
+ *     gain0, gain_end [N] (the gains before the first round and after the last); known_out uint8 [H][W] (the final kw; 0 / 1
+ *     once a pick was made, a copy of known otherwise; must not be occ, may be known): each may be NULL.  Unpicked robots read
+ *     -1, their ggain 0.  N == 0 writes those and returns.
+ *   How it runs.  The call only enqueues a fixed sequence of min(rounds, R, N) rounds; the host reads nothing in between.
+ *     Before the rounds the gains come from sc_view_gain_batch's / sc_view_gain_headings_batch's kernels.  A round is a
+ *     two-stage reduction over the R * N pairs on the total order (score, r, n) that stores the chosen row on the device; the
+ *     ray kernel of that row (vis_new); a delta pass over (tile of the chosen box, candidate) that walks a ray from the
+ *     candidate only to cells with vis_new and kw == 0 inside its disc and subtracts the count from gain[n] (with a table from
+ *     hist[n][bin] and c0[n], after which a wavefront per candidate re-derives best); and the combination of vis_new into kw.
+ *     When no pair is eligible a done word is set and every kernel of the later rounds leaves on reading it.  No workgroup
+ *     waits for another, integer atomics only, no output depends on the order of execution.  Timed as SC_K_MOVES (its parts).
+ *   Scratch (grows only): 64 B of state + W*H B for kw when known_out is NULL + 2 W*H B for vis_new (two buffers take turns, so
+ *     that no round needs a memset) + 12 N B of views + 4 N (B + 3) B for best, hist and c0 (8 N B full circle) + 4 (R + N) B of
+ *     marks + 4 R N B of gathered costs + 4 KiB of partial results.
+ *
+ * sc_frontier_centres: a candidate that does not depend on the robot.  slot int32 [G][H][W], csize int32 [G][Cmax], csum int64
+ *   [G][Cmax][2] as sc_frontier_batch wrote them.  centre[g][k] (int32 [G][Cmax]) = the cell of listed cluster k of grid g that
+ *   minimises |csize * x - sumx| + |csize * y - sumy| (int64); ties go to the smallest cell index; rows k >= min(L, Cmax) read
+ *   -1.  Two passes (key and cell do not fit one 64-bit word): a 64-bit atomicMin of the key, then an atomicMin of the cell
+ *   among those attaining it.  Two memsets and three kernels, timed as SC_K_MOVES.  Scratch: G * Cmax * 8 B.
+ *
+ * sc_fleet_explore_gain_batch: one grid; sc_frontier_batch -> sc_frontier_centres -> sc_explore_gain_batch with cand = centre,
+ *   N = Cmax (rows beyond L are -1, hence dead).  label, slot, ncl, rep, csize, cbox, csum and centre may each be NULL: what
+ *   the chain needs of them then lives in context scratch.  goal is what sc_field_paths_batch takes as targets (a -1 target
+ *   reads SC_Q_BAD_ENDPOINT by the existing rule).  Timed as its parts.
+ *
+ * Device pointers, except dirs; the calls only enqueue on the context's stream.  The _host forms take host pointers, check the
+ * data before any launch (a g value below 0: SC_ERR_INVALID), copy, run, copy back and synchronise.
+ * Errors: SC_ERR_INVALID for NULL mandatory pointers, W or H outside 1..SC_MAX_DIM, R outside 1..SC_ASSIGN_MAX_DIM, N (Cmax)
+ *   outside 0..SC_FRONTIER_MAX_CLUSTERS (1.. for Cmax), R * N > 2^26, r2 < 0, wg or wc outside 0..2^20, min_gain < 0, rounds
+ *   outside 0..SC_ASSIGN_MAX_DIM, a dirs table that is not valid, span outside 1 .. B - 1, known_out equal to occ, G <= 0,
+ *   min_size < 1. */
+int sc_explore_gain_batch(sc_ctx* ctx, const uint8_t* occ, const uint8_t* known, const int32_t* g, int R, const int32_t* cand, int N, int W,
+                          int H, int32_t r2, const int32_t* dirs, int B, int span, int32_t wg, int32_t wc, int32_t min_gain, int rounds,
+                          int32_t* goal, int32_t* gcost, int32_t* ggain, int32_t* head, int32_t* cand_of, int32_t* pick, int32_t* npick,
+                          int32_t* gain0, int32_t* gain_end, uint8_t* known_out);
+int sc_explore_gain_batch_host(sc_ctx* ctx, const uint8_t* occ, const uint8_t* known, const int32_t* g, int R, const int32_t* cand, int N,
+                               int W, int H, int32_t r2, const int32_t* dirs, int B, int span, int32_t wg, int32_t wc, int32_t min_gain,
+                               int rounds, int32_t* goal, int32_t* gcost, int32_t* ggain, int32_t* head, int32_t* cand_of, int32_t* pick,
+                               int32_t* npick, int32_t* gain0, int32_t* gain_end, uint8_t* known_out);
+int sc_frontier_centres(sc_ctx* ctx, const int32_t* slot, const int32_t* csize, const int64_t* csum, int G, int W, int H, int Cmax,
+                        int32_t* centre);
+int sc_frontier_centres_host(sc_ctx* ctx, const int32_t* slot, const int32_t* csize, const int64_t* csum, int G, int W, int H, int Cmax,
+                             int32_t* centre);
+int sc_fleet_explore_gain_batch(sc_ctx* ctx, const int32_t* d2, const uint8_t* known, int W, int H, int32_t r2_clear, int min_size, int Cmax,
+                                const uint8_t* occ, const int32_t* g, int R, int32_t r2, const int32_t* dirs, int B, int span, int32_t wg,
+                                int32_t wc, int32_t min_gain, int rounds, int32_t* label, int32_t* slot, int32_t* ncl, int32_t* rep,
+                                int32_t* csize, int32_t* cbox, int64_t* csum, int32_t* centre, int32_t* goal, int32_t* gcost, int32_t* ggain,
+                                int32_t* head, int32_t* cand_of, int32_t* pick, int32_t* npick, int32_t* gain0, int32_t* gain_end,
+                                uint8_t* known_out);
+int sc_fleet_explore_gain_batch_host(sc_ctx* ctx, const int32_t* d2, const uint8_t* known, int W, int H, int32_t r2_clear, int min_size,
+                                     int Cmax, const uint8_t* occ, const int32_t* g, int R, int32_t r2, const int32_t* dirs, int B, int span,
+                                     int32_t wg, int32_t wc, int32_t min_gain, int rounds, int32_t* label, int32_t* slot, int32_t* ncl,
+                                     int32_t* rep, int32_t* csize, int32_t* cbox, int64_t* csum, int32_t* centre, int32_t* goal,
+                                     int32_t* gcost, int32_t* ggain, int32_t* head, int32_t* cand_of, int32_t* pick, int32_t* npick,
+                                     int32_t* gain0, int32_t* gain_end, uint8_t* known_out);
+
 /* ---- planning in poses: heading fields with turn costs and oriented footprints --------------------------------------
  * The planners above plan for a disc without a heading: a state is a cell, turning is free, a goal carries no orientation.
  * These calls plan over poses (cell, heading): a per-heading collision mask of a rectangular body, exact cost fields over

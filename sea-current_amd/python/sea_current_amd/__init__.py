@@ -1370,6 +1370,111 @@ class Context:
         self._call("sc_views_from_cells" + A.suffix, _ptr(cell), N, W, H, r2, _ptr(out))
         return out
 
+    # ---- coordinated goals by gain (sc_explore_gain_batch, sc_frontier_centres, sc_fleet_explore_gain_batch) ----
+    def explore_gain(self, occ, known, g, cand, r2, dirs=None, span=0, wg=1, wc=1, min_gain=1, rounds=None, known_out=None, want_all=True):
+        """Greedy (robot, candidate) picks by what each view reveals (sc_explore_gain_batch; the definition is in
+        include/sea_current_hip.h).  occ, known uint8 [H,W], g int32 [R,H,W] (fields rooted at the robots) and cand int32 [N]
+        (candidate cells) on the GPU; r2 the sensing radius squared; dirs int32 [B,2] on the HOST (heading_dirs(B)) with span <
+        B for a sensor with a field of view, None for the full circle.  The pair of largest wg * gain - wc * g[r][cand] is taken
+        `rounds` times at most (None: min(R, N)); every pick's view is applied to a working copy of known before the next.
+        Returns dict(goal, gcost int32 [R] (-1: no pick), npick int32 [1]); with want_all also ggain, head, cand_of, pick int32
+        [R], gain0, gain_end int32 [N] and known_out uint8 [H,W] (the predicted known map; pass `known` itself as known_out to
+        update it in place).  head[r] is a bin of dirs: the sensor covers dirs[head] .. dirs[(head + span) % B], so its axis
+        points along angle (head + span / 2) * 2 pi / B; with dirs = heading_dirs(8) and an even span that is pose_fields' heading
+        (head + span // 2) % 8 (heading k points along k * 45 degrees); for an odd span, or any other table, rounding the axis to
+        a pose heading is the caller's job.  goal is what field_paths takes as
+        targets with qfield = arange(R).  Only enqueues."""
+        return self._explore_gain(_on(occ.device), occ, known, g, cand, r2, dirs, span, wg, wc, min_gain, rounds, known_out, want_all)
+
+    def explore_gain_host(self, occ, known, g, cand, r2, dirs=None, span=0, wg=1, wc=1, min_gain=1, rounds=None, want_all=True):
+        """Host form of explore_gain (numpy in, numpy out)."""
+        return self._explore_gain(_HOST, occ, known, g, cand, r2, dirs, span, wg, wc, min_gain, rounds, None, want_all)
+
+    @staticmethod
+    def _gain_out(A, R, N, H, W, known_out, want_all):
+        """The result dict of the picks by gain: what want_all adds is None without it."""
+        e = lambda s, t=A.i32: A.new(s, t)
+        out = dict(goal=e(R), gcost=e(R), npick=e(1))
+        for k in ("ggain", "head", "cand_of", "pick"):
+            out[k] = e(R) if want_all else None
+        out.update(gain0=e(N) if want_all else None, gain_end=e(N) if want_all else None,
+                   known_out=known_out if known_out is not None else (e((H, W), A.u8) if want_all else None))
+        return out
+
+    _GAIN_KEYS = ("goal", "gcost", "ggain", "head", "cand_of", "pick", "npick", "gain0", "gain_end", "known_out")
+
+    def _explore_gain(self, A, occ, known, g, cand, r2, dirs, span, wg, wc, min_gain, rounds, known_out, want_all):
+        occ, known, g, cand = A.arr(occ, A.u8), A.arr(known, A.u8), A.arr(g, A.i32), A.arr(cand, A.i32)
+        dirs = None if dirs is None else np.ascontiguousarray(dirs, dtype=np.int32).reshape(-1, 2)    # a host table in both forms
+        H, W = occ.shape
+        R, N, B = g.shape[0], _count(cand), 0 if dirs is None else dirs.shape[0]
+        rounds = min(R, N) if rounds is None else int(rounds)
+        out = self._gain_out(A, R, N, H, W, known_out, want_all)
+        _sized("known", known, W * H)
+        _sized("g", g, R * W * H)
+        _sized("known_out", out["known_out"], W * H)
+        self._call("sc_explore_gain_batch" + A.suffix, _ptr(occ), _ptr(known), _ptr(g), R, _ptr(cand), N, W, H, int(r2), _ptr(dirs), B, int(span),
+                   int(wg), int(wc), int(min_gain), rounds, *(_ptr(out[k]) for k in self._GAIN_KEYS))
+        return {k: v for k, v in out.items() if v is not None}
+
+    def frontier_centres(self, fr, W, H, out=None):
+        """A central cell per listed frontier cluster (sc_frontier_centres): fr the dict of frontiers (its slot, csize and csum;
+        want_slot and want_stats).  Returns centre int32 [G,Cmax]: the cluster's cell nearest its centroid in the 1-norm (ties:
+        the smallest cell), -1 for the rows beyond the listed clusters.  Only enqueues."""
+        return self._frontier_centres(_on(fr["slot"].device), fr, W, H, out)
+
+    def frontier_centres_host(self, fr, W, H):
+        """Host form of frontier_centres (numpy in, numpy out)."""
+        return self._frontier_centres(_HOST, fr, W, H)
+
+    def _frontier_centres(self, A, fr, W, H, out=None):
+        slot, csize, csum = A.arr(fr["slot"], A.i32), A.arr(fr["csize"], A.i32), A.arr(fr["csum"], A.i64)
+        G, Cmax = csize.shape
+        if out is None:
+            out = A.new((G, Cmax), A.i32)
+        _sized("slot", slot, G * W * H)
+        _sized("csum", csum, 2 * G * Cmax)
+        _sized("out", out, G * Cmax)
+        self._call("sc_frontier_centres" + A.suffix, _ptr(slot), _ptr(csize), _ptr(csum), G, W, H, Cmax, _ptr(out))
+        return out
+
+    def fleet_explore_gain(self, d2, known, occ, g, r2_sense, r2=0, min_size=1, Cmax=128, dirs=None, span=0, wg=1, wc=1, min_gain=1, rounds=None,
+                           known_out=None, want_all=False):
+        """A goal per robot by what its view reveals (sc_fleet_explore_gain_batch): frontiers of (d2, known) [H,W], a central cell
+        per cluster, then explore_gain over those cells with occ the observed map, g int32 [R,H,W] the robots' fields and
+        r2_sense the sensing radius squared (r2: the clearance of the frontier cells).  Returns explore_gain's dict with every
+        output; with want_all also label, slot, ncl, rep, csize, cbox, csum (frontiers' without the leading G) and centre int32
+        [Cmax].  goal is what field_paths takes as targets with qfield = arange(R); with dirs = heading_dirs(8), (goal, head)
+        gives a goal pose for pose_fields as explore_gain's docstring says.  Only enqueues."""
+        return self._fleet_explore_gain(_on(d2.device), d2, known, occ, g, r2_sense, r2, min_size, Cmax, dirs, span, wg, wc, min_gain, rounds,
+                                        known_out, want_all)
+
+    def fleet_explore_gain_host(self, d2, known, occ, g, r2_sense, r2=0, min_size=1, Cmax=128, dirs=None, span=0, wg=1, wc=1, min_gain=1,
+                                rounds=None, want_all=False):
+        """Host form of fleet_explore_gain (numpy in, numpy out)."""
+        return self._fleet_explore_gain(_HOST, d2, known, occ, g, r2_sense, r2, min_size, Cmax, dirs, span, wg, wc, min_gain, rounds, None,
+                                        want_all)
+
+    def _fleet_explore_gain(self, A, d2, known, occ, g, r2_sense, r2, min_size, Cmax, dirs, span, wg, wc, min_gain, rounds, known_out, want_all):
+        d2, known, occ, g = A.arr(d2, A.i32), A.arr(known, A.u8), A.arr(occ, A.u8), A.arr(g, A.i32)
+        dirs = None if dirs is None else np.ascontiguousarray(dirs, dtype=np.int32).reshape(-1, 2)
+        H, W = d2.shape
+        R, B = g.shape[0], 0 if dirs is None else dirs.shape[0]
+        rounds = min(R, Cmax, ASSIGN_MAX_DIM) if rounds is None else int(rounds)
+        out = self._gain_out(A, R, Cmax, H, W, known_out, True)
+        e = lambda s, t=A.i32: A.new(s, t)
+        mid = dict(label=e((H, W)), slot=e((H, W)), ncl=e(2), rep=e(Cmax), csize=e(Cmax), cbox=e((Cmax, 4)), csum=e((Cmax, 2), A.i64),
+                   centre=e(Cmax)) if want_all else {}
+        for what, x in (("known", known), ("occ", occ), ("known_out", out["known_out"])):
+            _sized(what, x, W * H)
+        _sized("g", g, R * W * H)
+        self._call("sc_fleet_explore_gain_batch" + A.suffix, _ptr(d2), _ptr(known), W, H, r2, min_size, Cmax, _ptr(occ), _ptr(g), R, int(r2_sense),
+                   _ptr(dirs), B, int(span), int(wg), int(wc), int(min_gain), rounds,
+                   *(_ptr(mid.get(k)) for k in ("label", "slot", "ncl", "rep", "csize", "cbox", "csum", "centre")),
+                   *(_ptr(out[k]) for k in self._GAIN_KEYS))
+        out.update(mid)
+        return out
+
     # ---- planning in poses (sc_footprint_mask_u8, sc_pose_field_batch, sc_pose_paths_batch) ----
     def footprint_mask(self, d2, front, back, left, right, r2=0, out=None):
         """The per-heading collision mask of a rectangular body (sc_footprint_mask_u8): d2 int32 [H,W] or [B,H,W] on the GPU,

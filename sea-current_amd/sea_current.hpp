@@ -45,6 +45,8 @@
 //   (new) occupancy_grid::scan_match_wide, logodds_grid::relocalise: the same over windows of thousands of cells, pruned
 //   (new) footprint, occupancy_grid::footprint_mask / pose_fields / pose_paths, planning_space::plan_to_pose: planning in
 //         poses (cell, heading) with a price for turning and reversing and a rectangular body
+//   (new) occupancy_grid::frontier_centres / explore_goals_by_gain, planner::gain_weight: goals picked by what each view
+//         reveals, every pick discounting the others
 //
 // Differences that are deliberate: obstacle::closed is initialised (the reference leaves it
 // uninitialised, :197); library code never prints or calls std::exit (SC_ASSERT throws in DEBUG);
@@ -774,6 +776,64 @@ public:
                                               f.label.data(), f.slot.data(), ncl, f.rep.data(), f.csize.data(), f.cbox.data(), f.csum.data(),
                                               r.cost.data(), r.cell.data(), r.col_of.data(), nullptr, info, r.goal.data(), r.gcost.data()),
                   "sc_fleet_explore_batch_host");
+        f.listed = ncl[0]; f.total = ncl[1];
+        return r;
+    }
+    // A central cell per listed cluster (sc_frontier_centres): the cluster's cell nearest its centroid in the 1-norm (ties to
+    // the smallest cell), -1 for the rows beyond the listed clusters; [Cmax].  Unlike explore_goals' cell it does not depend on
+    // a robot, so it can stand for the cluster as a candidate pose.
+    std::vector<int32_t> frontier_centres(const frontier_result& fr, gpu_context& ctx = default_context()) const {
+        if (fr.slot.size() != occ.size() || fr.csize.size() != (size_t)std::max(fr.Cmax, 0) || fr.csum.size() != 2 * fr.csize.size())
+            throw std::invalid_argument("occupancy_grid::frontier_centres: fr is not this grid's frontier_result");
+        std::vector<int32_t> centre(fr.csize.size(), -1);
+        if (occ.empty() || centre.empty()) return centre;
+        ctx.check(sc_frontier_centres_host(ctx.get(), fr.slot.data(), fr.csize.data(), fr.csum.data(), 1, W, H, fr.Cmax, centre.data()),
+                  "sc_frontier_centres_host");
+        return centre;
+    }
+    // Goals by what each view reveals (sc_d2_known_i32, sc_cost_field_batch, sc_fleet_explore_gain_batch): this grid's occ is
+    // the observed map (unknown cells 0).  The candidates are the clusters' centres; the pair (robot, centre) of largest
+    // wg * gain - wc * travel cost is picked, its view (r2_sense: the sensing radius squared in cells; with dirs and span < B the
+    // sector of the heading of largest gain) is applied to a copy of known, every other centre's gain falls by what it
+    // revealed, and so on, one pick per robot at most.  goal[r] the cell to drive to (-1: none), head[r] the bin of dirs the
+    // sensor should start at there (-1 for the full circle), ggain[r] the free cells the pick was predicted to reveal,
+    // known_out the predicted known map, g [R][H][W] the robots' fields the travel costs came from.
+    // 1 <= robots <= SC_ASSIGN_MAX_DIM, 1 <= Cmax <= SC_FRONTIER_MAX_CLUSTERS.
+    struct gain_result {
+        std::vector<int32_t> goal, gcost, ggain, head, cand_of, pick, centre, gain0, gain_end, g;
+        int32_t npick = 0;
+        std::vector<uint8_t> known_out;
+        frontier_result fr;
+    };
+    gain_result explore_goals_by_gain(const std::vector<uint8_t>& known, const std::vector<int32_t>& robots, int32_t r2_sense,
+                                      const heading_table& dirs = {}, int span = 0, int32_t wg = 1, int32_t wc = 1, int32_t min_gain = 1,
+                                      int32_t r2_clear = 0, int min_size = 1, int Cmax = 128, gpu_context& ctx = default_context()) {
+        if (known.size() != occ.size()) throw std::invalid_argument("occupancy_grid::explore_goals_by_gain: known is not [H][W]");
+        if (d2.size() != occ.size()) edt(ctx);
+        const int R = (int)robots.size();
+        gain_result r;
+        frontier_result& f = r.fr;
+        f.Cmax = Cmax;
+        const size_t C = (size_t)std::max(Cmax, 0);
+        f.label.assign(occ.size(), -1); f.slot.assign(occ.size(), -1);
+        f.rep.assign(C, -1); f.csize.assign(C, 0); f.cbox.assign(4 * C, 0); f.csum.assign(2 * C, 0);
+        r.centre.assign(C, -1); r.gain0.assign(C, 0); r.gain_end.assign(C, 0);
+        r.goal.assign(R, -1); r.gcost.assign(R, -1); r.ggain.assign(R, 0); r.head.assign(R, -1); r.cand_of.assign(R, -1); r.pick.assign(R, -1);
+        r.known_out = known;
+        if (R == 0 || occ.empty()) return r;
+        std::vector<int32_t> d2k(occ.size()), fstatus(R);
+        r.g.assign((size_t)R * occ.size(), SC_FIELD_INF);
+        ctx.check(sc_d2_known_i32_host(ctx.get(), d2.data(), known.data(), 1, W, H, d2k.data()), "sc_d2_known_i32_host");
+        ctx.check(sc_cost_field_batch_host(ctx.get(), d2k.data(), 1, nullptr, W, H, r2_clear, robots.data(), R, -1, r.g.data(), fstatus.data()),
+                  "sc_cost_field_batch_host");
+        int32_t ncl[2] = {0, 0};
+        ctx.check(sc_fleet_explore_gain_batch_host(ctx.get(), d2k.data(), known.data(), W, H, r2_clear, min_size, Cmax, occ.data(), r.g.data(), R,
+                                                   r2_sense, dirs.empty() ? nullptr : dirs[0].data(), (int)dirs.size(), span, wg, wc, min_gain,
+                                                   std::min(R, SC_ASSIGN_MAX_DIM), f.label.data(), f.slot.data(), ncl, f.rep.data(),
+                                                   f.csize.data(), f.cbox.data(), f.csum.data(), r.centre.data(), r.goal.data(), r.gcost.data(),
+                                                   r.ggain.data(), r.head.data(), r.cand_of.data(), r.pick.data(), &r.npick, r.gain0.data(),
+                                                   r.gain_end.data(), r.known_out.data()),
+                  "sc_fleet_explore_gain_batch_host");
         f.listed = ncl[0]; f.total = ncl[1];
         return r;
     }
@@ -1513,6 +1573,12 @@ private:
 //   the goal, or to -1); if that look adds no known cell it senses the full circle once, a turn on the
 //   spot, so a look from a frontier cell always adds one.  After the goal is picked, goal_heading is view_gain_headings' best
 //   heading at the goal on the observed map (-1 when the goal came from the cache).
+// gain_weight (0: off; every path above runs unchanged and nothing new is allocated).  With gain_weight > 0 the goal is
+//   occupancy_grid::explore_goals_by_gain's on the observed map with wg = gain_weight, wc = 1, min_gain = 1 and the sensing
+//   radius of line_of_sight, which must be set, else std::logic_error: the cluster centre of largest gain_weight * (the
+//   unknown cells a look from there is predicted to reveal) - path cost, not the nearest cluster cell.  With fov_span > 0
+//   (< headings here) the gain is that of the best heading and goal_heading is that heading.  The other clusters are not
+//   pushed onto goal_point_cache; without an eligible centre the cache's top is returned as above.
 class planner {
 public:
     planning_space ps;
@@ -1524,6 +1590,7 @@ public:
     logodds_grid map;
     logodds_params scan_params;
     int fov_span = 0;
+    int gain_weight = 0;
     int headings = 16;
     int heading = -1;
     int goal_heading = -1;
@@ -1533,6 +1600,7 @@ public:
     Vector2f pick_next_goal_point(const Vector2f& start, const int n, const float search_radius, gpu_context& ctx = default_context()) {
         if (line_of_sight && range_scan) throw std::logic_error("planner::pick_next_goal_point: line_of_sight and range_scan are both set");
         if (fov_span > 0 && !line_of_sight) throw std::logic_error("planner::pick_next_goal_point: fov_span needs line_of_sight");
+        if (gain_weight > 0 && !line_of_sight) throw std::logic_error("planner::pick_next_goal_point: gain_weight needs line_of_sight");
         if (!line_of_sight && !range_scan)
             ps.free_space_allocations.push_back([start, search_radius](Vector2f p) { return pt_dist(p, start) <= search_radius; });
         occupancy_grid g = ps.make_grid(ctx);
@@ -1558,6 +1626,18 @@ public:
             if (!known[c]) g.occ[c] = 0;                       // an obstacle the robot has not seen is not on its map
         g.edt(ctx);
         const int Cmax = std::clamp(n, 1, SC_ASSIGN_MAX_DIM);
+        if (gain_weight > 0) {
+            const float rc = search_radius / g.resolution;
+            const auto by_gain = g.explore_goals_by_gain(known, {g.cell_of(start)}, (int32_t)(rc * rc),
+                                                         fov_span > 0 ? heading_dirs(headings) : heading_table{}, fov_span, gain_weight, 1, 1,
+                                                         ps.clearance_r2(g), 1, Cmax, ctx);
+            goal_heading = by_gain.head[0];                    // -1 for the full circle and when nothing was picked
+            if (by_gain.goal[0] >= 0) return g.centre_of(by_gain.goal[0]);
+            if (goal_point_cache.empty()) throw std::runtime_error("planner::pick_next_goal_point: no reachable frontier and no cached goal");
+            const Vector2f cached = goal_point_cache.top();
+            goal_point_cache.pop();
+            return cached;
+        }
         const auto ex = g.explore_goals(known, {g.cell_of(start)}, ps.clearance_r2(g), 1, Cmax, 0, 0, ctx);
         if (ex.goal[0] >= 0) {
             std::vector<std::pair<int32_t, int32_t>> rest;     // (cost, cell) of the clusters not chosen
