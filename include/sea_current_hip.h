@@ -91,7 +91,13 @@ const char* sc_last_error(const sc_ctx* ctx);
 int sc_ctx_create(int device, sc_ctx** out);
 int sc_ctx_destroy(sc_ctx* ctx);
 /* Use the caller's hipStream_t (e.g. torch's current stream) instead of the
- * context's own; NULL means HIP's null (legacy default) stream. */
+ * context's own; NULL means HIP's null (legacy default) stream.
+ * Switching streams: the context's scratch and what one call leaves enqueued for
+ * the next (zeroed flag maps, stamps and lists of the field calls, the A* slots,
+ * the status block) are ordered on the OLD stream only.  Before the first call
+ * after a switch the caller synchronises (sc_ctx_synchronize, or on the old
+ * stream), or makes the new stream wait on an event recorded on the old one; the
+ * same holds for sc_ctx_use_own_stream.  The switch itself waits for nothing. */
 int sc_ctx_set_stream(sc_ctx* ctx, void* hip_stream);
 /* Go back to the context's own non-blocking stream (the default after create). */
 int sc_ctx_use_own_stream(sc_ctx* ctx);
