@@ -39,9 +39,14 @@
 //   an ancestor of it or its final owner, so the result does not depend on the order.  A launch counts the cells it left
 //   unresolved for the next one, which returns at once when that count is 0.
 //   Read-out: field_paths_kernel with the end cell seed[owner[target]] in place of the root.
+//
+// Repair after a map change (sc_cost_field_update_batch and the weighted form): the field of the old
+// map becomes that of the new one, bit-equal to a build: a raise pass over the cells that lost their support, then the
+// relaxation above seeded at the damage.  Its kernels stand together further down, before the host side.
 #include <type_traits>
 
 #include "tile_label.h"   // the wave shuffles
+#include "../../include/sea_current_hip_update.h"
 
 namespace {
 
@@ -657,11 +662,330 @@ __global__ __launch_bounds__(64 * RP_WAVES) void field_paths_kernel(std::conditi
 
 int field_default_rounds(int TX, int TY) { return 2 * (TX + TY) + 16; }
 
+// ---- repair after a map change (sc_cost_field_update_batch) -----------------------------------
+// g holds the field of the old map.  Phases, all on the stream, none reads on the host:
+//   masks of both maps; update_diff_kernel: changed cells per grid (count and the tiles whose 66 x 66 window holds one);
+//   update_prep_kernel: which fields are alive (grid and root in range, T'(root)), g[root] = 0, fstatus, stats;
+//   update_dead_kernel: a field that is not alive becomes all INF (its finite cells are its U);
+//   update_queue_kernel: every (alive field, flagged tile) is queued for the raise and marked for the relaxation;
+//   raise: raise_tile visits under the stamp / two-list / rounds / finisher scheme of the relaxation, with lists of its own;
+//   update_seed_kernel: the marked tiles become list 0 of the relaxation, which then runs as in a build.
+// raise_tile: one wavefront, the tile and its one-cell halo in a 66 x 66 LDS window of g with bit 31 set where the cell is
+// not traversable in the new map (so `w < FINF` reads "finite and traversable").  A finite cell with no tight legal
+// finite predecessor becomes INF.  Sweeps in four directions in turn -- rows downwards and upwards (lane = column), columns
+// rightwards and leftwards (lane = row) -- each testing every cell once, so an invalidation that runs through the tile
+// in any direction is carried across it by one sweep; the visit ends with the first sweep that raises nothing (every
+// cell was then tested against the final state).  In place this is sound: a cell is raised only when every tight
+// predecessor already is, and a value it reads from a neighbour tile is the old one or INF.  Values only rise: it
+// terminates.  Rows of the window are RS = 67 words apart: a row and a column of it each fall into 64 different banks.
+constexpr int RW = FT + 2;                 // window edge
+constexpr int RS = RW + 1;                 // words between its rows
+constexpr uint32_t RBLK = 0x80000000u;     // window word: not traversable in the new map, or off the grid
+constexpr int RAISE_FIN_WAVES = 4;         // wavefronts of the raise finisher: 4 windows of 17 KiB (+ 4 KiB penalties) beside its tile lists
+
+struct update_args {
+    const uint64_t* mask_old;  // [G][TY][W] of the old map (a.mask: the new one)
+    const uint8_t* pen_old;    // weighted: [G][H][W] (a.pen: the new one)
+    const int32_t* root;       // [F]
+    int32_t* stats;            // [F][2] or NULL
+    int32_t* gflag;            // [G][nt] != 0: the tile's window holds a changed cell
+    int32_t* gcount;           // [G] changed cells
+    int32_t* rstamp;           // [F][nt] raise round + 1 a tile is queued for
+    int32_t* rlist[2];         // [F * nt] each
+    int32_t* rctr;             // [raise rounds + 1]
+};
+
+// one lane per (grid, tile row, column) word
+template <bool WEIGHTED>
+__global__ void update_diff_kernel(field_args_w a, update_args u) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)a.G * a.TY * a.W) return;
+    const int W = a.W, H = a.H;
+    const int x = (int)(i % W);
+    const size_t gt = i / W;
+    const int ty = (int)(gt % a.TY), gi = (int)(gt / a.TY);
+    const uint64_t m0 = u.mask_old[i], m1 = a.mask[i];
+    uint64_t chg = m0 ^ m1;
+    if constexpr (WEIGHTED) {
+        if (u.pen_old != a.pen) {
+            const uint8_t* P0 = u.pen_old + (size_t)gi * W * H;
+            const uint8_t* P1 = a.pen + (size_t)gi * W * H;
+            const int y0 = ty * FT, th = min(FT, H - y0);
+            const uint64_t both = m0 & m1;
+            for (int y = 0; y < th; ++y) {
+                const size_t c = (size_t)(y0 + y) * W + x;
+                if (((both >> y) & 1ull) && min((uint32_t)P0[c], a.cap) != min((uint32_t)P1[c], a.cap)) chg |= 1ull << y;
+            }
+        }
+    }
+    if (chg == 0ull) return;
+    atomicAdd(u.gcount + gi, __popcll(chg));
+    const int th = min(FT, H - ty * FT);
+    const int txa = max(x - 1, 0) / FT, txb = min(x + 1, W - 1) / FT;
+    const int tya = (ty > 0 && (chg & 1ull)) ? ty - 1 : ty, tyb = (ty + 1 < a.TY && ((chg >> (th - 1)) & 1ull)) ? ty + 1 : ty;
+    for (int vy = tya; vy <= tyb; ++vy)
+        for (int vx = txa; vx <= txb; ++vx) u.gflag[(size_t)gi * a.nt + vy * a.TX + vx] = 1;
+}
+
+// one thread per field
+__global__ void update_prep_kernel(field_args a, update_args u, int32_t* fstatus) {
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= a.F) return;
+    const long long n = (long long)a.W * a.H;
+    const int gi = a.fgrid ? a.fgrid[f] : 0;
+    const bool gok = gi >= 0 && gi < a.G;
+    const int r = u.root[f];
+    const bool alive = gok && r >= 0 && r < n && a.d2[(size_t)gi * n + r] >= a.thr;
+    a.ok[f] = alive;
+    if (fstatus) fstatus[f] = alive ? SC_Q_OK : SC_Q_BAD_ENDPOINT;
+    if (alive) a.g[(size_t)f * n + r] = 0;
+    if (u.stats) {
+        u.stats[2 * f] = gok ? u.gcount[gi] : 0;
+        u.stats[2 * f + 1] = 0;
+    }
+}
+
+// a field that is not alive: all INF; on a grid in range its finite cells are its U.  Grid (blocks, fields), fields strided.
+__global__ void update_dead_kernel(field_args a, update_args u) {
+    const size_t n = (size_t)a.W * a.H;
+    for (int f = blockIdx.y; f < a.F; f += gridDim.y) {
+        if (a.ok[f]) continue;
+        const int gi = a.fgrid ? a.fgrid[f] : 0;
+        const bool count = u.stats && gi >= 0 && gi < a.G;
+        int32_t* G = a.g + (size_t)f * n;
+        int c = 0;
+        for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+            c += (uint32_t)G[i] < FINF;
+            G[i] = (int32_t)FINF;
+        }
+        if (count && c) atomicAdd(u.stats + 2 * f + 1, c);
+    }
+}
+
+// one thread per (field, tile)
+__global__ void update_queue_kernel(field_args a, update_args u) {
+    const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= (size_t)a.F * a.nt) return;
+    const int f = (int)(e / a.nt), t = (int)(e % a.nt);
+    if (!a.ok[f]) return;
+    const int gi = a.fgrid ? a.fgrid[f] : 0;
+    if (!u.gflag[(size_t)gi * a.nt + t]) return;
+    a.seeded[e] = 1;
+    u.rstamp[e] = 1;
+    u.rlist[0][atomicAdd(u.rctr, 1)] = (int32_t)e;
+}
+
+// after the raise: every marked tile of an alive field is list 0 of the relaxation
+__global__ void update_seed_kernel(field_args a) {
+    const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= (size_t)a.F * a.nt) return;
+    if (!a.ok[e / a.nt] || !a.seeded[e]) return;
+    a.stamp[e] = 1;
+    a.list[0][atomicAdd(a.ctr, 1)] = (int32_t)e;
+}
+
+// Raise visit of tile (tx, ty) of alive field f with one wavefront; win [RW * RS], pw [FT * FT] (WEIGHTED) are the
+// wavefront's own LDS.  mark(tx', ty') is called, by every lane, for the tile itself when it raised a cell and for every
+// neighbour whose halo holds a raised cell.
+template <bool WEIGHTED, class Mark>
+__device__ __forceinline__ void raise_tile(const field_args_w& a, const update_args& u, uint32_t* win, uint8_t* pw, int f, int tx, int ty,
+                                           Mark mark) {
+    const int lane = threadIdx.x & 63;
+    const int W = a.W, H = a.H;
+    const size_t n = (size_t)W * H;
+    const int gi = a.fgrid ? a.fgrid[f] : 0;
+    const int32_t* D = a.d2 + (size_t)gi * n;
+    int32_t* G = a.g + (size_t)f * n;
+    const int x0 = tx * FT, y0 = ty * FT;
+    const int tw = min(FT, W - x0), th = min(FT, H - y0);
+    const int r = u.root[f];
+    const int rlx = r % W - x0, rly = r / W - y0;
+    // row by row: lane l loads window column l, lanes 0 and 1 also columns 64 and 65
+    for (int ry = 0; ry < RW; ++ry) {
+        const int wy = y0 - 1 + ry;
+        for (int rx = lane; rx < RW; rx += 64) {
+            const int wx = x0 - 1 + rx;
+            uint32_t w = FINF | RBLK;
+            if (wx >= 0 && wx < W && wy >= 0 && wy < H) {
+                const size_t c = (size_t)wy * W + wx;
+                w = min((uint32_t)G[c], FINF);
+                if (D[c] < a.thr) w |= RBLK;
+            }
+            win[ry * RS + rx] = w;
+        }
+    }
+    if constexpr (WEIGHTED) {
+        const uint8_t* Pn = a.pen + (size_t)gi * n;
+        for (int i = lane; i < FT * FT; i += 64) {
+            const int lx = i % FT, ly = i / FT;
+            pw[i] = (lx < tw && ly < th) ? (uint8_t)min((uint32_t)Pn[(size_t)(y0 + ly) * W + x0 + lx], a.cap) : (uint8_t)0;
+        }
+    }
+    wave_lds_sync();
+    const bool colin = lane < tw;
+    bool some = false;   // a cell of the tile has been raised (uniform)
+    // the cells that lost traversability
+    for (int y = 0; y < th; ++y) {
+        const int idx = (y + 1) * RS + lane + 1;
+        const uint32_t w = win[idx];
+        const bool rz = colin && (w & RBLK) && (w & ~RBLK) < FINF;
+        if (rz) win[idx] = FINF | RBLK;
+        some |= __ballot(rz) != 0ull;
+    }
+    wave_lds_sync();
+    for (int dir = 0;; dir = (dir + 1) & 3) {
+        // dir 0, 1: row s of the tile, downwards / upwards, lane = column; dir 2, 3: column s, rightwards / leftwards, lane = row
+        const bool rows = dir < 2;
+        const int steps = rows ? th : tw;
+        const bool in = lane < (rows ? tw : th);
+        bool any = false;
+        for (int k = 0; k < steps; ++k) {
+            const int s = (dir & 1) ? steps - 1 - k : k;
+            const int lx = rows ? lane : s, ly = rows ? s : lane;
+            const int idx = (ly + 1) * RS + lx + 1;
+            const uint32_t* c = win + idx;
+            const uint32_t w = c[0];
+            bool rz = false;
+            if (in && w < FINF && !(lx == rlx && ly == rly)) {
+                uint32_t p = 0;
+                if constexpr (WEIGHTED) p = pw[ly * FT + lx];
+                const uint32_t t10 = w - 10u - p, t14 = w - 14u - p;   // what a tight predecessor holds (used only where they do not wrap)
+                const uint32_t wl = c[-1], wr = c[1], wu = c[-RS], wd = c[RS];
+                const bool fl = !(wl & RBLK), fr = !(wr & RBLK), fu = !(wu & RBLK), fd = !(wd & RBLK);
+                bool sup = (w >= 10u + p) && (wl == t10 || wr == t10 || wu == t10 || wd == t10);
+                if (w >= 14u + p) {
+                    sup |= fl && fu && c[-RS - 1] == t14;
+                    sup |= fr && fu && c[-RS + 1] == t14;
+                    sup |= fl && fd && c[RS - 1] == t14;
+                    sup |= fr && fd && c[RS + 1] == t14;
+                }
+                rz = !sup;
+            }
+            wave_lds_sync();   // every lane has read before any writes
+            if (rz) win[idx] = FINF;
+            wave_lds_sync();
+            any |= __ballot(rz) != 0ull;
+        }
+        if (!any) break;
+        some = true;
+    }
+    if (!some) return;
+    // the raised cells of this lane's column: finite in g, INF in the window
+    uint64_t raised = 0;
+    for (int y = 0; y < th; ++y) {
+        const size_t c = (size_t)(y0 + y) * W + x0 + lane;
+        if (colin && (uint32_t)G[c] < FINF && (win[(y + 1) * RS + lane + 1] & ~RBLK) >= FINF) {
+            raised |= 1ull << y;
+            G[c] = (int32_t)FINF;
+        }
+    }
+    if (u.stats) {
+        int cnt = __popcll(raised);
+        for (int s = 32; s >= 1; s >>= 1) cnt += __shfl_xor(cnt, s, 64);
+        if (lane == 0) atomicAdd(u.stats + 2 * f + 1, cnt);
+    }
+    mark(tx, ty);
+    const bool top = __ballot(raised & 1ull) != 0ull, bot = __ballot((raised >> (th - 1)) & 1ull) != 0ull;
+    const uint64_t cl = __builtin_amdgcn_readlane((int)(uint32_t)raised, 0) | ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(raised >> 32), 0) << 32);
+    const uint64_t cr = __builtin_amdgcn_readlane((int)(uint32_t)raised, tw - 1) |
+                        ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(raised >> 32), tw - 1) << 32);
+    const bool hasL = tx > 0, hasR = tx + 1 < a.TX, hasU = ty > 0, hasD = ty + 1 < a.TY;
+    if (hasU && top) mark(tx, ty - 1);
+    if (hasD && bot) mark(tx, ty + 1);
+    if (hasL && cl) mark(tx - 1, ty);
+    if (hasR && cr) mark(tx + 1, ty);
+    if (hasU && hasL && (cl & 1ull)) mark(tx - 1, ty - 1);
+    if (hasU && hasR && (cr & 1ull)) mark(tx + 1, ty - 1);
+    if (hasD && hasL && ((cl >> (th - 1)) & 1ull)) mark(tx - 1, ty + 1);
+    if (hasD && hasR && ((cr >> (th - 1)) & 1ull)) mark(tx + 1, ty + 1);
+}
+
+// chip-wide raise round r: one wavefront per queued (field, tile)
+template <bool WEIGHTED>
+__global__ __launch_bounds__(64) void raise_round_kernel(field_args_w a, update_args u, int r) {
+    __shared__ uint32_t win[RW * RS];
+    __shared__ uint8_t pw[WEIGHTED ? FT * FT : 1];
+    const int n = u.rctr[r];
+    const int32_t* cur = u.rlist[r & 1];
+    int32_t* nxt = u.rlist[(r + 1) & 1];
+    int32_t* nctr = u.rctr + r + 1;
+    const int lane = threadIdx.x;
+    for (int i = blockIdx.x; i < n; i += gridDim.x) {
+        const int e = cur[i];
+        const int f = e / a.nt, t = e % a.nt, tx = t % a.TX, ty = t / a.TX;
+        raise_tile<WEIGHTED>(a, u, win, pw, f, tx, ty, [&](int ux, int uy) {
+            if (lane == 0) {
+                const int v = f * a.nt + uy * a.TX + ux;
+                a.seeded[v] = 1;
+                if ((ux != tx || uy != ty) && atomicMax(u.rstamp + v, r + 2) < r + 2) nxt[atomicAdd(nctr, 1)] = v;
+            }
+        });
+        wave_lds_sync();
+    }
+}
+
+// raise finisher: one workgroup per field completes the tiles still queued after `rounds` chip-wide raise rounds
+template <bool WEIGHTED>
+__global__ __launch_bounds__(64 * RAISE_FIN_WAVES) void raise_finish_kernel(field_args_w a, update_args u, int rounds) {
+    __shared__ uint32_t win_all[RAISE_FIN_WAVES][RW * RS];
+    __shared__ uint8_t pw_all[WEIGHTED ? RAISE_FIN_WAVES : 1][WEIGHTED ? FT * FT : 1];
+    __shared__ uint32_t dirty[FIN_MAX_TILES / 32];
+    __shared__ uint16_t work[FIN_MAX_TILES];
+    __shared__ int count;
+    const int f = blockIdx.x;
+    if (!a.ok[f]) return;
+    const int nt = a.nt, nw = (nt + 31) / 32;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    for (int w = tid; w < nw; w += blockDim.x) {
+        uint32_t b = 0;
+        for (int k = 0; k < 32 && w * 32 + k < nt; ++k) b |= (uint32_t)(u.rstamp[(size_t)f * nt + w * 32 + k] == rounds + 1) << k;
+        dirty[w] = b;
+    }
+    __syncthreads();
+    for (;;) {
+        if (tid == 0) count = 0;
+        __syncthreads();
+        for (int w = tid; w < nw; w += blockDim.x) {
+            uint32_t b = dirty[w];
+            if (b) {
+                dirty[w] = 0;
+                int p = atomicAdd(&count, __popc(b));
+                while (b) {
+                    const int k = __ffs(b) - 1;
+                    b &= b - 1;
+                    work[p++] = (uint16_t)(w * 32 + k);
+                }
+            }
+        }
+        __syncthreads();
+        const int n = count;
+        if (n == 0) break;
+        for (int i = __builtin_amdgcn_readfirstlane(wave); i < n; i += RAISE_FIN_WAVES) {
+            const int t = __builtin_amdgcn_readfirstlane((int)work[i]);
+            const int tx = t % a.TX, ty = t / a.TX;
+            raise_tile<WEIGHTED>(a, u, win_all[wave], pw_all[WEIGHTED ? wave : 0], f, tx, ty, [&](int ux, int uy) {
+                if (lane == 0) {
+                    const int v = uy * a.TX + ux;
+                    a.seeded[(size_t)f * nt + v] = 1;
+                    if (ux != tx || uy != ty) atomicOr(&dirty[v >> 5], 1u << (v & 31));
+                }
+            });
+            wave_lds_sync();
+        }
+        __syncthreads();
+    }
+}
+
+int raise_default_rounds(int TX, int TY) { return TX + TY + 8; }
+constexpr int UPDATE_MAX_ROUNDS = 1 << 16;   // chip-wide launches per phase a repair enqueues at most
+
 }  // namespace
 
 // ---- host side -----------------------------------------------------------------------------------------------------
 // The twelve entries (three contracts x build / read-out x device / _host form) pack their arguments and call one of four
 // functions: field_build, field_read and their _host stagers.  field_args_ok is the argument contract of all of them.
+// The four repair entries (include/sea_current_hip_update.h) go through field_update and its _host stager in the same
+// way; field_relax is the round loop a build and a repair share.
 enum field_contract { FC_ROOTS, FC_ROOTS_WEIGHTED, FC_MULTI };
 
 // the map side of a call; pen NULL: unweighted (the FC_ROOTS entries pass none)
@@ -716,6 +1040,21 @@ static int owner_jumps(int W, int H) {
     return k;
 }
 
+// the relaxation of a build or a repair: `rounds` chip-wide launches over the queued tiles (list 0 is filled), then the
+// finisher; a.pen NULL: the unweighted kernels
+static void field_relax(sc_ctx* ctx, const field_args_w& a, int rounds) {
+    if (rounds > 0) {
+        const long long cap = (long long)ctx->cu_count * 8;
+        const unsigned blocks = (unsigned)((long long)a.F * a.nt < cap ? (long long)a.F * a.nt : cap);
+        for (int k = 0; k < rounds; ++k) {
+            if (a.pen) hipLaunchKernelGGL(field_round_kernel<true>, dim3(blocks), dim3(64), 0, ctx->stream, a, k);
+            else hipLaunchKernelGGL(field_round_kernel<false>, dim3(blocks), dim3(64), 0, ctx->stream, (field_args)a, k);
+        }
+    }
+    if (a.pen) hipLaunchKernelGGL((field_finish_kernel<true, FIN_WAVES_W>), dim3(a.F), dim3(64 * FIN_WAVES_W), 0, ctx->stream, a, rounds);
+    else hipLaunchKernelGGL((field_finish_kernel<false, FIN_WAVES>), dim3(a.F), dim3(64 * FIN_WAVES), 0, ctx->stream, (field_args)a, rounds);
+}
+
 // every build; m.pen NULL: the unweighted kernels.  owner != NULL: the owner pass follows.
 static int field_build(sc_ctx* ctx, field_contract c, const field_map& m, const seed_args& sa, int rounds, int32_t* g, int32_t* owner,
                        int32_t* fstatus) {
@@ -758,16 +1097,7 @@ static int field_build(sc_ctx* ctx, field_contract c, const field_map& m, const 
         hipLaunchKernelGGL(field_fill_kernel, dim3(bx, F < 65535 ? F : 65535), dim3(1024), 0, ctx->stream, (field_args)a, fstatus);
         hipLaunchKernelGGL(field_seed_kernel, dim3(F < 65535 ? F : 65535), dim3(64), 0, ctx->stream, (field_args)a, sa, fstatus);
     }
-    if (rounds > 0) {
-        const long long cap = (long long)ctx->cu_count * 8;
-        const unsigned blocks = (unsigned)((long long)F * nt < cap ? (long long)F * nt : cap);
-        for (int k = 0; k < rounds; ++k) {
-            if (m.pen) hipLaunchKernelGGL(field_round_kernel<true>, dim3(blocks), dim3(64), 0, ctx->stream, a, k);
-            else hipLaunchKernelGGL(field_round_kernel<false>, dim3(blocks), dim3(64), 0, ctx->stream, (field_args)a, k);
-        }
-    }
-    if (m.pen) hipLaunchKernelGGL((field_finish_kernel<true, FIN_WAVES_W>), dim3(F), dim3(64 * FIN_WAVES_W), 0, ctx->stream, a, rounds);
-    else hipLaunchKernelGGL((field_finish_kernel<false, FIN_WAVES>), dim3(F), dim3(64 * FIN_WAVES), 0, ctx->stream, (field_args)a, rounds);
+    field_relax(ctx, a, rounds);
     if (owner) {
         const size_t cells = (size_t)F * W * H;
         owner_args oa{m.d2, m.pen, m.fgrid, g, owner, (int32_t*)(b + o_left), G, W, H, F, a.thr, (uint32_t)m.pen_cap};
@@ -827,6 +1157,94 @@ static int field_build_host(sc_ctx* ctx, field_contract c, const field_map& m, c
         r = field_build(ctx, c, {staged(st, i_d2, m.d2), staged(st, i_pen, m.pen), m.pen_cap, m.G, staged(st, i_fg, m.fgrid), m.W, m.H, m.r2_clear, m.F},
                         {staged(st, i_sd, sa.seed), staged(st, i_sc, sa.cost), staged(st, i_so, sa.off), sa.n_seed}, rounds, staged(st, o_g, g),
                         staged(st, o_ow, owner), staged(st, o_st, fstatus));
+    return st.finish(r);
+}
+
+// the repair of single-root fields after a map change: m is the new map, d2_old / pen_old the old one (pen_old with m.pen)
+static int field_update(sc_ctx* ctx, field_contract c, const int32_t* d2_old, const uint8_t* pen_old, const field_map& m,
+                        const int32_t* root, int rounds, int32_t* g, int32_t* fstatus, int32_t* stats) {
+    if (!field_args_ok(ctx, c, m, {root, nullptr, nullptr, m.F}, g, nullptr, nullptr) || !d2_old || (m.pen && !pen_old)) return SC_ERR_INVALID;
+    SC_HIP(ctx, hipSetDevice(ctx->device));
+    const int G = m.G, W = m.W, H = m.H, F = m.F;
+    const int TX = (W + FT - 1) / FT, TY = (H + FT - 1) / FT, nt = TX * TY;
+    if ((long long)F * nt > 0x7FFFFFFF / 2 || (long long)G * nt > 0x7FFFFFFF / 2) return SC_ERR_INVALID;
+    if (rounds > UPDATE_MAX_ROUNDS) rounds = UPDATE_MAX_ROUNDS;   // the result does not depend on it; the counters are sized by it
+    const int rrounds = rounds < 0 ? raise_default_rounds(TX, TY) : rounds;
+    if (rounds < 0) rounds = field_default_rounds(TX, TY);
+    const size_t mask_b = (size_t)G * TY * W * 8, ft = al256((size_t)F * nt * 4);
+    // stamp | seeded and rstamp .. gcount lie next to each other: one memset clears each run
+    const size_t o_ok = 0, o_stamp = al256((size_t)F * 4), o_seeded = o_stamp + ft, o_l0 = o_seeded + ft, o_l1 = o_l0 + ft, o_ctr = o_l1 + ft,
+                 o_rstamp = o_ctr + al256((size_t)(rounds + 1) * 4), o_rctr = o_rstamp + ft, o_gflag = o_rctr + al256((size_t)(rrounds + 1) * 4),
+                 o_gcount = o_gflag + al256((size_t)G * nt * 4), o_rl0 = o_gcount + al256((size_t)G * 4), o_rl1 = o_rl0 + ft, total = o_rl1 + ft;
+    int r = sc_scratch_reserve(ctx, &ctx->fld_mask, mask_b);
+    if (r == SC_OK) r = sc_scratch_reserve(ctx, &ctx->fld_mask_old, mask_b);
+    if (r == SC_OK) r = sc_scratch_reserve(ctx, &ctx->fld_state, total);
+    if (r == SC_OK) r = field_cu_count(ctx);
+    if (r != SC_OK) return r;
+    char* b = (char*)ctx->fld_state.p;
+    field_args_w a;
+    a.pen = m.pen; a.cap = (uint32_t)m.pen_cap;
+    a.mask = (const uint64_t*)ctx->fld_mask.p; a.d2 = m.d2; a.fgrid = m.fgrid; a.g = g;
+    a.ok = (int32_t*)(b + o_ok); a.stamp = (int32_t*)(b + o_stamp); a.seeded = (int32_t*)(b + o_seeded);
+    a.list[0] = (int32_t*)(b + o_l0); a.list[1] = (int32_t*)(b + o_l1); a.ctr = (int32_t*)(b + o_ctr);
+    a.G = G; a.W = W; a.H = H; a.F = F; a.TX = TX; a.TY = TY; a.nt = nt;
+    a.thr = m.r2_clear > 1 ? m.r2_clear : 1;
+    update_args u;
+    u.mask_old = (const uint64_t*)ctx->fld_mask_old.p; u.pen_old = pen_old; u.root = root; u.stats = stats;
+    u.gflag = (int32_t*)(b + o_gflag); u.gcount = (int32_t*)(b + o_gcount); u.rstamp = (int32_t*)(b + o_rstamp);
+    u.rlist[0] = (int32_t*)(b + o_rl0); u.rlist[1] = (int32_t*)(b + o_rl1); u.rctr = (int32_t*)(b + o_rctr);
+    int tk = sc_time_begin(ctx, SC_K_ASTAR);
+    SC_HIP(ctx, hipMemsetAsync(b + o_stamp, 0, o_l0 - o_stamp, ctx->stream));
+    SC_HIP(ctx, hipMemsetAsync(b + o_ctr, 0, o_rl0 - o_ctr, ctx->stream));
+    const size_t nm = (size_t)G * TY * W, ne = (size_t)F * nt;
+    const dim3 gm((unsigned)((nm + 255) / 256)), ge((unsigned)((ne + 255) / 256));
+    hipLaunchKernelGGL(field_mask_kernel, gm, dim3(256), 0, ctx->stream, m.d2, G, W, H, TY, a.thr, (uint64_t*)ctx->fld_mask.p);
+    hipLaunchKernelGGL(field_mask_kernel, gm, dim3(256), 0, ctx->stream, d2_old, G, W, H, TY, a.thr, (uint64_t*)ctx->fld_mask_old.p);
+    if (m.pen) hipLaunchKernelGGL(update_diff_kernel<true>, gm, dim3(256), 0, ctx->stream, a, u);
+    else hipLaunchKernelGGL(update_diff_kernel<false>, gm, dim3(256), 0, ctx->stream, a, u);
+    hipLaunchKernelGGL(update_prep_kernel, dim3((unsigned)((F + 255) / 256)), dim3(256), 0, ctx->stream, (field_args)a, u, fstatus);
+    {
+        const size_t n = (size_t)W * H;
+        unsigned bx = (unsigned)((n + 1023) / 1024);
+        if (bx > 64) bx = 64;   // rarely more than an early exit per block
+        hipLaunchKernelGGL(update_dead_kernel, dim3(bx, F < 65535 ? F : 65535), dim3(1024), 0, ctx->stream, (field_args)a, u);
+    }
+    hipLaunchKernelGGL(update_queue_kernel, ge, dim3(256), 0, ctx->stream, (field_args)a, u);
+    {
+        const long long cap = (long long)ctx->cu_count * 8;
+        const unsigned blocks = (unsigned)((long long)ne < cap ? (long long)ne : cap);
+        for (int k = 0; k < rrounds; ++k) {
+            if (m.pen) hipLaunchKernelGGL(raise_round_kernel<true>, dim3(blocks), dim3(64), 0, ctx->stream, a, u, k);
+            else hipLaunchKernelGGL(raise_round_kernel<false>, dim3(blocks), dim3(64), 0, ctx->stream, a, u, k);
+        }
+        if (m.pen) hipLaunchKernelGGL(raise_finish_kernel<true>, dim3(F), dim3(64 * RAISE_FIN_WAVES), 0, ctx->stream, a, u, rrounds);
+        else hipLaunchKernelGGL(raise_finish_kernel<false>, dim3(F), dim3(64 * RAISE_FIN_WAVES), 0, ctx->stream, a, u, rrounds);
+    }
+    hipLaunchKernelGGL(update_seed_kernel, ge, dim3(256), 0, ctx->stream, (field_args)a);
+    field_relax(ctx, a, rounds);
+    sc_time_end(ctx, tk);
+    SC_HIP(ctx, hipGetLastError());
+    return SC_OK;
+}
+
+// the _host form of the repair: a negative g value is refused, g goes up and comes back
+static int field_update_host(sc_ctx* ctx, field_contract c, const int32_t* d2_old, const uint8_t* pen_old, const field_map& m,
+                             const int32_t* root, int rounds, int32_t* g, int32_t* fstatus, int32_t* stats) {
+    if (!field_args_ok(ctx, c, m, {root, nullptr, nullptr, m.F}, g, nullptr, nullptr) || !d2_old || (m.pen && !pen_old)) return SC_ERR_INVALID;
+    const size_t n = (size_t)m.W * m.H, fb = (size_t)m.F * 4;
+    for (size_t i = 0; i < (size_t)m.F * n; ++i)
+        if (g[i] < 0) return SC_ERR_INVALID;
+    SC_HIP(ctx, hipSetDevice(ctx->device));
+    sc_stage st(ctx);
+    const int i_d0 = st.in(d2_old, (size_t)m.G * n * 4), i_d1 = st.in(m.d2, (size_t)m.G * n * 4), i_p0 = st.in(pen_old, m.pen ? (size_t)m.G * n : 0),
+              i_p1 = st.in(m.pen, m.pen ? (size_t)m.G * n : 0), i_fg = st.in(m.fgrid, fb), i_rt = st.in(root, fb), i_g = st.in(g, fb * n);
+    st.back(i_g, g, fb * n);
+    const int o_st = st.out(fstatus, fb), o_ss = st.out(stats, fb * 2);
+    int r = st.upload();
+    if (r == SC_OK)
+        r = field_update(ctx, c, st.dev<const int32_t>(i_d0), staged(st, i_p0, pen_old),
+                         {st.dev<const int32_t>(i_d1), staged(st, i_p1, m.pen), m.pen_cap, m.G, staged(st, i_fg, m.fgrid), m.W, m.H, m.r2_clear, m.F},
+                         st.dev<const int32_t>(i_rt), rounds, st.dev<int32_t>(i_g), staged(st, o_st, fstatus), staged(st, o_ss, stats));
     return st.finish(r);
 }
 
@@ -941,4 +1359,33 @@ extern "C" int sc_field_paths_multi_batch_host(sc_ctx* ctx, const int32_t* d2, c
                                                int32_t* path, int32_t* len, int32_t* cost, int32_t* status, int32_t* which) {
     return field_read_host(ctx, FC_MULTI, {d2, pen, pen_cap, G, fgrid, W, H, r2_clear, F}, {seed, nullptr, nullptr, n_seed}, g, owner,
                            {qfield, target, Q, Lmax, to_seed, path, len, cost, status, which});
+}
+
+// ---- repair after a map change (include/sea_current_hip_update.h)
+extern "C" int sc_cost_field_update_batch(sc_ctx* ctx, const int32_t* d2_old, const int32_t* d2_new, int G, const int32_t* fgrid, int W, int H,
+                                          int32_t r2_clear, const int32_t* root, int F, int rounds, int32_t* g, int32_t* fstatus,
+                                          int32_t* stats) {
+    return field_update(ctx, FC_ROOTS, d2_old, nullptr, {d2_new, nullptr, 0, G, fgrid, W, H, r2_clear, F}, root, rounds, g, fstatus, stats);
+}
+
+extern "C" int sc_cost_field_update_batch_host(sc_ctx* ctx, const int32_t* d2_old, const int32_t* d2_new, int G, const int32_t* fgrid, int W,
+                                               int H, int32_t r2_clear, const int32_t* root, int F, int rounds, int32_t* g, int32_t* fstatus,
+                                               int32_t* stats) {
+    return field_update_host(ctx, FC_ROOTS, d2_old, nullptr, {d2_new, nullptr, 0, G, fgrid, W, H, r2_clear, F}, root, rounds, g, fstatus, stats);
+}
+
+extern "C" int sc_cost_field_weighted_update_batch(sc_ctx* ctx, const int32_t* d2_old, const uint8_t* pen_old, const int32_t* d2_new,
+                                                   const uint8_t* pen_new, int pen_cap, int G, const int32_t* fgrid, int W, int H,
+                                                   int32_t r2_clear, const int32_t* root, int F, int rounds, int32_t* g, int32_t* fstatus,
+                                                   int32_t* stats) {
+    return field_update(ctx, FC_ROOTS_WEIGHTED, d2_old, pen_old, {d2_new, pen_new, pen_cap, G, fgrid, W, H, r2_clear, F}, root, rounds, g,
+                        fstatus, stats);
+}
+
+extern "C" int sc_cost_field_weighted_update_batch_host(sc_ctx* ctx, const int32_t* d2_old, const uint8_t* pen_old, const int32_t* d2_new,
+                                                        const uint8_t* pen_new, int pen_cap, int G, const int32_t* fgrid, int W, int H,
+                                                        int32_t r2_clear, const int32_t* root, int F, int rounds, int32_t* g,
+                                                        int32_t* fstatus, int32_t* stats) {
+    return field_update_host(ctx, FC_ROOTS_WEIGHTED, d2_old, pen_old, {d2_new, pen_new, pen_cap, G, fgrid, W, H, r2_clear, F}, root, rounds, g,
+                             fstatus, stats);
 }

@@ -77,7 +77,9 @@ struct __attribute__((visibility("hidden"))) sc_ctx {
     sc_scratch sm_vlim;     // smoothing with per-stage limits: fp64 vlo [P][N+1] | vhi [P][N+1]
     sc_scratch occ_prep;    // polygon occupancy: float4 box [n_obs] | int2 cell-row range [n_obs] of every obstacle
     sc_scratch fld_mask;    // cost fields: uint64 [G][tile rows][W] traversability of 64 rows per column
+    sc_scratch fld_mask_old; // field repair: the same masks of the old map
     sc_scratch fld_state;   // cost fields: int32 ok [F] | stamp [F][tiles] | seeded [F][tiles] | list0, list1 [F * tiles] | ctr [rounds + 1] | left [jumps + 1]
+                            // a repair lays it out anew: ok | stamp | seeded | list0, list1 | ctr | rstamp [F][tiles] | rctr [raise rounds + 1] | gflag [G][tiles] | gcount [G] | rlist0, rlist1 [F * tiles]
     sc_scratch cmp_state;   // components: int32 [G][H][W] sizes when the caller passes none | uint64 [G] largest keys
     sc_scratch cmp_start;   // screened A*: int32 [Q] the starts, -1 where the endpoints lie in different components
     sc_scratch traj_part;   // path conflicts: partial results [P][slots] of the pair kernel | uint32 [P][ceil(P/32)] when the caller passes no matrix

@@ -23,6 +23,7 @@ NATIVE_DIR = os.path.normpath(os.path.join(_PKG, "..", ".."))          # sea-cur
 REPO_ROOT = os.path.normpath(os.path.join(NATIVE_DIR, ".."))
 LIB_PATH = os.environ.get("SC_LIB_PATH") or os.path.join(NATIVE_DIR, "libsea_current_hip.so")   # SC_LIB_PATH: experiment builds
 HEADER_PATH = os.path.join(REPO_ROOT, "include", "sea_current_hip.h")
+HEADER_UPDATE_PATH = os.path.join(REPO_ROOT, "include", "sea_current_hip_update.h")
 
 EDT_INF = 2**31 - 1
 FIELD_INF = 2**31 - 1
@@ -68,7 +69,7 @@ _SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "float":
 _RESULTS = {"void": None, "int": C.c_int, "int64_t": C.c_int64, "const char*": C.c_char_p}
 
 
-def _signatures(header):
+def _signatures(header, path=HEADER_PATH):
     """{name: (restype, argtypes)} of every function the header declares: a pointer is c_void_p (which also takes byref() of
     the scalar outputs), a scalar its exact ctype.  A declaration this cannot map raises; none is skipped."""
     src = re.sub(r"/\*.*?\*/|//[^\n]*", "", header, flags=re.S)
@@ -77,23 +78,27 @@ def _signatures(header):
         res = " ".join(res.replace("*", "* ").split()).replace(" *", "*")
         params = [" ".join(p.split()) for p in params.split(",")]
         if res not in _RESULTS:
-            raise SeaCurrentError(f"{HEADER_PATH}: {name}: no ctypes result type for '{res}'")
+            raise SeaCurrentError(f"{path}: {name}: no ctypes result type for '{res}'")
         args = []
         for p in ([] if params == ["void"] else params):
             words = [w for w in p.replace("*", " ").split() if w != "const"]
             if "*" not in p and (len(words) != 2 or words[0] not in _SCALARS):
-                raise SeaCurrentError(f"{HEADER_PATH}: {name}: no ctypes type for parameter '{p}'")
+                raise SeaCurrentError(f"{path}: {name}: no ctypes type for parameter '{p}'")
             args.append(C.c_void_p if "*" in p else _SCALARS[words[0]])
         sigs[name] = (_RESULTS[res], args)
     declared = set(re.findall(r"\b(sc_[a-z0-9_]+)\s*\(", src))
     if declared != set(sigs):
-        raise SeaCurrentError(f"{HEADER_PATH}: cannot read the declaration of {sorted(declared - set(sigs))}")
+        raise SeaCurrentError(f"{path}: cannot read the declaration of {sorted(declared - set(sigs))}")
     return sigs
 
 
 with open(HEADER_PATH) as _f:
     _SIGNATURES = _signatures(_f.read())
 EXPORTS = tuple(_SIGNATURES)
+# the field repair's header of its own: read the same way, kept in a table of its own
+with open(HEADER_UPDATE_PATH) as _f:
+    _SIGNATURES_UPDATE = _signatures(_f.read(), HEADER_UPDATE_PATH)
+EXPORTS_UPDATE = tuple(_SIGNATURES_UPDATE)
 
 
 def lib():
@@ -104,7 +109,7 @@ def lib():
             raise SeaCurrentError(f"{LIB_PATH} not built: run `python -c 'import __graft_entry__ as g; g.build()'` "
                                   "or `make -C sea-current_amd` (there is no CPU fallback)")
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGNATURES.items():
+        for name, (res, args) in list(_SIGNATURES.items()) + list(_SIGNATURES_UPDATE.items()):
             fn = getattr(l, name)
             fn.restype, fn.argtypes = res, args
         _lib = l
@@ -485,6 +490,36 @@ class Context:
             out = dict(g=A.new((F, H, W), A.i32), status=A.new(F, A.i32))
         name, costmap = A.field_entry("sc_cost_field", pen, pen_cap)
         self._call(name, _ptr(d2), *costmap, G, _ptr(fgrid), W, H, r2, _ptr(roots), F, rounds, _ptr(out["g"]), _ptr(out["status"]))
+        return out
+
+    def cost_fields_update(self, d2_old, d2_new, g, roots, r2=0, fgrid=None, rounds=-1, pen_old=None, pen_new=None, pen_cap=255, stats=True):
+        """Repair cost fields after a map change (sc_cost_field_update_batch): g int32 [F,H,W] holds the fields cost_fields
+        built on d2_old (with pen_old) for these roots, r2, fgrid and pen_cap, and is updated in place to what cost_fields
+        returns on d2_new (with pen_new), bit for bit.  Returns dict(g, status int32 [F], stats int32 [F,2] or None): per
+        field the changed cells of its grid and the cells that lost their support."""
+        return self._cost_fields_update(_on(d2_new.device), d2_old, d2_new, g, roots, r2, fgrid, rounds, pen_old, pen_new, pen_cap, stats)
+
+    def cost_fields_update_host(self, d2_old, d2_new, g, roots, r2=0, fgrid=None, rounds=-1, pen_old=None, pen_new=None, pen_cap=255,
+                                stats=True):
+        """Host form of cost_fields_update (numpy in, numpy out; the g returned is a copy, the caller's array stays)."""
+        return self._cost_fields_update(_HOST, d2_old, d2_new, g, roots, r2, fgrid, rounds, pen_old, pen_new, pen_cap, stats)
+
+    def _cost_fields_update(self, A, d2_old, d2_new, g, roots, r2, fgrid, rounds, pen_old, pen_new, pen_cap, stats):
+        d2_old, d2_new, roots, fgrid = (A.arr(a, A.i32) for a in (d2_old, d2_new, roots, fgrid))
+        pen_old, pen_new, g = A.arr(pen_old, A.u8), A.arr(pen_new, A.u8), A.own(g, A.i32)
+        G, H, W = _ghw(d2_new)
+        F = roots.shape[0]
+        if (pen_old is None) != (pen_new is None):
+            raise SeaCurrentError("pen_old and pen_new go together")
+        _sized("d2_old", d2_old, G * H * W)
+        _sized("pen_old", pen_old, G * H * W)
+        _sized("pen_new", pen_new, G * H * W)
+        _sized("g", g, F * H * W)
+        _sized("fgrid", fgrid, F)
+        out = dict(g=g, status=A.new(F, A.i32), stats=A.new((F, 2), A.i32) if stats else None)
+        name = "sc_cost_field" + ("" if pen_new is None else "_weighted") + "_update_batch" + A.suffix
+        maps = (_ptr(d2_old), _ptr(d2_new)) if pen_new is None else (_ptr(d2_old), _ptr(pen_old), _ptr(d2_new), _ptr(pen_new), pen_cap)
+        self._call(name, *maps, G, _ptr(fgrid), W, H, r2, _ptr(roots), F, rounds, _ptr(g), _ptr(out["status"]), _ptr(out["stats"]))
         return out
 
     def field_paths(self, d2, g, roots, qfield, targets, r2=0, Lmax=4096, to_root=False, fgrid=None, out=None, pen=None, pen_cap=255):

@@ -28,6 +28,7 @@
 //         soft_penalty: clearance-weighted cost fields (an inflation layer) behind plan_from / plan_to
 //   (new) occupancy_grid::cost_fields_multi / field_paths_multi, planning_space::plan_to_nearest: one field from many
 //         goals, every start to the cheapest of them
+//   (new) occupancy_grid::cost_fields_update: fields repaired after a map change instead of built again, bit-equal
 //   (new) fleet_conflicts: who meets whom among the results of smooth_paths_batch, when first, and how close
 //   (new) fleet_schedule: start slots by priority that let the lower-priority path wait until it meets nobody
 //   (new) fleet_replan: the paths no slot was free for, planned again in (cell, tick) around the scheduled ones
@@ -84,6 +85,7 @@
 #include <vector>
 
 #include "../include/sea_current_hip.h"
+#include "../include/sea_current_hip_update.h"
 
 #if __has_include(<Eigen/Dense>)
 #include <Eigen/Dense>
@@ -536,7 +538,40 @@ public:
         int32_t r2 = 0;
         std::vector<uint8_t> pen;               // the costmap of a weighted field ([H][W]), empty for an unweighted one:
         int pen_cap = 0;                        // field_paths reads a field with what cost_fields computed it with
+        int rounds = -1;                        // what cost_fields was called with: cost_fields_update repeats it
+        int32_t r2_soft = 0;                    // > 0: pen is clearance_penalty(r2, r2_soft, pen_max) of the grid (the soft knobs of
+        int pen_max = 0;                        // planning_space), and cost_fields_update recomputes it; 0: pen is the caller's own
     };
+    // Repair fields after a map change (sc_cost_field_update_batch): `fields` is what cost_fields
+    // returned on `before`, a grid of this grid's size; on return it is, bit for bit, what cost_fields returns on this
+    // grid for the roots, r2, rounds and costmap it remembers.  A costmap from the soft knobs (r2_soft > 0) is computed
+    // again for this grid; a caller's own costmap stays as it is.  stats (may be NULL): per field the changed cells and the
+    // cells that lost their support.
+    field_result& cost_fields_update(const occupancy_grid& before, field_result& fields, gpu_context& ctx = default_context(),
+                                     std::vector<std::array<int32_t, 2>>* stats = nullptr) {
+        if (before.W != W || before.H != H) throw std::invalid_argument("occupancy_grid::cost_fields_update: the grids differ in size");
+        if (before.d2.size() != before.occ.size()) throw std::invalid_argument("occupancy_grid::cost_fields_update: `before` has no distance map (edt)");
+        const int F = (int)fields.roots.size();
+        if (fields.g.size() != (size_t)F * W * H) throw std::invalid_argument("occupancy_grid::cost_fields_update: fields.g is not [F][H][W]");
+        if (d2.size() != occ.size()) edt(ctx);
+        fields.status.assign(F, SC_Q_BAD_ENDPOINT);
+        if (stats) stats->assign(F, std::array<int32_t, 2>{0, 0});
+        if (F == 0) return fields;
+        int32_t* st = stats ? (*stats)[0].data() : nullptr;
+        if (fields.pen.empty()) {
+            ctx.check(sc_cost_field_update_batch_host(ctx.get(), before.d2.data(), d2.data(), 1, nullptr, W, H, fields.r2, fields.roots.data(), F,
+                                                      fields.rounds, fields.g.data(), fields.status.data(), st),
+                      "sc_cost_field_update_batch_host");
+            return fields;
+        }
+        std::vector<uint8_t> pen_new = fields.r2_soft > 0 ? clearance_penalty(fields.r2, fields.r2_soft, fields.pen_max, ctx) : fields.pen;
+        ctx.check(sc_cost_field_weighted_update_batch_host(ctx.get(), before.d2.data(), fields.pen.data(), d2.data(), pen_new.data(),
+                                                           fields.pen_cap, 1, nullptr, W, H, fields.r2, fields.roots.data(), F, fields.rounds,
+                                                           fields.g.data(), fields.status.data(), st),
+                  "sc_cost_field_weighted_update_batch_host");
+        fields.pen = std::move(pen_new);
+        return fields;
+    }
     field_result cost_fields(const std::vector<int32_t>& roots, int32_t r2_clear = 0, int rounds = -1,
                              gpu_context& ctx = default_context()) {
         return cost_fields_with(roots, nullptr, 0, r2_clear, rounds, ctx);
@@ -976,6 +1011,7 @@ private:
         const int F = (int)roots.size();
         r.roots = roots;
         r.r2 = r2_clear;
+        r.rounds = rounds;
         if (pen) { r.pen = *pen; r.pen_cap = pen_cap; }
         r.g.assign((size_t)F * W * H, SC_FIELD_INF); r.status.assign(F, SC_Q_BAD_ENDPOINT);
         if (F == 0) return r;
@@ -1514,7 +1550,10 @@ private:
         int32_t r2_soft;
         int pen_max;
         soft_knobs(g, r2_soft, pen_max);
-        return g.cost_fields(roots, g.clearance_penalty(r2, r2_soft, pen_max, ctx), pen_max, r2, -1, ctx);
+        occupancy_grid::field_result fr = g.cost_fields(roots, g.clearance_penalty(r2, r2_soft, pen_max, ctx), pen_max, r2, -1, ctx);
+        fr.r2_soft = r2_soft;   // cost_fields_update computes the costmap of a changed grid with the same knobs
+        fr.pen_max = pen_max;
+        return fr;
     }
     // the costmap parameters the soft knobs stand for
     void soft_knobs(const occupancy_grid& g, int32_t& r2_soft, int& pen_max) const {
