@@ -103,6 +103,7 @@ struct __attribute__((visibility("hidden"))) sc_ctx {
     sc_scratch mw_state;    // wide scan matching: uint64 parents [2][S][max_nodes] | int32 bounds [S][max_nodes] | uint64 keys [S][R] | int32 counts [S][16] | int32 U [S][8]
     sc_scratch fp_sat;      // footprint mask: int32 [H+1][W+1] | int32 [W+H][W+H], the summed-area tables of one grid's blocked cells over (x, y) and over (x + y, y - x)
     sc_scratch pose_state;  // pose fields: int32 ok [F] | stamp [F][tiles] | list0, list1 [F * tiles] | ctr [rounds + 1]
+    sc_scratch car_state;   // car fields: the layout of pose_state
     sc_scratch eg_state;    // goals by gain: state words | kw [H][W] when the caller keeps none | vis [2][H][W] | views [N][3] | best [N][2] | hist [N][B] | c0 [N] | assigned [R] | taken [N] | cost [R][N] | partials
     sc_scratch eg_centre;   // sc_frontier_centres: uint64 [G][Cmax] smallest keys
     sc_scratch eg_fleet;    // sc_fleet_explore_gain_batch: the intermediate arrays the caller passes none of

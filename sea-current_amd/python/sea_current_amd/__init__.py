@@ -24,6 +24,7 @@ REPO_ROOT = os.path.normpath(os.path.join(NATIVE_DIR, ".."))
 LIB_PATH = os.environ.get("SC_LIB_PATH") or os.path.join(NATIVE_DIR, "libsea_current_hip.so")   # SC_LIB_PATH: experiment builds
 HEADER_PATH = os.path.join(REPO_ROOT, "include", "sea_current_hip.h")
 HEADER_UPDATE_PATH = os.path.join(REPO_ROOT, "include", "sea_current_hip_update.h")
+HEADER_CAR_PATH = os.path.join(REPO_ROOT, "include", "sea_current_hip_car.h")
 
 EDT_INF = 2**31 - 1
 FIELD_INF = 2**31 - 1
@@ -49,6 +50,7 @@ SCAN_MATCH_OVERFLOW, SCAN_MATCH_WIDE_MAX_HALF, SCAN_MATCH_WIDE_MAX_TOP = -2, 204
 VIEW_MAX_BINS = 64
 POSE_HEADINGS, FOOTPRINT_MAX = 8, 32
 POSE_HX, POSE_HY = (1, 1, 0, -1, -1, -1, 0, 1), (0, 1, 1, 1, 0, -1, -1, -1)   # heading k, counter-clockwise in (x, y)
+ARC_MAX = 4
 
 _lib = None
 
@@ -99,6 +101,10 @@ EXPORTS = tuple(_SIGNATURES)
 with open(HEADER_UPDATE_PATH) as _f:
     _SIGNATURES_UPDATE = _signatures(_f.read(), HEADER_UPDATE_PATH)
 EXPORTS_UPDATE = tuple(_SIGNATURES_UPDATE)
+# car-like pose planning's header of its own, likewise
+with open(HEADER_CAR_PATH) as _f:
+    _SIGNATURES_CAR = _signatures(_f.read(), HEADER_CAR_PATH)
+EXPORTS_CAR = tuple(_SIGNATURES_CAR)
 
 
 def lib():
@@ -109,7 +115,7 @@ def lib():
             raise SeaCurrentError(f"{LIB_PATH} not built: run `python -c 'import __graft_entry__ as g; g.build()'` "
                                   "or `make -C sea-current_amd` (there is no CPU fallback)")
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(_SIGNATURES.items()) + list(_SIGNATURES_UPDATE.items()):
+        for name, (res, args) in list(_SIGNATURES.items()) + list(_SIGNATURES_UPDATE.items()) + list(_SIGNATURES_CAR.items()):
             fn = getattr(l, name)
             fn.restype, fn.argtypes = res, args
         _lib = l
@@ -139,6 +145,12 @@ def _sized(what, x, n):
         raise SeaCurrentError(f"{what} has {_count(x)} elements, the call needs {n}")
 
 
+def _car_ranges(arc_n, arc_cost, rev_cost):
+    """The parameter ranges of the car calls (include/sea_current_hip_car.h), refused before the library is reached."""
+    if not (1 <= int(arc_n) <= ARC_MAX and 0 <= int(arc_cost) <= 255 and -1 <= int(rev_cost) <= 255):
+        raise SeaCurrentError(f"arc_n {arc_n} (1 .. {ARC_MAX}), arc_cost {arc_cost} (0 .. 255) or rev_cost {rev_cost} (-1 .. 255) out of range")
+
+
 def _ghw(d2):
     """(G, H, W) of a map-shaped tensor or array: [H,W] is one grid, [G,H,W] a stack."""
     return (1,) + tuple(d2.shape) if len(d2.shape) == 2 else tuple(d2.shape)
@@ -148,7 +160,7 @@ class _Home:
     """Where the arrays of a call live.  A device method and its _host twin are one body that takes a home: _HOST (numpy) or
     _on(device) (torch).  What differs between the twins is here and nowhere else: the suffix of the C name, how an output is
     allocated (new), how an input is taken (arr, own, words, seq), how a per-path argument is broadcast (per_path, rows4), and
-    the dtypes, of which only the bit words w32 / w64 differ."""
+    the dtypes, of which only the bit words w16 / w32 / w64 differ."""
 
     def paths_out(self, Q, Lmax, which=False):
         """The result dict of a path read-out (astar_batch's layout; which: the multi-source read-out's).  On the host path
@@ -181,6 +193,7 @@ class _Host(_Home):
     fill is given, bit words are unsigned."""
     suffix = "_host"
     u8, i32, i64, f32, f64, w32, w64 = np.uint8, np.int32, np.int64, np.float32, np.float64, np.uint32, np.uint64
+    w16 = np.uint16
 
     @staticmethod
     def new(shape, dtype, fill=None, host_fill=0):
@@ -236,7 +249,7 @@ class _Device(_Home):
         import torch
         self.torch, self.dev = torch, dev
         self.u8, self.i32, self.i64, self.f32, self.f64 = torch.uint8, torch.int32, torch.int64, torch.float32, torch.float64
-        self.w32, self.w64 = torch.int32, torch.int64
+        self.w16, self.w32, self.w64 = torch.int16, torch.int32, torch.int64
 
     def new(self, shape, dtype, fill=None, host_fill=0):
         if fill is None:
@@ -1595,6 +1608,106 @@ class Context:
                    int(bool(toward)), _ptr(gp), _ptr(roots), _ptr(rhead), F, _ptr(qfield), _ptr(targets), _ptr(thead), Q, Lmax,
                    int(bool(to_root)), int(bool(cells_only)), _ptr(out["path"]), _ptr(out["head"]), _ptr(out["len"]), _ptr(out["cost"]),
                    _ptr(out["status"]))
+        return out
+
+    # ---- car-like pose planning (sc_arc_mask_u16, sc_car_field_batch, sc_car_paths_batch) ----
+    def arc_mask(self, d2, arc_n, r2=0, hmask=None, out=None):
+        """The legal arcs of every pose (sc_arc_mask_u16): d2 int32 [H,W] or [B,H,W] on the GPU, hmask uint8 shaped like d2
+        (what footprint_mask returned) or None, arc_n 1 .. ARC_MAX.  An arc is arc_n cells straight, 45 degrees, arc_n cells
+        straight.  Returns int16 shaped like d2 (the bits of uint16): bit 2k of a cell is set where the arc from heading k to
+        k + 1 is legal, bit 2k + 1 where the one to k - 1 is.  Only enqueues."""
+        return self._arc_mask(_on(d2.device), d2, arc_n, r2, hmask, out)
+
+    def arc_mask_host(self, d2, arc_n, r2=0, hmask=None):
+        """Host form of arc_mask (numpy in, numpy uint16 out)."""
+        return self._arc_mask(_HOST, d2, arc_n, r2, hmask)
+
+    def _arc_mask(self, A, d2, arc_n, r2, hmask, out=None):
+        d2, hmask = A.arr(d2, A.i32), A.arr(hmask, A.u8)
+        B, H, W = _ghw(d2)
+        _car_ranges(arc_n, 0, -1)
+        if out is None:
+            out = A.new(tuple(d2.shape), A.w16)
+        _sized("hmask", hmask, B * H * W)
+        _sized("out", out, B * H * W)
+        self._call("sc_arc_mask_u16" + A.suffix, _ptr(d2), _ptr(hmask), W, H, B, r2, int(arc_n), _ptr(out))
+        return out
+
+    def car_fields(self, d2, amask, roots, rhead, arc_n, arc_cost=0, rev_cost=-1, toward=False, r2=0, hmask=None, fgrid=None, rounds=-1,
+                   out=None):
+        """Cost fields over poses for a car-like body (sc_car_field_batch): pose_fields' arguments, but the heading changes
+        only along the arcs of amask (what arc_mask returned for the same d2, hmask, r2 and arc_n), never on the spot.  A
+        forward move costs 10 / 14, an arc 24 arc_n + arc_cost, reversing rev_cost more per cell (-1: none).  toward: the cost
+        from every pose to the root pose.  Returns dict(gp int32 [F,8,H,W], status int32 [F]).  Only enqueues."""
+        return self._car_fields(_on(d2.device), d2, amask, roots, rhead, arc_n, arc_cost, rev_cost, toward, r2, hmask, fgrid, rounds, out)
+
+    def car_fields_host(self, d2, amask, roots, rhead, arc_n, arc_cost=0, rev_cost=-1, toward=False, r2=0, hmask=None, fgrid=None,
+                        rounds=-1):
+        """Host form of car_fields (numpy in, numpy out)."""
+        return self._car_fields(_HOST, d2, amask, roots, rhead, arc_n, arc_cost, rev_cost, toward, r2, hmask, fgrid, rounds)
+
+    def _car_fields(self, A, d2, amask, roots, rhead, arc_n, arc_cost, rev_cost, toward, r2, hmask, fgrid, rounds, out=None):
+        d2, roots, rhead, fgrid, hmask = A.arr(d2, A.i32), A.arr(roots, A.i32), A.arr(rhead, A.i32), A.arr(fgrid, A.i32), A.arr(hmask, A.u8)
+        amask = A.words(amask, A.w16)
+        G, H, W = _ghw(d2)
+        F = _count(roots)
+        _car_ranges(arc_n, arc_cost, rev_cost)
+        if amask is None:
+            raise SeaCurrentError("amask is mandatory: pass what arc_mask returned")
+        if out is None:
+            out = dict(gp=A.new((F, POSE_HEADINGS, H, W), A.i32), status=A.new(F, A.i32))
+        _sized("amask", amask, G * H * W)
+        _sized("rhead", rhead, F)
+        _sized("fgrid", fgrid, F)
+        _sized("hmask", hmask, G * H * W)
+        _sized("out['gp']", out["gp"], F * POSE_HEADINGS * H * W)
+        _sized("out['status']", out["status"], F)
+        self._call("sc_car_field_batch" + A.suffix, _ptr(d2), _ptr(hmask), _ptr(amask), G, _ptr(fgrid), W, H, r2, int(arc_n), int(arc_cost),
+                   int(rev_cost), int(bool(toward)), _ptr(roots), _ptr(rhead), F, rounds, _ptr(out["gp"]), _ptr(out["status"]))
+        return out
+
+    def car_paths(self, d2, amask, gp, roots, rhead, qfield, targets, thead, arc_n, arc_cost=0, rev_cost=-1, toward=False, r2=0, hmask=None,
+                  Lmax=4096, to_root=False, fgrid=None, out=None):
+        """Car paths read from car fields (sc_car_paths_batch): query q follows field qfield[q] (gp, roots, rhead, amask and the
+        costs as car_fields took and returned them) to the pose (targets[q], thead[q]); thead -1: the cheapest heading there.
+        Returns astar_batch's dict plus head uint8 [Q,Lmax]: one entry per cell, the cells of an arc included, so path is
+        8-connected and goes straight into path_waypoints; to_root writes target..root (the driving order of a toward field).
+        Only enqueues."""
+        return self._car_paths(_on(d2.device), d2, amask, gp, roots, rhead, qfield, targets, thead, arc_n, arc_cost, rev_cost, toward, r2,
+                               hmask, Lmax, to_root, fgrid, out)
+
+    def car_paths_host(self, d2, amask, gp, roots, rhead, qfield, targets, thead, arc_n, arc_cost=0, rev_cost=-1, toward=False, r2=0,
+                       hmask=None, Lmax=4096, to_root=False, fgrid=None):
+        """Host form of car_paths (numpy in, numpy out)."""
+        return self._car_paths(_HOST, d2, amask, gp, roots, rhead, qfield, targets, thead, arc_n, arc_cost, rev_cost, toward, r2, hmask, Lmax,
+                               to_root, fgrid)
+
+    def _car_paths(self, A, d2, amask, gp, roots, rhead, qfield, targets, thead, arc_n, arc_cost, rev_cost, toward, r2, hmask, Lmax, to_root,
+                   fgrid, out=None):
+        d2, gp, roots, rhead, qfield, targets, thead, fgrid = (A.arr(a, A.i32) for a in (d2, gp, roots, rhead, qfield, targets, thead, fgrid))
+        hmask, amask = A.arr(hmask, A.u8), A.words(amask, A.w16)
+        G, H, W = _ghw(d2)
+        F, Q = _count(roots), _count(targets)
+        _car_ranges(arc_n, arc_cost, rev_cost)
+        if amask is None:
+            raise SeaCurrentError("amask is mandatory: pass what arc_mask returned")
+        if Lmax < 1:
+            raise SeaCurrentError(f"Lmax is {Lmax}, the call needs at least 1")
+        if out is None:
+            out = A.paths_out(Q, Lmax)
+            out["head"] = A.new((Q, Lmax), A.u8)
+        _sized("amask", amask, G * H * W)
+        _sized("gp", gp, F * POSE_HEADINGS * H * W)
+        _sized("rhead", rhead, F)
+        _sized("fgrid", fgrid, F)
+        _sized("hmask", hmask, G * H * W)
+        _sized("qfield", qfield, Q)
+        _sized("thead", thead, Q)
+        _sized("out['path']", out["path"], Q * Lmax)
+        _sized("out['head']", out["head"], Q * Lmax)
+        self._call("sc_car_paths_batch" + A.suffix, _ptr(d2), _ptr(hmask), _ptr(amask), G, _ptr(fgrid), W, H, r2, int(arc_n), int(arc_cost),
+                   int(rev_cost), int(bool(toward)), _ptr(gp), _ptr(roots), _ptr(rhead), F, _ptr(qfield), _ptr(targets), _ptr(thead), Q, Lmax,
+                   int(bool(to_root)), _ptr(out["path"]), _ptr(out["head"]), _ptr(out["len"]), _ptr(out["cost"]), _ptr(out["status"]))
         return out
 
     # ---- occupancy from range scans (sc_scan_cast_batch, sc_logodds_update) ----

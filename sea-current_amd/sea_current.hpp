@@ -46,6 +46,8 @@
 //   (new) occupancy_grid::scan_match_wide, logodds_grid::relocalise: the same over windows of thousands of cells, pruned
 //   (new) footprint, occupancy_grid::footprint_mask / pose_fields / pose_paths, planning_space::plan_to_pose: planning in
 //         poses (cell, heading) with a price for turning and reversing and a rectangular body
+//   (new) car_model, occupancy_grid::arc_mask / car_fields / car_paths, planning_space::plan_to_pose(.., car_model, ..):
+//         car-like bodies, whose heading changes only along arcs
 //   (new) occupancy_grid::frontier_centres / explore_goals_by_gain, planner::gain_weight: goals picked by what each view
 //         reveals, every pick discounting the others
 //
@@ -86,6 +88,7 @@
 
 #include "../include/sea_current_hip.h"
 #include "../include/sea_current_hip_update.h"
+#include "../include/sea_current_hip_car.h"
 
 #if __has_include(<Eigen/Dense>)
 #include <Eigen/Dense>
@@ -395,6 +398,13 @@ struct footprint {
     int front = 0, back = 0, left = 0, right = 0;
 };
 
+// The motion model of a car-like body (include/sea_current_hip_car.h): the heading changes only along arcs of arc_n cells
+// straight, 45 degrees, arc_n cells straight (1 .. SC_ARC_MAX; a turning radius of about 3 arc_n cells), never on the spot.  An
+// arc costs 24 arc_n + arc_cost, reversing rev_cost more per cell (-1: no reversing), in the units of the move costs.
+struct car_model {
+    int arc_n = 1, arc_cost = 0, rev_cost = -1;
+};
+
 // ---- occupancy grid (new): the world model the GPU path works on ----------------------------------
 // Row-major uint8 occupancy over a bounding_rect; cell (ix, iy) covers
 // [x_min + ix*res, x_min + (ix+1)*res) x [y_min + iy*res, ...).  d2 is the exact squared distance (in
@@ -676,6 +686,66 @@ public:
                                            qfield.data(), targets.data(), thead.data(), Q, r.Lmax, to_root ? 1 : 0, cells_only ? 1 : 0,
                                            r.path.data(), r.head.data(), r.len.data(), r.cost.data(), r.status.data()),
                   "sc_pose_paths_batch_host");
+        return r;
+    }
+    // The legal arcs of every pose (sc_arc_mask_u16): bit 2k of mask[c] is set iff the arc from (c, k) to heading k + 1 is legal
+    // for the body of hmask (what footprint_mask returned, or empty for the disc), bit 2k + 1 iff the one to k - 1 is.
+    std::vector<uint16_t> arc_mask(int arc_n, int32_t r2_clear = 0, const std::vector<uint8_t>& hmask = {}, gpu_context& ctx = default_context()) {
+        if (!hmask.empty() && hmask.size() != occ.size()) throw std::invalid_argument("occupancy_grid::arc_mask: hmask is not [H][W]");
+        if (d2.size() != occ.size()) edt(ctx);
+        std::vector<uint16_t> m(occ.size(), 0);
+        if (occ.empty()) return m;
+        ctx.check(sc_arc_mask_u16_host(ctx.get(), d2.data(), hmask.empty() ? nullptr : hmask.data(), W, H, 1, r2_clear, arc_n, m.data()),
+                  "sc_arc_mask_u16_host");
+        return m;
+    }
+    // Cost fields over poses for a car-like body (sc_car_field_batch): pose_fields with car.arc_n-cell arcs in the place of
+    // turns on the spot.  The arc mask is computed here; the result remembers what car_paths needs.
+    struct car_field_result {
+        std::vector<int32_t> gp, status, roots, rhead;  // gp is [F][8][H][W]
+        std::vector<uint8_t> hmask;
+        std::vector<uint16_t> amask;
+        int32_t r2 = 0;
+        car_model car;
+        bool toward = false;
+    };
+    car_field_result car_fields(const std::vector<int32_t>& roots, const std::vector<int32_t>& rhead, const car_model& car, bool toward = false,
+                                int32_t r2_clear = 0, const std::vector<uint8_t>& hmask = {}, int rounds = -1,
+                                gpu_context& ctx = default_context()) {
+        if (roots.size() != rhead.size()) throw std::invalid_argument("occupancy_grid::car_fields: roots and rhead differ in size");
+        if (!hmask.empty() && hmask.size() != occ.size()) throw std::invalid_argument("occupancy_grid::car_fields: hmask is not [H][W]");
+        if (d2.size() != occ.size()) edt(ctx);
+        car_field_result r;
+        r.roots = roots; r.rhead = rhead; r.hmask = hmask; r.r2 = r2_clear; r.car = car; r.toward = toward;
+        const int F = (int)roots.size();
+        r.gp.assign((size_t)F * SC_POSE_HEADINGS * occ.size(), SC_FIELD_INF); r.status.assign(F, SC_Q_BAD_ENDPOINT);
+        r.amask = arc_mask(car.arc_n, r2_clear, hmask, ctx);
+        if (F == 0) return r;
+        ctx.check(sc_car_field_batch_host(ctx.get(), d2.data(), hmask.empty() ? nullptr : hmask.data(), r.amask.data(), 1, nullptr, W, H,
+                                          r2_clear, car.arc_n, car.arc_cost, car.rev_cost, toward ? 1 : 0, roots.data(), rhead.data(), F, rounds,
+                                          r.gp.data(), r.status.data()),
+                  "sc_car_field_batch_host");
+        return r;
+    }
+    // Car paths read from car fields (sc_car_paths_batch): one entry per cell, the cells of an arc included, so path is
+    // 8-connected; to_root writes target..root, the driving order of a toward field.
+    pose_paths_result car_paths(const car_field_result& fr, const std::vector<int32_t>& qfield, const std::vector<int32_t>& targets,
+                                const std::vector<int32_t>& thead, int Lmax = 0, bool to_root = false, gpu_context& ctx = default_context()) {
+        if (qfield.size() != targets.size() || thead.size() != targets.size())
+            throw std::invalid_argument("occupancy_grid::car_paths: qfield, targets and thead differ in size");
+        if (d2.size() != occ.size()) edt(ctx);
+        pose_paths_result r;
+        const int Q = (int)targets.size(), F = (int)fr.roots.size();
+        r.Lmax = Lmax > 0 ? Lmax : 16 * (W + H);
+        r.path.assign((size_t)Q * r.Lmax, -1); r.head.assign((size_t)Q * r.Lmax, 0);
+        r.len.assign(Q, 0); r.cost.assign(Q, -1); r.status.assign(Q, SC_Q_NO_PATH);
+        if (Q == 0) return r;
+        if (F == 0) { r.status.assign(Q, SC_Q_BAD_ENDPOINT); return r; }
+        ctx.check(sc_car_paths_batch_host(ctx.get(), d2.data(), fr.hmask.empty() ? nullptr : fr.hmask.data(), fr.amask.data(), 1, nullptr, W, H,
+                                          fr.r2, fr.car.arc_n, fr.car.arc_cost, fr.car.rev_cost, fr.toward ? 1 : 0, fr.gp.data(),
+                                          fr.roots.data(), fr.rhead.data(), F, qfield.data(), targets.data(), thead.data(), Q, r.Lmax,
+                                          to_root ? 1 : 0, r.path.data(), r.head.data(), r.len.data(), r.cost.data(), r.status.data()),
+                  "sc_car_paths_batch_host");
         return r;
     }
     // Multi-source cost fields (sc_cost_field_multi_batch): field f starts from seeds[seed_off[f] .. seed_off[f+1]-1], each
@@ -1430,6 +1500,38 @@ public:
         for (size_t q = 0; q < starts.size(); ++q)
             if (pr.status[q] == SC_Q_TRUNCATED) need = std::max(need, (int)pr.len[q]);
         if (need > 0) pr = g.pose_paths(fr, qf, s, start_heading, need, true, false, ctx);
+        std::vector<std::optional<std::vector<pose>>> out(starts.size());
+        for (size_t q = 0; q < starts.size(); ++q) {
+            if (pr.status[q] != SC_Q_OK) continue;
+            std::vector<pose> poses((size_t)pr.len[q]);
+            for (int i = 0; i < pr.len[q]; ++i) {
+                const int32_t c = pr.path[q * (size_t)pr.Lmax + i];
+                poses[(size_t)i] = pose{g.centre_of(c), c, (int)pr.head[q * (size_t)pr.Lmax + i]};
+            }
+            out[q] = std::move(poses);
+        }
+        return out;
+    }
+    // The same for a car-like body: one toward car field rooted at the goal pose (occupancy_grid::car_fields).  The heading
+    // changes only along arcs, so a route never pivots; one entry per cell, the cells of an arc included.
+    std::vector<std::optional<std::vector<pose>>> plan_to_pose(const std::vector<Vector2f>& starts, const std::vector<int32_t>& start_heading,
+                                                               const Vector2f& goal, int goal_heading, const car_model& car,
+                                                               const footprint& body = {}, gpu_context& ctx = default_context()) {
+        if (starts.size() != start_heading.size())
+            throw std::invalid_argument("planning_space::plan_to_pose: starts and start_heading differ in size");
+        occupancy_grid g = make_grid(ctx);
+        g.edt(ctx);
+        const int32_t r2 = clearance_r2(g);
+        const bool disc = body.front == 0 && body.back == 0 && body.left == 0 && body.right == 0;
+        auto fr = g.car_fields({g.cell_of(goal)}, {(int32_t)goal_heading}, car, true, r2,
+                               disc ? std::vector<uint8_t>{} : g.footprint_mask(body, r2, ctx), -1, ctx);
+        std::vector<int32_t> s(starts.size()), qf(starts.size(), 0);
+        for (size_t i = 0; i < starts.size(); ++i) s[i] = g.cell_of(starts[i]);
+        auto pr = g.car_paths(fr, qf, s, start_heading, 0, true, ctx);
+        int need = 0;                                       // a truncated read-out reports the count it needs: read again with room
+        for (size_t q = 0; q < starts.size(); ++q)
+            if (pr.status[q] == SC_Q_TRUNCATED) need = std::max(need, (int)pr.len[q]);
+        if (need > 0) pr = g.car_paths(fr, qf, s, start_heading, need, true, ctx);
         std::vector<std::optional<std::vector<pose>>> out(starts.size());
         for (size_t q = 0; q < starts.size(); ++q) {
             if (pr.status[q] != SC_Q_OK) continue;

@@ -72,7 +72,9 @@ def main():
         hm = ctx.footprint_mask(d2, *BODIES[1], r2=R2)
         ctx.synchronize()
         hmh = hm.cpu().numpy()
-        fit = np.array([c for c in s if hmh.ravel()[c] == 0xFF][:16], np.int32)       # roots the body fits at every heading
+        fit = [c for c in s if hmh.ravel()[c] == 0xFF][:16]                         # roots the body fits at every heading
+        # on salt20 the (3,3,1,1) body fits at every heading in 18 cells, none of them a query start: take those
+        fit = np.array(fit + [c for c in np.flatnonzero(hmh.ravel() == 0xFF) if c not in fit][:16 - len(fit)], np.int32)
         assert len(fit) == 16
         # field
         for F in (1, 16):
